@@ -18,7 +18,12 @@ so that K steps do identical work (8 device copies inside the timed step that a 
 N > 1: one process per GPU (torch.distributed, RCCL); every rank tracks its own window
 (independent sequences, no data-path collective), value = N*K / max-over-ranks time.
 
-Extra objects on the JSON line: "roofline" for the dominant hand-written HBM-bound kernel (the fused 4-level lookup; its
+A plain run does what the headline needs and nothing else: set-up, priming, W warm-up steps, the K timed steps, the
+JSON line (metric, value, ms_per_step, ...).  --dump-outputs DIR writes what the last timed step computed (step_outputs:
+poses, disparities, per-edge state, frame distances) as DIR/<name>.npy; inputs are seeded, so two builds compare file by
+file.  Everything below is measured only with --full.
+
+Extra objects on the JSON line with --full: "roofline" for the dominant hand-written HBM-bound kernel (the fused 4-level lookup; its
 duration = HIP events around it inside the timed steps minus what an event pair around nothing reads at the same place),
 "roofline_wide_conv" (matrix-core roofline of the wide 3x3 convolution, the kernel with the largest share of the step,
 with the shader clock the chip sustains under it and inside a step: pvo_clock_probe), "stage_us_in_step", "host",
@@ -291,13 +296,15 @@ REMOVAL_RATE = 0.25      # share of the sequence leg's keyframe updates that end
 
 
 def timed_steps(video, graph, snap, steps, world, probe_stage="lookup", updates_per_step=6):
-    """K keyframe updates bracketed as the driver's contract asks: barrier + synchronize on both sides, max over ranks"""
+    """K keyframe updates bracketed as the driver's contract asks: barrier + synchronize on both sides, max over ranks.
+    Returns (elapsed s, host issue time per step, probe readings, what the last step's keyframe_update returned)."""
     from pvo_amd import droid_backends as db
     if probe_stage:
         # HIP events around one kernel, on its stream, in the timed steps: one launch in PROBE_EVERY (co-prime with the updates
         # per step, so every position inside the step is sampled) - the event pair costs the launch stream ~7 us, 2 % of a step
         db.probe_arm(probe_stage, steps * updates_per_step, every=PROBE_EVERY)
     host_issue = []
+    last = None
     torch.cuda.synchronize()
     if world > 1:
         import torch.distributed as dist
@@ -306,7 +313,7 @@ def timed_steps(video, graph, snap, steps, world, probe_stage="lookup", updates_
     t0 = time.perf_counter()
     for _ in range(steps):
         th = time.perf_counter()
-        keyframe_update(video, graph, snap)
+        last = keyframe_update(video, graph, snap)
         host_issue.append(time.perf_counter() - th)
     torch.cuda.synchronize()
     if world > 1:
@@ -318,7 +325,7 @@ def timed_steps(video, graph, snap, steps, world, probe_stage="lookup", updates_
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     in_step = db.probe_read(steps * updates_per_step) if probe_stage else []
-    return elapsed, host_issue, in_step
+    return elapsed, host_issue, in_step, last
 
 
 def prime(video, graph, snap, max_blocks=40):
@@ -378,7 +385,7 @@ def workload_sa(device, steps):
     snap = Snapshot(video, graph)
     snap.edge_list = list(zip(graph._ii_h, graph._jj_h))
     prime(video, graph, snap, max_blocks=6)
-    elapsed, host_issue, in_step = timed_steps(video, graph, snap, steps, 1)
+    elapsed, host_issue, in_step, _ = timed_steps(video, graph, snap, steps, 1)
     E = len(graph._ii_h)
     return {"workload": "S-A: 30x101 maps (test_vo.py's 240x808 input), 10 keyframes, E=%d, itrs=2, synthetic" % E,
             "value": steps / elapsed, "unit": "keyframe updates/s", "ms_per_step": elapsed / steps * 1e3, "steps": steps,
@@ -1030,6 +1037,42 @@ def emit(obj):
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, line)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+NET_SAMPLE = 1 << 20        # hidden-state values kept by --dump-outputs (the whole state: 36 x 128 x 48 x 64 = 14.2 M)
+
+
+def step_outputs(video, graph, last):
+    """What a caller of the keyframe update receives from the last timed step, as float32 / float64 numpy arrays: the window's
+    poses and disparities after the bundle adjustments, the per-edge state the next update starts from (edge list, targets,
+    confidence weights, raw mask, dynamic-flow term; the hidden state as a fixed seeded sample of NET_SAMPLE values in logical
+    [edge, channel, row, column] order), the per-frame damping, and the two frame-distance results."""
+    def f(t):
+        a = t.detach().cpu().numpy()
+        return a if a.dtype.name in ("float32", "float64") else a.astype("float32")
+    n = graph.nkf
+    d, dk = last
+    net = graph.net.reshape(-1)
+    pick = torch.randint(net.numel(), (min(NET_SAMPLE, net.numel()),), generator=torch.Generator().manual_seed(0))
+    return {"poses": f(video.poses[:n]), "disps": f(video.disps[:n]), "damping": f(graph.damping[:n]),
+            "edges": f(torch.stack([graph.ii, graph.jj])), "target": f(graph.target_cam), "weight": f(graph.weight),
+            "raw_mask": f(graph.raw_mask), "delta_dy": f(graph.delta_dy), "net_sample": f(net[pick.to(net.device)]),
+            "distance_matrix": f(d), "distance_pair": f(dk)}
+
+
+def write_outputs(dirname, arrays):
+    """arrays -> dirname/<name>.npy (refuses more than DUMP_LIMIT_BYTES in all)"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("outputs of %d bytes exceed the %d-byte dump limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in arrays.items():
+        if a.dtype.name not in ("float32", "float64"):
+            raise ValueError("%s: dtype %s, the dump holds float32 / float64 only" % (name, a.dtype))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def self_launch(n):
     """run this script as n ranks of one node and return the launcher's exit status"""
     import socket
@@ -1053,10 +1096,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=120, help="timed keyframe updates (default 120: a timed region of ~0.5 s; the driver passes its own)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes, ~1 min); "
-                    "the committed profile of the same kernel source is reported instead")
-    ap.add_argument("--no-extras", action="store_true", help="skip the S-A workload and the edge-sharded leg")
+    ap.add_argument("--full", action="store_true", help="after the headline steps, also measure everything else the line can carry: "
+                    "four more blocks of K steps, per-stage and per-kernel (roofline) figures, the S-A / S-1 / training / full-sequence / "
+                    "edge-sharded legs, the CPU baseline, the synthetic ATE and the CPU-chain drift.  Without it a run sets up, primes, "
+                    "warms up, times the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (step_outputs) as "
+                    "DIR/<name>.npy, float32 / float64, at most 64 MB; inputs are seeded, so two builds can be compared file by file")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline, the synthetic ATE and the drift leg")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not measure roofline.traffic in this run (two rocprofv3 --pmc "
+                    "child passes, ~1 min); the committed profile of the same kernel source is reported instead")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the S-A, S-1, training, sequence and edge-sharded legs")
     ap.add_argument("--sequence-reps", type=int, default=3, help="passes per order of the full-sequence leg (the median pass is reported)")
     ap.add_argument("--sequence-order", choices=("both", "plain", "pipelined"), default="both",
                     help="profiling runs: trace one order of the tracker only (with --sequence-reps 1: calibration pass + one pass)")
@@ -1113,14 +1162,11 @@ def main():
     for _ in range(args.warmup):
         keyframe_update(video, graph, snap)
     updates_per_step = 6
-    elapsed, host_issue, in_step_lookup = timed_steps(video, graph, snap, args.steps, world)
-    # the same K steps four more times (each bracketed like the first): `value` is the FIRST block, as the contract defines it;
-    # the five block times say whether a 3 % move between two runs is the code or the box
-    block_ms = [elapsed / args.steps * 1e3]
-    if not args.steps_only:
-        for _ in range(4):
-            el_b, _, _ = timed_steps(video, graph, snap, args.steps, world, probe_stage=None)
-            block_ms.append(el_b / args.steps * 1e3)
+    # (the lookup's in-step event pairs feed only the --full roofline: a plain run times its steps without them)
+    probe = "lookup" if args.full or args.steps_only else None
+    elapsed, host_issue, in_step_lookup, last = timed_steps(video, graph, snap, args.steps, world, probe_stage=probe)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(video, graph, last))
 
     if args.steps_only:
         if rank == 0:
@@ -1129,6 +1175,35 @@ def main():
                               "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
                               "note": "bench.py --steps-only: the timed loop of the default run and nothing behind it"}))
         return
+    if rank == 0:
+        hi = sorted(host_issue)
+        out = {
+            "metric": "VO keyframe updates/sec (8-keyframe window, 512x384, 36 edges; 6 graph updates + edge rebuild per keyframe)",
+            "value": world * args.steps / elapsed, "unit": "keyframe updates/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f16 (volume, lookup, update operator) / f32 (BA assembly) / f64 (pose solve)",
+            "data": "synthetic",
+            "config": {"workload": "S-B: BASELINE.json configs[1] window (8 keyframes, 48x64 maps, E=36, itrs=2), synthetic",
+                       "edges": len(graph._ii_h), "graph_updates_per_step": updates_per_step, "parallelism": "independent window per GPU",
+                       "update_path": "pvo_graph_update: one native call per graph update, no MIOpen / hipBLASLt"},
+            "graph_updates_per_s": world * args.steps * updates_per_step / elapsed,
+            "host": {"issue_ms_per_step_median": 1e3 * hi[len(hi) // 2], "issue_ms_per_step_max": 1e3 * hi[-1],
+                     "priming_blocks_of_8_steps": blocks},
+        }
+    if not args.full:
+        if rank == 0:
+            emit(out)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # --full: the same K steps four more times (each bracketed like the first): `value` is the FIRST block, as the contract
+    # defines it; the five block times say whether a 3 % move between two runs is the code or the box
+    block_ms = [elapsed / args.steps * 1e3]
+    for _ in range(4):
+        el_b, _, _, _ = timed_steps(video, graph, snap, args.steps, world, probe_stage=None)
+        block_ms.append(el_b / args.steps * 1e3)
     # per-stage durations inside the step, from a few extra untimed steps (one probe at a time)
     stage_us = {}
     for stage in ("gates", "candidate", "ba", "update", "empty"):
@@ -1254,23 +1329,10 @@ def main():
             scat = scattered_ceiling(device, traffic, E * HW * 128 * 2, 1e3 * sum(in_step_lookup) / max(len(in_step_lookup), 1))
         except Exception as e:
             scat = {"error": repr(e)}
-        hi = sorted(host_issue)
-        out = {
-            "metric": "VO keyframe updates/sec (8-keyframe window, 512x384, 36 edges; 6 graph updates + edge rebuild per keyframe)",
-            "value": world * args.steps / elapsed, "unit": "keyframe updates/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f16 (volume, lookup, update operator) / f32 (BA assembly) / f64 (pose solve)",
-            "data": "synthetic",
-            "config": {"workload": "S-B: BASELINE.json configs[1] window (8 keyframes, 48x64 maps, E=36, itrs=2), synthetic",
-                       "edges": E, "graph_updates_per_step": updates_per_step, "parallelism": "independent window per GPU",
-                       "update_path": "pvo_graph_update: one native call per graph update, no MIOpen / hipBLASLt"},
-            "graph_updates_per_s": world * args.steps * updates_per_step / elapsed,
+        out.update({
             "step_ms_blocks": {"blocks_of_steps": args.steps, "ms_per_step": block_ms, "median": sorted(block_ms)[len(block_ms) // 2],
                                "min": min(block_ms), "max": max(block_ms), "spread_pct": 100.0 * (max(block_ms) - min(block_ms)) / min(block_ms),
                                "note": "five consecutive blocks of K steps, each barrier + synchronize bracketed; `value` is the first"},
-            "host": {"issue_ms_per_step_median": 1e3 * hi[len(hi) // 2], "issue_ms_per_step_max": 1e3 * hi[-1],
-                     "priming_blocks_of_8_steps": blocks},
             "roofline": dict(lookup_roofline(E, HW, in_step_lookup, traffic, stage_us.pop("empty", None)), isolated_cold_us=lookup_cold_us,
                              isolated_cold="Infinity Cache evicted by a 600 MB read before each of 20 launches",
                              warm_back_to_back_us=lookup_b2b_us, traffic_source=traffic_src, scattered_lines=scat),
@@ -1290,7 +1352,7 @@ def main():
                 "vendor_gemm": vendor_gemm,
                 "share_of_update_time": stage_us["gates"] / stage_us["update"] if stage_us["update"] else None},
             "stage_us_in_step": dict(stage_us, lookup=1e3 * sum(in_step_lookup) / max(len(in_step_lookup), 1)),
-        }
+        })
     # second workload and the edge-sharded mode: reported beside the headline, never part of `value`
     extra = {}
     if not args.no_extras:

@@ -3,10 +3,11 @@
 # dispatches AFTER MIOpen's find phase (its naive_conv_* candidates run only while solvers are
 # being searched during warm-up) so that per-kernel averages describe the timed steps.
 TAG=${1:-r01}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/pb
-rocprofv3 --kernel-trace --stats -f csv -d /tmp/pb -- python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline ${PROF_ARGS---steps-only} > /tmp/pb_bench.log 2>&1
+rocprofv3 --kernel-trace --stats -f csv -d /tmp/pb -- python $ROOT/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline ${PROF_ARGS---steps-only} > /tmp/pb_bench.log 2>&1
 mkdir -p $OUT
 cp /tmp/pb/*/*kernel_stats.csv $OUT/kernel_stats_full_run.csv
 grep "^{\"metric\"" /tmp/pb_bench.log | tail -1 > $OUT/bench_line.json
