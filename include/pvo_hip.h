@@ -72,7 +72,7 @@ const char* pvo_last_hip_error(void);
  * passed by pointer and have GROWN between versions (100 -> 101: pvo_graph_update_args.context_ahead / context_ready; 101 -> 102: no struct changed - new entry points
  * pvo_ba_pack / pvo_ba_finish_packed / pvo_ba_last_partition / pvo_proj_transform[_vjp], and pvo_ba_workspace_bytes returns more): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
-#define PVO_ABI_VERSION 103
+#define PVO_ABI_VERSION 104
 int pvo_version(void);
 size_t pvo_graph_update_args_size(void);
 
@@ -217,8 +217,8 @@ int pvo_gate_context(const float* glo_part, const float* wg_t, const float* g_bi
 int pvo_conv3x3_c128(const void* x, const void* w_taps, const float* bias, void* y,
                      int E, int H, int W, int Cout, int relu, int ystride, int yoff, int dtype, void* stream);
 /* the same for wide layers (implicit GEMM, 16x16 pixel tile x 128 outputs per workgroup): Cin % 32 == 0, Cout % 128 == 0.
- * The filter is read in MFMA-fragment order, [Cout/128][Cin/32 chunks][9 taps][2][2][2][64 lanes][8]: element
- * (cg, cc, t, wn, nt, ks, lane, j) = W[tap t][output cg*128 + wn*64 + nt*32 + (lane & 31)][input cc*32 + ks*16 + (lane >> 5)*8 + j]
+ * The filter is read in MFMA-fragment order, [Cout/128][Cin/32 chunks][9 taps][2][4][64 lanes][8]: element
+ * (cg, cc, t, wn, nt, lane, j) = W[tap t][output cg*128 + wn*64 + nt*16 + (lane & 15)][input cc*32 + (lane >> 4)*8 + j]
  * (one coalesced 1 KB load per fragment, no LDS staging of the filter). */
 int pvo_conv3x3(const void* x, const void* w_taps, const float* bias, void* y,
                 int E, int H, int W, int Cin, int Cout, int relu, int ystride, int yoff, int dtype, void* stream);

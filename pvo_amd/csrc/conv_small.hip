@@ -265,17 +265,20 @@ __global__ __launch_bounds__(256) void conv3x3_c128_kernel(const uint16_t* __res
 // pvo_conv3x3: y = act(conv3x3(x, w) + bias) for wide layers, x [E,H,W,Cin] -> y [E,H,W,Cout], Cin % 32 == 0,
 // Cout % 128 == 0 - the GRU gate / candidate convolutions (320 -> 256, 320 -> 128), the heads' first stage (128 -> 512),
 // corr_encoder[2], GraphAgg.conv1 and the static-input terms (MIOpen/CK ran these at 0.69-0.74 PFLOP/s).
-//   Implicit GEMM on v_mfma_f32_32x32x16: workgroup = 16x16 pixel tile (M = 256) x 128 output channels, 4 waves as 2 x 2,
-//   each wave 128 pixels (8 rows x 16 columns) x 64 channels = 8 accumulator tiles.  K runs over (32-channel chunk, tap).
-//   A: the chunk's 18x18 halo sits in LDS (80-byte position stride, 20-position row pitch), double buffered, staged once
-//      per chunk and shared by its 9 taps; one barrier per CHUNK.  An M-tile is 8 rows x 4 columns of pixels: with the
-//      80-byte stride and the 20-position pitch every ds_read_b128 lane group hits 64 distinct banks (the 2-row x 16-column
-//      M-tile used before had SQ_LDS_BANK_CONFLICT = 47 % of SQ_LDS_IDX_ACTIVE, profiles/r02_kernel_counters.json).
-//   B: the filter arrives in MFMA-FRAGMENT order, [Cout/128][chunk][tap][wave column wn][nt][ks][lane][8] (the host
+//   Implicit GEMM on v_mfma_f32_16x16x32: workgroup = 16x16 pixel tile (M = 256) x 128 output channels, 4 waves as 2 x 2,
+//   each wave 128 pixels (8 rows x 16 columns) x 64 channels = 8 x 4 accumulator tiles of 16 x 16.  K runs over (32-channel
+//   chunk, tap): one K step is one MFMA per accumulator tile.
+//   A: the chunk's 18x18 halo sits in LDS (96-byte position stride, 18-position row pitch), double buffered, staged once
+//      per chunk and shared by its 9 taps; one barrier per CHUNK.  An M-tile is 8 rows x 2 columns of pixels: with the
+//      96-byte stride and the 18-position pitch every ds_read_b128 lane group hits 64 distinct banks.
+//   B: the filter arrives in MFMA-FRAGMENT order, [Cout/128][chunk][tap][wave column wn][nt][lane][8] (the host
 //      arranges it once), and is streamed global -> registers: one coalesced 1 KB load per fragment, requested two
 //      steps ahead into one of three rotating register sets.  No LDS, ds_write, ds_read or barrier for the filter, and
 //      with the 9 taps unrolled every fragment address is base + immediate.  (The first version staged tap-major filter
 //      slabs through LDS with a barrier per (chunk, tap): ~160 non-MFMA instructions per 16-MFMA step, 10-14 % slower.)
+//   Why 16x16x32 and not 32x32x16 (the kernel's shape up to ABI 103): the two take the same cycles per FLOP, but under this
+//   kernel the chip runs power-capped, and on random operands it holds a higher clock under the 16x16x32 loop
+//   (tools/mfma_shape_probe.hip).
 // ---------------------------------------------------------------------------
 typedef float cs_v16f __attribute__((ext_vector_type(16)));
 template <typename T> __device__ __forceinline__ cs_v16f cs_mfma32(cs_u32x4 a, cs_u32x4 b, cs_v16f c);
@@ -316,12 +319,13 @@ struct BigEpi {
 
 constexpr int kBT = 16;                                   // 16 x 16 pixel tile
 constexpr int kBHalo = (kBT + 2) * (kBT + 2);             // 324 halo positions
-constexpr int kBPitch = 20;                               // LDS positions per halo row (18 used)
-constexpr int kBStride = 80;                              // bytes per position of a 32-channel chunk
-constexpr int kBA = 420 * kBStride;                       // 18 x 20 positions + 60 dummy ones (every thread parks 6 pieces, no exec branches)
+constexpr int kBPitch = kBT + 2;                          // LDS positions per halo row
+constexpr int kBStride = 96;                              // bytes per position of a 32-channel chunk (64 used)
+constexpr int kBA = 384 * kBStride;                       // 18 x 18 positions + 60 dummy ones (every thread parks 6 pieces, no exec branches)
+constexpr int kBLds = 2 * kBA;                            // two halo buffers (73728 B) >= the fp32 epilogue slab (128 px x 132 floats = 67584 B)
 
-// pixel (row, column) inside a wave's 8 x 16 block of accumulator row `m` (0..31) of M-tile `mt`
-__device__ __forceinline__ int big_pix(int mt, int m) { return (m >> 2) * 16 + 4 * mt + (m & 3); }
+// pixel (row * 16 + column) inside a wave's 8 x 16 block of accumulator row `q` (0..15) of M-tile `mt` (8 rows x 2 columns)
+__device__ __forceinline__ int big_pix(int mt, int q) { return (q >> 1) * 16 + 2 * mt + (q & 1); }
 
 // tools/conv_timeline.py builds this file with -DPVO_CONV_PROBE: every workgroup then records its shader-clock stamps
 // (start, main loop entered, main loop left, end) and the compute unit it ran on; the shipped library has none of it.
@@ -355,27 +359,27 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, kg = lane >> 5;
+  const int li = lane & 15, kg = lane >> 4;
   const int nC = Cin >> 5;                                // 32-channel chunks
   const uint16_t* xe = x + static_cast<size_t>(e) * H * W * Cin;
 
   // global -> register -> LDS staging of the halo chunk needed next (6 x 16 B per thread)
   cs_u32x4 ra[3];                                         // (three pieces at a time: registers)
   int apix[6];                                            // pixel index of this thread's halo pieces inside the image, -1 = zero
-  int lpos[6];                                            // their LDS byte offsets
 #pragma unroll
   for (int it = 0; it < 6; ++it) {
     const int id = tid + 256 * it;                        // piece = (position, 16-byte quarter of the 64-byte chunk row)
     const int pos = id >> 2;
     apix[it] = -1;
-    lpos[it] = (360 + (pos - kBHalo)) * kBStride + (id & 3) * 16;      // dummy slot
     if (pos < kBHalo) {
       const int hr = pos / (kBT + 2), hc = pos % (kBT + 2);
       const int hy = y0 - 1 + hr, hx = x0 - 1 + hc;
       if (hy >= 0 && hy < H && hx >= 0 && hx < W) apix[it] = hy * W + hx;
-      lpos[it] = (hr * kBPitch + hc) * kBStride + (id & 3) * 16;
     }
   }
+  // LDS byte offset of piece `it`: position pos (row pitch = halo width, so the dummy positions 324.. follow the halo)
+  const int lpos0 = (tid >> 2) * kBStride + (tid & 3) * 16;
+  auto lpos = [&](int it) { return lpos0 + it * 64 * kBStride; };
   const size_t img = static_cast<size_t>(e) * H * W;
   // (loads and stores are unconditional - out-of-image pieces read a clamped address and are zeroed by a select when they
   // are parked: exec-masked branches around VMEM operations make the compiler wait vmcnt(0) at every join)
@@ -400,35 +404,37 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
     for (int k = 0; k < 3; ++k) {
       cs_u32x4 v = ra[k];
       if (apix[3 * half + k] < 0) v = cs_u32x4{0u, 0u, 0u, 0u};
-      *reinterpret_cast<cs_u32x4*>(As + buf * kBA + lpos[3 * half + k]) = v;
+      *reinterpret_cast<cs_u32x4*>(As + buf * kBA + lpos(3 * half + k)) = v;
     }
   };
 
   // accumulators start from the per-(edge, channel) gate context of the fused GRU epilogues (column li of a tile = one
   // channel): one addition per value less in the epilogue, which is instruction-bound
-  float ginit[2] = {0.0f, 0.0f};
+  float ginit[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (!HEADS && ep.mode != 0) {
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-      ginit[nt] = ep.g[static_cast<size_t>(e) * 384 + (ep.mode == 1 ? cg * 128 : 256) + wn * 64 + nt * 32 + li];
+    for (int nt = 0; nt < 4; ++nt)
+      ginit[nt] = ep.g[static_cast<size_t>(e) * 384 + (ep.mode == 1 ? cg * 128 : 256) + wn * 64 + nt * 16 + li];
   }
-  cs_v16f acc[4][2];
+  cs_v4f acc[8][4];
 #pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
+  for (int mt = 0; mt < 8; ++mt)
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
+    for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][nt][r] = ginit[nt];
+      for (int r = 0; r < 4; ++r) acc[mt][nt][r] = ginit[nt];
 
   const int S = nC * 9;                                   // steps; S >= 9
   {
-    // this wave's fragments of step s: wf + ((cg * S + s) * 8 + wn * 4 + nt * 2 + ks) * 512 + lane * 8   (16-bit elements)
-    const uint16_t* wf = wt + (static_cast<size_t>(cg) * S * 8 + wn * 4) * 512 + lane * 8;
-    cs_u32x4 bset[3][4];                                    // three rotating sets of {nt0 ks0, nt0 ks1, nt1 ks0, nt1 ks1}
+    // this wave's fragments of step s: wf + ((cg * S + s) * 8 + wn * 4 + nt) * 512 + lane * 8   (16-bit elements)
+    // (workgroup-uniform base + a 32-bit lane offset: one address register instead of a 64-bit pointer per lane)
+    const uint16_t* wf = wt + (static_cast<size_t>(cg) * S * 8 + wn * 4) * 512;
+    const int lane_off = lane * 8;
+    cs_u32x4 bset[3][4];                                    // three rotating sets of the four N-tiles' fragments
     auto fetch_bf = [&](cs_u32x4 (&r)[4], int s) {          // (clamped, unconditional: exact s_waitcnt vmcnt counts)
       const uint16_t* p = wf + static_cast<size_t>(min(s, S - 1)) * 4096;
 #pragma unroll
-      for (int f = 0; f < 4; ++f) r[f] = *reinterpret_cast<const cs_u32x4*>(p + f * 512);
+      for (int f = 0; f < 4; ++f) r[f] = *reinterpret_cast<const cs_u32x4*>(p + lane_off + f * 512);
     };
     select_a(0);
     {
@@ -443,26 +449,55 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
       for (int k = 0; k < 6; ++k) {
         cs_u32x4 v = r6[k];
         if (apix[k] < 0) v = cs_u32x4{0u, 0u, 0u, 0u};
-        *reinterpret_cast<cs_u32x4*>(As + lpos[k]) = v;
+        *reinterpret_cast<cs_u32x4*>(As + lpos(k)) = v;
       }
     }
     __syncthreads();
     CONV_PROBE(1);
-    // this lane's A rows: M-tile mt of wave-row wm = tile rows 8 wm + (li >> 2), columns 4 mt + (li & 3)
-    const unsigned char* Abase = As + ((8 * wm + (li >> 2)) * kBPitch + (li & 3)) * kBStride + kg * 16;
-    // Software pipeline at half-step (k = 16) granularity, pinned with sched_barrier: the four A fragments of the NEXT
-    // half-step are requested before the eight MFMAs of the current one, so a fragment has 8 MFMAs (256 matrix-pipe
-    // cycles) to arrive.  Left to itself the compiler sinks each ds_read next to its first use ("read, wait lgkmcnt(0),
-    // two MFMAs" - the LDS latency exposed eight times per step; SQ_WAIT_ANY was 40 % of the wave cycles).
-    // The main loop exists twice: NMT = 4 for a full tile, NMT = 2 for a tile of which only the first two 4-pixel column groups
-    // (M-tiles) lie inside the image - the right-most tile column of a map whose width is not a multiple of 16 (101 = 6 x 16 + 5: a
-    // seventh of all tiles at the reference driver's 30 x 101).  Such a workgroup issues half the MFMAs; its waves wait at the
-    // same barriers, and the matrix cores they leave idle go to the second workgroup of the CU.
-    auto main_loop = [&](auto nmt_c) {
-    constexpr int NMT = decltype(nmt_c)::value;
-    auto read_half = [&](cs_u32x4 (&a)[4], const unsigned char* Ac, int toff, int ks) {
+    // this lane's A rows: M-tile mt of wave-row wm = tile rows 8 wm + (li >> 1), column 2 mt + (li & 1); k-group kg
+    const unsigned char* Abase = As + ((8 * wm + (li >> 1)) * kBPitch + (li & 1)) * kBStride + kg * 16;
+    // Software pipeline at half-step granularity (a half-step = M-tiles 4h .. 4h+3 of one tap against the 4 N-tiles: 16 MFMAs),
+    // pinned with sched_barrier: the four A fragments of the NEXT half-step are requested before the MFMAs of the current
+    // one, so a fragment has 16 MFMAs (256 matrix-pipe cycles) to arrive.  Left to itself the compiler sinks each ds_read
+    // next to its first use ("read, wait lgkmcnt(0), MFMAs" - the LDS latency exposed at every fragment).
+    // The main loop exists twice: NH = 2 half-steps per tap for a full tile, NH = 1 for a tile of which only the first eight
+    // columns (M-tiles 0..3) lie inside the image - the right-most tile column of a map whose width is not a multiple of 16
+    // (101 = 6 x 16 + 5: a seventh of all tiles at the reference driver's 30 x 101).  Such a workgroup issues half the
+    // MFMAs; its waves wait at the same barriers, and the matrix cores they leave idle go to the second workgroup of the CU.
+    auto main_loop = [&](auto nh_c) {
+    constexpr int NH = decltype(nh_c)::value;
+    auto read_half = [&](cs_u32x4 (&a)[4], const unsigned char* Ac, int toff, int h) {
 #pragma unroll
-      for (int mt = 0; mt < NMT; ++mt) a[mt] = *reinterpret_cast<const cs_u32x4*>(Ac + toff + mt * 4 * kBStride + ks * 32);
+      for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const cs_u32x4*>(Ac + toff + (4 * h + i) * 2 * kBStride);
+    };
+    // half 0 runs M-tile-major (its A fragments die one by one while the next half's arrive), the last half of a step
+    // N-tile-major (the step's filter fragments die one by one while the next step's A fragments arrive)
+    auto mfma_half = [&](const cs_u32x4 (&a)[4], const cs_u32x4 (&bf)[4], int h, bool n_major) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int i = n_major ? (j & 3) : (j >> 2), nt = n_major ? (j >> 2) : (j & 3);
+        acc[4 * h + i][nt] = cs_mfma<T>(a[i], bf[nt], acc[4 * h + i][nt]);
+      }
+    };
+    // issue order inside a half-step: one LDS read / global load / LDS write behind every one or two MFMAs (an MFMA holds
+    // the pipe for 16 cycles; clumped between the groups of sixteen the single-issue instructions are exposed)
+    auto pin_reads_b = [&]() {                              // 4 LDS reads + the 4 filter loads
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x20, 1, 0);
+      }
+    };
+    auto pin_reads = [&]() {                                // 4 LDS reads
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
+    };
+    auto pin_staging = [&](int t) {                         // the halo's 3 LDS writes (+ the next 3 halo loads at t = 3)
+      if (t == 3 || t == 7) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
+      }
+      if (t == 3) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x20, 3, 0); }
     };
 #pragma unroll 1
     for (int cc = 0; cc < nC; ++cc) {
@@ -474,47 +509,42 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
-        const int toff = ((t / 3) * kBPitch + (t % 3)) * kBStride;         // compile-time: ds_read immediates
+        const int toff = ((t / 3) * kBPitch + (t % 3)) * kBStride;                     // compile-time: ds_read immediates
+        const int toff1 = (((t + 1) / 3) * kBPitch + ((t + 1) % 3)) * kBStride;
         fetch_bf(bset[(t + 2) % 3], cc * 9 + t + 2);
-        read_half(a1, Ac, toff, 1);
         const cs_u32x4 (&bf)[4] = bset[t % 3];
+        if (NH == 2) {
+          read_half(a1, Ac, toff, 1);
+          mfma_half(a0, bf, 0, false);
+          pin_reads_b();
+          __builtin_amdgcn_sched_barrier(0);
+          if (t < 8) read_half(a0, Ac, toff1, 0);
+          if (t == 3) { store_a((cc + 1) & 1, 0); fetch_a(1); }   // (the other halo buffer was last read before the previous barrier)
+          if (t == 7) store_a((cc + 1) & 1, 1);
+          mfma_half(a1, bf, 1, true);
+          if (t < 8) pin_reads();
+          pin_staging(t);
+        } else {
+          cs_u32x4 (&cur)[4] = (t & 1) ? a1 : a0;
+          cs_u32x4 (&nxt)[4] = (t & 1) ? a0 : a1;
+          if (t < 8) read_half(nxt, Ac, toff1, 0);
+          if (t == 3) { store_a((cc + 1) & 1, 0); fetch_a(1); }
+          if (t == 7) store_a((cc + 1) & 1, 1);
+          mfma_half(cur, bf, 0, true);
+          if (t < 8) pin_reads_b();
+          else {
 #pragma unroll
-        for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = cs_mfma32<T>(a0[mt], bf[nt * 2], acc[mt][nt]);
-        // issue order inside the half-step: one LDS read / one global load behind each MFMA (an in-order wave hides
-        // about five single-issue instructions in the 32 cycles an MFMA holds the pipe; clumped between the groups of
-        // eight they are exposed)
-#pragma unroll
-        for (int i = 0; i < NMT; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-#pragma unroll
-        for (int i = 0; i < NMT; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x20, 4 / NMT, 0); }
-        __builtin_amdgcn_sched_barrier(0);
-        if (t < 8) read_half(a0, Ac, ((((t + 1) / 3) * kBPitch) + ((t + 1) % 3)) * kBStride, 0);
-        if (t == 3) { store_a((cc + 1) & 1, 0); fetch_a(1); }   // (the other halo buffer was last read before the previous barrier)
-        if (t == 7) store_a((cc + 1) & 1, 1);
-#pragma unroll
-        for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = cs_mfma32<T>(a1[mt], bf[nt * 2 + 1], acc[mt][nt]);
-        if (NMT == 4) {
-          if (t < 8) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
+            for (int i = 0; i < 4; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x20, 1, 0); }
           }
-          if (t == 3 || t == 7) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
-          }
-          if (t == 3) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x20, 3, 0); }
+          pin_staging(t);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
       __syncthreads();
     }
     };
-    if (x0 + 8 >= W) main_loop(std::integral_constant<int, 2>{});
-    else main_loop(std::integral_constant<int, 4>{});
+    if (x0 + 8 >= W) main_loop(std::integral_constant<int, 1>{});
+    else main_loop(std::integral_constant<int, 2>{});
   }
   CONV_PROBE(2);
 
@@ -583,14 +613,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
       request(half, 0);
       if (wm == half) {
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
+        for (int mt = 0; mt < 8; ++mt)
 #pragma unroll
-          for (int nt = 0; nt < 2; ++nt)
+          for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int m = big_pix(mt, (r & 3) + 8 * (r >> 2) + 4 * kg);
-              slab[m * 132 + wn * 64 + nt * 32 + li] = acc[mt][nt][r];
-            }
+            for (int r = 0; r < 4; ++r) slab[big_pix(mt, 4 * kg + r) * 132 + wn * 64 + nt * 16 + li] = acc[mt][nt][r];
       }
       __syncthreads();
       if (half == 0) CONV_PROBE(6);
@@ -604,10 +631,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
     return;
   }
   // epilogue: two halves of 128 pixels through an LDS slab [128 px][128 ch] (272-byte pixel stride) -> whole-row stores
-  // D layout of a 32x32 tile: column li = channel, rows (r & 3) + 8 * (r >> 2) + 4 * kg = pixel inside the M-tile
-  float bb[2];
+  // D layout of a 16x16 tile: column li = channel, rows 4 * kg + r = pixel inside the M-tile
+  float bb[4];
 #pragma unroll
-  for (int nt = 0; nt < 2; ++nt) bb[nt] = bias ? bias[cg * 128 + wn * 64 + nt * 32 + li] : 0.0f;
+  for (int nt = 0; nt < 4; ++nt) bb[nt] = bias ? bias[cg * 128 + wn * 64 + nt * 16 + li] : 0.0f;
   unsigned char* w2s = bs + 36 * 1024;                      // mode 3: this head's second-stage fragments (8 KB) above the slab
   if (HEADS) {
     const cs_u32x4* src = reinterpret_cast<const cs_u32x4*>(ep.w2f + static_cast<size_t>(cg) * 4096) + tid;
@@ -619,15 +646,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
   for (int half = 0; half < 2; ++half) {
     if (wm == half) {
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
+      for (int mt = 0; mt < 8; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
+        for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int m = big_pix(mt, (r & 3) + 8 * (r >> 2) + 4 * kg);         // pixel inside this wave-row's 8 x 16 block
+          for (int r = 0; r < 4; ++r) {
+            const int m = big_pix(mt, 4 * kg + r);                                 // pixel inside this wave-row's 8 x 16 block
             float v = acc[mt][nt][r] + bb[nt];
             if (relu) v = fmaxf(v, 0.0f);
-            *reinterpret_cast<uint16_t*>(bs + m * 272 + (wn * 64 + nt * 32 + li) * 2) = static_cast<uint16_t>(cs_bits<T>(v));
+            *reinterpret_cast<uint16_t*>(bs + m * 272 + (wn * 64 + nt * 16 + li) * 2) = static_cast<uint16_t>(cs_bits<T>(v));
           }
     }
     __syncthreads();
@@ -636,16 +663,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
       cs_v16f zz;
 #pragma unroll
       for (int r = 0; r < 16; ++r) zz[r] = 0.0f;
-      const unsigned char* arow = bs + (32 * wave + li) * 272 + kg * 16;
+      const int l32 = lane & 31, k32 = lane >> 5;            // (32x32 operand / D layout: column l32, k-group / row group k32)
+      const unsigned char* arow = bs + (32 * wave + l32) * 272 + k32 * 16;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks)
         zz = cs_mfma32<T>(*reinterpret_cast<const cs_u32x4*>(arow + ks * 32), *reinterpret_cast<const cs_u32x4*>(w2s + (ks * 64 + lane) * 16), zz);
-      if (li < 18) {
+      if (l32 < 18) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int m = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * kg;
+          const int m = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * k32;
           const int gy = y0 + 8 * half + (m >> 4), gx = x0 + (m & 15);
-          if (gy < H && gx < W) ep.z[(((static_cast<size_t>(e) * H + gy) * W + gx) * (Cout >> 7) + cg) * 18 + li] = zz[r];
+          if (gy < H && gx < W) ep.z[(((static_cast<size_t>(e) * H + gy) * W + gx) * (Cout >> 7) + cg) * 18 + l32] = zz[r];
         }
       }
     } else {
@@ -916,7 +944,7 @@ static int launch_big(const void* x, const void* w_taps, const float* bias, void
   if (static_cast<long long>(H) * W * Cin > 0x7fffffffLL) return PVO_EUNSUPPORTED;
   hipStream_t st = pvo_stream(stream);
   const int ntx = (W + kBT - 1) / kBT;
-  const size_t lds = 67584;      // two halo buffers (67200 B) / the fp32 epilogue slab (128 px x 132 floats = 67584 B)
+  const size_t lds = kBLds;
   dim3 grid(ntx * (Cout / 128), (H + kBT - 1) / kBT, E);
   const uint16_t* xp = static_cast<const uint16_t*>(x);
   const uint16_t* wp = static_cast<const uint16_t*>(w_taps);

@@ -774,13 +774,13 @@ def conv3x3_c128_weights(weight, dtype):
 
 def conv3x3_weights(weight, dtype):
     """[Cout,Cin,3,3] conv filter (Cin % 32 == 0, Cout % 128 == 0) -> the layout pvo_conv3x3 / pvo_gru_conv_* read, as a
-    [9,Cout,Cin]-shaped tensor holding MFMA-fragment order [Cout/128][Cin/32][9][2][2][2][64][8] (include/pvo_hip.h)"""
+    [9,Cout,Cin]-shaped tensor holding MFMA-fragment order [Cout/128][Cin/32][9][2][4][64][8] (include/pvo_hip.h)"""
     co, ci, kh, kw = weight.shape
     if (kh, kw) != (3, 3) or ci % 32 or co % 128:
         raise PvoHipError("conv3x3: filter must be [Cout,Cin,3,3] with Cin % 32 == 0 and Cout % 128 == 0")
     taps = weight.detach().permute(2, 3, 0, 1).reshape(9, co, ci).to(dtype)
-    # (t, cg, wn, nt, li, cc, ks, kg, j) -> (cg, cc, t, wn, nt, ks, kg, li, j)
-    f = taps.reshape(9, co // 128, 2, 2, 32, ci // 32, 2, 2, 8).permute(1, 5, 0, 2, 3, 6, 7, 4, 8)
+    # (t, cg, wn, nt, li, cc, kg, j) -> (cg, cc, t, wn, nt, kg, li, j): lane = kg * 16 + li of v_mfma_f32_16x16x32
+    f = taps.reshape(9, co // 128, 2, 4, 16, ci // 32, 4, 8).permute(1, 5, 0, 2, 3, 6, 4, 7)
     return f.contiguous().view(9, co, ci)
 
 
