@@ -43,6 +43,8 @@
  *     radius-3 graph use 121 KB - and dense in global memory beyond that, which is slow: O(P band^2) dependent fp64 steps
  *     through L2)
  *   - panoptic segments per frame: `max_segments` of the caller (DepthVideo: 1024 dense labels)
+ *   - training bundle adjustment (pvo_ba_train[_vjp]): at most 16 free poses (the reduced system, at most 96 x 96, is factorised
+ *     in LDS by one workgroup per batch element), rig 1, fp32 / fp64
  */
 #ifndef PVO_HIP_H
 #define PVO_HIP_H
@@ -70,9 +72,11 @@ const char* pvo_strerror(int code);
 const char* pvo_last_hip_error(void);
 /* ABI version of the library that was loaded; PVO_ABI_VERSION is the one this header describes.  The argument structs below are
  * passed by pointer and have GROWN between versions (100 -> 101: pvo_graph_update_args.context_ahead / context_ready; 101 -> 102: no struct changed - new entry points
- * pvo_ba_pack / pvo_ba_finish_packed / pvo_ba_last_partition / pvo_proj_transform[_vjp], and pvo_ba_workspace_bytes returns more): a caller
+ * pvo_ba_pack / pvo_ba_finish_packed / pvo_ba_last_partition / pvo_proj_transform[_vjp], and pvo_ba_workspace_bytes returns more;
+ * 104 -> 105: no struct changed - new entry points pvo_ba_train_workspace_bytes / pvo_ba_train_vjp_scratch_bytes /
+ * pvo_ba_train / pvo_ba_train_vjp): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
-#define PVO_ABI_VERSION 104
+#define PVO_ABI_VERSION 105
 int pvo_version(void);
 size_t pvo_graph_update_args_size(void);
 
@@ -677,6 +681,37 @@ int pvo_ba_finish_conv1x1(float* poses, float* disps, void* sys,
                           void* workspace, size_t workspace_bytes,
                           const void* cx, const void* cw, const float* cbias, void* cy, long long crows, int cCout, int cdtype,
                           void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Differentiable bundle adjustment of the training path                      */
+/* ------------------------------------------------------------------------- */
+
+/* One Gauss-Newton step of pvo_amd.geom.ba.BA (VO_Module/droid_slam/geom/ba.py:31-106, geom/chol.py:5-73) and its vector-Jacobian
+ * product, for rig = 1, in fp32 (PVO_F32, the Cholesky included) or fp64 (PVO_F64).  Kernels: pvo_amd/csrc/ba_train.hip.
+ *   poses [B,P,7], disps [B,P,ht,wd] (inverse depth), intr [B,P,4], target / weight [B,N,ht,wd,2], eta [B,M,ht,wd]; ii / jj [N] int64
+ *   in [0, P); the plan: kx [M] the keyframes (torch.unique(ii)), kk [N] the keyframe of each edge, kptr [M+1] / kedge [N] the edges of
+ *   each keyframe in edge order (CSR), int32.  Poses < fixedp are held and blocks that touch them dropped; P - fixedp <= 16.
+ *   Weights 0.001 * valid * weight; depth diagonal C + eta + 1e-7; pose diagonal damped by ep = 0.1 + lm = 1e-4 times itself;
+ *   per batch element a system that is not SPD gives dx = 0 and no gradient through the solve; then poses <- Exp(dx) * poses,
+ *   disps[kx] += dz, and on all frames values > 10 set to 0 and clamp(min = 0).
+ * pvo_ba_train writes poses_out, disps_out, dx_out [B, 6 (P - fixedp)] (may be NULL) and the state the backward reads into
+ * `workspace` (pvo_ba_train_workspace_bytes): one workspace per call, kept until its pvo_ba_train_vjp.  No floating-point
+ * atomics and no host synchronisation: two identical calls give bit-identical outputs.
+ * pvo_ba_train_vjp: from the gradients of poses_out / disps_out (ambient coordinates), writes those of target, weight, eta,
+ * poses (ambient) and disps; the inputs and `workspace` must be the forward's (read only), `scratch`
+ * (pvo_ba_train_vjp_scratch_bytes) is needed only while the call's kernels run.  The pose and depth gradients through the
+ * Jacobians are summed with fp atomics (pvo_proj_transform_vjp), so they are not bitwise reproducible. */
+size_t pvo_ba_train_workspace_bytes(int B, int P, int N, int M, int HW, int dtype);
+size_t pvo_ba_train_vjp_scratch_bytes(int B, int P, int N, int M, int HW, int dtype);
+int pvo_ba_train(const void* poses, const void* disps, const void* intr, const void* target, const void* weight, const void* eta,
+                 const int64_t* ii, const int64_t* jj, const int* kx, const int* kk, const int* kptr, const int* kedge,
+                 int B, int P, int N, int M, int ht, int wd, int fixedp, void* poses_out, void* disps_out, void* dx_out,
+                 void* workspace, size_t workspace_bytes, int dtype, void* stream);
+int pvo_ba_train_vjp(const void* poses, const void* disps, const void* intr, const void* target, const void* weight,
+                     const int64_t* ii, const int64_t* jj, const int* kx, const int* kk, const int* kptr, const int* kedge,
+                     int B, int P, int N, int M, int ht, int wd, int fixedp, const void* g_poses_out, const void* g_disps_out,
+                     void* g_target, void* g_weight, void* g_eta, void* g_poses, void* g_disps,
+                     const void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

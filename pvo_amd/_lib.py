@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpvo_hip.so")
 
 PVO_F32, PVO_F16, PVO_BF16, PVO_F64 = 0, 1, 2, 3
-PVO_ABI_VERSION = 104          # include/pvo_hip.h
+PVO_ABI_VERSION = 105          # include/pvo_hip.h
 
 _c = ctypes
 _vp, _i, _f, _sz = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t
@@ -95,6 +95,12 @@ SIGNATURES = {
                                   _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
     "pvo_ba_finish_conv1x1": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _f,
                                    _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _c.c_longlong, _i, _i, _vp]),
+    "pvo_ba_train_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "pvo_ba_train_vjp_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "pvo_ba_train": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
+                          _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "pvo_ba_train_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _i, _vp]),
 }
 
 

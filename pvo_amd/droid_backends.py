@@ -1414,6 +1414,66 @@ def proj_transform_vjp(poses, depths, intrinsics, ii, jj, g_x1, g_Ji, g_Jj, g_Jz
     return gp, gd
 
 
+def _check_ba_plan(plan, N, P):
+    """the plan of ba_train (ba_native.make_plan): four contiguous int32 vectors kx [M], kk [N], kptr [M+1], kedge [N], 1 <= M <= P.
+    Returns M.  (Whether it was built from this ii is not checked: that would read the device.)"""
+    if len(plan) != 4 or any(not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() for t in plan):
+        raise PvoHipError("ba_train: the plan is four contiguous int32 vectors (kx, kk, kptr, kedge), as ba_native.make_plan builds it")
+    kx, kk, kptr, kedge = plan
+    M = kx.shape[0]
+    if not 1 <= M <= P or kk.shape[0] != N or kedge.shape[0] != N or kptr.shape[0] != M + 1:
+        raise PvoHipError("ba_train: plan of %d keyframes with kk [%d], kptr [%d], kedge [%d] does not fit %d edges over %d frames"
+                          % (M, kk.shape[0], kptr.shape[0], kedge.shape[0], N, P))
+    return M
+
+
+def ba_train(poses, disps, intrinsics, target, weight, eta, ii, jj, plan, fixedp):
+    """one Gauss-Newton step of geom.ba.BA (pvo_ba_train): poses [B,P,7], disps [B,P,H,W], intrinsics [B,P,4], target / weight
+    [B,N,H,W,2], eta [B,M,H,W] of one dtype (fp32 / fp64) on one device; ii / jj int64 [N] and the plan (kx, kk, kptr, kedge: int32)
+    there too -> (poses [B,P,7], disps [B,P,H,W], dx [B,6(P-fixedp)], workspace).  The workspace holds the state pvo_ba_train_vjp reads:
+    keep it with the call until its backward"""
+    dev = _dev(poses, disps, intrinsics, target, weight, eta, ii, jj, *plan)
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (target, "target"), (weight, "weight"), (eta, "eta"),
+                 (ii, "ii"), (jj, "jj")):
+        _contig(t, n)
+    _long(ii, "ii"); _long(jj, "jj")
+    B, P, ht, wd = disps.shape
+    N, M = ii.shape[0], _check_ba_plan(plan, ii.shape[0], P)
+    if (poses.shape != (B, P, 7) or intrinsics.shape != (B, P, 4) or target.shape != (B, N, ht, wd, 2) or weight.shape != target.shape
+            or eta.numel() != B * M * ht * wd or len({t.dtype for t in (poses, disps, intrinsics, target, weight, eta)}) != 1):
+        raise PvoHipError("ba_train: poses [B,P,7], disps [B,P,H,W], intrinsics [B,P,4], target / weight [B,N,H,W,2], eta [B,M,H,W] of one dtype")
+    dt = _DT[disps.dtype]
+    lib = _lib.load()
+    ws = torch.empty(lib.pvo_ba_train_workspace_bytes(B, P, N, M, ht * wd, dt), dtype=torch.uint8, device=dev)
+    pout, dout = torch.empty_like(poses), torch.empty_like(disps)
+    dx = torch.empty(B, 6 * (P - fixedp), dtype=disps.dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.pvo_ba_train(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(target), _ptr(weight), _ptr(eta), _ptr(ii), _ptr(jj),
+                               *[_ptr(t) for t in plan], B, P, N, M, ht, wd, fixedp, _ptr(pout), _ptr(dout), _ptr(dx),
+                               _ptr(ws), ws.numel(), dt, _stream(dev)), "ba_train")
+    return pout, dout, dx, ws
+
+
+def ba_train_vjp(poses, disps, intrinsics, target, weight, ii, jj, plan, fixedp, ws, g_poses, g_disps):
+    """gradients of ba_train's poses / disps (the forward's inputs and workspace) -> (grad target, weight, eta [B,M,H,W], poses, disps);
+    the backward's scratch is allocated here and released with the call"""
+    dev = _dev(poses, disps, intrinsics, target, weight, ii, jj, ws, g_poses, g_disps, *plan)
+    g_poses, g_disps = g_poses.contiguous(), g_disps.contiguous()
+    B, P, ht, wd = disps.shape
+    N, M = ii.shape[0], _check_ba_plan(plan, ii.shape[0], P)
+    lib = _lib.load()
+    scratch = torch.empty(lib.pvo_ba_train_vjp_scratch_bytes(B, P, N, M, ht * wd, _DT[disps.dtype]), dtype=torch.uint8, device=dev)
+    gt, gw = torch.empty_like(target), torch.empty_like(weight)
+    ge = torch.empty(B, M, ht, wd, dtype=disps.dtype, device=dev)
+    gp, gd = torch.empty_like(poses), torch.empty_like(disps)
+    with torch.cuda.device(dev):
+        check(lib.pvo_ba_train_vjp(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(target), _ptr(weight), _ptr(ii), _ptr(jj),
+                                   *[_ptr(t) for t in plan], B, P, N, M, ht, wd, fixedp, _ptr(g_poses), _ptr(g_disps),
+                                   _ptr(gt), _ptr(gw), _ptr(ge), _ptr(gp), _ptr(gd), _ptr(ws), ws.numel(), _ptr(scratch), scratch.numel(),
+                                   _DT[disps.dtype], _stream(dev)), "ba_train_vjp")
+    return gt, gw, ge, gp, gd
+
+
 STAGES = {"lookup": 0, "gates": 1, "candidate": 2, "ba": 3, "update": 4, "empty": 5}
 
 

@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .geom import projective_ops as pops
+from .geom import ba_native
 from .geom.ba import BA
 from .geom.graph_utils import graph_to_edge_list, keyframe_indicies
 from .modules.corr import CorrBlock
@@ -68,15 +69,19 @@ class DroidNet(nn.Module):
         return fmaps, torch.tanh(net), torch.relu(inp)
 
     def forward(self, Gs, images, disps, intrinsics, graph=None, num_steps=12, fixedp=2, ret_flow=False,
-                downsample=False, segments=None, corr_dtype=None):
+                downsample=False, segments=None, corr_dtype=None, native_ba=False):
         """Unrolled estimation over a frame graph (droid_net.py:342-439).  Returns per-step lists
         (Gs, upsampled disps, residuals[, full flows], masks[, affine-brightness params]).
         corr_dtype (e.g. torch.bfloat16, BASELINE.json configs[4]): the all-pairs volume, its pyramid and the lookup
         (forward and backward, HIP) run in that type - half the volume's HBM footprint and traffic; features, update
-        operator and the BA stay in the module's dtype (the BA in fp32)."""
+        operator and the BA stay in the module's dtype (the BA in fp32).
+        native_ba: the two BA steps per update go through pvo_amd.geom.ba_native.BA (libpvo_hip, forward and backward) instead of
+        the PyTorch BA; its plan is built once here, the graph being the same for every update.  Device tensors only (ValueError
+        otherwise)."""
         ii, jj, _ = graph_to_edge_list(graph)
         ii = ii.to(device=images.device, dtype=torch.long)
         jj = jj.to(device=images.device, dtype=torch.long)
+        ba_plan = ba_native.make_plan(ii) if native_ba else None
         dy_thresh, mask_num = 0.5, 2
 
         fmaps, net, inp = self.extract_features(images)
@@ -114,7 +119,10 @@ class DroidNet(nn.Module):
             weight = torch.sigmoid(weight + (1 - bin_mask) * 10)
 
             for _ in range(2):                                    # droid_net.py:408-410 (fixedp=2 hard-wired)
-                Gs, disps = BA(target_cam, weight, eta, Gs, disps, intrinsics, ii, jj, fixedp=2)
+                if native_ba:
+                    Gs, disps = ba_native.BA(target_cam, weight, eta, Gs, disps, intrinsics, ii, jj, fixedp=2, plan=ba_plan)
+                else:
+                    Gs, disps = BA(target_cam, weight, eta, Gs, disps, intrinsics, ii, jj, fixedp=2)
 
             coords1, valid = pops.projective_transform(Gs, disps, intrinsics, ii, jj)
             residual = (target_cam - coords1) * valid

@@ -72,6 +72,8 @@ def parse_args(argv=None):
     # this build
     p.add_argument("--crop_size", type=int, nargs=2, default=[200, 400])
     p.add_argument("--corr_dtype", default="bfloat16", choices=["float32", "bfloat16", "float16"])
+    p.add_argument("--native_ba", type=str2bool, default=False,
+                   help="the unrolled BA steps in libpvo_hip (pvo_amd.geom.ba_native) instead of the PyTorch BA; GPU only")
     p.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu: gloo, for the plumbing tests")
     p.add_argument("--port", type=int, default=12356)
     p.add_argument("--dist_backend", default="auto", choices=["auto", "nccl", "gloo"],
@@ -214,7 +216,8 @@ def train(rank, args, report=None):
                     r = rng.random()
                     want_flow = args.flow_label or args.ph_loss
                     out = ddp(Gs, images, disp0, intrinsics / 8.0, graph, num_steps=args.iters, fixedp=2, ret_flow=want_flow,
-                              downsample=args.downsample, **({"segments": segments} if want_flow else {}), corr_dtype=corr_dtype)
+                              downsample=args.downsample, **({"segments": segments} if want_flow else {}), corr_dtype=corr_dtype,
+                              native_ba=args.native_ba)
                     loss, metrics = objective(args, L, out, (images, Ps, disps, intrinsics, gt_masks, gt_vals), graph, ssim, total)
                     loss.backward()
                     Gs = out[0][-1].detach()
