@@ -38,10 +38,10 @@
  * Limits (PVO_EUNSUPPORTED beyond them)
  *   - edges / images per call: 65535 (they index a grid's y or z dimension)
  *   - one image: H * W * channels < 2^31 elements
- *   - bundle adjustment: at most 2048 free poses; the reduced pose system is factorised by ONE workgroup in envelope
- *     form (dense in LDS up to 21 free poses, compact envelope blocks in LDS while they fit ~140 KB - 63 poses of a
- *     radius-3 graph use 121 KB - and dense in global memory beyond that, which is slow: O(P band^2) dependent fp64 steps
- *     through L2)
+ *   - bundle adjustment: at most 2048 free poses; the reduced pose system is factorised dense on the matrix cores up to 29
+ *     free poses, dense in 48 x 48 blocks beyond that when a dense image has more than 8 edges per pose, and otherwise by
+ *     one or two workgroups in envelope form (compact envelope blocks in LDS while they fit ~140 KB - 63 poses of a radius-3
+ *     graph use 121 KB - and dense in global memory beyond that, which is slow: O(P band^2) dependent fp64 steps through L2)
  *   - panoptic segments per frame: `max_segments` of the caller (DepthVideo: 1024 dense labels)
  *   - training bundle adjustment (pvo_ba_train[_vjp]): at most 16 free poses (the reduced system, at most 96 x 96, is factorised
  *     in LDS by one workgroup per batch element), rig 1, fp32 / fp64
@@ -86,7 +86,7 @@ size_t pvo_graph_update_args_size(void);
  * process-wide, not thread-safe against running calls.  A product caller never needs it: every knob defaults to 0 = "the shipped
  * choice".  Returns PVO_EINVAL for an unknown knob.  (Reference counterpart: none - droid.cpp has no such switches.) */
 enum {
-  PVO_KNOB_BA_SOLVER = 0,         /* 0 shipped choice by size | 1 blocked | 2 one wave | 3 pipelined | 4 partitioned (two workgroups) | 5 dense on the fp64 matrix cores (<= 29 poses) | 6 dense in 48 x 48 blocks over many workgroups (beyond the LDS path) */
+  PVO_KNOB_BA_SOLVER = 0,         /* 0 shipped choice by size | 1 blocked | 2 one wave | 3 pipelined: the envelope solve as one chain, any size | 4 the envelope solve, partitioned where it can be, any size | 5 dense on the fp64 matrix cores up to 29 poses, the envelope solve beyond | 6 dense in 48 x 48 blocks over many workgroups for every dense image (a packed message: the shipped choice) */
   PVO_KNOB_HEADS_GATHER_FLAT = 1, /* 1: pvo_heads_gather without its LDS-tiled form */
   PVO_KNOB_NO_RIDERS = 2,         /* 1: pvo_graph_update computes the upsampling mask and the next gate context as launches of their own */
   PVO_KNOB_POST_SEPARATE = 3,     /* 1: pvo_graph_update runs pvo_graph_post as a launch of its own instead of as the epilogue of the heads' gather */
@@ -609,7 +609,7 @@ int pvo_ba(float* poses, float* disps, const float* intrinsics,
 int pvo_ba_plan(const int64_t* ii, const int64_t* jj, int E, int nframes, int HW,
                 int K_eta, int t0, int t1, void* workspace, size_t workspace_bytes,
                 void* stream);
-/* The pose solve beyond 21 free poses (the global bundle adjustment; the reference: Eigen's sparse LLT on the host,
+/* The envelope pose solve beyond 29 free poses (the global bundle adjustment; the reference: Eigen's sparse LLT on the host,
  * droid_kernels.cu:1160-1198) is PARTITIONED when the system is block-banded: two workgroups eliminate the pose chain from
  * both ends at once, the separator - the poses that couple the two parts - last (ba.hip, ba_solve_twin_kernel).  Same
  * result on every rank of an edge-sharded run (same integer system, same partition); against the one-chain solve it agrees

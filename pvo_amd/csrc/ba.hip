@@ -21,8 +21,9 @@
 //            poses form M; (M Q) M^T and M (Q w) are accumulated by fp32 MFMA
 //            (v_mfma_f32_16x16x4_f32, exact fp32 FMA chains, K = pixels) and atomically
 //            SUBTRACTED from the system.
-//   solve    one workgroup: damping, fp64 Cholesky (LDS when (6P)^2 fits, global
-//            otherwise), forward/back substitution, dx, pose retraction.
+//   solve    damping, fp64 Cholesky, forward/back substitution, dx, pose retraction, in the
+//            form solve_form picks by size: dense on the matrix cores (windows), envelope
+//            (chains), dense in 48 x 48 blocks (densely connected global graphs).
 //   backsub  grid (pixel chunk, depth frame): dz = Q (w - sum_r E_r^T dx), disps += dz.
 //
 // `sys` = [(6P)^2 row-major A-S | 6P rhs] in fp64 is also the message an edge-sharded
@@ -61,8 +62,6 @@ constexpr int kPPT = 2;                 // pixels per thread in assemble (1: 432
 constexpr int kChunkA = 256 * kPPT;     // pixels per assemble workgroup
 constexpr int kMaxSep = 12;                                      // separator poses of the partitioned solve (beyond: not partitioned)
 constexpr int kXchgDoubles = 2 + 36 * kMaxSep * kMaxSep + 12 * kMaxSep;
-constexpr int kLdsCholMax = 126;        // (6P) up to which the fp64 system lives DENSE in LDS (126*127*8 + 21*27*8 + 208 = 132.7 KB of the 143 KB the
-                                        // solve kernel's static tables leave); beyond, the compact envelope form
 
 
 // tools/ba_kernel_timeline.py builds this file with -DPVO_BA_PROBE=3: every workgroup of the assembly / Schur / back-substitution
@@ -86,7 +85,7 @@ struct Plan {            // int region of the workspace
   int* eptr;             // [F+1] CSR over depth index -> edges (ascending edge id)
   int* eidx;             // [E]
   int* meta;             // [8]   0:K 1:status(non-SPD) 2:eta mismatch 3:row table overflow 4:non-finite / out-of-range system entry
-  int* env;              // [P]   numeric envelope of a system too large for the dense LDS path (ba_env_kernel; INT_MAX between solves)
+  int* env;              // [P]   numeric envelope of a system for the envelope solve (ba_env_kernel; INT_MAX between solves)
 };
 
 struct Ws {
@@ -1185,21 +1184,20 @@ __device__ __forceinline__ bool chol6(const double D[21], double L[21], double r
 // frame both observe): at 63 free poses and temporal radius 3 the envelope holds 12 % of the matrix.  (The reference
 // uses a sparse LLT for the same reason, droid_kernels.cu:1178-1184.)
 // The matrix behind an accessor A(i, c): (n+1) x n, row n = rhs.  Two storages:
-//   DenseMat  row-major, in LDS (up to 22 free poses) or in global memory (anything, slow: every access an L2 round trip);
+//   DenseMat  row-major in global memory: an envelope too large for LDS (slow: every access an L2 round trip);
 //   EnvMat    only the blocks inside the envelope, block row b = blocks first[b] .. b of 36 doubles each at rowbase[b], + the
 //             rhs - what lets a 63-pose system of a radius-3 graph (envelope 12 % of the matrix: 121 KB) live in LDS.
 struct MatRow {            // one row of either storage: element c at base[c + k * (c / 6)]
   double* base; int k;
   __device__ __forceinline__ double& operator()(int c) const { return base[c + k * (c / 6)]; }
 };
-template <typename Index>      // int for the LDS copy (32-bit address arithmetic), long long for a matrix in global memory
 struct DenseMat {
-  double* p; Index n;
+  double* p; long long n;
   __device__ __forceinline__ MatRow row(int i) const { return MatRow{p + i * n, 0}; }
-  __device__ __forceinline__ Index rowstep() const { return n; }      // distance between the same column of rows i and i + 1
+  __device__ __forceinline__ long long rowstep() const { return n; }  // distance between the same column of rows i and i + 1
   __device__ __forceinline__ int blockstep() const { return 6; }       // ... between the same entry of blocks (ib, cb) and (ib, cb + 1)
   // six contiguous (16-byte aligned) entries: row r of 6 x 6 block (ib, cb); the rhs entries of block cb
-  __device__ __forceinline__ double* brow(int ib, int r, int cb) const { return p + static_cast<Index>(6 * ib + r) * n + 6 * cb; }
+  __device__ __forceinline__ double* brow(int ib, int r, int cb) const { return p + static_cast<long long>(6 * ib + r) * n + 6 * cb; }
   __device__ __forceinline__ double* yrow(int cb) const { return p + n * n + 6 * cb; }
 };
 struct EnvMat {
@@ -1860,8 +1858,8 @@ __device__ __forceinline__ void chol_solve_pipe(Mat A, double* Ld, int n, int* f
 }
 
 
-// ---- systems beyond the dense LDS path (more than 22 free poses: the global bundle adjustment) --------------------------
-// Two multi-workgroup kernels prepare the one-workgroup solve (inside it, reading 1.1 MB of fixed point through a single CU
+// ---- the ENVELOPE form (systems beyond the dense matrix-core solve: the global bundle adjustment) ------------------------
+// Two multi-workgroup kernels prepare the envelope solve (inside it, reading 1.1 MB of fixed point through a single CU
 // was 429 k of its 1479 k cycles at 63 poses - tools/ba_solve_timeline.py):
 //   ba_env_kernel      numeric envelope: env[b] = first block column with a non-zero in block row b (atomicMin; the table is
 //                      INT_MAX between solves).  Numeric, not structural: in an edge-sharded BA the system is the all-reduced
@@ -2145,144 +2143,22 @@ __device__ __forceinline__ void ride(unsigned char* smem, const Riders r, int b)
   if (b < r.xblocks) glt::gate_context_256(reinterpret_cast<float*>(smem), r.xpart, r.xwt, r.xbias, r.xg, r.xchunks, b);
 }
 
-// (experiment hook, tools/variant.py: -DPVO_SOLVE_ATTR='__attribute__((amdgpu_waves_per_eu(3,4)))' caps the registers of the fused
-// solve + riders kernel for three workgroups per CU - measured within noise of the default)
-#ifndef PVO_SOLVE_ATTR
-#define PVO_SOLVE_ATTR
-#endif
-__global__ __launch_bounds__(256) PVO_SOLVE_ATTR void ba_solve_kernel(
-    long long* __restrict__ sys, double* __restrict__ chol_global, float* __restrict__ poses,
-    float* __restrict__ dx_ws, float* __restrict__ dx_out, int* __restrict__ meta, int* __restrict__ status_out,
-    int P, int t0, float lm, float ep, int use_lds, int* __restrict__ env, long long lds_budget, int solver, Riders riders) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [16 B flags | fp64 matrix + rhs | ...]
-  if (blockIdx.x > 0) {                                                  // rider workgroups (launched only with riders)
-    ride(smem, riders, blockIdx.x - 1);
-    return;
-  }
-  int& fail = *reinterpret_cast<int*>(smem);
-  const int n = 6 * P;
-  __shared__ int first[kMaxEnvBlocks];                                           // envelope: first non-zero block column per block row
-  __shared__ int reach[kMaxEnvBlocks];                                           // ... and last block row that reaches a block column
-  __shared__ unsigned short act_rows[2][kMaxActiveRows];                         // lists of a step's active block rows (wave / pipe solvers)
-  __shared__ PipeCtl pipe_ctl;
-  __shared__ int blocks_s;
-  BA_PROBE(0);
-  if (threadIdx.x == 0) {
-    fail = 0;
-    pipe_ctl.panel = -1; pipe_ctl.done[0] = pipe_ctl.done[1] = pipe_ctl.done[2] = -1; pipe_ctl.abort = 0; pipe_ctl.total = 0;
-  }
-  double* xrow = nullptr;                                                        // where the solution ends up
-  if (!use_lds) {
-    // prepared by ba_env_kernel + ba_prepare_kernel
-    int* rowbase = nullptr;
-    {
-      // the offset table sits behind the doubles of the compact layout; its position depends on the block count, which
-      // thread 0 computes into a scratch copy first
-      int* tmp = reinterpret_cast<int*>(smem + 16);
-      env_layout(env, P, first, tmp, &blocks_s);
-    }
-    const int blocks = blocks_s;
-    const bool compact = env_lds_bytes(blocks, n, P) <= lds_budget;
-    if (compact) {
-      double* blk = reinterpret_cast<double*>(smem + 16);
-      double* rhs = blk + blocks;
-      double* Ld = rhs + n;
-      rowbase = reinterpret_cast<int*>(Ld + 27 * P + 24);
-      // (the offsets computed into the scratch copy move to their final place behind the doubles; the scratch is about to be
-      // overwritten by the matrix, so they travel through registers)
-      int rb_keep[kMaxEnvBlocks / 256];
-#pragma unroll
-      for (int q = 0; q < kMaxEnvBlocks / 256; ++q) {
-        const int b = q * 256 + threadIdx.x;
-        rb_keep[q] = b < P ? reinterpret_cast<const int*>(smem + 16)[b] : 0;
-      }
-      __syncthreads();
-      {
-        // 124 KB at 63 poses through one workgroup: sixteen 16-byte loads in flight per thread (one 8-byte load at a time
-        // was 57 k cycles of latency)
-        const int nd2 = (blocks + n) >> 1;                                          // blocks is a multiple of 36: pairs cover blocks + n but for an odd n
-        const double2* src = reinterpret_cast<const double2*>(chol_global);
-        double2* dst = reinterpret_cast<double2*>(blk);
-        // (sixteen per thread, every load unconditional on a clamped index: a guarded `v[u] = src[i]` sends the array to scratch)
-        for (int base = 0; base < nd2; base += 16 * blockDim.x) {
-          double2 v[16];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) { const int i = base + u * blockDim.x + threadIdx.x; v[u] = src[i < nd2 ? i : nd2 - 1]; }
-#pragma unroll
-          for (int u = 0; u < 16; ++u) { const int i = base + u * blockDim.x + threadIdx.x; if (i < nd2) dst[i] = v[u]; }
-        }
-        if (((blocks + n) & 1) && threadIdx.x == 0) blk[blocks + n - 1] = chol_global[blocks + n - 1];
-      }
-#pragma unroll
-      for (int q = 0; q < kMaxEnvBlocks / 256; ++q) {
-        const int b = q * 256 + threadIdx.x;
-        if (b < P) rowbase[b] = rb_keep[q] - 36 * first[b];                        // (as EnvMat::rowoff)
-      }
-      for (int b = threadIdx.x; b < P; b += blockDim.x) env[b] = 0x7fffffff;
-      __syncthreads();
-      envelope_reach(first, reach, P);
-      BA_PROBE(1);
-      if (solver == 2 && pipe_lists(first, reach, P, act_rows[0], &pipe_ctl))
-        chol_solve_pipe(EnvMat{blk, rhs, rowbase, n}, Ld, n, &fail, first, reach, act_rows[0], &pipe_ctl);
-      else if (solver >= 1) { if (threadIdx.x < 64) chol_solve_wave(EnvMat{blk, rhs, rowbase, n}, Ld, n, &fail, first, reach, act_rows[0]); }
-      else chol_solve_blocked(EnvMat{blk, rhs, rowbase, n}, Ld, n, &fail, first, reach);
-      xrow = rhs;
-    } else {
-      for (int b = threadIdx.x; b < P; b += blockDim.x) env[b] = 0x7fffffff;
-      double* A = chol_global;
-      __syncthreads();
-      envelope_reach(first, reach, P);
-      BA_PROBE(1);
-      chol_solve_blocked(DenseMat<long long>{A, n}, A + static_cast<long long>(n) * n + n, n, &fail, first, reach);
-      xrow = A + static_cast<long long>(n) * n;
-    }
-  } else {
-    double* A = reinterpret_cast<double*>(smem + 16);                              // (n+1) x n: system, then the rhs row
-    for (int b = threadIdx.x; b < P; b += blockDim.x) first[b] = b;
-    __syncthreads();
-    // (eight loads in flight per thread: one at a time, behind the zeroing store of the previous one, the 1806 entries of a
-    // 7-pose system cost eight serial L2 round trips - a third of this kernel)
-    const int N = n * n + n;
-    for (int base = 0; base < N; base += 8 * blockDim.x) {
-      long long raw[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int idx = base + u * blockDim.x + threadIdx.x;
-        raw[u] = idx < N ? sys[idx] : 0;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int idx = base + u * blockDim.x + threadIdx.x;
-        if (idx >= N) continue;
-        double v = static_cast<double>(raw[u]) * kInvFix;       // fixed point -> fp64
-        sys[idx] = 0LL;                                // ready for the next Gauss-Newton step's accumulation
-        if (idx < n * n) {
-          const int r = idx / n, c = idx - r * n;
-          if (r == c) v += static_cast<double>(ep) + static_cast<double>(lm) * v;   // droid_kernels.cu:1176
-          if (raw[u] != 0 && c < r) atomicMin(&first[r / 6], c / 6);
-        }
-        A[idx] = v;
-      }
-    }
-    __syncthreads();
-    envelope_reach(first, reach, P);
-    BA_PROBE(1);
-    if (solver == 2 && pipe_lists(first, reach, P, act_rows[0], &pipe_ctl))
-      chol_solve_pipe(DenseMat<int>{A, n}, A + n * n + n, n, &fail, first, reach, act_rows[0], &pipe_ctl);
-    else if (solver >= 1) { if (threadIdx.x < 64) chol_solve_wave(DenseMat<int>{A, n}, A + n * n + n, n, &fail, first, reach, act_rows[0]); }
-    else chol_solve_blocked(DenseMat<int>{A, n}, A + n * n + n, n, &fail, first, reach);
-    xrow = A + n * n;
-  }
-  __syncthreads();
-  BA_PROBE(4);
-  const int failed = fail | meta[4] | meta[2];      // (meta[2]: eta's row count != K - the whole step is a no-op, see ba_plan_kernel)
-  for (int idx = threadIdx.x; idx < n; idx += blockDim.x) {
-    const float v = failed ? 0.0f : static_cast<float>(xrow[idx]);    // zeros on failure (:1186-1189)
+// The end of every pose solve: dx out (the workspace copy the depth back-substitution reads, and the caller's), retraction of the
+// poses [g0, g1) this workgroup owns, then - with `status` - thread 0's status words.  x(idx) = entry idx of the solution; a failed
+// solve gives zeros (:1186-1189), and with nan_to_zero (the dense forms) so does a NaN entry.  `retracted` stamps a probe.  A
+// workgroup of 256 threads (every solve kernel's; the constant stride keeps the dense solves' register allocation as it was).
+template <class X, class Stamp>
+__device__ __forceinline__ void solve_epilogue(X x, int failed, bool nan_to_zero, int g0, int g1, int t0, float* __restrict__ poses,
+                                               float* __restrict__ dx_ws, float* __restrict__ dx_out, int* __restrict__ meta,
+                                               int* __restrict__ status_out, bool status, Stamp retracted) {
+  for (int idx = 6 * g0 + threadIdx.x; idx < 6 * g1; idx += 256) {
+    float v = 0.0f;
+    if (!failed) { const double xv = x(idx); v = (nan_to_zero && !(xv == xv)) ? 0.0f : static_cast<float>(xv); }
     dx_ws[idx] = v;
     if (dx_out) dx_out[idx] = v;
   }
   __syncthreads();
-  for (int p = threadIdx.x; p < P; p += blockDim.x) {               // pose_retr_kernel (:877-910)
+  for (int p = g0 + threadIdx.x; p < g1; p += 256) {                     // pose_retr_kernel (:877-910)
     float xi[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) xi[c] = dx_ws[6 * p + c];
@@ -2292,17 +2168,24 @@ __global__ __launch_bounds__(256) PVO_SOLVE_ATTR void ba_solve_kernel(
     ps[3] = T.q.x; ps[4] = T.q.y; ps[5] = T.q.z; ps[6] = T.q.w;
   }
   __syncthreads();
-  BA_PROBE(5);
-  if (threadIdx.x == 0) {
+  retracted();
+  if (threadIdx.x == 0 && status) {
     meta[4] = 0;
     if (failed) meta[1] = 1;
     if (status_out) { status_out[0] = meta[1]; status_out[1] = meta[0]; status_out[2] = meta[2]; status_out[3] = meta[3]; }
   }
 }
 
-// ---- the PARTITIONED pose solve (systems in the compact envelope form: the global bundle adjustment) ----------------------
-// The factorisation is a serial chain of P block columns (chol_solve_pipe: ~4 k cycles each), replicated on every rank of an
-// edge-sharded run.  A keyframe graph's pose system is block-banded away from its loop closures, and a banded chain can be
+// ---- the ENVELOPE pose solve: one chain, or PARTITIONED (systems beyond the dense matrix-core solve: the global BA) ---------
+// Reads what ba_prepare_kernel / ba_prepare_packed_kernel left: the damped fp64 system in the compact envelope layout (dense in
+// global memory when that does not fit the LDS budget) and in `xchg` the partition, m = s = 0 for none.
+// ONE CHAIN (m = 0): workgroup 0 factorises the whole system with the bit-identical form `chol` names - 0 chol_solve_blocked,
+// 1 chol_solve_wave, 2 chol_solve_pipe (the shipped one; the wave form when its active-row lists do not fit).  tools/
+// ba_solve_timeline.py: cycles of the whole solve at 7 free poses 44.8 k blocked / 48.0 k wave / 52.1 k pipe, 12: 87.5 k blocked /
+// 86.0 k pipe, 21: 168 k / 157 k, 63: 578 k blocked / 485 k wave / 364 k pipe - the pipeline wins once the envelope makes most of a
+// step's candidate rows inactive.
+// PARTITIONED: the factorisation is a serial chain of P block columns (chol_solve_pipe: ~4 k cycles each), replicated on every rank
+// of an edge-sharded run.  A keyframe graph's pose system is block-banded away from its loop closures, and a banded chain can be
 // eliminated from BOTH ends at once (a "twisted" factorisation, the two-way case of nested dissection): ba_prepare_kernel
 // picks poses m <= s (choose_partition) such that nothing below m couples with anything from s on; then
 //   workgroup 0   loads block rows [0, s), eliminates [0, m), waits for workgroup 1's terms on the separator [m, s), adds them,
@@ -2338,7 +2221,7 @@ __device__ __forceinline__ int twin_wait(int* flag) {                      // th
 __global__ __launch_bounds__(256) void ba_solve_twin_kernel(
     double* __restrict__ chol_global, float* __restrict__ poses, float* __restrict__ dx_ws, float* __restrict__ dx_out,
     int* __restrict__ meta, int* __restrict__ status_out, int P, int t0, int* __restrict__ env, long long lds_budget,
-    double* __restrict__ xchg, Riders riders) {
+    double* __restrict__ xchg, int chol, Riders riders) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (blockIdx.x > 1) {
     ride(smem, riders, blockIdx.x - 2);
@@ -2366,7 +2249,7 @@ __global__ __launch_bounds__(256) void ba_solve_twin_kernel(
   env_layout(env, P, first, tmp, &blocks_s);
   const int blocks = blocks_s;
   if (!split) {
-    // one chain (what ba_solve_kernel does with a compact system)
+    BA_PROBE(0);
     double* blk = reinterpret_cast<double*>(smem + 16);
     double* rhs = blk + blocks;
     double* Ld = rhs + n;
@@ -2374,6 +2257,8 @@ __global__ __launch_bounds__(256) void ba_solve_twin_kernel(
     const bool compact = env_lds_bytes(blocks, n, P) <= lds_budget;
     double* xrow;
     if (compact) {
+      // (the offsets env_layout computed into the scratch copy move to their place behind the doubles; the scratch is about to be
+      // overwritten by the matrix, so they travel through registers)
       int rb_keep[kMaxEnvBlocks / 256];
 #pragma unroll
       for (int q = 0; q < kMaxEnvBlocks / 256; ++q) {
@@ -2381,6 +2266,8 @@ __global__ __launch_bounds__(256) void ba_solve_twin_kernel(
         rb_keep[q] = b < P ? tmp[b] : 0;
       }
       __syncthreads();
+      // 124 KB at 63 poses through one workgroup: sixteen 16-byte loads in flight per thread, every one unconditional on a clamped
+      // index (one 8-byte load at a time was 57 k cycles of latency; a guarded `v[u] = src[i]` sends the array to scratch)
       const int nd2 = (blocks + n) >> 1;
       const double2* src = reinterpret_cast<const double2*>(chol_global);
       double2* dst = reinterpret_cast<double2*>(blk);
@@ -2395,46 +2282,29 @@ __global__ __launch_bounds__(256) void ba_solve_twin_kernel(
 #pragma unroll
       for (int q = 0; q < kMaxEnvBlocks / 256; ++q) {
         const int b = q * 256 + threadIdx.x;
-        if (b < P) rowbase[b] = rb_keep[q] - 36 * first[b];
+        if (b < P) rowbase[b] = rb_keep[q] - 36 * first[b];                  // (as EnvMat::rowoff)
       }
       for (int b = threadIdx.x; b < P; b += blockDim.x) env[b] = 0x7fffffff;
       __syncthreads();
       envelope_reach(first, reach, P);
-      if (pipe_lists(first, reach, P, act_rows[0], &pipe_ctl))
-        chol_solve_pipe(EnvMat{blk, rhs, rowbase, n}, Ld, n, &fail, first, reach, act_rows[0], &pipe_ctl);
-      else if (threadIdx.x < 64) chol_solve_wave(EnvMat{blk, rhs, rowbase, n}, Ld, n, &fail, first, reach, act_rows[0]);
+      BA_PROBE(1);
+      const EnvMat A{blk, rhs, rowbase, n};
+      if (chol == 2 && pipe_lists(first, reach, P, act_rows[0], &pipe_ctl)) chol_solve_pipe(A, Ld, n, &fail, first, reach, act_rows[0], &pipe_ctl);
+      else if (chol >= 1) { if (threadIdx.x < 64) chol_solve_wave(A, Ld, n, &fail, first, reach, act_rows[0]); }
+      else chol_solve_blocked(A, Ld, n, &fail, first, reach);
       xrow = rhs;
     } else {
       for (int b = threadIdx.x; b < P; b += blockDim.x) env[b] = 0x7fffffff;
       double* A = chol_global;
       __syncthreads();
       envelope_reach(first, reach, P);
-      chol_solve_blocked(DenseMat<long long>{A, n}, A + static_cast<long long>(n) * n + n, n, &fail, first, reach);
+      BA_PROBE(1);
+      chol_solve_blocked(DenseMat{A, n}, A + static_cast<long long>(n) * n + n, n, &fail, first, reach);
       xrow = A + static_cast<long long>(n) * n;
     }
     __syncthreads();
-    const int failed = fail | meta4;
-    for (int idx = threadIdx.x; idx < n; idx += blockDim.x) {
-      const float v = failed ? 0.0f : static_cast<float>(xrow[idx]);
-      dx_ws[idx] = v;
-      if (dx_out) dx_out[idx] = v;
-    }
-    __syncthreads();
-    for (int p = threadIdx.x; p < P; p += blockDim.x) {
-      float xi6[6];
-#pragma unroll
-      for (int c = 0; c < 6; ++c) xi6[c] = dx_ws[6 * p + c];
-      float* ps = poses + 7 * static_cast<long long>(t0 + p);
-      const Pose T = retract(xi6, load_pose(ps));
-      ps[0] = T.t.x; ps[1] = T.t.y; ps[2] = T.t.z;
-      ps[3] = T.q.x; ps[4] = T.q.y; ps[5] = T.q.z; ps[6] = T.q.w;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      meta[4] = 0;
-      if (failed) meta[1] = 1;
-      if (status_out) { status_out[0] = meta[1]; status_out[1] = meta[0]; status_out[2] = meta[2]; status_out[3] = meta[3]; }
-    }
+    BA_PROBE(4);
+    solve_epilogue([&](int i) { return xrow[i]; }, fail | meta4, false, 0, P, t0, poses, dx_ws, dx_out, meta, status_out, true, [] { BA_PROBE(5); });
     return;
   }
 
@@ -2605,31 +2475,10 @@ __global__ __launch_bounds__(256) void ba_solve_twin_kernel(
   }
   __syncthreads();
   TWIN_PROBE(10);
-  const int failed = fail | meta4;
-  const int g0 = bottom ? s : 0, g1 = bottom ? P : s;                      // the poses this part owns
-  for (int idx = 6 * g0 + threadIdx.x; idx < 6 * g1; idx += blockDim.x) {
-    const int g = idx / 6, c = idx - 6 * g;
-    const float v = failed ? 0.0f : static_cast<float>(rhs[bottom ? 6 * (P - 1 - g) + c : idx]);
-    dx_ws[idx] = v;
-    if (dx_out) dx_out[idx] = v;
-  }
-  __syncthreads();
-  for (int p = g0 + threadIdx.x; p < g1; p += blockDim.x) {               // pose_retr_kernel (:877-910)
-    float xi6[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) xi6[c] = dx_ws[6 * p + c];
-    float* ps = poses + 7 * static_cast<long long>(t0 + p);
-    const Pose T = retract(xi6, load_pose(ps));
-    ps[0] = T.t.x; ps[1] = T.t.y; ps[2] = T.t.z;
-    ps[3] = T.q.x; ps[4] = T.q.y; ps[5] = T.q.z; ps[6] = T.q.w;
-  }
-  __syncthreads();
-  TWIN_PROBE(11);
-  if (threadIdx.x == 0 && !bottom) {
-    meta[4] = 0;
-    if (failed) meta[1] = 1;
-    if (status_out) { status_out[0] = meta[1]; status_out[1] = meta[0]; status_out[2] = meta[2]; status_out[3] = meta[3]; }
-  }
+  // the poses this part owns; the bottom part's right-hand side is reversed
+  auto x = [&](int i) { const int g = i / 6; return rhs[bottom ? 6 * (P - 1 - g) + (i - 6 * g) : i]; };
+  solve_epilogue(x, fail | meta4, false, bottom ? s : 0, bottom ? P : s, t0, poses, dx_ws, dx_out, meta, status_out, !bottom,
+                 [] { TWIN_PROBE(11); });
 }
 
 // ---- the DENSE pose solve on the fp64 matrix cores (round 6): windows up to kDenseMaxPoses free poses, one launch ---------------
@@ -2968,30 +2817,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   __syncthreads();
   BA_PROBE(4);
-  const int failed = fail | meta[4] | meta[2];      // (meta[2]: eta's row count != K - the whole step is a no-op, see ba_plan_kernel)
-  for (int idx = tid; idx < n; idx += 256) {
-    double xv = xs[idx];
-    const float v = (failed || !(xv == xv)) ? 0.0f : static_cast<float>(xv);    // zeros on failure (:1186-1189)
-    dx_ws[idx] = v;
-    if (dx_out) dx_out[idx] = v;
-  }
-  __syncthreads();
-  for (int p = tid; p < P; p += 256) {               // pose_retr_kernel (:877-910)
-    float xi[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) xi[c] = dx_ws[6 * p + c];
-    float* ps = poses + 7 * static_cast<long long>(t0 + p);
-    const Pose Tn = retract(xi, load_pose(ps));
-    ps[0] = Tn.t.x; ps[1] = Tn.t.y; ps[2] = Tn.t.z;
-    ps[3] = Tn.q.x; ps[4] = Tn.q.y; ps[5] = Tn.q.z; ps[6] = Tn.q.w;
-  }
-  __syncthreads();
-  BA_PROBE(5);
-  if (tid == 0) {
-    meta[4] = 0;
-    if (failed) meta[1] = 1;
-    if (status_out) { status_out[0] = meta[1]; status_out[1] = meta[0]; status_out[2] = meta[2]; status_out[3] = meta[3]; }
-  }
+  // (meta[2]: eta's row count != K - the whole step is a no-op, see ba_plan_kernel)
+  solve_epilogue([&](int i) { return xs[i]; }, fail | meta[4] | meta[2], true, 0, P, t0, poses, dx_ws, dx_out, meta, status_out, true,
+                 [] { BA_PROBE(5); });
 }
 
 // ---- BLOCKED pose solve over MANY workgroups (round 6): big systems that are not narrow-banded - the backend's global graph ---------
@@ -3195,6 +3023,7 @@ __global__ __launch_bounds__(256) void dense_back_kernel(const double* __restric
   }
 }
 
+// (with P = 0 the whole of a solve: the status words, and the riders)
 __global__ __launch_bounds__(256) void dense_finish_kernel(const double* __restrict__ xvec, float* __restrict__ poses, float* __restrict__ dx_ws,
                                                            float* __restrict__ dx_out, int* __restrict__ meta, int* __restrict__ status_out,
                                                            int P, int t0, Riders riders) {
@@ -3203,30 +3032,7 @@ __global__ __launch_bounds__(256) void dense_finish_kernel(const double* __restr
     ride(smem, riders, blockIdx.x - 1);
     return;
   }
-  const int n = 6 * P, tid = threadIdx.x;
-  const int failed = meta[4] | meta[2];
-  for (int idx = tid; idx < n; idx += 256) {
-    const double xv = xvec[idx];
-    const float v = (failed || !(xv == xv)) ? 0.0f : static_cast<float>(xv);    // zeros on failure (:1186-1189)
-    dx_ws[idx] = v;
-    if (dx_out) dx_out[idx] = v;
-  }
-  __syncthreads();
-  for (int p = tid; p < P; p += 256) {               // pose_retr_kernel (:877-910)
-    float xi[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) xi[c] = dx_ws[6 * p + c];
-    float* ps = poses + 7 * static_cast<long long>(t0 + p);
-    const Pose Tn = retract(xi, load_pose(ps));
-    ps[0] = Tn.t.x; ps[1] = Tn.t.y; ps[2] = Tn.t.z;
-    ps[3] = Tn.q.x; ps[4] = Tn.q.y; ps[5] = Tn.q.z; ps[6] = Tn.q.w;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    meta[4] = 0;
-    if (failed) meta[1] = 1;
-    if (status_out) { status_out[0] = meta[1]; status_out[1] = meta[0]; status_out[2] = meta[2]; status_out[3] = meta[3]; }
-  }
+  solve_epilogue([&](int i) { return xvec[i]; }, meta[4] | meta[2], true, 0, P, t0, poses, dx_ws, dx_out, meta, status_out, true, [] {});
 }
 
 // ---------------------------------------------------------------------------
@@ -3235,7 +3041,7 @@ __global__ __launch_bounds__(256) void dense_finish_kernel(const double* __restr
 __device__ __forceinline__ void ba_backsub_body(
     const Plan& pl, const int64_t* __restrict__ jj, const float* __restrict__ Ei, const float* __restrict__ Eij,
     const float* __restrict__ Q, const float* __restrict__ w, const float* __restrict__ dx,
-    float* __restrict__ disps, float* __restrict__ dz_out, int dz_rows, int HW, int t0, int P, int flags,
+    float* __restrict__ disps, float* __restrict__ dz_out, int dz_rows, int HW, int t0, int P,
     int clamp_frames, float disp_min) {
   const int k = blockIdx.y;
   const int x = blockIdx.x * 256 + threadIdx.x;
@@ -3246,7 +3052,7 @@ __device__ __forceinline__ void ba_backsub_body(
   const bool live = k < pl.meta[0] && !pl.meta[2];        // (uniform; meta[2]: eta's row count != K - nothing is updated)
   const int e0 = live ? pl.eptr[k] : 0, deg = live ? pl.eptr[k + 1] - e0 : 0;
   const bool in_lds = deg <= 255;
-  const int lo = (flags & 1) ? 0 : 1;                     // EvT6x1_kernel returns early for pose index <= 0 (:1084): window pose 0 never reaches dz
+  constexpr int lo = 1;                                   // EvT6x1_kernel returns early for pose index <= 0 (:1084): window pose 0 never reaches dz
   if (live && in_lds && static_cast<int>(threadIdx.x) <= deg) {
     const int r = static_cast<int>(threadIdx.x) - 1;      // row -1 = the frame's own pose row (Ei), rows 0.. = its out-edges (Eij)
     int e = 0, p;
@@ -3300,9 +3106,9 @@ __device__ __forceinline__ void ba_backsub_body(
 __global__ __launch_bounds__(256) void ba_backsub_kernel(
     Plan pl, const int64_t* __restrict__ jj, const float* __restrict__ Ei, const float* __restrict__ Eij,
     const float* __restrict__ Q, const float* __restrict__ w, const float* __restrict__ dx,
-    float* __restrict__ disps, float* __restrict__ dz_out, int dz_rows, int HW, int t0, int P, int flags,
+    float* __restrict__ disps, float* __restrict__ dz_out, int dz_rows, int HW, int t0, int P,
     int clamp_frames, float disp_min) {
-  ba_backsub_body(pl, jj, Ei, Eij, Q, w, dx, disps, dz_out, dz_rows, HW, t0, P, flags, clamp_frames, disp_min);
+  ba_backsub_body(pl, jj, Ei, Eij, Q, w, dx, disps, dz_out, dz_rows, HW, t0, P, clamp_frames, disp_min);
 }
 
 int check_common(int E, int F, int ht, int wd, int t0, int t1) {
@@ -3325,6 +3131,14 @@ extern "C" int pvo_debug_ba_probe(void* buf) { return hipMemcpyToSymbol(HIP_SYMB
 extern "C" size_t pvo_ba_workspace_bytes(int E, int P, int nframes, int HW) {
   if (E < 0 || P < 0 || nframes < 0 || HW < 0) return 0;
   return carve(nullptr, E, P, nframes, HW).bytes + 256;
+}
+
+// a kernel's dynamic LDS beyond the default 48 KB: allowed once per process
+template <auto Kernel>
+static bool allow_lds(int bytes) {
+  static bool done = false;
+  if (!done) done = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+  return done;
 }
 
 static inline void* ws_base(void* workspace) {
@@ -3366,18 +3180,16 @@ extern "C" int pvo_ba_local(const float* poses, const float* disps, const float*
   // say so with bit 1 of motion_only and save the memset
   const size_t n6 = static_cast<size_t>(6) * P;
   const bool clean = (motion_only & 2) != 0;
-  const bool only_assemble = (motion_only & 4) != 0, only_schur = (motion_only & 8) != 0;   // (halves of this call: schedule experiments)
   motion_only &= 1;
-  if (!clean && !only_schur && hipMemsetAsync(sys, 0, sizeof(long long) * (n6 * n6 + n6), st) != hipSuccess) return PVO_ELAUNCH;
+  if (!clean && hipMemsetAsync(sys, 0, sizeof(long long) * (n6 * n6 + n6), st) != hipSuccess) return PVO_ELAUNCH;
   if (E == 0) return PVO_OK;
   const bool two_stage = !motion_only;      // the chunk sums go through the Schur kernel (there is none in a motion-only BA)
   const int chunksA = (HW + kChunkA - 1) / kChunkA;
-  if (!only_schur)
   hipLaunchKernelGGL(ba_assemble_kernel, dim3((HW + kChunkA - 1) / kChunkA, E), dim3(256), 0, st,
                      poses, disps, intrinsics, targets, weights, ii, jj, w.Eii, w.Eij, w.Cii, w.bz,
                      sys, w.plan.meta, HW, wd, t0, P, motion_only, two_stage ? w.part : nullptr);
   PVO_CHECK_LAUNCH();
-  if (!motion_only && !only_assemble) {
+  if (!motion_only) {
     const int Kmax = (nframes < P + E) ? nframes : (P + E);
     // pixels per workgroup: 256 while the grid fits the chip's resident slots (two 55 KB workgroups per CU); a global bundle
     // adjustment (64 keyframes x 12 chunks: 768 workgroups in two rounds, every one issuing ~1000 atomics into the same 63 x 63
@@ -3410,15 +3222,8 @@ extern "C" int pvo_ba_local(const float* poses, const float* disps, const float*
     constexpr int kSchurRowsLds = 110 * 1024;
     const size_t sdyn = dense_window ? kSchurRowsLds : 0;
     const int lds_floats = static_cast<int>(sdyn / sizeof(float));
-    if (dense_window) {
-      static bool schur_attr_set = false;
-      if (!schur_attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ba_schur_mfma_kernel<true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, kSchurRowsLds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(ba_schur_mfma_kernel<false, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, kSchurRowsLds) != hipSuccess)
-          return PVO_ELAUNCH;
-        schur_attr_set = true;
-      }
-    }
+    if (dense_window && !(allow_lds<ba_schur_mfma_kernel<true, 256>>(kSchurRowsLds) && allow_lds<ba_schur_mfma_kernel<false, 256>>(kSchurRowsLds)))
+      return PVO_ELAUNCH;
     if (depth_done) {
       hipLaunchKernelGGL(ba_depth_kernel, dim3((HW + 255) / 256, Kgrid), dim3(256), 0, st, w.plan, eta, K_eta, w.Eii, w.Cii, w.bz, w.Ei, w.Q, w.w, HW, t0, P);
       PVO_CHECK_LAUNCH();
@@ -3515,6 +3320,27 @@ extern "C" int pvo_ba_finish_packed(float* poses, float* disps, const void* msg,
                         clamp_frames, disp_min, dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, stream);
 }
 
+// The form that factorises the reduced pose system, from the free poses P, this call's edge count E, whether the system arrives as a
+// packed message (an edge-sharded step, whose ranks must all choose alike) and the debug knob PVO_KNOB_BA_SOLVER.  Shipped (knob 0):
+//   P = 0                     status words only (a packed message: nothing at all);
+//   P <= kDenseMaxPoses       dense on the fp64 matrix cores, ba_solve_dense_kernel: a window, one launch;
+//   E > 8 P, dense image      dense in 48 x 48 blocks over many workgroups: a global graph connected by proximity rather than a
+//                             keyframe chain, whose envelope fits no LDS and has no separator;
+//   otherwise                 the envelope solve, partitioned where the chain allows it (ba_solve_twin_kernel).
+// Knob 1-3: the envelope solve as one chain with the named factorisation (tests compare them bit for bit); 4: the envelope solve at
+// every size; 5: the shipped choice without the 48 x 48 form; 6: the 48 x 48 form for every dense image.
+enum SolveKind { kSolveStatus, kSolveDense, kSolveEnvelope, kSolveChain, kSolveBlocks };
+struct SolveForm { SolveKind kind; int chol; };      // chol: the one-chain factorisation, 0 blocked | 1 wave | 2 pipelined
+static SolveForm solve_form(int P, int E, bool packed, int knob) {
+  if (P == 0) return {kSolveStatus, 0};
+  if (knob >= 1 && knob <= 3) return {kSolveChain, knob - 1};
+  if (knob == 4) return {kSolveEnvelope, 2};
+  if (knob == 6 && !packed) return {kSolveBlocks, 0};
+  if (P <= kDenseMaxPoses) return {kSolveDense, 0};
+  if (knob != 5 && !packed && static_cast<long long>(E) > 8LL * P) return {kSolveBlocks, 0};
+  return {kSolveEnvelope, 2};
+}
+
 static int ba_finish_impl(float* poses, float* disps, void* sys_, const long long* msg, const int* first_s,
                           const int64_t* ii, const int64_t* jj,
                           int E, int nframes, int ht, int wd, int t0, int t1,
@@ -3562,136 +3388,63 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
   Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   hipStream_t st = pvo_stream(stream);
   const int n6 = 6 * P;
-  // Round 6: a window's system (up to kDenseMaxPoses free poses; dense image or packed message) is factorised DENSE in the registers of one
-  // workgroup on the fp64 matrix cores (ba_solve_dense_kernel) - one launch where the envelope forms took three beyond 21 poses.
-  // pvo_debug_config(PVO_KNOB_BA_SOLVER, 1..4) selects the older forms (tests compare them), 5 names this one.
-  const int solver_env = pvo_knob(PVO_KNOB_BA_SOLVER) - 1;      // (pvo_debug_config: -1 = the choice by size below)
-  if (P > 0 && P <= kDenseMaxPoses && (solver_env < 0 || solver_env == 4)) {
+  const SolveForm form = solve_form(P, E, msg != nullptr, pvo_knob(PVO_KNOB_BA_SOLVER));
+  if (msg && form.kind == kSolveStatus) return PVO_OK;
+  constexpr size_t kSolveLdsMax = 142000;      // dynamic LDS of a one-workgroup solve: the CU's 163840 B minus the envelope solve's 20528 B of static tables
+  if (form.kind == kSolveDense) {
     const size_t dl = dense_lds_bytes(n6);
-    const size_t lds_d = dl > rider_lds ? dl : rider_lds;
+    const size_t lds = dl > rider_lds ? dl : rider_lds;
     const int Td = dense_N(n6) / 16;                            // tiles per side: 4 slots per wave up to 5 (15 tiles), 14 up to 10 (55: 26 poses), 17 up to 11
-    static bool dense_attr_set = false;
-    if (!dense_attr_set) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_dense_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 142000) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_dense_kernel<14>), hipFuncAttributeMaxDynamicSharedMemorySize, 142000) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_dense_kernel<17>), hipFuncAttributeMaxDynamicSharedMemorySize, 142000) != hipSuccess)
-        return PVO_ELAUNCH;
-      dense_attr_set = true;
+    if (!allow_lds<ba_solve_dense_kernel<4>>(kSolveLdsMax) || !allow_lds<ba_solve_dense_kernel<14>>(kSolveLdsMax) ||
+        !allow_lds<ba_solve_dense_kernel<17>>(kSolveLdsMax))
+      return PVO_ELAUNCH;
+    const auto kernel = Td <= 5 ? ba_solve_dense_kernel<4> : (Td <= 10 ? ba_solve_dense_kernel<14> : ba_solve_dense_kernel<17>);
+    hipLaunchKernelGGL(kernel, dim3(1 + rider_blocks), dim3(256), lds, st, sys, msg, first_s, poses, w.dx, dx_out, w.plan.meta, status_out,
+                       P, t0, lm, ep, rider);
+  } else if (form.kind == kSolveEnvelope || form.kind == kSolveChain) {
+    int* part = form.kind == kSolveEnvelope ? reinterpret_cast<int*>(w.xchg) : nullptr;      // where ba_prepare_* writes the partition
+    if (msg) {
+      hipLaunchKernelGGL(ba_env_packed_kernel, dim3(P), dim3(256), 0, st, msg, first_s, w.plan.env, n6);
+      hipLaunchKernelGGL(ba_prepare_packed_kernel, dim3(P + 1), dim3(256), 0, st, msg, first_s, w.chol, w.plan.env, n6, lm, ep,
+                         static_cast<long long>(kSolveLdsMax), part);
+    } else {
+      hipLaunchKernelGGL(ba_env_kernel, dim3((n6 * n6 + 2047) / 2048), dim3(256), 0, st, sys, w.plan.env, n6);
+      hipLaunchKernelGGL(ba_prepare_kernel, dim3((n6 * n6 + n6 + 2047) / 2048), dim3(256), 0, st, sys, w.chol, w.plan.env, n6, lm, ep,
+                         static_cast<long long>(kSolveLdsMax), part);
     }
-    if (Td <= 5)
-      hipLaunchKernelGGL(ba_solve_dense_kernel<4>, dim3(1 + rider_blocks), dim3(256), lds_d, st, sys, msg, first_s, poses, w.dx, dx_out, w.plan.meta, status_out,
-                         P, t0, lm, ep, rider);
-    else if (Td <= 10)
-      hipLaunchKernelGGL(ba_solve_dense_kernel<14>, dim3(1 + rider_blocks), dim3(256), lds_d, st, sys, msg, first_s, poses, w.dx, dx_out, w.plan.meta, status_out,
-                         P, t0, lm, ep, rider);
-    else
-      hipLaunchKernelGGL(ba_solve_dense_kernel<17>, dim3(1 + rider_blocks), dim3(256), lds_d, st, sys, msg, first_s, poses, w.dx, dx_out, w.plan.meta, status_out,
-                         P, t0, lm, ep, rider);
     PVO_CHECK_LAUNCH();
-    if (!motion_only && E + P > 0) {
-      const int Kmax = (nframes < P + E) ? nframes : (P + E);
-      hipLaunchKernelGGL(ba_backsub_kernel, dim3((HW + 255) / 256, Kmax > clamp_frames ? Kmax : clamp_frames), dim3(256), 0, st,
-                         w.plan, jj, w.Ei, w.Eij, w.Q, w.w, w.dx, disps, dz_out, dz_rows, HW, t0, P, 0, clamp_frames, disp_min);
+    if (!part && hipMemsetAsync(w.xchg, 0, 16, st) != hipSuccess) return PVO_ELAUNCH;      // (one chain: no partition)
+    if (!allow_lds<ba_solve_twin_kernel>(kSolveLdsMax)) return PVO_ELAUNCH;
+    hipLaunchKernelGGL(ba_solve_twin_kernel, dim3(2 + rider_blocks), dim3(256), kSolveLdsMax > rider_lds ? kSolveLdsMax : rider_lds, st,
+                       w.chol, poses, w.dx, dx_out, w.plan.meta, status_out, P, t0, w.plan.env, static_cast<long long>(kSolveLdsMax), w.xchg,
+                       form.chol, rider);
+  } else {                                                      // 48 x 48 blocks, or no free pose: dense_finish_kernel ends the solve
+    if (form.kind == kSolveBlocks) {
+      // (no envelope pass: ba_prepare_kernel with no LDS budget writes the dense row-major image whatever `env` holds - INT_MAX between solves)
+      hipLaunchKernelGGL(ba_prepare_kernel, dim3((n6 * n6 + n6 + 2047) / 2048), dim3(256), 0, st, sys, w.chol, w.plan.env, n6, lm, ep,
+                         0LL /* no LDS budget: the dense row-major image */, static_cast<int*>(nullptr));
       PVO_CHECK_LAUNCH();
-    }
-    return PVO_OK;
-  }
-  const int use_lds = n6 <= kLdsCholMax && !msg;               // (a packed message is factorised from the compact image at every size)
-  constexpr size_t kSolveLdsMax = 142000;      // dynamic LDS of the solve: the CU's 163840 B minus its 20528 B of static tables (envelope, reach, active rows, scan buffers)
-  size_t lds = use_lds ? 16 + sizeof(double) * (static_cast<size_t>(n6) * n6 + n6 + 27 * P + 24) : kSolveLdsMax;
-  if (lds < rider_lds) lds = rider_lds;                                   // (the riders' tiles live in the dynamic segment)
-  if (lds > 48 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(kSolveLdsMax)) != hipSuccess) return PVO_ELAUNCH;
-      attr_set = true;
-    }
-  }
-  // Three bit-identical factorisations of a system that lives in LDS (chol_solve_blocked: four waves and barriers;
-  // chol_solve_wave: one wave, none; chol_solve_pipe: wave 0 on the critical chain, three worker waves behind it).  Measured
-  // with tools/ba_solve_timeline.py, cycles of the whole kernel: 7 free poses 44.8 k blocked / 48.0 k wave / 52.1 k pipe,
-  // 12: 87.5 k blocked / 86.0 k pipe, 21: 168 k / 157 k, 63: 578 k blocked / 485 k wave / 364 k pipe - the pipeline wins once the
-  // envelope makes most of a step's candidate rows inactive.  pvo_debug_config(PVO_KNOB_BA_SOLVER, ..) overrides (tests compare
-  // the three bit for bit).
-  // Beyond the dense LDS path a fourth form, the PARTITIONED solve (ba_solve_twin_kernel: two workgroups eliminate the pose
-  // chain from both ends, tools/ba_solve_timeline.py), is the default; its result equals the others' to fp64 rounding.
-  // Round 6: a big system that is not narrow-banded - more than 8 edges per pose, i.e. a global graph connected by proximity rather than
-  // a keyframe chain - is factorised DENSE in 48 x 48 blocks over many workgroups (dense_panel / dense_update / dense_back kernels).
-  // By P and this call's E: used for the dense image only (an edge-sharded step arrives as a packed message and keeps the forms every
-  // rank chooses alike).  pvo_debug_config(PVO_KNOB_BA_SOLVER, 6) forces it at any size beyond the LDS path.
-  if (!msg && !use_lds && P > 0 && ((solver_env < 0 && static_cast<long long>(E) > 8LL * P) || solver_env == 5)) {
-    // (no envelope pass: ba_prepare_kernel with no LDS budget writes the dense row-major image whatever `env` holds - INT_MAX between solves)
-    hipLaunchKernelGGL(ba_prepare_kernel, dim3((n6 * n6 + n6 + 2047) / 2048), dim3(256), 0, st, sys, w.chol, w.plan.env, n6, lm, ep,
-                       0LL /* no LDS budget: the dense row-major image */, static_cast<int*>(nullptr));
-    PVO_CHECK_LAUNCH();
-    if (hipMemsetAsync(w.xchg, 0, 16, st) != hipSuccess) return PVO_ELAUNCH;                                       // (pvo_ba_last_partition: no partition)
-    const int nkb = (n6 + kNB - 1) / kNB, nrb = (n6 + 1 + kNB - 1) / kNB;
-    for (int kb = 0; kb < nkb; ++kb) {
-      hipLaunchKernelGGL(dense_panel_kernel, dim3(nrb - kb), dim3(256), 0, st, w.chol, w.ldiag, n6, kb, w.plan.meta);
-      const int m = nrb - kb - 1;
-      if (m > 0) hipLaunchKernelGGL(dense_update_kernel, dim3(m * (m + 1) / 2), dim3(256), 0, st, w.chol, n6, kb, nrb);
-    }
-    PVO_CHECK_LAUNCH();
-    double* yrow = w.chol + static_cast<size_t>(n6) * n6;
-    for (int kb = nkb - 1; kb >= 0; --kb)
-      hipLaunchKernelGGL(dense_back_kernel, dim3(kb + 1), dim3(256), 0, st, w.chol, w.ldiag, yrow, w.xvec, n6, kb);
-    PVO_CHECK_LAUNCH();
-    if (rider_lds > 48 * 1024) {
-      static bool fin_attr_set = false;
-      if (!fin_attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(dense_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kSolveLdsMax)) != hipSuccess)
-          return PVO_ELAUNCH;
-        fin_attr_set = true;
+      if (hipMemsetAsync(w.xchg, 0, 16, st) != hipSuccess) return PVO_ELAUNCH;                                       // (no partition)
+      const int nkb = (n6 + kNB - 1) / kNB, nrb = (n6 + 1 + kNB - 1) / kNB;
+      for (int kb = 0; kb < nkb; ++kb) {
+        hipLaunchKernelGGL(dense_panel_kernel, dim3(nrb - kb), dim3(256), 0, st, w.chol, w.ldiag, n6, kb, w.plan.meta);
+        const int m = nrb - kb - 1;
+        if (m > 0) hipLaunchKernelGGL(dense_update_kernel, dim3(m * (m + 1) / 2), dim3(256), 0, st, w.chol, n6, kb, nrb);
       }
-    }
-    hipLaunchKernelGGL(dense_finish_kernel, dim3(1 + rider_blocks), dim3(256), rider_lds, st, w.xvec, poses, w.dx, dx_out, w.plan.meta, status_out, P, t0, rider);
-    PVO_CHECK_LAUNCH();
-    if (!motion_only && E + P > 0) {
-      const int Kmax = (nframes < P + E) ? nframes : (P + E);
-      hipLaunchKernelGGL(ba_backsub_kernel, dim3((HW + 255) / 256, Kmax > clamp_frames ? Kmax : clamp_frames), dim3(256), 0, st,
-                         w.plan, jj, w.Ei, w.Eij, w.Q, w.w, w.dx, disps, dz_out, dz_rows, HW, t0, P, 0, clamp_frames, disp_min);
+      PVO_CHECK_LAUNCH();
+      double* yrow = w.chol + static_cast<size_t>(n6) * n6;
+      for (int kb = nkb - 1; kb >= 0; --kb)
+        hipLaunchKernelGGL(dense_back_kernel, dim3(kb + 1), dim3(256), 0, st, w.chol, w.ldiag, yrow, w.xvec, n6, kb);
       PVO_CHECK_LAUNCH();
     }
-    return PVO_OK;
-  }
-  const int solver_pick = (solver_env >= 0 && solver_env < 4) ? solver_env : (use_lds ? (P > 12 ? 2 : 0) : 3);      // 0 blocked | 1 wave | 2 pipe | 3 partitioned
-  const bool twin = solver_pick == 3 && !use_lds;
-  const int solver_wave = solver_pick == 3 ? 2 : solver_pick;
-  if (msg) {
-    if (P == 0) return PVO_OK;
-    hipLaunchKernelGGL(ba_env_packed_kernel, dim3(P), dim3(256), 0, st, msg, first_s, w.plan.env, n6);
-    PVO_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ba_prepare_packed_kernel, dim3(P + 1), dim3(256), 0, st, msg, first_s, w.chol, w.plan.env, n6, lm, ep,
-                       static_cast<long long>(kSolveLdsMax), twin ? reinterpret_cast<int*>(w.xchg) : nullptr);
-    PVO_CHECK_LAUNCH();
-  } else if (!use_lds) {
-    hipLaunchKernelGGL(ba_env_kernel, dim3((n6 * n6 + 2047) / 2048), dim3(256), 0, st, sys, w.plan.env, n6);
-    PVO_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ba_prepare_kernel, dim3((n6 * n6 + n6 + 2047) / 2048), dim3(256), 0, st, sys, w.chol, w.plan.env, n6, lm, ep,
-                       static_cast<long long>(kSolveLdsMax), twin ? reinterpret_cast<int*>(w.xchg) : nullptr);
-    PVO_CHECK_LAUNCH();
-  }
-  if (!use_lds && !twin && hipMemsetAsync(w.xchg, 0, 16, st) != hipSuccess) return PVO_ELAUNCH;      // (pvo_ba_last_partition: one chain)
-  if (twin) {
-    static bool twin_attr_set = false;
-    if (!twin_attr_set) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_twin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(kSolveLdsMax)) != hipSuccess) return PVO_ELAUNCH;
-      twin_attr_set = true;
-    }
-    hipLaunchKernelGGL(ba_solve_twin_kernel, dim3(2 + rider_blocks), dim3(256), lds, st, w.chol, poses, w.dx, dx_out,
-                       w.plan.meta, status_out, P, t0, w.plan.env, static_cast<long long>(kSolveLdsMax), w.xchg, rider);
-  } else {
-    hipLaunchKernelGGL(ba_solve_kernel, dim3(1 + rider_blocks), dim3(256), lds, st, sys, w.chol, poses, w.dx, dx_out,
-                       w.plan.meta, status_out, P, t0, lm, ep, use_lds, w.plan.env, static_cast<long long>(kSolveLdsMax), solver_wave, rider);
+    if (rider_lds > 48 * 1024 && !allow_lds<dense_finish_kernel>(kSolveLdsMax)) return PVO_ELAUNCH;
+    hipLaunchKernelGGL(dense_finish_kernel, dim3(1 + rider_blocks), dim3(256), rider_lds, st, w.xvec, poses, w.dx, dx_out, w.plan.meta, status_out, P, t0, rider);
   }
   PVO_CHECK_LAUNCH();
   if (!motion_only && E + P > 0) {
     const int Kmax = (nframes < P + E) ? nframes : (P + E);
-    const int flags = 0;
     hipLaunchKernelGGL(ba_backsub_kernel, dim3((HW + 255) / 256, Kmax > clamp_frames ? Kmax : clamp_frames), dim3(256), 0, st,
-                       w.plan, jj, w.Ei, w.Eij, w.Q, w.w, w.dx, disps, dz_out, dz_rows, HW, t0, P, flags, clamp_frames, disp_min);
+                       w.plan, jj, w.Ei, w.Eij, w.Q, w.w, w.dx, disps, dz_out, dz_rows, HW, t0, P, clamp_frames, disp_min);
     PVO_CHECK_LAUNCH();
   }
   return PVO_OK;
@@ -3703,11 +3456,8 @@ extern "C" int pvo_ba_last_partition(void* workspace, size_t workspace_bytes, in
   if (!workspace || !out || E < 0 || P < 0) return PVO_EINVAL;
   if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
   out[0] = out[1] = 0;
-  if (6 * P <= kLdsCholMax) return PVO_OK;
-  {
-    const int k = pvo_knob(PVO_KNOB_BA_SOLVER);
-    if (P <= kDenseMaxPoses && (k == 0 || k == 5)) return PVO_OK;      // (the dense solve: nothing to partition; a packed message never asks here)
-  }
+  const SolveKind kind = solve_form(P, E, false, pvo_knob(PVO_KNOB_BA_SOLVER)).kind;
+  if (kind == kSolveStatus || kind == kSolveDense) return PVO_OK;      // (nothing to partition; a packed message never asks here)
   Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   int host[4] = {0, 0, 0, 0};
   if (hipMemcpyAsync(host, w.xchg, sizeof(host), hipMemcpyDeviceToHost, pvo_stream(stream)) != hipSuccess) return PVO_ELAUNCH;

@@ -1,6 +1,6 @@
 // conv1x1_tile.h — one workgroup's share of y = x W^T + b for a 128-channel channels-last tensor (pvo_conv1x1_c128): 64 rows x
 // 192 output channels.  A device function so that two kernels can carry it: conv1x1_c128_kernel (operator_small.hip) and, as a
-// rider beside the one-workgroup pose solve, ba_solve_kernel (ba.hip).
+// rider beside the pose solve (ba.hip: ride).
 #pragma once
 #include "common.h"
 

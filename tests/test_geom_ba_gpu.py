@@ -77,9 +77,9 @@ def test_ba_matches_oracle(cuda, cfg, iters):
 @pytest.mark.parametrize("P,closure", [(30, False), (30, True), (23, True), (22, True), (64, "many")])
 def test_ba_long_window_envelope_cholesky_matches_oracle(cuda, P, closure):
     """A long keyframe chain (block-banded reduced pose system; with `closure` loop-closure edges that create fill inside
-    the envelope): the envelope-form Cholesky of ba_solve_kernel against the oracle's dense fp64 solve - dense in LDS at
-    P = 22 (21 free poses), compact envelope blocks in LDS at 23 and 30 (ba_env_kernel + ba_prepare_kernel), and at P = 64
-    with ten frames closing back to frame 1 an envelope that does not fit LDS: the dense global-memory path"""
+    the envelope) against the oracle's dense fp64 solve: up to 29 free poses (P = 22, 23, 30) the dense matrix-core solve, and
+    at P = 64 with ten frames closing back to frame 1 the envelope solve with an envelope that does not fit LDS: its dense
+    global-memory path"""
     ht, wd = 8, 10
     s = _scene(P * 7 + int(bool(closure)), P, ht, wd, 2, 1)
     if closure:
@@ -309,7 +309,7 @@ def test_ba_fixed_source_frame_and_broadcast_eta(cuda):
 
 @pytest.mark.parametrize("P,radius", [(64, 3), (40, 2), (31, 3)])
 def test_partitioned_pose_solve_partitions_a_chain_and_matches_the_oracle(cuda, P, radius):
-    """the pose solve beyond the dense LDS path (ba_solve_twin_kernel): a keyframe chain is eliminated from both ends by two
+    """the pose solve beyond the dense matrix-core solve (ba_solve_twin_kernel): a keyframe chain is eliminated from both ends by two
     workgroups, the separator last - the partition is reported, balanced, and the result is the oracle's (dense fp64 solve)"""
     from pvo_amd import droid_backends as db
     ht, wd = 8, 10
@@ -485,8 +485,8 @@ def test_reproject_matches_reference_python_fixture(cuda):
 def test_wave_and_blocked_cholesky_are_bit_identical(P, ht, wd, radius):
     """the look-ahead pipeline (the default: wave 0 on the critical path, three worker waves behind it), the one-wave
     (barrier-free) and the four-wave blocked factorisation of the pose system perform the same operations on every entry in
-    the same order: poses and depths agree bit for bit (dense-in-LDS and compact-envelope storage, with a loop closure in
-    the long windows).  Each solver in its own process: the choice is read once per process."""
+    the same order: poses and depths agree bit for bit (the envelope solve's compact storage, in short and long windows).
+    Each solver in its own process: the debug knob is process-wide."""
     import subprocess
     import sys
     code = ("import sys, torch; sys.path.insert(0, %r); sys.path.insert(0, %r); from test_geom_ba_gpu import _scene; from pvo_amd import droid_backends as db; "

@@ -204,8 +204,8 @@ def test_ba_is_bitwise_reproducible(cuda):
 def test_envelope_allreduce_path_is_bit_identical_on_the_hip_solver(cuda, nf, ht, wd):
     """ShardedBA with the envelope message forced on one rank - packed by the library (pvo_ba_pack / pvo_ba_finish_packed: the
     message is read in place of the dense system) and, as before round 4, by index_select / index_copy_ around the dense
-    system - against the dense message: poses and depths bit-identical.  64 keyframes: the partitioned solve; 8: a window-sized
-    system, which the packed path factorises from the compact image too."""
+    system - against the dense message: poses and depths bit-identical.  64 keyframes: the partitioned solve; 30 and 8:
+    window-sized systems, which the dense matrix-core solve reads from the message as it reads the dense image."""
     from test_geom_ba_gpu import _scene
     s = _scene(13, nf, ht, wd, 3, 1)
     d = lambda t: t.to(cuda)
@@ -227,14 +227,16 @@ def test_envelope_allreduce_path_is_bit_identical_on_the_hip_solver(cuda, nf, ht
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("nf,ht,wd,dt", [(8, 48, 64, torch.float16), (30, 12, 16, torch.float16), (8, 24, 32, torch.bfloat16)])
-def test_pose_solve_with_a_convolution_riding_in_its_dispatch(cuda, nf, ht, wd, dt):
-    """pvo_ba_finish_conv1x1: the one-workgroup pose solve and an independent 1x1 convolution (GraphAgg's upsampling mask in
-    pvo_graph_update) share a dispatch.  Poses and depths are bit-identical to the plain call over repeated runs, and the
-    convolution equals pvo_conv1x1_c128 bit for bit (window-sized system in LDS, and a 29-pose system on the envelope path)."""
+@pytest.mark.parametrize("nf,ht,wd,dt,radius", [(8, 48, 64, torch.float16, 3), (30, 12, 16, torch.float16, 3), (8, 24, 32, torch.bfloat16, 3),
+                                                (40, 8, 10, torch.float16, 3), (40, 8, 10, torch.float16, 6)])
+def test_pose_solve_with_a_convolution_riding_in_its_dispatch(cuda, nf, ht, wd, dt, radius):
+    """pvo_ba_finish_conv1x1: the pose solve and an independent 1x1 convolution (GraphAgg's upsampling mask in pvo_graph_update)
+    share a dispatch.  Poses and depths are bit-identical to the plain call over repeated runs, and the convolution equals
+    pvo_conv1x1_c128 bit for bit - in each form's dispatch: the dense matrix-core solve (8 and 30 frames), the partitioned envelope
+    solve (40 frames, radius 3) and dense_finish_kernel behind the 48 x 48 blocks (40 frames, radius 6: more than 8 edges per pose)."""
     from pvo_amd import droid_backends as db
     from test_geom_ba_gpu import _scene
-    s = _scene(11, nf, ht, wd, 3, 1)
+    s = _scene(11, nf, ht, wd, radius, 1)
     d = lambda t: t.to(cuda)
     F = s["disps"].shape[0]
     P = s["t1"] - s["t0"]

@@ -1,5 +1,7 @@
-"""Phase split of ba_solve_kernel (one workgroup: fixed point -> fp64, blocked Cholesky, substitution, retraction) from
-in-kernel clock stamps.   python tools/ba_solve_timeline.py --build   |   NF=8 python tools/ba_solve_timeline.py"""
+"""Phase split of the pose solve from in-kernel clock stamps: load, factorisation, substitution, dx out + retraction of the dense
+matrix-core solve (up to 29 free poses) or of the envelope solve as one chain (ba_solve_twin_kernel without a partition), and the
+timeline of both workgroups of a partitioned envelope solve.
+    python tools/ba_solve_timeline.py --build   |   NF=8 python tools/ba_solve_timeline.py"""
 import ctypes, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
