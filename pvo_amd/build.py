@@ -51,11 +51,9 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 EXTRA_FLAGS = {"geom.hip": ["-ffp-contract=off"]}
 
 
-def _newer(target, deps):
-    if not os.path.exists(target):
-        return True
-    t = os.path.getmtime(target)
-    return any(os.path.getmtime(d) > t for d in deps)
+def flags_for(src):
+    """the compile flags of one translation unit of csrc/ (build_hip, build_probe, tools/variant.py)"""
+    return HIPCC_FLAGS + EXTRA_FLAGS.get(src, [])
 
 
 def _digest(paths, extra=()):
@@ -104,7 +102,7 @@ def build_hip(force=False, verbose=False):
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace(".hip", ".o"))
         objs.append(o)
-        flags = HIPCC_FLAGS + EXTRA_FLAGS.get(src, [])
+        flags = flags_for(src)
         if force or _stale(o, [s] + headers, flags):
             cmd = [hipcc] + flags + ["-c", s, "-o", o]
             if verbose:
@@ -128,10 +126,12 @@ def build_probe(force=False):
     """libpvo_probe.so: the shader-clock and memory-request probes, kept out of the product library"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     src = os.path.join(CSRC, "probe_tools.hip")
-    deps = [src, os.path.join(CSRC, "common.h"), os.path.join(ROOT, "include", "pvo_probe.h"), os.path.join(ROOT, "include", "pvo_hip.h")]
-    if force or _stale(PROBE_LIB, deps, HIPCC_FLAGS):
-        _run([hipcc] + HIPCC_FLAGS + ["-shared", "-o", PROBE_LIB, src])
-        _stamp(PROBE_LIB, deps, HIPCC_FLAGS)
+    deps = [src, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "operand16.h"),
+            os.path.join(ROOT, "include", "pvo_probe.h"), os.path.join(ROOT, "include", "pvo_hip.h")]
+    flags = flags_for("probe_tools.hip")
+    if force or _stale(PROBE_LIB, deps, flags):
+        _run([hipcc] + flags + ["-shared", "-o", PROBE_LIB, src])
+        _stamp(PROBE_LIB, deps, flags)
     return PROBE_LIB
 
 

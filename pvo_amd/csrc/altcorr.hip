@@ -165,7 +165,7 @@ extern "C" int pvo_altcorr_forward(const void* fmap1, const void* fmap2, const f
   if (static_cast<long long>(B) * S > 65535) return PVO_EUNSUPPORTED;
   hipStream_t st = pvo_stream(stream);
   const int HW = H1 * W1;
-  const bool al = (((reinterpret_cast<uintptr_t>(fmap1) | reinterpret_cast<uintptr_t>(fmap2)) & 15) == 0);
+  const bool al = !pvo_misaligned16(fmap1, fmap2);
   if (radius == 3 && ((C & 3) != 0 || al))
     hipLaunchKernelGGL(altcorr_fwd_r3_kernel, dim3((HW + kPix - 1) / kPix, B * S), dim3(256), 0, st,
                        static_cast<const float*>(fmap1), static_cast<const float*>(fmap2), coords,

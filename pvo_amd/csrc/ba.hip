@@ -430,21 +430,21 @@ __global__ __launch_bounds__(256) void ba_assemble_kernel(
 #pragma unroll
     for (int q = 0; q < 12; ++q) {
       const float keep = b3 ? c[q + 12] : c[q], send = b3 ? c[q] : c[q + 12];
-      c[q] = keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0x140, 0xf, 0xf, true));      // row_mirror
+      c[q] = keep + pvo_dpp_move<0x140>(send);      // row_mirror
     }
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
       const float keep = b2 ? c[q + 6] : c[q], send = b2 ? c[q] : c[q + 6];
-      c[q] = keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0x141, 0xf, 0xf, true));      // row_half_mirror
+      c[q] = keep + pvo_dpp_move<0x141>(send);      // row_half_mirror
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       const float keep = b1 ? c[q + 3] : c[q], send = b1 ? c[q] : c[q + 3];
-      c[q] = keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0x1b, 0xf, 0xf, true));       // quad_perm [3,2,1,0]
+      c[q] = keep + pvo_dpp_move<0x1b>(send);       // quad_perm [3,2,1,0]
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q)
-      c[q] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, c[q]), 0xb1, 0xf, 0xf, true));             // quad_perm [1,0,3,2]
+      c[q] = pvo_dpp_step<0xb1>(c[q]);             // quad_perm [1,0,3,2]
     const int start = ((lane >> 5) & 1) * 48 + ((lane >> 4) & 1) * 24 + ((lane >> 3) & 1) * 12 + ((lane >> 2) & 1) * 6 + ((lane >> 1) & 1) * 3;
     if (!(lane & 1)) {
 #pragma unroll
@@ -3133,14 +3133,6 @@ extern "C" size_t pvo_ba_workspace_bytes(int E, int P, int nframes, int HW) {
   return carve(nullptr, E, P, nframes, HW).bytes + 256;
 }
 
-// a kernel's dynamic LDS beyond the default 48 KB: allowed once per process
-template <auto Kernel>
-static bool allow_lds(int bytes) {
-  static bool done = false;
-  if (!done) done = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-  return done;
-}
-
 static inline void* ws_base(void* workspace) {
   return reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
 }
@@ -3222,7 +3214,7 @@ extern "C" int pvo_ba_local(const float* poses, const float* disps, const float*
     constexpr int kSchurRowsLds = 110 * 1024;
     const size_t sdyn = dense_window ? kSchurRowsLds : 0;
     const int lds_floats = static_cast<int>(sdyn / sizeof(float));
-    if (dense_window && !(allow_lds<ba_schur_mfma_kernel<true, 256>>(kSchurRowsLds) && allow_lds<ba_schur_mfma_kernel<false, 256>>(kSchurRowsLds)))
+    if (dense_window && !(pvo_allow_lds<ba_schur_mfma_kernel<true, 256>>(kSchurRowsLds) && pvo_allow_lds<ba_schur_mfma_kernel<false, 256>>(kSchurRowsLds)))
       return PVO_ELAUNCH;
     if (depth_done) {
       hipLaunchKernelGGL(ba_depth_kernel, dim3((HW + 255) / 256, Kgrid), dim3(256), 0, st, w.plan, eta, K_eta, w.Eii, w.Cii, w.bz, w.Ei, w.Q, w.w, HW, t0, P);
@@ -3353,7 +3345,7 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
   if (jobs && jobs->cy && jobs->crows > 0) {
     if (!jobs->cx || !jobs->cw || jobs->cCout <= 0 || jobs->cCout % 192) return PVO_EINVAL;
     if (jobs->cdtype != PVO_F16 && jobs->cdtype != PVO_BF16) return PVO_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(jobs->cx) | reinterpret_cast<uintptr_t>(jobs->cw) | reinterpret_cast<uintptr_t>(jobs->cy)) & 15) return PVO_EINVAL;
+    if (pvo_misaligned16(jobs->cx, jobs->cw, jobs->cy)) return PVO_EINVAL;
     if (jobs->crows > (1LL << 24)) return PVO_EUNSUPPORTED;
     rider.cx = static_cast<const uint16_t*>(jobs->cx); rider.cw = static_cast<const uint16_t*>(jobs->cw); rider.cbias = jobs->cbias;
     rider.cy = static_cast<uint16_t*>(jobs->cy); rider.crows = jobs->crows; rider.cCout = jobs->cCout; rider.cdtype = jobs->cdtype;
@@ -3364,7 +3356,7 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
   if (jobs && jobs->gpart && jobs->gE > 0 && jobs->gHW > 0) {
     if (!jobs->gnet || !jobs->gw || jobs->gE > 65535) return PVO_EINVAL;
     if (jobs->gdtype != PVO_F16 && jobs->gdtype != PVO_BF16) return PVO_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(jobs->gnet) | reinterpret_cast<uintptr_t>(jobs->gw)) & 15) return PVO_EINVAL;
+    if (pvo_misaligned16(jobs->gnet, jobs->gw)) return PVO_EINVAL;
     rider.gnet = static_cast<const uint16_t*>(jobs->gnet); rider.gw = static_cast<const uint16_t*>(jobs->gw); rider.gbias = jobs->gbias;
     rider.gpart = jobs->gpart; rider.gHW = jobs->gHW; rider.gchunks = (jobs->gHW + 255) / 256; rider.gdtype = jobs->gdtype;
     rider.gblocks = jobs->gE * rider.gchunks;
@@ -3395,8 +3387,8 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
     const size_t dl = dense_lds_bytes(n6);
     const size_t lds = dl > rider_lds ? dl : rider_lds;
     const int Td = dense_N(n6) / 16;                            // tiles per side: 4 slots per wave up to 5 (15 tiles), 14 up to 10 (55: 26 poses), 17 up to 11
-    if (!allow_lds<ba_solve_dense_kernel<4>>(kSolveLdsMax) || !allow_lds<ba_solve_dense_kernel<14>>(kSolveLdsMax) ||
-        !allow_lds<ba_solve_dense_kernel<17>>(kSolveLdsMax))
+    if (!pvo_allow_lds<ba_solve_dense_kernel<4>>(kSolveLdsMax) || !pvo_allow_lds<ba_solve_dense_kernel<14>>(kSolveLdsMax) ||
+        !pvo_allow_lds<ba_solve_dense_kernel<17>>(kSolveLdsMax))
       return PVO_ELAUNCH;
     const auto kernel = Td <= 5 ? ba_solve_dense_kernel<4> : (Td <= 10 ? ba_solve_dense_kernel<14> : ba_solve_dense_kernel<17>);
     hipLaunchKernelGGL(kernel, dim3(1 + rider_blocks), dim3(256), lds, st, sys, msg, first_s, poses, w.dx, dx_out, w.plan.meta, status_out,
@@ -3414,7 +3406,7 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
     }
     PVO_CHECK_LAUNCH();
     if (!part && hipMemsetAsync(w.xchg, 0, 16, st) != hipSuccess) return PVO_ELAUNCH;      // (one chain: no partition)
-    if (!allow_lds<ba_solve_twin_kernel>(kSolveLdsMax)) return PVO_ELAUNCH;
+    if (!pvo_allow_lds<ba_solve_twin_kernel>(kSolveLdsMax)) return PVO_ELAUNCH;
     hipLaunchKernelGGL(ba_solve_twin_kernel, dim3(2 + rider_blocks), dim3(256), kSolveLdsMax > rider_lds ? kSolveLdsMax : rider_lds, st,
                        w.chol, poses, w.dx, dx_out, w.plan.meta, status_out, P, t0, w.plan.env, static_cast<long long>(kSolveLdsMax), w.xchg,
                        form.chol, rider);
@@ -3437,7 +3429,7 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
         hipLaunchKernelGGL(dense_back_kernel, dim3(kb + 1), dim3(256), 0, st, w.chol, w.ldiag, yrow, w.xvec, n6, kb);
       PVO_CHECK_LAUNCH();
     }
-    if (rider_lds > 48 * 1024 && !allow_lds<dense_finish_kernel>(kSolveLdsMax)) return PVO_ELAUNCH;
+    if (rider_lds > 48 * 1024 && !pvo_allow_lds<dense_finish_kernel>(kSolveLdsMax)) return PVO_ELAUNCH;
     hipLaunchKernelGGL(dense_finish_kernel, dim3(1 + rider_blocks), dim3(256), rider_lds, st, w.xvec, poses, w.dx, dx_out, w.plan.meta, status_out, P, t0, rider);
   }
   PVO_CHECK_LAUNCH();

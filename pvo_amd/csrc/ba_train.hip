@@ -26,7 +26,6 @@
 // device; the plan kx [M] (keyframes, ascending), kk [N] (keyframe of each edge), kptr [M+1] / kedge [N] (edges of each keyframe
 // in edge order) int32.  Free poses a = frame - fixedp in [0, Pf); blocks that touch a fixed pose are dropped.
 #include "se3_dual.h"
-#include <atomic>
 
 namespace {
 
@@ -541,18 +540,8 @@ int train_fwd(const F* poses, const F* disps, const F* intr, const F* target, co
   hipLaunchKernelGGL(ba_train_depth<F>, dim3(d.nch, d.M, d.B), dim3(256), 0, st, w, d, eta, ii, jj, kptr, kedge);
   if (d.Pf > 0) hipLaunchKernelGGL(ba_train_schur<F>, dim3(d.nch, d.Pf * d.Pf, d.B), dim3(64), 0, st, w, d);
   const int lds = lds_bytes<F>(d.Pf);
-  if (lds > 48 * 1024) {
-    // once per device and type (the largest system, 96 x 96, at once); a device beyond the mask's 64 bits sets it at every call
-    static std::atomic<unsigned long long> attr_set{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return PVO_ELAUNCH;
-    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ULL << dev : 0;
-    if (!bit || !(attr_set.load() & bit)) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(ba_train_solve<F>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              lds_bytes<F>(kMaxFree)) != hipSuccess) return PVO_ELAUNCH;
-      attr_set.fetch_or(bit);
-    }
-  }
+  // (the largest system, 96 x 96, is asked for at once: one grant per device and type)
+  if (lds > 48 * 1024 && !pvo_allow_lds<ba_train_solve<F>>(lds_bytes<F>(kMaxFree))) return PVO_ELAUNCH;
   hipLaunchKernelGGL(ba_train_solve<F>, dim3(d.B), dim3(256), lds, st, w, d, poses, ii, jj, poses_out, dx_out);
   hipLaunchKernelGGL(ba_train_backsub<F>, dim3(d.nch, d.P, d.B), dim3(256), 0, st, w, d, disps, kx, disps_out);
   PVO_CHECK_LAUNCH();
@@ -606,13 +595,12 @@ extern "C" int pvo_ba_train(const void* poses, const void* disps, const void* in
   if (workspace_bytes < pvo_ba_train_workspace_bytes(B, P, N, M, ht * wd, dtype)) return PVO_EWORKSPACE;
   const Dims d = make_dims(B, P, N, M, ht * wd, fixedp);
   const hipStream_t st = pvo_stream(stream);
-  if (dtype == PVO_F32)
-    return train_fwd<float>(static_cast<const float*>(poses), static_cast<const float*>(disps), static_cast<const float*>(intr),
-                            static_cast<const float*>(target), static_cast<const float*>(weight), static_cast<const float*>(eta), ii, jj, kx, kptr, kedge, ht, d,
-                            static_cast<float*>(poses_out), static_cast<float*>(disps_out), static_cast<float*>(dx_out), workspace, dtype, st);
-  return train_fwd<double>(static_cast<const double*>(poses), static_cast<const double*>(disps), static_cast<const double*>(intr),
-                           static_cast<const double*>(target), static_cast<const double*>(weight), static_cast<const double*>(eta), ii, jj, kx, kptr, kedge, ht, d,
-                           static_cast<double*>(poses_out), static_cast<double*>(disps_out), static_cast<double*>(dx_out), workspace, dtype, st);
+  return pvo_dispatch<float, double>(dtype, [&](auto tag) -> int {
+    using F = decltype(tag);
+    return train_fwd<F>(static_cast<const F*>(poses), static_cast<const F*>(disps), static_cast<const F*>(intr), static_cast<const F*>(target),
+                        static_cast<const F*>(weight), static_cast<const F*>(eta), ii, jj, kx, kptr, kedge, ht, d,
+                        static_cast<F*>(poses_out), static_cast<F*>(disps_out), static_cast<F*>(dx_out), workspace, dtype, st);
+  });
 }
 
 extern "C" int pvo_ba_train_vjp(const void* poses, const void* disps, const void* intr, const void* target, const void* weight,
@@ -630,15 +618,11 @@ extern "C" int pvo_ba_train_vjp(const void* poses, const void* disps, const void
       scratch_bytes < pvo_ba_train_vjp_scratch_bytes(B, P, N, M, ht * wd, dtype)) return PVO_EWORKSPACE;
   const Dims d = make_dims(B, P, N, M, ht * wd, fixedp);
   const hipStream_t st = pvo_stream(stream);
-  if (dtype == PVO_F32)
-    return train_vjp<float>(static_cast<const float*>(poses), static_cast<const float*>(disps), static_cast<const float*>(intr),
-                            static_cast<const float*>(target), static_cast<const float*>(weight), ii, jj, kx, kk, ht, d,
-                            static_cast<const float*>(g_poses_out), static_cast<const float*>(g_disps_out), static_cast<float*>(g_target),
-                            static_cast<float*>(g_weight), static_cast<float*>(g_eta), static_cast<float*>(g_poses), static_cast<float*>(g_disps),
-                            workspace, scratch, dtype, st);
-  return train_vjp<double>(static_cast<const double*>(poses), static_cast<const double*>(disps), static_cast<const double*>(intr),
-                           static_cast<const double*>(target), static_cast<const double*>(weight), ii, jj, kx, kk, ht, d,
-                           static_cast<const double*>(g_poses_out), static_cast<const double*>(g_disps_out), static_cast<double*>(g_target),
-                           static_cast<double*>(g_weight), static_cast<double*>(g_eta), static_cast<double*>(g_poses), static_cast<double*>(g_disps),
-                           workspace, scratch, dtype, st);
+  return pvo_dispatch<float, double>(dtype, [&](auto tag) -> int {
+    using F = decltype(tag);
+    return train_vjp<F>(static_cast<const F*>(poses), static_cast<const F*>(disps), static_cast<const F*>(intr), static_cast<const F*>(target),
+                        static_cast<const F*>(weight), ii, jj, kx, kk, ht, d, static_cast<const F*>(g_poses_out), static_cast<const F*>(g_disps_out),
+                        static_cast<F*>(g_target), static_cast<F*>(g_weight), static_cast<F*>(g_eta), static_cast<F*>(g_poses), static_cast<F*>(g_disps),
+                        workspace, scratch, dtype, st);
+  });
 }

@@ -2,27 +2,9 @@
 // 192 output channels.  A device function so that two kernels can carry it: conv1x1_c128_kernel (operator_small.hip) and, as a
 // rider beside the pose solve (ba.hip: ride).
 #pragma once
-#include "common.h"
+#include "operand16.h"
 
 namespace c1t {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-typedef __bf16 v8b __attribute__((ext_vector_type(8)));
-
-template <typename T> __device__ __forceinline__ v4f mfma(u32x4 a, u32x4 b, v4f c);
-template <> __device__ __forceinline__ v4f mfma<pvo_half>(u32x4 a, u32x4 b, v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ v4f mfma<pvo_bf16>(u32x4 a, u32x4 b, v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8b, a), __builtin_bit_cast(v8b, b), c, 0, 0, 0);
-}
-template <typename T> __device__ __forceinline__ uint32_t bits(float x);
-template <> __device__ __forceinline__ uint32_t bits<pvo_half>(float x) {
-  union { _Float16 h; uint16_t u; } c; c.h = static_cast<_Float16>(x); return c.u;
-}
-template <> __device__ __forceinline__ uint32_t bits<pvo_bf16>(float x) { return pvo_f32_to_bf16(x); }
 
 constexpr int kStride = 272;                 // input tile row stride (bytes)
 constexpr int kTileBytes = 64 * 400;         // LDS the function needs: the input tile (64 x 272 B), later the output slab (64 x 400 B)
@@ -62,7 +44,7 @@ __device__ __forceinline__ void conv1x1_c128_tile(unsigned char* tile, const uin
     for (int kc = 0; kc < 4; ++kc) {
       const u32x4 a = *reinterpret_cast<const u32x4*>(tile + (g * 16 + li) * kStride + kc * 64 + lk * 16);
 #pragma unroll
-      for (int nt = 0; nt < 3; ++nt) d[g][nt] = mfma<T>(a, bf[kc][nt], d[g][nt]);
+      for (int nt = 0; nt < 3; ++nt) d[g][nt] = pvo_mfma<T>(a, bf[kc][nt], d[g][nt]);
     }
   __syncthreads();
   float bb[3];
@@ -76,7 +58,7 @@ __device__ __forceinline__ void conv1x1_c128_tile(unsigned char* tile, const uin
       for (int r = 0; r < 4; ++r) {                        // D rows lk*4 + r = pixels, column li = channel
         float v = d[g][nt][r] + bb[nt];
         if (relu) v = fmaxf(v, 0.0f);
-        *reinterpret_cast<uint16_t*>(tile + (g * 16 + lk * 4 + r) * 400 + (wave * 48 + nt * 16 + li) * 2) = static_cast<uint16_t>(bits<T>(v));
+        *reinterpret_cast<uint16_t*>(tile + (g * 16 + lk * 4 + r) * 400 + (wave * 48 + nt * 16 + li) * 2) = static_cast<uint16_t>(pvo_bits<T>(v));
       }
   __syncthreads();
   for (int id = tid; id < 64 * 24; id += 256) {             // 24 chunks of 16 B per row

@@ -10,48 +10,12 @@
 //   MFMAs (the last one padded with zero weights).  A workgroup owns a 16x16 pixel tile whose 22x22 halo (7.7 KB) sits
 //   in LDS; wave w owns output channels [32w, 32w+32) and keeps its 26 weight fragments in registers for all 16 tile rows.
 //   Weights arrive pre-arranged as [52 taps (49 + 3 zero)][128 outputs][8 channels] 16-bit.
-#include "common.h"
+#include "operand16.h"
 #include <type_traits>
 #include "glo_tile.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef uint32_t cs_u32x4 __attribute__((ext_vector_type(4)));
-typedef float cs_v4f __attribute__((ext_vector_type(4)));
-typedef _Float16 cs_v8h __attribute__((ext_vector_type(8)));
-typedef __bf16 cs_v8b __attribute__((ext_vector_type(8)));
-
-template <typename T> __device__ __forceinline__ cs_v4f cs_mfma(cs_u32x4 a, cs_u32x4 b, cs_v4f c);
-template <> __device__ __forceinline__ cs_v4f cs_mfma<pvo_half>(cs_u32x4 a, cs_u32x4 b, cs_v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cs_v8h, a), __builtin_bit_cast(cs_v8h, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ cs_v4f cs_mfma<pvo_bf16>(cs_u32x4 a, cs_u32x4 b, cs_v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cs_v8b, a), __builtin_bit_cast(cs_v8b, b), c, 0, 0, 0);
-}
-
-template <typename T> __device__ __forceinline__ uint32_t cs_bits(float x);
-template <> __device__ __forceinline__ uint32_t cs_bits<pvo_half>(float x) {
-  union { _Float16 h; uint16_t u; } c; c.h = static_cast<_Float16>(x); return c.u;
-}
-template <> __device__ __forceinline__ uint32_t cs_bits<pvo_bf16>(float x) { return pvo_f32_to_bf16(x); }
-
-template <typename T> __device__ __forceinline__ float cs_val(uint32_t b);
-template <> __device__ __forceinline__ float cs_val<pvo_half>(uint32_t b) {
-  union { uint16_t u; _Float16 h; } c; c.u = static_cast<uint16_t>(b); return static_cast<float>(c.h);
-}
-template <> __device__ __forceinline__ float cs_val<pvo_bf16>(uint32_t b) { return pvo_bf16_to_f32(static_cast<uint16_t>(b)); }
-template <typename T> __device__ __forceinline__ void cs_unpack8(cs_u32x4 v, float f[8]) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { f[2 * k] = cs_val<T>(w[k] & 0xffffu); f[2 * k + 1] = cs_val<T>(w[k] >> 16); }
-}
-template <typename T> __device__ __forceinline__ cs_u32x4 cs_pack8(const float f[8]) {
-  cs_u32x4 v;
-  v.x = cs_bits<T>(f[0]) | (cs_bits<T>(f[1]) << 16); v.y = cs_bits<T>(f[2]) | (cs_bits<T>(f[3]) << 16);
-  v.z = cs_bits<T>(f[4]) | (cs_bits<T>(f[5]) << 16); v.w = cs_bits<T>(f[6]) | (cs_bits<T>(f[7]) << 16);
-  return v;
-}
 
 constexpr int kTH = 8, kTW = 16, kR = 3;
 #ifndef PVO_CONV7_ROWS                                      // (experiment hook, tools/variant.py: 8 / 4 rows measured, no change in the update)
@@ -75,19 +39,19 @@ __global__ __launch_bounds__(256) void conv7x7_c8_kernel(const uint16_t* __restr
 
   // weight fragments of this wave's two 16-channel column tiles: B[k = (tap, ch)][n]; lane (li, lk) holds column li,
   // k-group lk = tap 4*s + lk of step s, all 8 channels
-  cs_u32x4 bf[kSteps][2];
+  u32x4 bf[kSteps][2];
 #pragma unroll
   for (int s = 0; s < kSteps; ++s)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
-      bf[s][nt] = *reinterpret_cast<const cs_u32x4*>(wt + (static_cast<size_t>(4 * s + lk) * 128 + wave * 32 + nt * 16 + li) * 8);
+      bf[s][nt] = *reinterpret_cast<const u32x4*>(wt + (static_cast<size_t>(4 * s + lk) * 128 + wave * 32 + nt * 16 + li) * 8);
 
   const uint16_t* xe = x + static_cast<size_t>(e) * H * W * 8;
   for (int pos = tid; pos < kHH7 * kHW_; pos += 256) {
     const int hy = y0 - kR + pos / kHW_, hx = x0 - kR + pos % kHW_;
-    cs_u32x4 v = {0u, 0u, 0u, 0u};
-    if (hy >= 0 && hy < H && hx >= 0 && hx < W) v = *reinterpret_cast<const cs_u32x4*>(xe + (static_cast<size_t>(hy) * W + hx) * 8);
-    *reinterpret_cast<cs_u32x4*>(halo + pos * 16) = v;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (hy >= 0 && hy < H && hx >= 0 && hx < W) v = *reinterpret_cast<const u32x4*>(xe + (static_cast<size_t>(hy) * W + hx) * 8);
+    *reinterpret_cast<u32x4*>(halo + pos * 16) = v;
   }
   // LDS offset of this lane's tap in step s, relative to the tile row: taps >= 49 have zero weights, any address does
   int toff[kSteps];
@@ -103,17 +67,17 @@ __global__ __launch_bounds__(256) void conv7x7_c8_kernel(const uint16_t* __restr
 
   for (int py = 0; py < kTH7; ++py) {
     if (y0 + py >= H) break;                                  // (uniform) rows below the image
-    cs_v4f d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+    v4f d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
     const unsigned char* rowp = halo + py * kHW_ * 16;
     // (clock64 stamps: 5k cycles of set-up + 1364 cycles per row per workgroup, i.e. the kernel's ~19 us is one workgroup's
     // latency - only 1.7 workgroups per CU exist at S-B - not a throughput limit; forcing the reads ahead changed nothing)
-    cs_u32x4 afr[kSteps];
+    u32x4 afr[kSteps];
 #pragma unroll
-    for (int s = 0; s < kSteps; ++s) afr[s] = *reinterpret_cast<const cs_u32x4*>(rowp + toff[s]);
+    for (int s = 0; s < kSteps; ++s) afr[s] = *reinterpret_cast<const u32x4*>(rowp + toff[s]);
 #pragma unroll
     for (int s = 0; s < kSteps; ++s) {
-      d0 = cs_mfma<T>(afr[s], bf[s][0], d0);
-      d1 = cs_mfma<T>(afr[s], bf[s][1], d1);
+      d0 = pvo_mfma<T>(afr[s], bf[s][0], d0);
+      d1 = pvo_mfma<T>(afr[s], bf[s][1], d1);
     }
     // D: column li = channel, rows lk*4 + r = pixels.  bias + ReLU, then the four waves' 32-channel slices meet in a
     // workgroup slab so that every pixel leaves as one contiguous 256-byte row (a wave storing its own 64-byte slice
@@ -122,15 +86,15 @@ __global__ __launch_bounds__(256) void conv7x7_c8_kernel(const uint16_t* __restr
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int p = lk * 4 + r;
-      *reinterpret_cast<uint16_t*>(sl + p * 272 + (wave * 32 + li) * 2) = static_cast<uint16_t>(cs_bits<T>(fmaxf(d0[r] + bb[0], 0.0f)));
-      *reinterpret_cast<uint16_t*>(sl + p * 272 + (wave * 32 + 16 + li) * 2) = static_cast<uint16_t>(cs_bits<T>(fmaxf(d1[r] + bb[1], 0.0f)));
+      *reinterpret_cast<uint16_t*>(sl + p * 272 + (wave * 32 + li) * 2) = static_cast<uint16_t>(pvo_bits<T>(fmaxf(d0[r] + bb[0], 0.0f)));
+      *reinterpret_cast<uint16_t*>(sl + p * 272 + (wave * 32 + 16 + li) * 2) = static_cast<uint16_t>(pvo_bits<T>(fmaxf(d1[r] + bb[1], 0.0f)));
     }
     __syncthreads();                                          // (double buffered: one barrier per tile row)
     const int p = tid >> 4, c = tid & 15;
-    const cs_u32x4 v = *reinterpret_cast<const cs_u32x4*>(sl + p * 272 + c * 16);
+    const u32x4 v = *reinterpret_cast<const u32x4*>(sl + p * 272 + c * 16);
     const int gy = y0 + py, gx = x0 + p;
     if (gy < H && gx < W)
-      *reinterpret_cast<cs_u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * 128 + c * 8) = v;
+      *reinterpret_cast<u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * 128 + c * 8) = v;
   }
 }
 
@@ -186,25 +150,25 @@ __global__ __launch_bounds__(256) void conv3x3_c128_kernel(const uint16_t* __res
       const int pos = (tid >> 4) + 16 * it;
       if (pos < kC3Halo) {
         const int hy = y0 - 1 + pos / (kTW + 2), hx = x0 - 1 + pos % (kTW + 2);
-        cs_u32x4 v = {0u, 0u, 0u, 0u};
-        if (hy >= 0 && hy < H && hx >= 0 && hx < W) v = *reinterpret_cast<const cs_u32x4*>(xe + (static_cast<size_t>(hy) * W + hx) * 128 + ch * 8);
-        *reinterpret_cast<cs_u32x4*>(c3s + pos * kC3Stride + ch * 16) = v;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (hy >= 0 && hy < H && hx >= 0 && hx < W) v = *reinterpret_cast<const u32x4*>(xe + (static_cast<size_t>(hy) * W + hx) * 128 + ch * 8);
+        *reinterpret_cast<u32x4*>(c3s + pos * kC3Stride + ch * 16) = v;
       }
     }
   }
   // weight fragments: B[k = cin][n = cout] of tap t; lane (li, lk) holds column li of tile nt, input channels kc*32 + lk*8 ..+8
   const uint16_t* wl = wt + (static_cast<size_t>(co0 + li)) * 128 + lk * 8;
   const size_t tap_stride = static_cast<size_t>(Cout) * 128;
-  cs_u32x4 bcur[4][NT], bnxt[4][NT];
+  u32x4 bcur[4][NT], bnxt[4][NT];
 #pragma unroll
   for (int kc = 0; kc < 4; ++kc)
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) bcur[kc][nt] = *reinterpret_cast<const cs_u32x4*>(wl + static_cast<size_t>(nt) * 16 * 128 + kc * 32);
-  cs_v4f acc[kTH][NT];
+    for (int nt = 0; nt < NT; ++nt) bcur[kc][nt] = *reinterpret_cast<const u32x4*>(wl + static_cast<size_t>(nt) * 16 * 128 + kc * 32);
+  v4f acc[kTH][NT];
 #pragma unroll
   for (int py = 0; py < kTH; ++py)
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[py][nt] = cs_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int nt = 0; nt < NT; ++nt) acc[py][nt] = v4f{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
 
 #pragma unroll 1
@@ -214,16 +178,16 @@ __global__ __launch_bounds__(256) void conv3x3_c128_kernel(const uint16_t* __res
       for (int kc = 0; kc < 4; ++kc)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
-          bnxt[kc][nt] = *reinterpret_cast<const cs_u32x4*>(wl + (t + 1) * tap_stride + static_cast<size_t>(nt) * 16 * 128 + kc * 32);
+          bnxt[kc][nt] = *reinterpret_cast<const u32x4*>(wl + (t + 1) * tap_stride + static_cast<size_t>(nt) * 16 * 128 + kc * 32);
     }
     const unsigned char* tp = c3s + ((t / 3) * (kTW + 2) + (t % 3) + li) * kC3Stride + lk * 16;
 #pragma unroll
     for (int py = 0; py < kTH; ++py) {
 #pragma unroll
       for (int kc = 0; kc < 4; ++kc) {
-        const cs_u32x4 a = *reinterpret_cast<const cs_u32x4*>(tp + py * (kTW + 2) * kC3Stride + kc * 64);
+        const u32x4 a = *reinterpret_cast<const u32x4*>(tp + py * (kTW + 2) * kC3Stride + kc * 64);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[py][nt] = cs_mfma<T>(a, bcur[kc][nt], acc[py][nt]);
+        for (int nt = 0; nt < NT; ++nt) acc[py][nt] = pvo_mfma<T>(a, bcur[kc][nt], acc[py][nt]);
       }
     }
     if (t < 8) {
@@ -248,7 +212,7 @@ __global__ __launch_bounds__(256) void conv3x3_c128_kernel(const uint16_t* __res
         float v = acc[py][nt][r] + bb[nt];
         if (relu) v = fmaxf(v, 0.0f);
         *reinterpret_cast<uint16_t*>(c3s + (py * 16 + lk * 4 + r) * kOutStride + (wave * 16 * NT + nt * 16 + li) * 2) =
-            static_cast<uint16_t>(cs_bits<T>(v));
+            static_cast<uint16_t>(pvo_bits<T>(v));
       }
   __syncthreads();
   constexpr int kChunks = kCoutWG / 8;                        // 16-byte chunks per pixel
@@ -256,8 +220,8 @@ __global__ __launch_bounds__(256) void conv3x3_c128_kernel(const uint16_t* __res
     const int p = id / kChunks, c = id - p * kChunks;
     const int gy = y0 + (p >> 4), gx = x0 + (p & 15);
     if (gy < H && gx < W)
-      *reinterpret_cast<cs_u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * ystride + yoff + cg * kCoutWG + c * 8) =
-          *reinterpret_cast<const cs_u32x4*>(c3s + p * kOutStride + c * 16);
+      *reinterpret_cast<u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * ystride + yoff + cg * kCoutWG + c * 8) =
+          *reinterpret_cast<const u32x4*>(c3s + p * kOutStride + c * 16);
   }
 }
 
@@ -280,14 +244,6 @@ __global__ __launch_bounds__(256) void conv3x3_c128_kernel(const uint16_t* __res
 //   kernel the chip runs power-capped, and on random operands it holds a higher clock under the 16x16x32 loop
 //   (tools/mfma_shape_probe.hip).
 // ---------------------------------------------------------------------------
-typedef float cs_v16f __attribute__((ext_vector_type(16)));
-template <typename T> __device__ __forceinline__ cs_v16f cs_mfma32(cs_u32x4 a, cs_u32x4 b, cs_v16f c);
-template <> __device__ __forceinline__ cs_v16f cs_mfma32<pvo_half>(cs_u32x4 a, cs_u32x4 b, cs_v16f c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cs_v8h, a), __builtin_bit_cast(cs_v8h, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ cs_v16f cs_mfma32<pvo_bf16>(cs_u32x4 a, cs_u32x4 b, cs_v16f c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cs_v8b, a), __builtin_bit_cast(cs_v8b, b), c, 0, 0, 0);
-}
 
 // Optional fused ConvGRU epilogues (VO_Module/droid_slam/modules/gru.py:26-31) and a segmented input:
 //   mode 1 (gates, Cout = 256): channel group 0 -> y  = Z  = sigmoid(acc + g[e, c] + P[row, c])                [rows,128]
@@ -364,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
   const uint16_t* xe = x + static_cast<size_t>(e) * H * W * Cin;
 
   // global -> register -> LDS staging of the halo chunk needed next (6 x 16 B per thread)
-  cs_u32x4 ra[3];                                         // (three pieces at a time: registers)
+  u32x4 ra[3];                                         // (three pieces at a time: registers)
   int apix[6];                                            // pixel index of this thread's halo pieces inside the image, -1 = zero
 #pragma unroll
   for (int it = 0; it < 6; ++it) {
@@ -397,14 +353,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
   auto fetch_a = [&](int half) {                                   // pieces 3 half .. 3 half + 2
 #pragma unroll
     for (int k = 0; k < 3; ++k)
-      ra[k] = *reinterpret_cast<const cs_u32x4*>(a_src + static_cast<size_t>(max(apix[3 * half + k], 0)) * a_stride + a_coff + (tid & 3) * 8);
+      ra[k] = *reinterpret_cast<const u32x4*>(a_src + static_cast<size_t>(max(apix[3 * half + k], 0)) * a_stride + a_coff + (tid & 3) * 8);
   };
   auto store_a = [&](int buf, int half) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      cs_u32x4 v = ra[k];
-      if (apix[3 * half + k] < 0) v = cs_u32x4{0u, 0u, 0u, 0u};
-      *reinterpret_cast<cs_u32x4*>(As + buf * kBA + lpos(3 * half + k)) = v;
+      u32x4 v = ra[k];
+      if (apix[3 * half + k] < 0) v = u32x4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<u32x4*>(As + buf * kBA + lpos(3 * half + k)) = v;
     }
   };
 
@@ -416,7 +372,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
     for (int nt = 0; nt < 4; ++nt)
       ginit[nt] = ep.g[static_cast<size_t>(e) * 384 + (ep.mode == 1 ? cg * 128 : 256) + wn * 64 + nt * 16 + li];
   }
-  cs_v4f acc[8][4];
+  v4f acc[8][4];
 #pragma unroll
   for (int mt = 0; mt < 8; ++mt)
 #pragma unroll
@@ -430,26 +386,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
     // (workgroup-uniform base + a 32-bit lane offset: one address register instead of a 64-bit pointer per lane)
     const uint16_t* wf = wt + (static_cast<size_t>(cg) * S * 8 + wn * 4) * 512;
     const int lane_off = lane * 8;
-    cs_u32x4 bset[3][4];                                    // three rotating sets of the four N-tiles' fragments
-    auto fetch_bf = [&](cs_u32x4 (&r)[4], int s) {          // (clamped, unconditional: exact s_waitcnt vmcnt counts)
+    u32x4 bset[3][4];                                    // three rotating sets of the four N-tiles' fragments
+    auto fetch_bf = [&](u32x4 (&r)[4], int s) {          // (clamped, unconditional: exact s_waitcnt vmcnt counts)
       const uint16_t* p = wf + static_cast<size_t>(min(s, S - 1)) * 4096;
 #pragma unroll
-      for (int f = 0; f < 4; ++f) r[f] = *reinterpret_cast<const cs_u32x4*>(p + lane_off + f * 512);
+      for (int f = 0; f < 4; ++f) r[f] = *reinterpret_cast<const u32x4*>(p + lane_off + f * 512);
     };
     select_a(0);
     {
       // prologue: all six halo pieces of chunk 0 and the first two filter sets are requested together (the accumulators do
       // not exist yet, so the registers are there): ONE exposed memory latency in front of the loop instead of two
-      cs_u32x4 r6[6];
+      u32x4 r6[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k)
-        r6[k] = *reinterpret_cast<const cs_u32x4*>(a_src + static_cast<size_t>(max(apix[k], 0)) * a_stride + a_coff + (tid & 3) * 8);
+        r6[k] = *reinterpret_cast<const u32x4*>(a_src + static_cast<size_t>(max(apix[k], 0)) * a_stride + a_coff + (tid & 3) * 8);
       fetch_bf(bset[0], 0); fetch_bf(bset[1], 1);
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
-        cs_u32x4 v = r6[k];
-        if (apix[k] < 0) v = cs_u32x4{0u, 0u, 0u, 0u};
-        *reinterpret_cast<cs_u32x4*>(As + lpos(k)) = v;
+        u32x4 v = r6[k];
+        if (apix[k] < 0) v = u32x4{0u, 0u, 0u, 0u};
+        *reinterpret_cast<u32x4*>(As + lpos(k)) = v;
       }
     }
     __syncthreads();
@@ -466,17 +422,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
     // MFMAs; its waves wait at the same barriers, and the matrix cores they leave idle go to the second workgroup of the CU.
     auto main_loop = [&](auto nh_c) {
     constexpr int NH = decltype(nh_c)::value;
-    auto read_half = [&](cs_u32x4 (&a)[4], const unsigned char* Ac, int toff, int h) {
+    auto read_half = [&](u32x4 (&a)[4], const unsigned char* Ac, int toff, int h) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const cs_u32x4*>(Ac + toff + (4 * h + i) * 2 * kBStride);
+      for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const u32x4*>(Ac + toff + (4 * h + i) * 2 * kBStride);
     };
     // half 0 runs M-tile-major (its A fragments die one by one while the next half's arrive), the last half of a step
     // N-tile-major (the step's filter fragments die one by one while the next step's A fragments arrive)
-    auto mfma_half = [&](const cs_u32x4 (&a)[4], const cs_u32x4 (&bf)[4], int h, bool n_major) {
+    auto mfma_half = [&](const u32x4 (&a)[4], const u32x4 (&bf)[4], int h, bool n_major) {
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int i = n_major ? (j & 3) : (j >> 2), nt = n_major ? (j >> 2) : (j & 3);
-        acc[4 * h + i][nt] = cs_mfma<T>(a[i], bf[nt], acc[4 * h + i][nt]);
+        acc[4 * h + i][nt] = pvo_mfma<T>(a[i], bf[nt], acc[4 * h + i][nt]);
       }
     };
     // issue order inside a half-step: one LDS read / global load / LDS write behind every one or two MFMAs (an MFMA holds
@@ -504,7 +460,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
       const unsigned char* Ac = Abase + (cc & 1) * kBA;
       select_a(min(cc + 1, nC - 1));                        // next chunk's halo: two halves, each in flight for three taps
       fetch_a(0);
-      cs_u32x4 a0[4], a1[4];
+      u32x4 a0[4], a1[4];
       read_half(a0, Ac, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -512,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
         const int toff = ((t / 3) * kBPitch + (t % 3)) * kBStride;                     // compile-time: ds_read immediates
         const int toff1 = (((t + 1) / 3) * kBPitch + ((t + 1) % 3)) * kBStride;
         fetch_bf(bset[(t + 2) % 3], cc * 9 + t + 2);
-        const cs_u32x4 (&bf)[4] = bset[t % 3];
+        const u32x4 (&bf)[4] = bset[t % 3];
         if (NH == 2) {
           read_half(a1, Ac, toff, 1);
           mfma_half(a0, bf, 0, false);
@@ -525,8 +481,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
           if (t < 8) pin_reads();
           pin_staging(t);
         } else {
-          cs_u32x4 (&cur)[4] = (t & 1) ? a1 : a0;
-          cs_u32x4 (&nxt)[4] = (t & 1) ? a0 : a1;
+          u32x4 (&cur)[4] = (t & 1) ? a1 : a0;
+          u32x4 (&nxt)[4] = (t & 1) ? a0 : a1;
           if (t < 8) read_half(nxt, Ac, toff1, 0);
           if (t == 3) { store_a((cc + 1) & 1, 0); fetch_a(1); }
           if (t == 7) store_a((cc + 1) & 1, 1);
@@ -561,7 +517,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
     const uint16_t* gate_p = ep.P + (ep.mode == 1 ? cg * 128 : 0) + c * 8;
     uint16_t* const dst = (ep.mode == 1 && cg != 0) ? ep.y2 : y;
     const int ep_ = ep.p_slots ? ep.p_slots[e] : e;         // image of the static term (workgroup-uniform)
-    cs_u32x4 pv[4], nv[4], zv[4];
+    u32x4 pv[4], nv[4], zv[4];
     auto request = [&](int half, int b) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -570,9 +526,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
         const bool in = gy < H && gx < W;
         const size_t rr = in ? (static_cast<size_t>(e) * H + gy) * W + gx : 0;      // a valid address either way; the value is dropped
         const size_t rp = in ? (static_cast<size_t>(ep_) * H + gy) * W + gx : 0;
-        pv[k] = *reinterpret_cast<const cs_u32x4*>(gate_p + rp * pstride);
-        nv[k] = *reinterpret_cast<const cs_u32x4*>(ep.net + rr * 128 + c * 8);
-        if (ep.mode == 2) zv[k] = *reinterpret_cast<const cs_u32x4*>(ep.Z + rr * 128 + c * 8);
+        pv[k] = *reinterpret_cast<const u32x4*>(gate_p + rp * pstride);
+        nv[k] = *reinterpret_cast<const u32x4*>(ep.net + rr * 128 + c * 8);
+        if (ep.mode == 2) zv[k] = *reinterpret_cast<const u32x4*>(ep.Z + rr * 128 + c * 8);
       }
     };
     auto finish = [&](int half, int b) {
@@ -583,8 +539,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
         float a[8], pp[8], nn[8], o[8];
         const float4 a0 = *reinterpret_cast<const float4*>(slab + m * 132 + c * 8), a1 = *reinterpret_cast<const float4*>(slab + m * 132 + c * 8 + 4);
         a[0] = a0.x; a[1] = a0.y; a[2] = a0.z; a[3] = a0.w; a[4] = a1.x; a[5] = a1.y; a[6] = a1.z; a[7] = a1.w;
-        cs_unpack8<T>(pv[k], pp);
-        cs_unpack8<T>(nv[k], nn);
+        pvo_unpack8<T>(pv[k], pp);
+        pvo_unpack8<T>(nv[k], nn);
         if (ep.mode == 1) {
           // sigmoid = 1 / (1 + 2^(-x log2 e)) on the raw v_exp_f32 / v_rcp_f32 (1 ulp each; exp -> inf gives 0, exp -> 0 gives 1:
           // the library exp's denormal-range rescaling - two selects, an add and a multiply per value - buys nothing here)
@@ -596,7 +552,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
           }
         } else {
           float zz[8];
-          cs_unpack8<T>(zv[k], zz);
+          pvo_unpack8<T>(zv[k], zz);
 #pragma unroll
           for (int q = 0; q < 8; ++q) {
             // tanh(x) = 1 - 2 / (1 + exp(2x)): exact limits at both ends (exp -> inf gives 1, exp -> 0 gives -1), ~1e-6
@@ -605,7 +561,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
             o[q] = (1.0f - zz[q]) * nn[q] + zz[q] * th;
           }
         }
-        if (gy < H && gx < W) *reinterpret_cast<cs_u32x4*>(dst + ((static_cast<size_t>(e) * H + gy) * W + gx) * 128 + c * 8) = cs_pack8<T>(o);
+        if (gy < H && gx < W) *reinterpret_cast<u32x4*>(dst + ((static_cast<size_t>(e) * H + gy) * W + gx) * 128 + c * 8) = pvo_pack8<T>(o);
       }
     };
 #pragma unroll 1
@@ -637,10 +593,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
   for (int nt = 0; nt < 4; ++nt) bb[nt] = bias ? bias[cg * 128 + wn * 64 + nt * 16 + li] : 0.0f;
   unsigned char* w2s = bs + 36 * 1024;                      // mode 3: this head's second-stage fragments (8 KB) above the slab
   if (HEADS) {
-    const cs_u32x4* src = reinterpret_cast<const cs_u32x4*>(ep.w2f + static_cast<size_t>(cg) * 4096) + tid;
-    const cs_u32x4 f0 = src[0], f1 = src[256];
-    *reinterpret_cast<cs_u32x4*>(w2s + tid * 16) = f0;        // (the main loop's last barrier is behind every wave: the halo is dead)
-    *reinterpret_cast<cs_u32x4*>(w2s + 4096 + tid * 16) = f1;
+    const u32x4* src = reinterpret_cast<const u32x4*>(ep.w2f + static_cast<size_t>(cg) * 4096) + tid;
+    const u32x4 f0 = src[0], f1 = src[256];
+    *reinterpret_cast<u32x4*>(w2s + tid * 16) = f0;        // (the main loop's last barrier is behind every wave: the halo is dead)
+    *reinterpret_cast<u32x4*>(w2s + 4096 + tid * 16) = f1;
   }
 #pragma unroll 1
   for (int half = 0; half < 2; ++half) {
@@ -654,20 +610,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
             const int m = big_pix(mt, 4 * kg + r);                                 // pixel inside this wave-row's 8 x 16 block
             float v = acc[mt][nt][r] + bb[nt];
             if (relu) v = fmaxf(v, 0.0f);
-            *reinterpret_cast<uint16_t*>(bs + m * 272 + (wn * 64 + nt * 16 + li) * 2) = static_cast<uint16_t>(cs_bits<T>(v));
+            *reinterpret_cast<uint16_t*>(bs + m * 272 + (wn * 64 + nt * 16 + li) * 2) = static_cast<uint16_t>(pvo_bits<T>(v));
           }
     }
     __syncthreads();
     if (HEADS) {
       // wave w takes rows 32 w .. 32 w + 31 of the slab: Z[32 px][32 (18 used)] = hidden[32 px][128] . W2'[128][32]
-      cs_v16f zz;
+      v16f zz;
 #pragma unroll
       for (int r = 0; r < 16; ++r) zz[r] = 0.0f;
       const int l32 = lane & 31, k32 = lane >> 5;            // (32x32 operand / D layout: column l32, k-group / row group k32)
       const unsigned char* arow = bs + (32 * wave + l32) * 272 + k32 * 16;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks)
-        zz = cs_mfma32<T>(*reinterpret_cast<const cs_u32x4*>(arow + ks * 32), *reinterpret_cast<const cs_u32x4*>(w2s + (ks * 64 + lane) * 16), zz);
+        zz = pvo_mfma32<T>(*reinterpret_cast<const u32x4*>(arow + ks * 32), *reinterpret_cast<const u32x4*>(w2s + (ks * 64 + lane) * 16), zz);
       if (l32 < 18) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -681,8 +637,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_big_kernel(const uint16_t* __r
         const int m = id >> 4, c = id & 15;
         const int gy = y0 + 8 * half + (m >> 4), gx = x0 + (m & 15);
         if (gy < H && gx < W)
-          *reinterpret_cast<cs_u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * ystride + yoff + cg * 128 + c * 8) =
-              *reinterpret_cast<const cs_u32x4*>(bs + m * 272 + c * 16);
+          *reinterpret_cast<u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * ystride + yoff + cg * 128 + c * 8) =
+              *reinterpret_cast<const u32x4*>(bs + m * 272 + c * 16);
       }
     }
     __syncthreads();
@@ -724,20 +680,20 @@ __global__ __launch_bounds__(256) void flow_encoder_kernel(const uint16_t* __res
 
   // ---- stage 1: 7x7, 8 -> 128 channels, on the 10 x 16 positions (y0 - 1 .., x0 - 1 ..); wave w owns channels [32w, 32w + 32)
   {
-    cs_u32x4 bf[kSteps][2];
+    u32x4 bf[kSteps][2];
 #pragma unroll
     for (int s = 0; s < kSteps; ++s)
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
-        bf[s][nt] = *reinterpret_cast<const cs_u32x4*>(w7 + (static_cast<size_t>(4 * s + lk) * 128 + wave * 32 + nt * 16 + li) * 8);
+        bf[s][nt] = *reinterpret_cast<const u32x4*>(w7 + (static_cast<size_t>(4 * s + lk) * 128 + wave * 32 + nt * 16 + li) * 8);
     const uint16_t* xe = x + static_cast<size_t>(e) * H * W * 8;
     for (int pos = tid; pos < kFeM7Pos; pos += 256) {
       const int hy = y0 - 1 - kR + pos / kFeM7W, hx = x0 - 1 - kR + pos % kFeM7W;
-      cs_u32x4 v = {0u, 0u, 0u, 0u};
-      if (hy >= 0 && hy < H && hx >= 0 && hx < W) v = *reinterpret_cast<const cs_u32x4*>(xe + (static_cast<size_t>(hy) * W + hx) * 8);
-      *reinterpret_cast<cs_u32x4*>(halo + pos * 16) = v;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (hy >= 0 && hy < H && hx >= 0 && hx < W) v = *reinterpret_cast<const u32x4*>(xe + (static_cast<size_t>(hy) * W + hx) * 8);
+      *reinterpret_cast<u32x4*>(halo + pos * 16) = v;
     }
-    if (tid < 2 * 17) *reinterpret_cast<cs_u32x4*>(f1 + kFeRows * 16 * kC3Stride + tid * 16) = cs_u32x4{0u, 0u, 0u, 0u};
+    if (tid < 2 * 17) *reinterpret_cast<u32x4*>(f1 + kFeRows * 16 * kC3Stride + tid * 16) = u32x4{0u, 0u, 0u, 0u};
     int toff[kSteps];
 #pragma unroll
     for (int s = 0; s < kSteps; ++s) {
@@ -748,17 +704,17 @@ __global__ __launch_bounds__(256) void flow_encoder_kernel(const uint16_t* __res
     __syncthreads();
     for (int r = 0; r < kFeRows; ++r) {
       const int gy = y0 - 1 + r;
-      cs_v4f d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+      v4f d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
       const bool row_in = gy >= 0 && gy < H;                   // (uniform)
       if (row_in) {
         const unsigned char* rowp = halo + r * kFeM7W * 16;
-        cs_u32x4 afr[kSteps];
+        u32x4 afr[kSteps];
 #pragma unroll
-        for (int s = 0; s < kSteps; ++s) afr[s] = *reinterpret_cast<const cs_u32x4*>(rowp + toff[s]);
+        for (int s = 0; s < kSteps; ++s) afr[s] = *reinterpret_cast<const u32x4*>(rowp + toff[s]);
 #pragma unroll
         for (int s = 0; s < kSteps; ++s) {
-          d0 = cs_mfma<T>(afr[s], bf[s][0], d0);
-          d1 = cs_mfma<T>(afr[s], bf[s][1], d1);
+          d0 = pvo_mfma<T>(afr[s], bf[s][0], d0);
+          d1 = pvo_mfma<T>(afr[s], bf[s][1], d1);
         }
       }
 #pragma unroll
@@ -766,8 +722,8 @@ __global__ __launch_bounds__(256) void flow_encoder_kernel(const uint16_t* __res
         const int p = lk * 4 + q, gx = x0 - 1 + p;
         const bool in = row_in && gx >= 0 && gx < W;
         unsigned char* dst = f1 + (r * 16 + p) * kC3Stride + (wave * 32 + li) * 2;
-        *reinterpret_cast<uint16_t*>(dst) = in ? static_cast<uint16_t>(cs_bits<T>(fmaxf(d0[q] + bb0, 0.0f))) : static_cast<uint16_t>(0);
-        *reinterpret_cast<uint16_t*>(dst + 32) = in ? static_cast<uint16_t>(cs_bits<T>(fmaxf(d1[q] + bb1, 0.0f))) : static_cast<uint16_t>(0);
+        *reinterpret_cast<uint16_t*>(dst) = in ? static_cast<uint16_t>(pvo_bits<T>(fmaxf(d0[q] + bb0, 0.0f))) : static_cast<uint16_t>(0);
+        *reinterpret_cast<uint16_t*>(dst + 32) = in ? static_cast<uint16_t>(pvo_bits<T>(fmaxf(d1[q] + bb1, 0.0f))) : static_cast<uint16_t>(0);
       }
     }
   }
@@ -775,26 +731,26 @@ __global__ __launch_bounds__(256) void flow_encoder_kernel(const uint16_t* __res
   const int co0 = wave * 16;
   const uint16_t* wl = w3 + (static_cast<size_t>(co0 + li)) * 128 + lk * 8;
   constexpr size_t tap_stride = static_cast<size_t>(64) * 128;
-  cs_u32x4 bcur[4], bnxt[4];
+  u32x4 bcur[4], bnxt[4];
 #pragma unroll
-  for (int kc = 0; kc < 4; ++kc) bcur[kc] = *reinterpret_cast<const cs_u32x4*>(wl + kc * 32);
-  cs_v4f acc[kTH];
+  for (int kc = 0; kc < 4; ++kc) bcur[kc] = *reinterpret_cast<const u32x4*>(wl + kc * 32);
+  v4f acc[kTH];
 #pragma unroll
-  for (int py = 0; py < kTH; ++py) acc[py] = cs_v4f{0.f, 0.f, 0.f, 0.f};
+  for (int py = 0; py < kTH; ++py) acc[py] = v4f{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
 #pragma unroll 1
   for (int t = 0; t < 9; ++t) {
     if (t < 8) {
 #pragma unroll
-      for (int kc = 0; kc < 4; ++kc) bnxt[kc] = *reinterpret_cast<const cs_u32x4*>(wl + (t + 1) * tap_stride + kc * 32);
+      for (int kc = 0; kc < 4; ++kc) bnxt[kc] = *reinterpret_cast<const u32x4*>(wl + (t + 1) * tap_stride + kc * 32);
     }
     const unsigned char* tp = f1 + ((t / 3) * 16 + (t % 3) + li) * kC3Stride + lk * 16;
 #pragma unroll
     for (int py = 0; py < kTH; ++py) {
 #pragma unroll
       for (int kc = 0; kc < 4; ++kc) {
-        const cs_u32x4 a = *reinterpret_cast<const cs_u32x4*>(tp + py * 16 * kC3Stride + kc * 64);
-        acc[py] = cs_mfma<T>(a, bcur[kc], acc[py]);
+        const u32x4 a = *reinterpret_cast<const u32x4*>(tp + py * 16 * kC3Stride + kc * 64);
+        acc[py] = pvo_mfma<T>(a, bcur[kc], acc[py]);
       }
     }
     if (t < 8) {
@@ -810,14 +766,14 @@ __global__ __launch_bounds__(256) void flow_encoder_kernel(const uint16_t* __res
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       *reinterpret_cast<uint16_t*>(f1 + (py * 16 + lk * 4 + q) * kOutStride + (co0 + li) * 2) =
-          static_cast<uint16_t>(cs_bits<T>(fmaxf(acc[py][q] + bb, 0.0f)));
+          static_cast<uint16_t>(pvo_bits<T>(fmaxf(acc[py][q] + bb, 0.0f)));
   __syncthreads();
   for (int id = tid; id < kTH * 16 * 8; id += 256) {           // 8 chunks of 16 B per pixel
     const int p = id >> 3, c = id & 7;
     const int px = p & 15, gy = y0 + (p >> 4), gx = x0 + px;
     if (px < kFeOW && gy < H && gx < W)
-      *reinterpret_cast<cs_u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * ystride + yoff + c * 8) =
-          *reinterpret_cast<const cs_u32x4*>(f1 + p * kOutStride + c * 16);
+      *reinterpret_cast<u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * ystride + yoff + c * 8) =
+          *reinterpret_cast<const u32x4*>(f1 + p * kOutStride + c * 16);
   }
 }
 
@@ -834,19 +790,16 @@ extern "C" int pvo_conv7x7_c8(const void* x, const void* w_taps, const float* bi
   if (E < 0 || H < 0 || W < 0) return PVO_EINVAL;
   if (E == 0 || H == 0 || W == 0) return PVO_OK;
   if (!x || !w_taps || !bias || !y || E > 65535) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_taps) | reinterpret_cast<uintptr_t>(y)) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(x, w_taps, y)) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   dim3 grid((W + kTW - 1) / kTW, (H + kTH7 - 1) / kTH7, E);
-  if (dtype == PVO_F16)
-    hipLaunchKernelGGL(conv7x7_c8_kernel<pvo_half>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x),
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(conv7x7_c8_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x),
                        static_cast<const uint16_t*>(w_taps), bias, static_cast<uint16_t*>(y), H, W);
-  else if (dtype == PVO_BF16)
-    hipLaunchKernelGGL(conv7x7_c8_kernel<pvo_bf16>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x),
-                       static_cast<const uint16_t*>(w_taps), bias, static_cast<uint16_t*>(y), H, W);
-  else
-    return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_flow_encoder(const void* x, const void* w7_taps, const float* bias7, const void* w3_taps, const float* bias3,
@@ -856,26 +809,17 @@ extern "C" int pvo_flow_encoder(const void* x, const void* w7_taps, const float*
   if (ystride < yoff + 64 || yoff < 0 || (ystride & 7) || (yoff & 7)) return PVO_EINVAL;
   if (E == 0 || H == 0 || W == 0) return PVO_OK;
   if (!x || !w7_taps || !bias7 || !w3_taps || !y || E > 65535) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w7_taps) | reinterpret_cast<uintptr_t>(w3_taps) | reinterpret_cast<uintptr_t>(y)) & 15)
-    return PVO_EINVAL;
+  if (pvo_misaligned16(x, w7_taps, w3_taps, y)) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   const dim3 grid((W + kFeOW - 1) / kFeOW, (H + kTH - 1) / kTH, E);
   const uint16_t *xp = static_cast<const uint16_t*>(x), *w7 = static_cast<const uint16_t*>(w7_taps), *w3 = static_cast<const uint16_t*>(w3_taps);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(flow_encoder_kernel<pvo_half>), hipFuncAttributeMaxDynamicSharedMemorySize, kFeLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(flow_encoder_kernel<pvo_bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, kFeLds) != hipSuccess)
-      return PVO_ELAUNCH;
-    attr_set = true;
-  }
-  if (dtype == PVO_F16)
-    hipLaunchKernelGGL(flow_encoder_kernel<pvo_half>, grid, dim3(256), kFeLds, st, xp, w7, bias7, w3, bias3, static_cast<uint16_t*>(y), H, W, ystride, yoff);
-  else if (dtype == PVO_BF16)
-    hipLaunchKernelGGL(flow_encoder_kernel<pvo_bf16>, grid, dim3(256), kFeLds, st, xp, w7, bias7, w3, bias3, static_cast<uint16_t*>(y), H, W, ystride, yoff);
-  else
-    return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (!pvo_allow_lds<flow_encoder_kernel<T>>(kFeLds)) return PVO_ELAUNCH;
+    hipLaunchKernelGGL(flow_encoder_kernel<T>, grid, dim3(256), kFeLds, st, xp, w7, bias7, w3, bias3, static_cast<uint16_t*>(y), H, W, ystride, yoff);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_gru_glo_chunks(int HW) { return HW <= 0 ? 0 : (HW + 255) / 256; }
@@ -885,20 +829,17 @@ extern "C" int pvo_gru_glo_fused(const void* net, const void* w_weight, const fl
   if (E < 0 || HW < 0) return PVO_EINVAL;
   if (E == 0 || HW == 0) return PVO_OK;
   if (!net || !w_weight || !glo_part || E > 65535) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(net) | reinterpret_cast<uintptr_t>(w_weight)) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(net, w_weight)) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   const int chunk = 256;
   dim3 grid(pvo_gru_glo_chunks(HW), E);
-  if (dtype == PVO_F16)
-    hipLaunchKernelGGL(gru_glo_mfma_kernel<pvo_half>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(net),
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(gru_glo_mfma_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(net),
                        static_cast<const uint16_t*>(w_weight), w_bias, glo_part, HW, chunk);
-  else if (dtype == PVO_BF16)
-    hipLaunchKernelGGL(gru_glo_mfma_kernel<pvo_bf16>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(net),
-                       static_cast<const uint16_t*>(w_weight), w_bias, glo_part, HW, chunk);
-  else
-    return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_conv3x3_c128(const void* x, const void* w_taps, const float* bias, void* y,
@@ -909,26 +850,25 @@ extern "C" int pvo_conv3x3_c128(const void* x, const void* w_taps, const float* 
   if (ystride < yoff + Cout || yoff < 0 || (ystride & 7) || (yoff & 7)) return PVO_EINVAL;
   if (E == 0 || H == 0 || W == 0) return PVO_OK;
   if (!x || !w_taps || !y || E > 65535) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_taps) | reinterpret_cast<uintptr_t>(y)) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(x, w_taps, y)) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   const int ntx = (W + kTW - 1) / kTW;
   const size_t lds = static_cast<size_t>(kC3Halo) * kC3Stride;      // 48960 B >= the output slab (128 px x 272 B)
   const uint16_t* xp = static_cast<const uint16_t*>(x);
   const uint16_t* wp = static_cast<const uint16_t*>(w_taps);
   uint16_t* yp = static_cast<uint16_t*>(y);
-  if (Cout == 64) {
-    dim3 grid(ntx, (H + kTH - 1) / kTH, E);
-    if (dtype == PVO_F16) hipLaunchKernelGGL((conv3x3_c128_kernel<pvo_half, 1>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cout, relu, ystride, yoff);
-    else if (dtype == PVO_BF16) hipLaunchKernelGGL((conv3x3_c128_kernel<pvo_bf16, 1>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cout, relu, ystride, yoff);
-    else return PVO_EUNSUPPORTED;
-  } else {
-    dim3 grid(ntx * (Cout / 128), (H + kTH - 1) / kTH, E);
-    if (dtype == PVO_F16) hipLaunchKernelGGL((conv3x3_c128_kernel<pvo_half, 2>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cout, relu, ystride, yoff);
-    else if (dtype == PVO_BF16) hipLaunchKernelGGL((conv3x3_c128_kernel<pvo_bf16, 2>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cout, relu, ystride, yoff);
-    else return PVO_EUNSUPPORTED;
-  }
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (Cout == 64) {
+      dim3 grid(ntx, (H + kTH - 1) / kTH, E);
+      hipLaunchKernelGGL((conv3x3_c128_kernel<T, 1>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cout, relu, ystride, yoff);
+    } else {
+      dim3 grid(ntx * (Cout / 128), (H + kTH - 1) / kTH, E);
+      hipLaunchKernelGGL((conv3x3_c128_kernel<T, 2>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cout, relu, ystride, yoff);
+    }
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 static int launch_big(const void* x, const void* w_taps, const float* bias, void* y,
@@ -940,7 +880,7 @@ static int launch_big(const void* x, const void* w_taps, const float* bias, void
   if (ystride < yoff + Cout || yoff < 0 || (ystride & 7) || (yoff & 7)) return PVO_EINVAL;
   if (E == 0 || H == 0 || W == 0) return PVO_OK;
   if (!x || !w_taps || !y || E > 65535) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_taps) | reinterpret_cast<uintptr_t>(y)) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(x, w_taps, y)) return PVO_EINVAL;
   if (static_cast<long long>(H) * W * Cin > 0x7fffffffLL) return PVO_EUNSUPPORTED;
   hipStream_t st = pvo_stream(stream);
   const int ntx = (W + kBT - 1) / kBT;
@@ -949,23 +889,18 @@ static int launch_big(const void* x, const void* w_taps, const float* bias, void
   const uint16_t* xp = static_cast<const uint16_t*>(x);
   const uint16_t* wp = static_cast<const uint16_t*>(w_taps);
   uint16_t* yp = static_cast<uint16_t*>(y);
-  static bool attr_set[4] = {false, false, false, false};  // hipFuncSetAttribute once per process, not per launch
-  auto go = [&](auto kernel, int slot) -> int {
-    if (!attr_set[slot]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) return PVO_ELAUNCH;
-      attr_set[slot] = true;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (ep.mode == 3) {                                     // the output heads' fused second stage
+      if (!pvo_allow_lds<conv3x3_big_kernel<T, true>>(lds)) return PVO_ELAUNCH;
+      hipLaunchKernelGGL((conv3x3_big_kernel<T, true>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cin, Cout, relu, ystride, yoff, ep);
+    } else {
+      if (!pvo_allow_lds<conv3x3_big_kernel<T, false>>(lds)) return PVO_ELAUNCH;
+      hipLaunchKernelGGL((conv3x3_big_kernel<T, false>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cin, Cout, relu, ystride, yoff, ep);
     }
-    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cin, Cout, relu, ystride, yoff, ep);
+    PVO_CHECK_LAUNCH();
     return PVO_OK;
-  };
-  const bool heads = ep.mode == 3;
-  int rc;
-  if (dtype == PVO_F16) rc = heads ? go(conv3x3_big_kernel<pvo_half, true>, 2) : go(conv3x3_big_kernel<pvo_half, false>, 0);
-  else if (dtype == PVO_BF16) rc = heads ? go(conv3x3_big_kernel<pvo_bf16, true>, 3) : go(conv3x3_big_kernel<pvo_bf16, false>, 1);
-  else return PVO_EUNSUPPORTED;
-  if (rc != PVO_OK) return rc;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  });
 }
 
 extern "C" int pvo_conv3x3(const void* x, const void* w_taps, const float* bias, void* y,
@@ -975,7 +910,7 @@ extern "C" int pvo_conv3x3(const void* x, const void* w_taps, const float* bias,
 
 extern "C" int pvo_conv3x3_heads(const void* x, const void* w1_taps, const float* bias1, const void* w2_frags, float* z,
                                  int E, int H, int W, int dtype, void* stream) {
-  if (!bias1 || !w2_frags || !z || (reinterpret_cast<uintptr_t>(w2_frags) & 15)) return PVO_EINVAL;
+  if (!bias1 || !w2_frags || !z || pvo_misaligned16(w2_frags)) return PVO_EINVAL;
   BigEpi ep{};
   ep.mode = 3; ep.w2f = static_cast<const uint16_t*>(w2_frags); ep.z = z;
   return launch_big(x, w1_taps, bias1, z, E, H, W, 128, 512, 1, 0, 0, dtype, stream, ep);      // (y is not written in this mode)
@@ -985,7 +920,7 @@ extern "C" int pvo_conv3x3_heads(const void* x, const void* w1_taps, const float
 // encoders' output written side by side (relu(corr features) | relu(flow features)) by their own convolutions
 static int seg_setup(BigEpi& ep, const void* first, const void* cf, int cf_channels) {
   if (!first || !cf) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(first) | reinterpret_cast<uintptr_t>(cf)) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(first, cf)) return PVO_EINVAL;
   if (cf_channels <= 0 || (cf_channels & 31)) return PVO_EUNSUPPORTED;
   ep.nseg = 2;
   ep.seg_p[0] = static_cast<const uint16_t*>(first); ep.seg_stride[0] = 128; ep.seg_chunks[0] = 4;
@@ -996,7 +931,7 @@ static int seg_setup(BigEpi& ep, const void* first, const void* cf, int cf_chann
 extern "C" int pvo_gru_conv_gates(const void* net, const void* cf, int cf_channels, const void* w_taps, const float* g,
                                   const void* P_zr, const int* p_slots, void* Z, void* RN, int E, int H, int W, int dtype, void* stream) {
   if (!g || !P_zr || !RN) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(P_zr) | reinterpret_cast<uintptr_t>(RN)) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(P_zr, RN)) return PVO_EINVAL;
   BigEpi ep{};
   const int rc = seg_setup(ep, net, cf, cf_channels);
   if (rc != PVO_OK) return rc;
@@ -1009,7 +944,7 @@ extern "C" int pvo_gru_conv_candidate(const void* RN, const void* cf, int cf_cha
                                       const void* P_q, const int* p_slots, const void* Z, const void* net, void* net_out,
                                       int E, int H, int W, int dtype, void* stream) {
   if (!g || !P_q || !net || !Z) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(P_q) | reinterpret_cast<uintptr_t>(net) | reinterpret_cast<uintptr_t>(Z)) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(P_q, net, Z)) return PVO_EINVAL;
   BigEpi ep{};
   const int rc = seg_setup(ep, RN, cf, cf_channels);
   if (rc != PVO_OK) return rc;

@@ -20,14 +20,9 @@
 //   right / bottom border are dropped, as avg_pool2d does).
 // generic path (fp32 / fp64 / odd C, NCHW or NHWC): LDS-tiled FMA GEMM + one pooling launch
 //   per level.  Used by the fp32 training configuration and as the layout-agnostic fallback.
-#include "common.h"
+#include "operand16.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-typedef __bf16 v8b __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPatchH = 8, kPatchW = 32, kPatchPix = kPatchH * kPatchW;  // 256 target pixels
 constexpr int kTileM = 128;                                              // source pixels per workgroup
@@ -41,38 +36,13 @@ struct BuildArgs {
   int tiled;                        // level l stored [N, HW, ceil(Hl/8), ceil(Wl/8), 8, 8] (see corr_lookup.hip)
 };
 
-template <typename T> struct Cvt16;
-template <> struct Cvt16<pvo_half> {
-  static __device__ __forceinline__ uint32_t bits(float x) {
-    union { _Float16 h; uint16_t u; } c; c.h = static_cast<_Float16>(x); return c.u;
-  }
-  static __device__ __forceinline__ float val(uint32_t b) {
-    union { _Float16 h; uint16_t u; } c; c.u = static_cast<uint16_t>(b); return static_cast<float>(c.h);
-  }
-  static __device__ __forceinline__ v16f mfma(u32x4 a, u32x4 b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), c, 0, 0, 0);
-  }
-};
-template <> struct Cvt16<pvo_bf16> {
-  static __device__ __forceinline__ uint32_t bits(float x) { return pvo_f32_to_bf16(x); }
-  static __device__ __forceinline__ float val(uint32_t b) { return pvo_bf16_to_f32(static_cast<uint16_t>(b)); }
-  static __device__ __forceinline__ v16f mfma(u32x4 a, u32x4 b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8b, a), __builtin_bit_cast(v8b, b), c, 0, 0, 0);
-  }
-};
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-
 // pooled = round16(((a + b) + c) + d) / 4), ATen avg_pool2d window order (kh, kw)
 template <typename T>
 __device__ __forceinline__ float pool4(float a, float b, float c, float d) {
   float s = ((a + b) + c) + d;
   s *= 0.25f;
   asm volatile("" : "+v"(s));           // keep the fp32 rounding before the 16-bit one (no mixlo fusion)
-  return Cvt16<T>::val(Cvt16<T>::bits(s));
+  return pvo_round<T>(s);
 }
 
 template <typename T>
@@ -136,7 +106,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const u32x4 b = *reinterpret_cast<const u32x4*>(smem + (t * 32 + (lane & 31)) * rowB + (s * 16 + kg * 8) * 2);
-        acc[t] = Cvt16<T>::mfma(afrag[s], b, acc[t]);
+        acc[t] = pvo_mfma32<T>(afrag[s], b, acc[t]);
       }
     }
   }
@@ -171,8 +141,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     for (int t = 0; t < 8; ++t) {
       float sc = acc[t][r] * 0.0625f;                // (f1/4).(f2/4)
       asm volatile("" : "+v"(sc));
-      const uint32_t bb = Cvt16<T>::bits(sc);
-      v0[t] = Cvt16<T>::val(bb);
+      const uint32_t bb = pvo_bits<T>(sc);
+      v0[t] = pvo_val<T>(bb);
       *reinterpret_cast<uint16_t*>(slab0 + mrow * RS0 + (t * 32 + x2l) * 2) = static_cast<uint16_t>(bb);
     }
     // level 1: patch rows (2q, 2q+1), lanes (x, x^1); level 2: rows (2q,2q+1) of level 1, lanes (x, x^2);
@@ -180,21 +150,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     float v1[4], v2[2];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      v1[q] = pool4<T>(v0[2 * q], dpp_f<0xB1>(v0[2 * q]), v0[2 * q + 1], dpp_f<0xB1>(v0[2 * q + 1]));
+      v1[q] = pool4<T>(v0[2 * q], pvo_dpp_move<0xB1>(v0[2 * q]), v0[2 * q + 1], pvo_dpp_move<0xB1>(v0[2 * q + 1]));
       if ((lane & 1) == 0)
-        *reinterpret_cast<uint16_t*>(slab1 + mrow * RS1 + (q * 16 + (x2l >> 1)) * 2) = static_cast<uint16_t>(Cvt16<T>::bits(v1[q]));
+        *reinterpret_cast<uint16_t*>(slab1 + mrow * RS1 + (q * 16 + (x2l >> 1)) * 2) = static_cast<uint16_t>(pvo_bits<T>(v1[q]));
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      v2[q] = pool4<T>(v1[2 * q], dpp_f<0x4E>(v1[2 * q]), v1[2 * q + 1], dpp_f<0x4E>(v1[2 * q + 1]));
+      v2[q] = pool4<T>(v1[2 * q], pvo_dpp_move<0x4E>(v1[2 * q]), v1[2 * q + 1], pvo_dpp_move<0x4E>(v1[2 * q + 1]));
       if ((lane & 3) == 0)
-        *reinterpret_cast<uint16_t*>(slab2 + mrow * RS2 + (q * 8 + (x2l >> 2)) * 2) = static_cast<uint16_t>(Cvt16<T>::bits(v2[q]));
+        *reinterpret_cast<uint16_t*>(slab2 + mrow * RS2 + (q * 8 + (x2l >> 2)) * 2) = static_cast<uint16_t>(pvo_bits<T>(v2[q]));
     }
     {
       const float n0 = __shfl_xor(v2[0], 4, 64), n1 = __shfl_xor(v2[1], 4, 64);
       const float v3 = pool4<T>(v2[0], n0, v2[1], n1);
       if ((lane & 7) == 0)
-        *reinterpret_cast<uint16_t*>(slab3 + mrow * RS3 + (x2l >> 3) * 2) = static_cast<uint16_t>(Cvt16<T>::bits(v3));
+        *reinterpret_cast<uint16_t*>(slab3 + mrow * RS3 + (x2l >> 3) * 2) = static_cast<uint16_t>(pvo_bits<T>(v3));
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -422,10 +392,7 @@ int build_mfma(const BuildArgs& a, hipStream_t st) {
   const size_t lds_in = static_cast<size_t>(kPatchPix) * (a.C * 2 + 16);
   const size_t lds_out = 4 * 16 * static_cast<size_t>((kPatchPix * 2 + 16) + (64 * 2 + 16) + (16 * 2 + 16) + 16);      // half-size slabs: two passes
   const size_t lds = lds_in > lds_out ? lds_in : lds_out;
-  if (lds > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(corr_build_mfma_kernel<T>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) return PVO_ELAUNCH;
-  }
+  if (lds > 48 * 1024 && !pvo_allow_lds<corr_build_mfma_kernel<T>>(lds)) return PVO_ELAUNCH;      // (lds grows with C)
   const int npatch = ((a.H + kPatchH - 1) / kPatchH) * ((a.W + kPatchW - 1) / kPatchW);
   dim3 grid((HW + kTileM - 1) / kTileM, npatch, a.N);
   hipLaunchKernelGGL(corr_build_mfma_kernel<T>, grid, dim3(256), lds, st, a);
@@ -440,19 +407,17 @@ extern "C" int pvo_corr_build_tiled(const void* fmap1, const void* fmap2, void* 
   if (N < 0 || C <= 0 || H < 0 || W < 0 || !levels_host) return PVO_EINVAL;
   if (N == 0 || H == 0 || W == 0) return PVO_OK;
   if (!fmap1 || !fmap2 || N > 65535) return PVO_EINVAL;
-  uintptr_t al = reinterpret_cast<uintptr_t>(fmap1) | reinterpret_cast<uintptr_t>(fmap2);
-  for (int l = 0; l < 4; ++l) {
+  for (int l = 0; l < 4; ++l)
     if (!levels_host[l]) return PVO_EINVAL;
-    al |= reinterpret_cast<uintptr_t>(levels_host[l]);
-  }
   // the tiled writer is the matrix-core kernel's aligned epilogue
-  if ((dtype != PVO_F16 && dtype != PVO_BF16) || C < 16 || C > kMaxC || (C & (C - 1)) || W < 8 || H < 8 || (al & 15))
+  if (C < 16 || C > kMaxC || (C & (C - 1)) || W < 8 || H < 8 ||
+      pvo_misaligned16(fmap1, fmap2, levels_host[0], levels_host[1], levels_host[2], levels_host[3]))
     return PVO_EUNSUPPORTED;
   BuildArgs a{};
   a.f1 = fmap1; a.f2 = fmap2; a.N = N; a.C = C; a.H = H; a.W = W; a.nlev = 4; a.out_slots = out_slots; a.tiled = 1;
   for (int l = 0; l < 4; ++l) a.lv[l] = levels_host[l];
   hipStream_t st = pvo_stream(stream);
-  return dtype == PVO_F16 ? build_mfma<pvo_half>(a, st) : build_mfma<pvo_bf16>(a, st);
+  return pvo_dispatch16(dtype, [&](auto tag) -> int { return build_mfma<decltype(tag)>(a, st); });
 }
 
 extern "C" int pvo_corr_build(const void* fmap1, const void* fmap2, void* const* levels_host,
@@ -465,19 +430,15 @@ extern "C" int pvo_corr_build(const void* fmap1, const void* fmap2, void* const*
     if (!levels_host[l] && (H >> l) > 0 && (W >> l) > 0) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   const bool fast = channels_last && (dtype == PVO_F16 || dtype == PVO_BF16) && C >= 16 && C <= kMaxC && (C & (C - 1)) == 0 &&
-                    ((reinterpret_cast<uintptr_t>(fmap1) | reinterpret_cast<uintptr_t>(fmap2)) & 15) == 0;
+                    !pvo_misaligned16(fmap1, fmap2);
   if (fast) {
     BuildArgs a{};
     a.f1 = fmap1; a.f2 = fmap2; a.N = N; a.C = C; a.H = H; a.W = W; a.nlev = num_levels; a.out_slots = out_slots;
     for (int l = 0; l < num_levels; ++l) a.lv[l] = levels_host[l];
-    return dtype == PVO_F16 ? build_mfma<pvo_half>(a, st) : build_mfma<pvo_bf16>(a, st);
+    return pvo_dispatch16(dtype, [&](auto tag) -> int { return build_mfma<decltype(tag)>(a, st); });
   }
   if (out_slots) return PVO_EUNSUPPORTED;   // slot-pool output is a feature of the matrix-core path
-  switch (dtype) {
-    case PVO_F32: return build_generic<float>(fmap1, fmap2, levels_host, N, C, H, W, num_levels, channels_last, st);
-    case PVO_F16: return build_generic<pvo_half>(fmap1, fmap2, levels_host, N, C, H, W, num_levels, channels_last, st);
-    case PVO_BF16: return build_generic<pvo_bf16>(fmap1, fmap2, levels_host, N, C, H, W, num_levels, channels_last, st);
-    case PVO_F64: return build_generic<double>(fmap1, fmap2, levels_host, N, C, H, W, num_levels, channels_last, st);
-    default: return PVO_EINVAL;
-  }
+  return pvo_dispatch<float, pvo_half, pvo_bf16, double>(dtype, [&](auto tag) -> int {
+    return build_generic<decltype(tag)>(fmap1, fmap2, levels_host, N, C, H, W, num_levels, channels_last, st);
+  }, PVO_EINVAL);
 }

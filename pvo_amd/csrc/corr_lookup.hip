@@ -25,7 +25,7 @@
 // Floating-point contraction is OFF for this file; the FMAs are explicit.
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "operand16.h"
 
 namespace {
 
@@ -85,14 +85,6 @@ template <> struct Arith<pvo_bf16> {
 
 struct __attribute__((packed, aligned(4))) U4A4 { uint32_t x, y, z, w; };
 
-__device__ __forceinline__ float h16_to_f32(uint32_t bits, pvo_half*) {
-  union { uint16_t u; _Float16 h; } c; c.u = static_cast<uint16_t>(bits);
-  return static_cast<float>(c.h);
-}
-__device__ __forceinline__ float h16_to_f32(uint32_t bits, pvo_bf16*) {
-  return pvo_bf16_to_f32(static_cast<uint16_t>(bits));
-}
-
 // Fetch 8 consecutive 16-bit elements g..g+7 of a level tensor as 4 packed dwords
 // (element 2k in the low half of u[k]).  Elements whose mask bit is clear are never
 // dereferenced outside [0,total); their lanes of u[] hold don't-care bits.
@@ -124,22 +116,21 @@ __device__ __forceinline__ void fetch_row8_16(const uint16_t* base, long long g,
 // window touches at most 4 lines instead of 8 row segments in 8 different lines).  Fetch row iy, columns
 // ix..ix+7: they live in row (iy & 7) of tiles c0 = ix >> 3 and c0 + 1; two aligned 16-byte loads and a
 // funnel shift by (ix & 7) elements.  Elements outside [0, w2) hold don't-care bits (masked by the caller).
-typedef uint32_t lk_u32x4 __attribute__((ext_vector_type(4)));
 // The two halves are separate so that a lane can have the loads of all pyramid levels in flight before it consumes
 // the first one (with the fetch inside the level loop the compiler waits after every level: two loads in flight per
 // lane, the HBM latency exposed eight times per workgroup).  Addresses are clamped into the plane instead of
 // predicated: no exec-mask branches between the loads; whatever a clamped load returns is masked by the caller.
 __device__ __forceinline__ void tiled_issue(const uint16_t* base, long long pbase, int tw, int h2, int iy, int ix,
-                                            lk_u32x4& A, lk_u32x4& B) {
+                                            u32x4& A, u32x4& B) {
   const int c0 = ix >> 3;
   const int iyc = min(max(iy, 0), h2 - 1);
   const int ca = min(max(c0, 0), tw - 1), cb = min(max(c0 + 1, 0), tw - 1);
   const uint16_t* rowp = base + pbase + static_cast<long long>(iyc >> 3) * tw * 64 + (iyc & 7) * 8;
-  A = *reinterpret_cast<const lk_u32x4*>(rowp + ca * 64);
-  B = *reinterpret_cast<const lk_u32x4*>(rowp + cb * 64);
+  A = *reinterpret_cast<const u32x4*>(rowp + ca * 64);
+  B = *reinterpret_cast<const u32x4*>(rowp + cb * 64);
 }
 
-__device__ __forceinline__ void tiled_finish(lk_u32x4 A, lk_u32x4 B, int ix, uint32_t u[4]) {
+__device__ __forceinline__ void tiled_finish(u32x4 A, u32x4 B, int ix, uint32_t u[4]) {
   const int s = ix & 7;
   // funnel shift of the 8 dwords (A:B) by s elements, written with scalars only (local arrays of the
   // selects end up in scratch memory: 64 B/lane and 5x the HBM write traffic, measured)
@@ -170,29 +161,16 @@ __device__ __forceinline__ void fetch_row8_32(const float* base, long long g, ui
 
 template <typename T>
 __device__ __forceinline__ void unpack8(const uint32_t u[4], float v[8]) {
-  T* tag = nullptr;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    v[2 * k] = h16_to_f32(u[k] & 0xffffu, tag);
-    v[2 * k + 1] = h16_to_f32(u[k] >> 16, tag);
+    v[2 * k] = pvo_val<T>(u[k] & 0xffffu);
+    v[2 * k + 1] = pvo_val<T>(u[k] >> 16);
   }
 }
 
 // ---------------------------------------------------------------------------
 // r == 3 fast path.
 // ---------------------------------------------------------------------------
-typedef float lk_v4f __attribute__((ext_vector_type(4)));
-typedef _Float16 lk_v8h __attribute__((ext_vector_type(8)));
-typedef __bf16 lk_v8b __attribute__((ext_vector_type(8)));
-template <typename T> __device__ __forceinline__ lk_v4f lk_mfma(lk_u32x4 x, lk_u32x4 w, lk_v4f c);
-template <> __device__ __forceinline__ lk_v4f lk_mfma<pvo_half>(lk_u32x4 x, lk_u32x4 w, lk_v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(lk_v8h, x), __builtin_bit_cast(lk_v8h, w), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ lk_v4f lk_mfma<pvo_bf16>(lk_u32x4 x, lk_u32x4 w, lk_v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(lk_v8b, x), __builtin_bit_cast(lk_v8b, w), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ lk_v4f lk_mfma<float>(lk_u32x4, lk_u32x4, lk_v4f c) { return c; }   // never instantiated with ENC
-
 // ENC: the lookup's 196 channels never leave the workgroup; they feed the update operator's first correlation-encoder
 // layer, relu(W corr + b) with W [128,196] (droid_net.py:172-175: Conv2d(196,128,1) + ReLU), on the matrix cores, and the
 // 128 encoded channels are written instead: 28 MB of output instead of 43 MB, and the 1x1 convolution's 27 us + 9 us
@@ -252,7 +230,7 @@ __device__ __forceinline__ void corr_lookup_r3_body(const LookupArgs& a) {
     }
     const long long plane = static_cast<long long>(a.slots ? a.slots[n] : n) * HW + (pix_ok ? pix : pix0);
 
-    lk_u32x4 RA[kMaxLevels], RB[kMaxLevels];
+    u32x4 RA[kMaxLevels], RB[kMaxLevels];
     if constexpr (TILED && sizeof(S) == 2) {
 #pragma unroll
       for (int l = 0; l < kMaxLevels; ++l) {
@@ -393,21 +371,21 @@ __device__ __forceinline__ void corr_lookup_r3_body(const LookupArgs& a) {
     const uint16_t* W16 = reinterpret_cast<const uint16_t*>(a.enc_w);
     unsigned char* oslab = smem_raw;                                     // [64 px][272 B], over the staging once it is consumed
     constexpr int MT = STRIP / 16;                                       // 16-pixel M-tiles
-    lk_v4f dd[2][MT];
+    v4f dd[2][MT];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       const int nn = wave * 32 + nt * 16 + li;
-      lk_u32x4 wf[kEncK / 32];
+      u32x4 wf[kEncK / 32];
 #pragma unroll
       for (int ks = 0; ks < kEncK / 32; ++ks)
-        wf[ks] = *reinterpret_cast<const lk_u32x4*>(W16 + static_cast<size_t>(nn) * kEncK + ks * 32 + lk * 8);
+        wf[ks] = *reinterpret_cast<const u32x4*>(W16 + static_cast<size_t>(nn) * kEncK + ks * 32 + lk * 8);
 #pragma unroll
       for (int g = 0; g < MT; ++g) {
-        lk_v4f d = {0.f, 0.f, 0.f, 0.f};
+        v4f d = {0.f, 0.f, 0.f, 0.f};
         const unsigned char* arow = smem_raw + (g * 16 + li) * (kEncStride * 2) + lk * 16;
 #pragma unroll
         for (int ks = 0; ks < kEncK / 32; ++ks)
-          d = lk_mfma<T>(*reinterpret_cast<const lk_u32x4*>(arow + ks * 64), wf[ks], d);
+          d = pvo_mfma<T>(*reinterpret_cast<const u32x4*>(arow + ks * 64), wf[ks], d);
         dd[nt][g] = d;
       }
       asm volatile("" ::: "memory");      // keep the second tile's weight loads below the first tile's MFMAs (registers)
@@ -432,8 +410,8 @@ __device__ __forceinline__ void corr_lookup_r3_body(const LookupArgs& a) {
     for (int it = 0; it < STRIP / 16; ++it) {                         // STRIP px x 16 chunks of 16 B: whole 256-byte pixel rows
       const int id = tid + 256 * it, px = id >> 4, c = id & 15;
       if (px < npix)
-        *reinterpret_cast<lk_u32x4*>(o + static_cast<long long>(px) * 128 + c * 8) =
-            *reinterpret_cast<const lk_u32x4*>(oslab + px * (kEncOutStride * 2) + c * 16);
+        *reinterpret_cast<u32x4*>(o + static_cast<long long>(px) * 128 + c * 8) =
+            *reinterpret_cast<const u32x4*>(oslab + px * (kEncOutStride * 2) + c * 16);
     }
     LK_PROBE(5);
 #ifdef PVO_LOOKUP_PROBE
@@ -725,7 +703,7 @@ extern "C" int pvo_corr_pyramid_lookup_tiled(const void* const* volumes_host, co
   for (int l = 0; l < num_levels; ++l) {
     const int hl = h2 >> l, wl = w2 >> l;
     if (hl <= 0 || wl <= 0) return PVO_EUNSUPPORTED;
-    if (!volumes_host[l] || (reinterpret_cast<uintptr_t>(volumes_host[l]) & 15)) return PVO_EINVAL;
+    if (!volumes_host[l] || pvo_misaligned16(volumes_host[l])) return PVO_EINVAL;
     const int th = (hl + 7) >> 3, tw = (wl + 7) >> 3;
     const long long pe = static_cast<long long>(th) * tw * 64;
     a.lv[l] = LookupLevel{volumes_host[l], static_cast<long long>(slots ? num_slots : N) * h1 * w1 * pe, hl, wl,
@@ -745,14 +723,14 @@ extern "C" int pvo_corr_lookup_encode_tiled(const void* const* volumes_host, con
   if (dtype != PVO_F16 && dtype != PVO_BF16) return PVO_EUNSUPPORTED;
   if (N == 0 || h1 == 0 || w1 == 0) return PVO_OK;
   if (!coords || !out || !enc_weight || !enc_bias) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(enc_weight) | reinterpret_cast<uintptr_t>(out)) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(enc_weight, out)) return PVO_EINVAL;
   if (N > 65535) return PVO_EUNSUPPORTED;
   if (slots && num_slots <= 0) return PVO_EINVAL;
   LookupArgs a{};
   for (int l = 0; l < kMaxLevels; ++l) {
     const int hl = h1 >> l, wl = w1 >> l;
     if (hl <= 0 || wl <= 0) return PVO_EUNSUPPORTED;
-    if (!volumes_host[l] || (reinterpret_cast<uintptr_t>(volumes_host[l]) & 15)) return PVO_EINVAL;
+    if (!volumes_host[l] || pvo_misaligned16(volumes_host[l])) return PVO_EINVAL;
     const int th = (hl + 7) >> 3, tw = (wl + 7) >> 3;
     const long long pe = static_cast<long long>(th) * tw * 64;
     a.lv[l] = LookupLevel{volumes_host[l], static_cast<long long>(slots ? num_slots : N) * h1 * w1 * pe, hl, wl,
@@ -776,13 +754,10 @@ extern "C" int pvo_corr_index_backward(const float* coords, const void* corr_gra
   if (nblk > 0x7fffffffLL) return PVO_EUNSUPPORTED;
   hipStream_t st = pvo_stream(stream);
   dim3 grid(static_cast<unsigned>(nblk)), block(256);
-  switch (dtype) {
-    case PVO_F32: hipLaunchKernelGGL(corr_lookup_backward_kernel<float>, grid, block, 0, st, coords, corr_grad, volume_grad, N, h1 * w1, h2, w2, radius); break;
-    case PVO_F16: hipLaunchKernelGGL(corr_lookup_backward_kernel<pvo_half>, grid, block, 0, st, coords, corr_grad, volume_grad, N, h1 * w1, h2, w2, radius); break;
-    case PVO_BF16: hipLaunchKernelGGL(corr_lookup_backward_kernel<pvo_bf16>, grid, block, 0, st, coords, corr_grad, volume_grad, N, h1 * w1, h2, w2, radius); break;
-    case PVO_F64: hipLaunchKernelGGL(corr_lookup_backward_kernel<double>, grid, block, 0, st, coords, corr_grad, volume_grad, N, h1 * w1, h2, w2, radius); break;
-    default: return PVO_EINVAL;
-  }
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch<float, pvo_half, pvo_bf16, double>(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(corr_lookup_backward_kernel<T>, grid, block, 0, st, coords, corr_grad, volume_grad, N, h1 * w1, h2, w2, radius);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  }, PVO_EINVAL);
 }

@@ -14,21 +14,10 @@
 //     t = max(t, 0)                                if relu_outer
 // x, residual, y: [N, C, HW] planes (NCHW, contiguous), 16-bit; one workgroup per plane: the plane (6-97 KB) is read from L2 three
 // times (mean, variance about the mean, output) - the statistics are two-pass, not E[x^2] - E[x]^2.
-#include "common.h"
+#include "operand16.h"
 
 namespace {
 
-template <typename T> __device__ __forceinline__ float eo_val(uint16_t b);
-template <> __device__ __forceinline__ float eo_val<pvo_half>(uint16_t b) {
-  union { uint16_t u; _Float16 h; } c; c.u = b; return static_cast<float>(c.h);
-}
-template <> __device__ __forceinline__ float eo_val<pvo_bf16>(uint16_t b) { return pvo_bf16_to_f32(b); }
-template <typename T> __device__ __forceinline__ uint16_t eo_bits(float x);
-template <> __device__ __forceinline__ uint16_t eo_bits<pvo_half>(float x) {
-  union { _Float16 h; uint16_t u; } c; c.h = static_cast<_Float16>(x); return c.u;
-}
-template <> __device__ __forceinline__ uint16_t eo_bits<pvo_bf16>(float x) { return pvo_f32_to_bf16(x); }
-template <typename T> __device__ __forceinline__ float eo_round(float x) { return eo_val<T>(eo_bits<T>(x)); }
 
 // sum over the workgroup (every thread gets it); `red` holds one float per wave
 __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -51,7 +40,7 @@ __global__ void bias_norm_act_kernel(const uint16_t* __restrict__ x, const uint1
   const uint16_t* xp = x + plane * HW;
   const uint16_t* rp = residual ? residual + plane * HW : nullptr;
   uint16_t* yp = y + plane * HW;
-  const float b = bias ? eo_val<T>(bias[c]) : 0.0f;
+  const float b = bias ? pvo_val<T>(bias[c]) : 0.0f;
   const bool pairs = (HW & 1) == 0;                   // planes of an even pixel count are read / written two values at a time
   float mean = 0.0f, invstd = 1.0f;
   if (norm) {
@@ -59,32 +48,32 @@ __global__ void bias_norm_act_kernel(const uint16_t* __restrict__ x, const uint1
     if (pairs) {
       for (int i = threadIdx.x; i < HW / 2; i += blockDim.x) {
         const uint32_t v = reinterpret_cast<const uint32_t*>(xp)[i];
-        s += eo_round<T>(eo_val<T>(static_cast<uint16_t>(v & 0xffffu)) + b) + eo_round<T>(eo_val<T>(static_cast<uint16_t>(v >> 16)) + b);
+        s += pvo_round<T>(pvo_val<T>(v & 0xffffu) + b) + pvo_round<T>(pvo_val<T>(v >> 16) + b);
       }
     } else {
-      for (int i = threadIdx.x; i < HW; i += blockDim.x) s += eo_round<T>(eo_val<T>(xp[i]) + b);
+      for (int i = threadIdx.x; i < HW; i += blockDim.x) s += pvo_round<T>(pvo_val<T>(xp[i]) + b);
     }
     mean = block_sum(s, red) / static_cast<float>(HW);
     float q = 0.0f;
     if (pairs) {
       for (int i = threadIdx.x; i < HW / 2; i += blockDim.x) {
         const uint32_t v = reinterpret_cast<const uint32_t*>(xp)[i];
-        const float d0 = eo_round<T>(eo_val<T>(static_cast<uint16_t>(v & 0xffffu)) + b) - mean;
-        const float d1 = eo_round<T>(eo_val<T>(static_cast<uint16_t>(v >> 16)) + b) - mean;
+        const float d0 = pvo_round<T>(pvo_val<T>(v & 0xffffu) + b) - mean;
+        const float d1 = pvo_round<T>(pvo_val<T>(v >> 16) + b) - mean;
         q += d0 * d0 + d1 * d1;
       }
     } else {
-      for (int i = threadIdx.x; i < HW; i += blockDim.x) { const float d = eo_round<T>(eo_val<T>(xp[i]) + b) - mean; q += d * d; }
+      for (int i = threadIdx.x; i < HW; i += blockDim.x) { const float d = pvo_round<T>(pvo_val<T>(xp[i]) + b) - mean; q += d * d; }
     }
     invstd = 1.0f / sqrtf(block_sum(q, red) / static_cast<float>(HW) + eps);
   }
   auto finish = [&](uint16_t xv, uint16_t rv) -> uint16_t {
-    float t = eo_round<T>(eo_val<T>(xv) + b);
-    if (norm) t = eo_round<T>((t - mean) * invstd);
+    float t = pvo_round<T>(pvo_val<T>(xv) + b);
+    if (norm) t = pvo_round<T>((t - mean) * invstd);
     if (relu_inner) t = fmaxf(t, 0.0f);
-    if (rp) t = eo_round<T>(eo_val<T>(rv) + t);
+    if (rp) t = pvo_round<T>(pvo_val<T>(rv) + t);
     if (relu_outer) t = fmaxf(t, 0.0f);
-    return eo_bits<T>(t);
+    return static_cast<uint16_t>(pvo_bits<T>(t));
   };
   if (pairs) {
     for (int i = threadIdx.x; i < HW / 2; i += blockDim.x) {
@@ -111,12 +100,12 @@ __global__ __launch_bounds__(256) void bna_stats_kernel(const uint16_t* __restri
   const long long plane = blockIdx.y;
   const int s = blockIdx.x, lo = s * L, hi = min(HW, lo + L), n = max(hi - lo, 0);
   const uint16_t* xp = x + plane * HW;
-  const float b = bias ? eo_val<T>(bias[static_cast<int>(plane % C)]) : 0.0f;
+  const float b = bias ? pvo_val<T>(bias[static_cast<int>(plane % C)]) : 0.0f;
   float sum = 0.0f;
-  for (int i = lo + threadIdx.x; i < hi; i += 256) sum += eo_round<T>(eo_val<T>(xp[i]) + b);
+  for (int i = lo + threadIdx.x; i < hi; i += 256) sum += pvo_round<T>(pvo_val<T>(xp[i]) + b);
   const float mean = n > 0 ? block_sum(sum, red) / static_cast<float>(n) : 0.0f;
   float q = 0.0f;
-  for (int i = lo + threadIdx.x; i < hi; i += 256) { const float d = eo_round<T>(eo_val<T>(xp[i]) + b) - mean; q += d * d; }
+  for (int i = lo + threadIdx.x; i < hi; i += 256) { const float d = pvo_round<T>(pvo_val<T>(xp[i]) + b) - mean; q += d * d; }
   q = block_sum(q, red);
   if (threadIdx.x == 0) { ws[(plane * S + s) * 2] = mean; ws[(plane * S + s) * 2 + 1] = q; }
 }
@@ -130,7 +119,7 @@ __global__ __launch_bounds__(256) void bna_apply_kernel(const uint16_t* __restri
   const uint16_t* xp = x + plane * HW;
   const uint16_t* rp = residual ? residual + plane * HW : nullptr;
   uint16_t* yp = y + plane * HW;
-  const float b = bias ? eo_val<T>(bias[static_cast<int>(plane % C)]) : 0.0f;
+  const float b = bias ? pvo_val<T>(bias[static_cast<int>(plane % C)]) : 0.0f;
   float mean = 0.0f, invstd = 1.0f;
   if (norm) {
     float cnt = 0.0f, m2 = 0.0f;                       // (every thread the same S steps: no communication)
@@ -146,12 +135,12 @@ __global__ __launch_bounds__(256) void bna_apply_kernel(const uint16_t* __restri
     invstd = 1.0f / sqrtf(m2 / static_cast<float>(HW) + eps);
   }
   for (int i = lo + threadIdx.x; i < hi; i += 256) {
-    float t = eo_round<T>(eo_val<T>(xp[i]) + b);
-    if (norm) t = eo_round<T>((t - mean) * invstd);
+    float t = pvo_round<T>(pvo_val<T>(xp[i]) + b);
+    if (norm) t = pvo_round<T>((t - mean) * invstd);
     if (relu_inner) t = fmaxf(t, 0.0f);
-    if (rp) t = eo_round<T>(eo_val<T>(rp[i]) + t);
+    if (rp) t = pvo_round<T>(pvo_val<T>(rp[i]) + t);
     if (relu_outer) t = fmaxf(t, 0.0f);
-    yp[i] = eo_bits<T>(t);
+    yp[i] = static_cast<uint16_t>(pvo_bits<T>(t));
   }
 }
 
@@ -192,7 +181,7 @@ __global__ __launch_bounds__(256) void conv1x1_planes_kernel(const uint16_t* __r
     for (int ci = 0; ci < kC1Ci; ++ci) {
       float xv[4], wv[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { xv[k] = eo_val<T>(xs[ci][tp + k]); wv[k] = eo_val<T>(ws[ci][tc + k]); }
+      for (int k = 0; k < 4; ++k) { xv[k] = pvo_val<T>(xs[ci][tp + k]); wv[k] = pvo_val<T>(ws[ci][tc + k]); }
 #pragma unroll
       for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -202,11 +191,11 @@ __global__ __launch_bounds__(256) void conv1x1_planes_kernel(const uint16_t* __r
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
     const int co = co0 + tc + a;
-    const float bv = bias ? eo_val<T>(bias[co]) : 0.0f;
+    const float bv = bias ? pvo_val<T>(bias[co]) : 0.0f;
     uint16_t* yr = y + (n * Cout + co) * static_cast<long long>(HWout) + p0 + tp;
 #pragma unroll
     for (int b = 0; b < 4; ++b)
-      if (p0 + tp + b < HWout) yr[b] = eo_bits<T>(eo_round<T>(acc[a][b]) + bv);
+      if (p0 + tp + b < HWout) yr[b] = static_cast<uint16_t>(pvo_bits<T>(pvo_round<T>(acc[a][b]) + bv));
   }
 }
 
@@ -221,7 +210,7 @@ __global__ void frame_normalise_kernel(const IN* __restrict__ img, uint16_t* __r
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float v = static_cast<float>(img[static_cast<size_t>(2 - c) * HW + p]) / 255.0f;
-    out[static_cast<size_t>(c) * HW + p] = eo_bits<T>((v - mean[c]) / stdv[c]);
+    out[static_cast<size_t>(c) * HW + p] = static_cast<uint16_t>(pvo_bits<T>((v - mean[c]) / stdv[c]));
   }
 }
 
@@ -236,15 +225,13 @@ extern "C" int pvo_conv1x1_planes(const void* x, const void* w, const void* bias
   const int Hout = (Hin - 1) / stride + 1, Wout = (Win - 1) / stride + 1;
   const dim3 grid((Hout * Wout + kC1Pix - 1) / kC1Pix, Cout / kC1Co, N);
   hipStream_t st = pvo_stream(stream);
-  if (dtype == PVO_F16)
-    hipLaunchKernelGGL(conv1x1_planes_kernel<pvo_half>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w),
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(conv1x1_planes_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w),
                        static_cast<const uint16_t*>(bias), static_cast<uint16_t*>(y), Cin, Cout, Win, Hin * Win, Wout, Hout * Wout, stride);
-  else if (dtype == PVO_BF16)
-    hipLaunchKernelGGL(conv1x1_planes_kernel<pvo_bf16>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w),
-                       static_cast<const uint16_t*>(bias), static_cast<uint16_t*>(y), Cin, Cout, Win, Hin * Win, Wout, Hout * Wout, stride);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 // in_kind: 0 = int32, 1 = uint8, 2 = float32
@@ -255,16 +242,17 @@ extern "C" int pvo_frame_normalise(const void* img, void* out, int H, int W, con
   const int HW = H * W;
   const dim3 grid((HW + 255) / 256);
   hipStream_t st = pvo_stream(stream);
-#define PVO_FN_LAUNCH(T, IN) hipLaunchKernelGGL((frame_normalise_kernel<T, IN>), grid, dim3(256), 0, st, static_cast<const IN*>(img), static_cast<uint16_t*>(out), HW, \
-                                                mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2])
-  if (dtype == PVO_F16) {
-    if (in_kind == 0) PVO_FN_LAUNCH(pvo_half, int); else if (in_kind == 1) PVO_FN_LAUNCH(pvo_half, uint8_t); else if (in_kind == 2) PVO_FN_LAUNCH(pvo_half, float); else return PVO_EUNSUPPORTED;
-  } else if (dtype == PVO_BF16) {
-    if (in_kind == 0) PVO_FN_LAUNCH(pvo_bf16, int); else if (in_kind == 1) PVO_FN_LAUNCH(pvo_bf16, uint8_t); else if (in_kind == 2) PVO_FN_LAUNCH(pvo_bf16, float); else return PVO_EUNSUPPORTED;
-  } else return PVO_EUNSUPPORTED;
-#undef PVO_FN_LAUNCH
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    auto launch = [&](auto in) {
+      using IN = decltype(in);
+      hipLaunchKernelGGL((frame_normalise_kernel<T, IN>), grid, dim3(256), 0, st, static_cast<const IN*>(img), static_cast<uint16_t*>(out), HW,
+                         mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    };
+    if (in_kind == 0) launch(int{}); else if (in_kind == 1) launch(uint8_t{}); else if (in_kind == 2) launch(float{}); else return PVO_EUNSUPPORTED;
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 // slices per plane of the split form (0: planes of this size keep the one-workgroup kernel)
@@ -280,18 +268,14 @@ extern "C" int pvo_bias_norm_act_split(const void* x, const void* bias, const vo
   const int L = (HW + S - 1) / S;
   const dim3 grid(S, static_cast<unsigned>(planes));
   hipStream_t st = pvo_stream(stream);
-#define PVO_BNA_SPLIT(T)                                                                                                                        \
-  do {                                                                                                                                          \
-    if (norm) hipLaunchKernelGGL(bna_stats_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(bias), ws, C, HW, S, L); \
-    hipLaunchKernelGGL(bna_apply_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(bias),        \
-                       static_cast<const uint16_t*>(residual), static_cast<uint16_t*>(y), ws, C, HW, S, L, norm, eps, relu_inner, relu_outer);   \
-  } while (0)
-  if (dtype == PVO_F16) PVO_BNA_SPLIT(pvo_half);
-  else if (dtype == PVO_BF16) PVO_BNA_SPLIT(pvo_bf16);
-  else return PVO_EUNSUPPORTED;
-#undef PVO_BNA_SPLIT
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (norm) hipLaunchKernelGGL(bna_stats_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(bias), ws, C, HW, S, L);
+    hipLaunchKernelGGL(bna_apply_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(bias),
+                       static_cast<const uint16_t*>(residual), static_cast<uint16_t*>(y), ws, C, HW, S, L, norm, eps, relu_inner, relu_outer);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_bias_norm_act(const void* x, const void* bias, const void* residual, void* y, long long planes, int C, int HW,
@@ -303,13 +287,11 @@ extern "C" int pvo_bias_norm_act(const void* x, const void* bias, const void* re
   const int threads = HW >= 16384 ? 1024 : (HW >= 2048 ? 512 : 256);
   const dim3 grid(static_cast<unsigned>(planes));
   hipStream_t st = pvo_stream(stream);
-  if (dtype == PVO_F16)
-    hipLaunchKernelGGL(bias_norm_act_kernel<pvo_half>, grid, dim3(threads), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(bias),
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(bias_norm_act_kernel<T>, grid, dim3(threads), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(bias),
                        static_cast<const uint16_t*>(residual), static_cast<uint16_t*>(y), C, HW, norm, eps, relu_inner, relu_outer);
-  else if (dtype == PVO_BF16)
-    hipLaunchKernelGGL(bias_norm_act_kernel<pvo_bf16>, grid, dim3(threads), 0, st, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(bias),
-                       static_cast<const uint16_t*>(residual), static_cast<uint16_t*>(y), C, HW, norm, eps, relu_inner, relu_outer);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }

@@ -10,6 +10,7 @@
 // 256-thread block per edge.  The relative pose is recomputed per thread from 14
 // scalar-cached floats instead of going through LDS and two barriers.
 // frame_distance keeps one workgroup per pair but reduces with wave shuffles.
+#include "operand16.h"
 #include "se3.h"
 
 namespace {
@@ -265,11 +266,6 @@ extern "C" int pvo_depth_filter(const float* poses, const float* disps, const fl
   return PVO_OK;
 }
 
-template <typename T> __device__ __forceinline__ uint32_t bits16(float x);
-template <> __device__ __forceinline__ uint32_t bits16<pvo_half>(float x) {
-  union { _Float16 h; uint16_t u; } c; c.h = static_cast<_Float16>(x); return c.u;
-}
-template <> __device__ __forceinline__ uint32_t bits16<pvo_bf16>(float x) { return pvo_f32_to_bf16(x); }
 
 // reproject + FactorGraph.update's motion features (graph_glue.hip: graph_motion_kernel, the same arithmetic on the same
 // values) in one pass: alone at the head of a graph update this costs what the reprojection costs, while the separate motion
@@ -310,7 +306,7 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const float a = fminf(fmaxf(f[2 * q], -64.0f), 64.0f), b = fminf(fmaxf(f[2 * q + 1], -64.0f), 64.0f);
-    o[q] = bits16<T>(a) | (bits16<T>(b) << 16);
+    o[q] = pvo_bits<T>(a) | (pvo_bits<T>(b) << 16);
   }
   *reinterpret_cast<uint4*>(motn + idx * 8) = make_uint4(o[0], o[1], o[2], o[3]);
 }
@@ -322,19 +318,17 @@ extern "C" int pvo_reproject_motion(const float* poses, const float* disps, cons
   PVO_REQ(E >= 0 && ht >= 0 && wd >= 0);
   if (E == 0 || ht * wd == 0) return PVO_OK;
   PVO_REQ(poses && disps && intrinsics && ii && jj && coords && valid && target && delta_dy && raw_mask && motn && E <= 65535);
-  PVO_REQ(!(reinterpret_cast<uintptr_t>(motn) & 15) && !((reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(delta_dy) |
+  PVO_REQ(!pvo_misaligned16(motn) && !((reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(delta_dy) |
            reinterpret_cast<uintptr_t>(raw_mask) | reinterpret_cast<uintptr_t>(coords)) & 7));
   const dim3 grid((ht * wd + 255) / 256, E);
   auto f2 = [](const float* p) { return reinterpret_cast<const float2*>(p); };
-  if (dtype == PVO_F16)
-    hipLaunchKernelGGL(reproject_motion_kernel<pvo_half>, grid, dim3(256), 0, pvo_stream(stream), poses, disps, intrinsics, ii, jj, coords, valid,
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(reproject_motion_kernel<T>, grid, dim3(256), 0, pvo_stream(stream), poses, disps, intrinsics, ii, jj, coords, valid,
                        f2(target), f2(delta_dy), f2(raw_mask), static_cast<uint16_t*>(motn), ht * wd, wd);
-  else if (dtype == PVO_BF16)
-    hipLaunchKernelGGL(reproject_motion_kernel<pvo_bf16>, grid, dim3(256), 0, pvo_stream(stream), poses, disps, intrinsics, ii, jj, coords, valid,
-                       f2(target), f2(delta_dy), f2(raw_mask), static_cast<uint16_t*>(motn), ht * wd, wd);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_reproject(const float* poses, const float* disps, const float* intrinsics,

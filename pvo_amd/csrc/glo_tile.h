@@ -7,9 +7,6 @@
 
 namespace glt {
 
-using c1t::u32x4;
-using c1t::v4f;
-
 constexpr int kTile = 64, kStride = 272;
 constexpr int kTileBytes = kTile * kStride;          // LDS of glo_partial_means
 
@@ -64,8 +61,8 @@ __device__ __forceinline__ void glo_partial_means(unsigned char* tile, const uin
       v4f d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kc = 0; kc < 4; ++kc) {
-        d0 = c1t::mfma<T>(afr[g][kc], bf[kc][0], d0);
-        d1 = c1t::mfma<T>(afr[g][kc], bf[kc][1], d1);
+        d0 = pvo_mfma<T>(afr[g][kc], bf[kc][0], d0);
+        d1 = pvo_mfma<T>(afr[g][kc], bf[kc][1], d1);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {                       // D rows lk*4 + r = pixels, column li = channel

@@ -8,7 +8,7 @@
 //                      full_flow = coords1 + delta_dy - coords0; and the [E,2,H,W] target / weight the BA reads
 // In PyTorch this is ~25 element-wise / cat / permute launches over 1-2 MB tensors per graph update (launch-bound);
 // the head outputs are read straight from the [E,H,W,8] tensor heads_out writes (delta | delta_dy | weight | delta_mask).
-#include "common.h"
+#include "operand16.h"
 #include "graph_post.h"
 
 namespace {
@@ -27,14 +27,7 @@ __global__ __launch_bounds__(256) void graph_motion_kernel(const float2* __restr
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float a = fminf(fmaxf(f[2 * k], -64.0f), 64.0f), b = fminf(fmaxf(f[2 * k + 1], -64.0f), 64.0f);
-    uint32_t lo, hi;
-    if constexpr (sizeof(typename Elem<T>::store_t) == 2 && __is_same(T, pvo_half)) {
-      union { _Float16 h; uint16_t u; } ca, cb; ca.h = static_cast<_Float16>(a); cb.h = static_cast<_Float16>(b);
-      lo = ca.u; hi = cb.u;
-    } else {
-      lo = pvo_f32_to_bf16(a); hi = pvo_f32_to_bf16(b);
-    }
-    o[k] = lo | (hi << 16);
+    o[k] = pvo_bits<T>(a) | (pvo_bits<T>(b) << 16);
   }
   *reinterpret_cast<uint4*>(motn + static_cast<size_t>(idx) * 8) = make_uint4(o[0], o[1], o[2], o[3]);
 }
@@ -59,18 +52,17 @@ extern "C" int pvo_graph_motion(const float* target, const float* coords1, const
   const long long n = static_cast<long long>(E) * H * W;
   if (n == 0) return PVO_OK;
   if (!target || !coords1 || !delta_dy || !raw_mask || !motn || n >= (1LL << 31)) return PVO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(motn) & 15) || ((reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(coords1) |
+  if (pvo_misaligned16(motn) || ((reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(coords1) |
        reinterpret_cast<uintptr_t>(delta_dy) | reinterpret_cast<uintptr_t>(raw_mask)) & 7)) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   const dim3 grid(static_cast<unsigned>((n + 255) / 256));
   auto f2 = [](const float* p) { return reinterpret_cast<const float2*>(p); };
-  if (dtype == PVO_F16)
-    hipLaunchKernelGGL(graph_motion_kernel<pvo_half>, grid, dim3(256), 0, st, f2(target), f2(coords1), f2(delta_dy), f2(raw_mask), static_cast<uint16_t*>(motn), E, H * W, W);
-  else if (dtype == PVO_BF16)
-    hipLaunchKernelGGL(graph_motion_kernel<pvo_bf16>, grid, dim3(256), 0, st, f2(target), f2(coords1), f2(delta_dy), f2(raw_mask), static_cast<uint16_t*>(motn), E, H * W, W);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(graph_motion_kernel<T>, grid, dim3(256), 0, st, f2(target), f2(coords1), f2(delta_dy), f2(raw_mask), static_cast<uint16_t*>(motn), E, H * W, W);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_graph_post(const float* coords1, const void* heads, float* raw_mask, float* target, float* delta_dy,
@@ -81,17 +73,16 @@ extern "C" int pvo_graph_post(const float* coords1, const void* heads, float* ra
   const long long n = static_cast<long long>(E) * H * W;
   if (n == 0) return PVO_OK;
   if (!coords1 || !heads || !raw_mask || !target || !delta_dy || !weight || !target_ba || !weight_ba || !full_flow || n >= (1LL << 31)) return PVO_EINVAL;
-  if (reinterpret_cast<uintptr_t>(heads) & 15) return PVO_EINVAL;
+  if (pvo_misaligned16(heads)) return PVO_EINVAL;
   if (segm && (!vote_tot || !vote_dyn || max_segments <= 0)) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   const dim3 grid(static_cast<unsigned>((n + 255) / 256));
   auto f2 = [](float* p) { return reinterpret_cast<float2*>(p); };
   const GraphPostArgs g = {reinterpret_cast<const float2*>(coords1), f2(raw_mask), f2(target), f2(delta_dy), f2(weight), target_ba, weight_ba, f2(full_flow), dy_thresh};
-  if (dtype == PVO_F16)
-    hipLaunchKernelGGL(graph_post_kernel<pvo_half>, grid, dim3(256), 0, st, g, static_cast<const uint16_t*>(heads), E, H * W, W, segm, vote_tot, vote_dyn, max_segments, vote_thresh);
-  else if (dtype == PVO_BF16)
-    hipLaunchKernelGGL(graph_post_kernel<pvo_bf16>, grid, dim3(256), 0, st, g, static_cast<const uint16_t*>(heads), E, H * W, W, segm, vote_tot, vote_dyn, max_segments, vote_thresh);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(graph_post_kernel<T>, grid, dim3(256), 0, st, g, static_cast<const uint16_t*>(heads), E, H * W, W, segm, vote_tot, vote_dyn, max_segments, vote_thresh);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }

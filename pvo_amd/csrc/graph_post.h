@@ -2,7 +2,7 @@
 // graph_post_kernel (graph_glue.hip) and the output-head gather that does it in its epilogue (gru_fused.hip): one text, the same
 // operations in the same order wherever it runs.
 #pragma once
-#include "common.h"
+#include "operand16.h"
 
 struct GraphPostArgs {
   const float2* coords1;
@@ -12,22 +12,16 @@ struct GraphPostArgs {
   float dy_thresh;
 };
 
-template <typename T>
-__device__ __forceinline__ float gp_h2f(uint32_t bits) {
-  if constexpr (__is_same(T, pvo_half)) { union { uint16_t u; _Float16 h; } c; c.u = static_cast<uint16_t>(bits); return static_cast<float>(c.h); }
-  else return pvo_bf16_to_f32(static_cast<uint16_t>(bits));
-}
-
 // q = the pixel's eight 16-bit head outputs (delta | delta_dy | weight logits | delta_mask), idx = e * HW + pix
 template <typename T>
 __device__ __forceinline__ void graph_post_pixel(int idx, int e, int pix, uint4 q, const GraphPostArgs& g, int HW, int W,
                                                  const int* __restrict__ segm, const int* __restrict__ vote_tot,
                                                  const int* __restrict__ vote_dyn, int S, float vote_thresh) {
   const float x0 = static_cast<float>(pix % W), y0 = static_cast<float>(pix / W);
-  const float d0 = gp_h2f<T>(q.x & 0xffffu), d1 = gp_h2f<T>(q.x >> 16);      // delta
-  const float g0 = gp_h2f<T>(q.y & 0xffffu), g1 = gp_h2f<T>(q.y >> 16);      // delta_dy (raw)
-  const float w0 = gp_h2f<T>(q.z & 0xffffu), w1 = gp_h2f<T>(q.z >> 16);      // weight logits
-  const float m0 = gp_h2f<T>(q.w & 0xffffu), m1 = gp_h2f<T>(q.w >> 16);      // delta_mask
+  const float d0 = pvo_val<T>(q.x & 0xffffu), d1 = pvo_val<T>(q.x >> 16);      // delta
+  const float g0 = pvo_val<T>(q.y & 0xffffu), g1 = pvo_val<T>(q.y >> 16);      // delta_dy (raw)
+  const float w0 = pvo_val<T>(q.z & 0xffffu), w1 = pvo_val<T>(q.z >> 16);      // weight logits
+  const float m0 = pvo_val<T>(q.w & 0xffffu), m1 = pvo_val<T>(q.w >> 16);      // delta_mask
   const float2 c1 = g.coords1[idx];
   float2 rm = g.raw_mask[idx];
   rm.x += m0; rm.y += m1;

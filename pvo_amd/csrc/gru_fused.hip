@@ -4,39 +4,11 @@
 //               with conv1's bias + ReLU applied as the input is read
 //   heads_out   the second stage of the four output heads, 4 x (ReLU + Conv3x3(128 -> 2)) (droid_net.py:184-210)
 // Layout: channels-last fp16/bf16 rows ([E, H*W, C]); 8 channels (16 B) per thread per access; arithmetic in fp32.
-#include "common.h"
+#include "operand16.h"
 #include "graph_post.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct H8 {   // 8 x 16-bit <-> 8 x float
-  static __device__ __forceinline__ void unpack(u32x4 v, float f[8]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      f[2 * k] = Elem<T>::to_f32(from_bits(v[k] & 0xffffu));
-      f[2 * k + 1] = Elem<T>::to_f32(from_bits(v[k] >> 16));
-    }
-  }
-  static __device__ __forceinline__ u32x4 pack(const float f[8]) {
-    u32x4 v;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = to_bits(Elem<T>::from_f32(f[2 * k])) | (to_bits(Elem<T>::from_f32(f[2 * k + 1])) << 16);
-    return v;
-  }
-  static __device__ __forceinline__ typename Elem<T>::store_t from_bits(uint32_t b);
-  static __device__ __forceinline__ uint32_t to_bits(typename Elem<T>::store_t s);
-};
-template <> __device__ __forceinline__ _Float16 H8<pvo_half>::from_bits(uint32_t b) {
-  union { uint16_t u; _Float16 h; } c; c.u = static_cast<uint16_t>(b); return c.h;
-}
-template <> __device__ __forceinline__ uint32_t H8<pvo_half>::to_bits(_Float16 s) {
-  union { uint16_t u; _Float16 h; } c; c.h = s; return c.u;
-}
-template <> __device__ __forceinline__ uint16_t H8<pvo_bf16>::from_bits(uint32_t b) { return static_cast<uint16_t>(b); }
-template <> __device__ __forceinline__ uint32_t H8<pvo_bf16>::to_bits(uint16_t s) { return s; }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
@@ -77,10 +49,10 @@ __global__ __launch_bounds__(256) void seg_mean_kernel(const uint16_t* __restric
       for (int u = 0; u < 4; ++u) {
         if (o + u >= e1) break;
         float f[8];
-        H8<T>::unpack(v[u], f);
+        pvo_unpack8<T>(v[u], f);
         if (in_bias) {    // x is a bias-free convolution output: relu(x + b), rounded to the storage type as a separate pass would
 #pragma unroll
-          for (int q = 0; q < 8; ++q) f[q] = Elem<T>::to_f32(Elem<T>::from_f32(fmaxf(f[q] + bb[q], 0.0f)));
+          for (int q = 0; q < 8; ++q) f[q] = pvo_round<T>(fmaxf(f[q] + bb[q], 0.0f));
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) acc[q] += f[q];
@@ -88,7 +60,7 @@ __global__ __launch_bounds__(256) void seg_mean_kernel(const uint16_t* __restric
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) acc[q] *= inv;
-    *reinterpret_cast<u32x4*>(out + (static_cast<long long>(k) * per + id) * 8) = H8<T>::pack(acc);
+    *reinterpret_cast<u32x4*>(out + (static_cast<long long>(k) * per + id) * 8) = pvo_pack8<T>(acc);
   }
 }
 
@@ -97,30 +69,22 @@ inline unsigned grid_for(long long items) {
   return static_cast<unsigned>(b < 1 ? 1 : (b > 256 * 32 ? 256 * 32 : b));
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
-
-#define GRU_DISPATCH(dtype, CALL_H, CALL_B)        \
-  do {                                             \
-    if ((dtype) == PVO_F16) { CALL_H; }            \
-    else if ((dtype) == PVO_BF16) { CALL_B; }      \
-    else return PVO_EUNSUPPORTED;                  \
-  } while (0)
 
 extern "C" int pvo_segment_mean(const void* x, const int* seg_ptr, const int* seg_idx, const float* in_bias, void* out,
                                 int K, int HW, int C, int dtype, void* stream) {
   if (K < 0 || HW < 0 || C <= 0 || (C & 7)) return PVO_EINVAL;
   if (K == 0 || HW == 0) return PVO_OK;
-  if (!x || !seg_ptr || !seg_idx || !out || !aligned16(x) || !aligned16(out) || K > 65535) return PVO_EINVAL;
+  if (!x || !seg_ptr || !seg_idx || !out || pvo_misaligned16(x, out) || K > 65535) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   const long long per = static_cast<long long>(HW) * (C >> 3);
   dim3 grid(static_cast<unsigned>((per + 255) / 256 > 1024 ? 1024 : (per + 255) / 256), K);
-  GRU_DISPATCH(dtype,
-    hipLaunchKernelGGL(seg_mean_kernel<pvo_half>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), seg_ptr, seg_idx, in_bias, static_cast<uint16_t*>(out), HW, C),
-    hipLaunchKernelGGL(seg_mean_kernel<pvo_bf16>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), seg_ptr, seg_idx, in_bias, static_cast<uint16_t*>(out), HW, C));
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(seg_mean_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), seg_ptr, seg_idx, in_bias, static_cast<uint16_t*>(out), HW, C);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -141,17 +105,6 @@ namespace {
 constexpr int kHT = 8, kWT = 16;                 // pixel tile
 constexpr int kHaloW = kWT + 2, kHaloPos = (kHT + 2) * kHaloW;   // 180 positions
 constexpr int kPosStride = 128 * 2 + 16;         // bytes per halo position (padded against b128 bank conflicts)
-
-typedef float ho_v4f __attribute__((ext_vector_type(4)));
-typedef _Float16 ho_v8h __attribute__((ext_vector_type(8)));
-typedef __bf16 ho_v8b __attribute__((ext_vector_type(8)));
-template <typename T> __device__ __forceinline__ ho_v4f ho_mfma(u32x4 a, u32x4 b, ho_v4f c);
-template <> __device__ __forceinline__ ho_v4f ho_mfma<pvo_half>(u32x4 a, u32x4 b, ho_v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ho_v8h, a), __builtin_bit_cast(ho_v8h, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ ho_v4f ho_mfma<pvo_bf16>(u32x4 a, u32x4 b, ho_v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(ho_v8b, a), __builtin_bit_cast(ho_v8b, b), c, 0, 0, 0);
-}
 
 // History (all measured on MI355X, S-B): packed-dot versions (v_dot2c, weights through LDS, SGPRs, ...) sat at 72-86 us
 // whatever their memory schedule: probe builds showed 31 us of HBM streaming, 20 us of staging and the rest dot issue.
@@ -209,10 +162,10 @@ __global__ __launch_bounds__(256) void heads_out_kernel(const uint16_t* __restri
           u32x4 v = {0u, 0u, 0u, 0u};
           if (off[it] >= 0) {                                 // zero padding is applied AFTER bias + ReLU
             float f[8];
-            H8<T>::unpack(raw[it], f);
+            pvo_unpack8<T>(raw[it], f);
 #pragma unroll
             for (int k = 0; k < 8; ++k) f[k] = fmaxf(f[k] + bb[k], 0.0f);
-            v = H8<T>::pack(f);
+            v = pvo_pack8<T>(f);
           }
           *reinterpret_cast<u32x4*>(xs + pos * kPosStride + ch * 16) = v;
         }
@@ -232,7 +185,7 @@ __global__ __launch_bounds__(256) void heads_out_kernel(const uint16_t* __restri
     // per (tap, 32-channel chunk).  7/8 of the columns multiply zeros - still 4x cheaper than 576 v_dot2c per thread
     // (the packed-dot version sat at 75 us whatever its memory schedule was: it was dot-issue bound).
     // wave w owns tile rows 2w, 2w+1; lane: pixel li = lane & 15, channel group lk = lane >> 4 (8 channels).
-    ho_v4f d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+    v4f d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
     // B fragments come from the head's weights in LDS ([out][tap][128 ch]); columns >= 2 read a zero row (a per-tap
     // global load of the fragments cost 20 us of the 62: measured with probe builds)
     const unsigned char* wrow = li < 2 ? wl + li * 9 * 256 + lk * 16 : wzero;
@@ -248,8 +201,8 @@ __global__ __launch_bounds__(256) void heads_out_kernel(const uint16_t* __restri
       const unsigned char* xp1 = xp0 + kHaloW * kPosStride;
 #pragma unroll
       for (int kc = 0; kc < 4; ++kc) {
-        d0 = ho_mfma<T>(*reinterpret_cast<const u32x4*>(xp0 + kc * 64), bf[kc], d0);
-        d1 = ho_mfma<T>(*reinterpret_cast<const u32x4*>(xp1 + kc * 64), bf[kc], d1);
+        d0 = pvo_mfma<T>(*reinterpret_cast<const u32x4*>(xp0 + kc * 64), bf[kc], d0);
+        d1 = pvo_mfma<T>(*reinterpret_cast<const u32x4*>(xp1 + kc * 64), bf[kc], d1);
       }
     }
 #pragma unroll
@@ -273,7 +226,7 @@ __global__ __launch_bounds__(256) void heads_out_kernel(const uint16_t* __restri
       float f[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) f[k] = ys[tid * 8 + k] + bias2[k];
-      *reinterpret_cast<u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * 8) = H8<T>::pack(f);
+      *reinterpret_cast<u32x4*>(y + ((static_cast<size_t>(e) * H + gy) * W + gx) * 8) = pvo_pack8<T>(f);
     }
   }
 }
@@ -302,7 +255,7 @@ __global__ __launch_bounds__(256) void heads_gather_kernel(const float* __restri
 #pragma unroll
   for (int t = 0; t < 9; ++t)
     if (ok[t]) { a0 += v[t].x; a1 += v[t].y; }
-  const uint32_t lo = H8<T>::to_bits(Elem<T>::from_f32(a0)), hi = H8<T>::to_bits(Elem<T>::from_f32(a1));
+  const uint32_t lo = pvo_bits<T>(a0), hi = pvo_bits<T>(a1);
   *reinterpret_cast<uint32_t*>(y + p * 8 + 2 * head) = lo | (hi << 16);
 }
 
@@ -321,7 +274,6 @@ __global__ __launch_bounds__(256) void heads_gather_tiled_kernel(const float* __
   extern __shared__ __attribute__((aligned(16))) unsigned char hgs[];
   const int e = blockIdx.z, y0 = blockIdx.y * kHgTH, x0 = blockIdx.x * kHgTW, tid = threadIdx.x;
   const float* ze = z + static_cast<size_t>(e) * H * W * 72;
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   constexpr int kChunks = kHgPos * 18, kIter = (kChunks + 255) / 256;              // 16-byte chunks of the halo: 18 per position
   u32x4 stg[kIter];
 #pragma unroll
@@ -354,7 +306,7 @@ __global__ __launch_bounds__(256) void heads_gather_tiled_kernel(const float* __
         a0 += v.x; a1 += v.y;
       }
     }
-    const uint32_t lo = H8<T>::to_bits(Elem<T>::from_f32(a0)), hi = H8<T>::to_bits(Elem<T>::from_f32(a1));
+    const uint32_t lo = pvo_bits<T>(a0), hi = pvo_bits<T>(a1);
     const uint32_t mine = (lo & 0xffffu) | (hi << 16);
     *reinterpret_cast<uint32_t*>(y + ((static_cast<size_t>(e) * H + py) * W + px) * 8 + 2 * head) = mine;
     if (POST) {
@@ -380,40 +332,34 @@ static int heads_gather_launch(const float* z, const float* bias2, void* y, cons
   if (!z || !bias2 || !y || (reinterpret_cast<uintptr_t>(z) & 7) || (reinterpret_cast<uintptr_t>(y) & 3)) return PVO_EINVAL;
   hipStream_t st = pvo_stream(stream);
   const bool flat = pvo_knob(PVO_KNOB_HEADS_GATHER_FLAT) != 0;      // (pvo_debug_config: a test compares the two forms bit for bit)
-  if (!flat && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && E <= 65535) {
+  uint16_t* yp = static_cast<uint16_t*>(y);
+  if (!flat && !pvo_misaligned16(z) && E <= 65535) {
     const dim3 grid((W + kHgTW - 1) / kHgTW, (H + kHgTH - 1) / kHgTH, E);
     constexpr size_t lds = static_cast<size_t>(kHgPos) * kHgRow;                      // 54720 B
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(heads_gather_tiled_kernel<pvo_half, false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(heads_gather_tiled_kernel<pvo_bf16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(heads_gather_tiled_kernel<pvo_half, true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(heads_gather_tiled_kernel<pvo_bf16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
-        return PVO_ELAUNCH;
-      attr_set = true;
-    }
-    if (dtype != PVO_F16 && dtype != PVO_BF16) return PVO_EUNSUPPORTED;
     const bool with_post = post != nullptr && static_cast<long long>(E) * H * W < (1LL << 31);
     const GraphPostArgs gp = with_post ? *post : GraphPostArgs{};
-    uint16_t* yp = static_cast<uint16_t*>(y);
-    if (with_post) {
-      if (dtype == PVO_F16) hipLaunchKernelGGL((heads_gather_tiled_kernel<pvo_half, true>), grid, dim3(256), lds, st, z, bias2, yp, H, W, gp);
-      else hipLaunchKernelGGL((heads_gather_tiled_kernel<pvo_bf16, true>), grid, dim3(256), lds, st, z, bias2, yp, H, W, gp);
-      if (fused) *fused = 1;
-    } else {
-      if (dtype == PVO_F16) hipLaunchKernelGGL((heads_gather_tiled_kernel<pvo_half, false>), grid, dim3(256), lds, st, z, bias2, yp, H, W, gp);
-      else hipLaunchKernelGGL((heads_gather_tiled_kernel<pvo_bf16, false>), grid, dim3(256), lds, st, z, bias2, yp, H, W, gp);
-    }
-    PVO_CHECK_LAUNCH();
-    return PVO_OK;
+    return pvo_dispatch16(dtype, [&](auto tag) -> int {
+      using T = decltype(tag);
+      if (with_post) {
+        if (!pvo_allow_lds<heads_gather_tiled_kernel<T, true>>(lds)) return PVO_ELAUNCH;
+        hipLaunchKernelGGL((heads_gather_tiled_kernel<T, true>), grid, dim3(256), lds, st, z, bias2, yp, H, W, gp);
+        if (fused) *fused = 1;
+      } else {
+        if (!pvo_allow_lds<heads_gather_tiled_kernel<T, false>>(lds)) return PVO_ELAUNCH;
+        hipLaunchKernelGGL((heads_gather_tiled_kernel<T, false>), grid, dim3(256), lds, st, z, bias2, yp, H, W, gp);
+      }
+      PVO_CHECK_LAUNCH();
+      return PVO_OK;
+    });
   }
   const long long total = static_cast<long long>(E) * H * W * 4;
   const dim3 grid(static_cast<unsigned>((total + 255) / 256));
-  if (dtype == PVO_F16) hipLaunchKernelGGL(heads_gather_kernel<pvo_half>, grid, dim3(256), 0, st, z, bias2, static_cast<uint16_t*>(y), H, W, total);
-  else if (dtype == PVO_BF16) hipLaunchKernelGGL(heads_gather_kernel<pvo_bf16>, grid, dim3(256), 0, st, z, bias2, static_cast<uint16_t*>(y), H, W, total);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(heads_gather_kernel<T>, grid, dim3(256), 0, st, z, bias2, yp, H, W, total);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_heads_gather(const float* z, const float* bias2, void* y, int E, int H, int W, int dtype, void* stream) {
@@ -429,21 +375,16 @@ extern "C" int pvo_heads_out(const void* h1, const float* bias1, const void* w2,
                              int E, int H, int W, int dtype, void* stream) {
   if (E < 0 || H < 0 || W < 0) return PVO_EINVAL;
   if (E == 0 || H == 0 || W == 0) return PVO_OK;
-  if (!h1 || !bias1 || !w2 || !bias2 || !y || !aligned16(h1) || !aligned16(w2) || !aligned16(y) ||
-      (reinterpret_cast<uintptr_t>(bias1) & 15) || E > 65535) return PVO_EINVAL;
+  if (!h1 || !bias1 || !w2 || !bias2 || !y || pvo_misaligned16(h1, w2, y, bias1) || E > 65535) return PVO_EINVAL;
   if (static_cast<long long>(H) * W * 512 > 0x7fffffffLL) return PVO_EUNSUPPORTED;   // per-image offsets are 32-bit
   hipStream_t st = pvo_stream(stream);
   const size_t lds = static_cast<size_t>(kHaloPos) * kPosStride + 2 * 9 * 256 + 16;   // 53584 B
   dim3 grid((W + kWT - 1) / kWT, (H + kHT - 1) / kHT, E);
-  if (dtype == PVO_F16) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(heads_out_kernel<pvo_half>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) return PVO_ELAUNCH;
-    hipLaunchKernelGGL(heads_out_kernel<pvo_half>, grid, dim3(256), lds, st, static_cast<const uint16_t*>(h1), bias1, static_cast<const uint32_t*>(w2), bias2, static_cast<uint16_t*>(y), H, W);
-  } else if (dtype == PVO_BF16) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(heads_out_kernel<pvo_bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) return PVO_ELAUNCH;
-    hipLaunchKernelGGL(heads_out_kernel<pvo_bf16>, grid, dim3(256), lds, st, static_cast<const uint16_t*>(h1), bias1, static_cast<const uint32_t*>(w2), bias2, static_cast<uint16_t*>(y), H, W);
-  } else {
-    return PVO_EUNSUPPORTED;
-  }
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch16(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (!pvo_allow_lds<heads_out_kernel<T>>(lds)) return PVO_ELAUNCH;
+    hipLaunchKernelGGL(heads_out_kernel<T>, grid, dim3(256), lds, st, static_cast<const uint16_t*>(h1), bias1, static_cast<const uint32_t*>(w2), bias2, static_cast<uint16_t*>(y), H, W);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }

@@ -1,6 +1,6 @@
 // probe_tools.hip — MEASUREMENT kernels (libpvo_probe.so, include/pvo_probe.h): the shader-clock probe and the memory-request probe
 // that bench.py / tools/mem_probe.py report.  Built beside libpvo_hip.so, not part of it: nothing of the product calls them.
-#include "common.h"
+#include "operand16.h"
 #include "../../include/pvo_probe.h"
 
 // One wave runs a dependent chain of `iters` x 64 v_fma_f32 and reports how many shader cycles (s_memtime) and how many
@@ -31,20 +31,19 @@ extern "C" int pvo_clock_probe(void* out3_u64, int iters, void* stream) {
 // whose windows are a few partial lines each at data-dependent places (measured: ~56 G requests/s whether a request is 64 or
 // 128 bytes, i.e. 3.6 TB/s of half lines, 7.1 TB/s of whole lines, 7.4 TB/s streaming).
 namespace {
-typedef uint32_t mp_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint32_t mp_mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16; return x; }
 __global__ __launch_bounds__(256) void mem_probe_kernel(const unsigned char* __restrict__ buf, uint32_t nlines, int iters, int lanes, int stream_mode,
                                                         uint32_t* __restrict__ sink) {
   const uint32_t gid = blockIdx.x * 256u + threadIdx.x;
   const uint32_t grp = gid / lanes, sub = gid % lanes, ngrp = gridDim.x * 256u / lanes, bytes = lanes * 16u;
-  mp_u32x4 acc = {0u, 0u, 0u, 0u};
+  u32x4 acc = {0u, 0u, 0u, 0u};
   for (int it = 0; it < iters; ++it) {
-    mp_u32x4 v[8];
+    u32x4 v[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const uint32_t idx = (it * 8u + k) * ngrp + grp;
       const uint32_t line = stream_mode ? idx % nlines : mp_mix(idx * 2654435761u + 12345u) % nlines;
-      v[k] = *reinterpret_cast<const mp_u32x4*>(buf + static_cast<size_t>(line) * bytes + sub * 16u);
+      v[k] = *reinterpret_cast<const u32x4*>(buf + static_cast<size_t>(line) * bytes + sub * 16u);
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc ^= v[k];

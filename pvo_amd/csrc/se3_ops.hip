@@ -252,13 +252,12 @@ extern "C" int pvo_se3_unary(int op, const void* x, void* y, long long n, int dt
   if (n == 0) return PVO_OK;
   if (!x || !y) return PVO_EINVAL;
   const dim3 grid(static_cast<unsigned>((n + 255) / 256));
-  if (dtype == PVO_F32)
-    hipLaunchKernelGGL(se3_unary_kernel<float>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const float*>(x), static_cast<float*>(y), n);
-  else if (dtype == PVO_F64)
-    hipLaunchKernelGGL(se3_unary_kernel<double>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const double*>(x), static_cast<double*>(y), n);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch<float, double>(dtype, [&](auto tag) -> int {
+    using F = decltype(tag);
+    hipLaunchKernelGGL(se3_unary_kernel<F>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const F*>(x), static_cast<F*>(y), n);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_se3_binary(int op, const void* a, long long rep_a, const void* b, long long rep_b, void* y, long long n,
@@ -267,15 +266,13 @@ extern "C" int pvo_se3_binary(int op, const void* a, long long rep_a, const void
   if (n == 0) return PVO_OK;
   if (!a || !b || !y) return PVO_EINVAL;
   const dim3 grid(static_cast<unsigned>((n + 255) / 256));
-  if (dtype == PVO_F32)
-    hipLaunchKernelGGL(se3_binary_kernel<float>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const float*>(a), rep_a,
-                       static_cast<const float*>(b), rep_b, static_cast<float*>(y), n);
-  else if (dtype == PVO_F64)
-    hipLaunchKernelGGL(se3_binary_kernel<double>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const double*>(a), rep_a,
-                       static_cast<const double*>(b), rep_b, static_cast<double*>(y), n);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch<float, double>(dtype, [&](auto tag) -> int {
+    using F = decltype(tag);
+    hipLaunchKernelGGL(se3_binary_kernel<F>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const F*>(a), rep_a,
+                       static_cast<const F*>(b), rep_b, static_cast<F*>(y), n);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 // Backward of pvo_se3_unary / pvo_se3_binary (ambient-coordinate vector-Jacobian products; see the head of this file).
@@ -286,13 +283,12 @@ extern "C" int pvo_se3_unary_vjp(int op, const void* x, const void* gy, void* gx
   if (n == 0) return PVO_OK;
   if (!x || !gy || !gx) return PVO_EINVAL;
   const dim3 grid(static_cast<unsigned>((n + 255) / 256));
-  if (dtype == PVO_F32)
-    hipLaunchKernelGGL(se3_unary_vjp_kernel<float>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const float*>(x), static_cast<const float*>(gy), static_cast<float*>(gx), n);
-  else if (dtype == PVO_F64)
-    hipLaunchKernelGGL(se3_unary_vjp_kernel<double>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const double*>(x), static_cast<const double*>(gy), static_cast<double*>(gx), n);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch<float, double>(dtype, [&](auto tag) -> int {
+    using F = decltype(tag);
+    hipLaunchKernelGGL(se3_unary_vjp_kernel<F>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const F*>(x), static_cast<const F*>(gy), static_cast<F*>(gx), n);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 extern "C" int pvo_se3_binary_vjp(int op, const void* a, long long rep_a, const void* b, long long rep_b, const void* gy,
@@ -301,15 +297,13 @@ extern "C" int pvo_se3_binary_vjp(int op, const void* a, long long rep_a, const 
   if (n == 0) return PVO_OK;
   if (!a || !b || !gy || (!ga && !gb)) return PVO_EINVAL;
   const dim3 grid(static_cast<unsigned>((n + 255) / 256));
-  if (dtype == PVO_F32)
-    hipLaunchKernelGGL(se3_binary_vjp_kernel<float>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const float*>(a), rep_a, static_cast<const float*>(b), rep_b,
-                       static_cast<const float*>(gy), static_cast<float*>(ga), static_cast<float*>(gb), n);
-  else if (dtype == PVO_F64)
-    hipLaunchKernelGGL(se3_binary_vjp_kernel<double>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const double*>(a), rep_a, static_cast<const double*>(b), rep_b,
-                       static_cast<const double*>(gy), static_cast<double*>(ga), static_cast<double*>(gb), n);
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch<float, double>(dtype, [&](auto tag) -> int {
+    using F = decltype(tag);
+    hipLaunchKernelGGL(se3_binary_vjp_kernel<F>, grid, dim3(256), 0, pvo_stream(stream), op, static_cast<const F*>(a), rep_a, static_cast<const F*>(b), rep_b,
+                       static_cast<const F*>(gy), static_cast<F*>(ga), static_cast<F*>(gb), n);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 // projective_transform forward / backward (see proj_terms above).  Jj == NULL: coordinates and validity only.
@@ -323,17 +317,14 @@ extern "C" int pvo_proj_transform(const void* poses, const void* depths, const v
   if (N > 65535 || B > 65535) return PVO_EUNSUPPORTED;      // an edge / batch index is a grid coordinate (include/pvo_hip.h "Limits")
   const int HW = ht * wd;
   const dim3 grid((HW + 255) / 256, N, B);
-  if (dtype == PVO_F32)
-    hipLaunchKernelGGL(proj_fwd_kernel<float>, grid, dim3(256), 0, pvo_stream(stream), static_cast<const float*>(poses), static_cast<const float*>(depths),
-                       static_cast<const float*>(intr), ii, jj, P, N, HW, wd, nx, static_cast<float*>(x1), static_cast<float*>(valid),
-                       static_cast<float*>(Ji), static_cast<float*>(Jj), static_cast<float*>(Jz));
-  else if (dtype == PVO_F64)
-    hipLaunchKernelGGL(proj_fwd_kernel<double>, grid, dim3(256), 0, pvo_stream(stream), static_cast<const double*>(poses), static_cast<const double*>(depths),
-                       static_cast<const double*>(intr), ii, jj, P, N, HW, wd, nx, static_cast<double*>(x1), static_cast<double*>(valid),
-                       static_cast<double*>(Ji), static_cast<double*>(Jj), static_cast<double*>(Jz));
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch<float, double>(dtype, [&](auto tag) -> int {
+    using F = decltype(tag);
+    hipLaunchKernelGGL(proj_fwd_kernel<F>, grid, dim3(256), 0, pvo_stream(stream), static_cast<const F*>(poses), static_cast<const F*>(depths),
+                       static_cast<const F*>(intr), ii, jj, P, N, HW, wd, nx, static_cast<F*>(x1), static_cast<F*>(valid),
+                       static_cast<F*>(Ji), static_cast<F*>(Jj), static_cast<F*>(Jz));
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }
 
 // gposes [B,P,7] and gdepths [B,P,ht*wd] must be ZERO on entry (the products of all edges and pixels are added into them)
@@ -347,15 +338,12 @@ extern "C" int pvo_proj_transform_vjp(const void* poses, const void* depths, con
   if (N > 65535 || B > 65535) return PVO_EUNSUPPORTED;
   const int HW = ht * wd;
   const dim3 grid((HW + 255) / 256, N, B);
-  if (dtype == PVO_F32)
-    hipLaunchKernelGGL(proj_vjp_kernel<float>, grid, dim3(256), 0, pvo_stream(stream), static_cast<const float*>(poses), static_cast<const float*>(depths),
-                       static_cast<const float*>(intr), ii, jj, P, N, HW, wd, nx, static_cast<const float*>(g_x1), static_cast<const float*>(g_Ji),
-                       static_cast<const float*>(g_Jj), static_cast<const float*>(g_Jz), static_cast<float*>(gposes), static_cast<float*>(gdepths));
-  else if (dtype == PVO_F64)
-    hipLaunchKernelGGL(proj_vjp_kernel<double>, grid, dim3(256), 0, pvo_stream(stream), static_cast<const double*>(poses), static_cast<const double*>(depths),
-                       static_cast<const double*>(intr), ii, jj, P, N, HW, wd, nx, static_cast<const double*>(g_x1), static_cast<const double*>(g_Ji),
-                       static_cast<const double*>(g_Jj), static_cast<const double*>(g_Jz), static_cast<double*>(gposes), static_cast<double*>(gdepths));
-  else return PVO_EUNSUPPORTED;
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return pvo_dispatch<float, double>(dtype, [&](auto tag) -> int {
+    using F = decltype(tag);
+    hipLaunchKernelGGL(proj_vjp_kernel<F>, grid, dim3(256), 0, pvo_stream(stream), static_cast<const F*>(poses), static_cast<const F*>(depths),
+                       static_cast<const F*>(intr), ii, jj, P, N, HW, wd, nx, static_cast<const F*>(g_x1), static_cast<const F*>(g_Ji),
+                       static_cast<const F*>(g_Jj), static_cast<const F*>(g_Jz), static_cast<F*>(gposes), static_cast<F*>(gdepths));
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
 }

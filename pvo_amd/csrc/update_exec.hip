@@ -379,7 +379,7 @@ extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_upd
   // (the rider has preconditions the stand-alone convolution does not: at most 2^24 rows and 16-byte aligned operands,
   // pvo_ba_finish_riders - beyond them the mask is computed the old way, on this stream, instead of failing the update)
   const bool rider_fits = static_cast<long long>(K) * HW <= (1LL << 24) &&
-                          !((reinterpret_cast<uintptr_t>(b.a2) | reinterpret_cast<uintptr_t>(w->up_w) | reinterpret_cast<uintptr_t>(a.upmask)) & 15);
+                          !pvo_misaligned16(b.a2, w->up_w, a.upmask);
   const bool mask_rides = u->itrs > 0 && a.K > 0 && a.upmask && !rider_off && rider_fits;
   // ... and so does the gate context of the NEXT update (a function of this update's net_out and the weights): its partial
   // means in the first solve, the 1x1 context convolutions in the second

@@ -18,7 +18,7 @@ if sys.argv[1] == "build":
     build.build_hip()
     os.makedirs(PROBE_DIR, exist_ok=True)
     obj = os.path.join(PROBE_DIR, "%s_%s" % (tag, src.replace(".hip", ".o")))
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + build.HIPCC_FLAGS + defs + ["-c", os.path.join(build.CSRC, src), "-o", obj])
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + build.flags_for(src) + defs + ["-c", os.path.join(build.CSRC, src), "-o", obj])
     objs = [obj if s == src else os.path.join(build.CSRC, s.replace(".hip", ".o")) for s in build.HIP_SOURCES]
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path(tag)] + objs)
     print(lib_path(tag))
