@@ -74,9 +74,10 @@ const char* pvo_last_hip_error(void);
  * passed by pointer and have GROWN between versions (100 -> 101: pvo_graph_update_args.context_ahead / context_ready; 101 -> 102: no struct changed - new entry points
  * pvo_ba_pack / pvo_ba_finish_packed / pvo_ba_last_partition / pvo_proj_transform[_vjp], and pvo_ba_workspace_bytes returns more;
  * 104 -> 105: no struct changed - new entry points pvo_ba_train_workspace_bytes / pvo_ba_train_vjp_scratch_bytes /
- * pvo_ba_train / pvo_ba_train_vjp): a caller
+ * pvo_ba_train / pvo_ba_train_vjp; 105 -> 106: no struct changed - new entry points pvo_conv_planes_supported /
+ * pvo_conv_planes_filter_bytes / pvo_conv_planes_pack / pvo_conv_planes): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
-#define PVO_ABI_VERSION 105
+#define PVO_ABI_VERSION 106
 int pvo_version(void);
 size_t pvo_graph_update_args_size(void);
 
@@ -340,6 +341,26 @@ int pvo_bias_norm_act_split(const void* x, const void* bias, const void* residua
  * PVO_BF16).  Cin a multiple of 32, Cout of 64 (PVO_EUNSUPPORTED otherwise: callers keep the library convolution). */
 int pvo_conv1x1_planes(const void* x, const void* w, const void* bias, void* y, int N, int Cin, int Cout, int Hin, int Win, int stride,
                        int dtype, void* stream);
+/* The encoders' 3 x 3 and 7 x 7 convolutions on NCHW planes, on the matrix cores and DETERMINISTIC BY CONSTRUCTION (encoder_conv.hip; the
+ * stem and the twelve 3 x 3 convolutions of BasicEncoder, extractor.py:130-139 and :14-15, which the vendor library otherwise runs with kernels it picks from
+ * timings, split-K with atomics among them):
+ *   y[n][co][oy][ox] = epilogue(sum_{ci,ky,kx} w[co][ci][ky][kx] x[n][ci][oy stride + ky - p][ox stride + kx - p]),  zero padding p = ksize / 2,
+ * 16-bit products accumulated in fp32 (v_mfma_f32_16x16x32_f16 / _bf16) in an order fixed by the shape alone: no atomics, K is not split.
+ *   epilogue: t = round(acc); if bias: t = round(t + bias[co]); if relu_inner: relu; if residual: t = round(residual + t); if relu_outer:
+ *   relu - the operations, order and roundings of pvo_bias_norm_act with norm = 0; with everything off, y is the bare rounded convolution.
+ * Supported (pvo_conv_planes_supported returns 1, a HOST function; everything else: 0, and the calls return PVO_EUNSUPPORTED):
+ *   ksize 3, stride 1 or 2, Cin and Cout positive multiples of 32;   ksize 7, stride 2, Cin = 3, Cout a positive multiple of 32.
+ * pvo_conv_planes_pack re-arranges w [Cout][Cin][ksize][ksize] (`dtype`) ONCE per parameter version, on the device, into the order the
+ * kernel reads its filter fragments in: w_frag, pvo_conv_planes_filter_bytes(ksize, Cin, Cout) bytes (a multiple of 16; the stem's K = 147 is
+ * padded with zeros to 192; 0 for an unsupported shape), 16-byte aligned.
+ * pvo_conv_planes: x [N,Cin,H,W], y and residual (or NULL) [N,Cout,Ho,Wo] with Ho = (H - 1) / stride + 1, bias [Cout] or NULL, all `dtype`
+ * (PVO_F16 / PVO_BF16), contiguous; x, w_frag and y 16-byte aligned (PVO_EINVAL otherwise); y must not overlap x (PVO_EINVAL); residual may
+ * be y.  Any N >= 0, H, W >= 0: an empty input returns PVO_OK.  No allocation, synchronisation or host round trip: capturable. */
+int pvo_conv_planes_supported(int ksize, int stride, int Cin, int Cout);
+size_t pvo_conv_planes_filter_bytes(int ksize, int Cin, int Cout);
+int pvo_conv_planes_pack(const void* w, void* w_frag, int ksize, int Cin, int Cout, int dtype, void* stream);
+int pvo_conv_planes(const void* x, const void* w_frag, const void* bias, const void* residual, void* y, int N, int Cin, int Cout,
+                    int H, int W, int ksize, int stride, int relu_inner, int relu_outer, int dtype, void* stream);
 /* A frame as the stream hands it over ([3][H][W] BGR 0..255; in_kind 0 = int32, 1 = uint8, 2 = float32) -> the encoders' input [3][H][W] RGB
  * `dtype`: ((v / 255) - mean[c]) / std[c] in fp32, the operations and order of motion_filter.py:52-54, then rounded.  mean3 / std3: HOST
  * pointers to three floats each. */

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpvo_hip.so")
 
 PVO_F32, PVO_F16, PVO_BF16, PVO_F64 = 0, 1, 2, 3
-PVO_ABI_VERSION = 105          # include/pvo_hip.h
+PVO_ABI_VERSION = 106          # include/pvo_hip.h
 
 _c = ctypes
 _vp, _i, _f, _sz = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t
@@ -54,6 +54,10 @@ SIGNATURES = {
     "pvo_bias_norm_act_slices": (_i, [_i]),
     "pvo_bias_norm_act_split": (_i, [_vp, _vp, _vp, _vp, _c.c_longlong, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
     "pvo_conv1x1_planes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "pvo_conv_planes_supported": (_i, [_i, _i, _i, _i]),
+    "pvo_conv_planes_filter_bytes": (_sz, [_i, _i, _i]),
+    "pvo_conv_planes_pack": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "pvo_conv_planes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "pvo_frame_normalise": (_i, [_vp, _vp, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _i, _i, _vp]),
     "pvo_segment_hist": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "pvo_graph_post": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i, _f, _i, _vp]),

@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "update_exec.hip",
     "se3_ops.hip",
     "encoder_ops.hip",
+    "encoder_conv.hip",
     "ba.hip",
     "ba_train.hip",
 ]

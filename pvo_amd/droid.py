@@ -57,6 +57,9 @@ class Droid:
                 # the encoders run under fp16 autocast (motion_filter.py:50): every convolution, norm and add is an fp16 operation
                 # either way, but fp32 parameters are cast again in EVERY forward - 33 tiny kernels of ~120 per frame.  Cast once.
                 self.net.fnet.half(); self.net.cnet.half()
+        if getattr(self.args, "native_encoders", False):
+            # the encoders' 3 x 3 / 7 x 7 convolutions on the library's own deterministic kernel instead of the vendor library (opt-in)
+            self.net.fnet.native_convs = self.net.cnet.native_convs = True
 
     def track(self, tstamp, image, depth=None, intrinsics=None, segments=None):
         """one frame (droid.py:64-75).  args.pipelined (default False: the reference's order, the video is final for this frame when

@@ -1275,6 +1275,69 @@ def conv1x1_planes(x, w, bias=None, stride=1):
     return y
 
 
+def conv_planes_supported(ksize, stride, cin, cout):
+    """what pvo_conv_planes runs: 3 x 3 (padding 1) with stride 1 or 2, Cin and Cout multiples of 32; the 7 x 7 stride-2 stem (Cin = 3)"""
+    return bool(_lib.load().pvo_conv_planes_supported(int(ksize), int(stride), int(cin), int(cout)))
+
+
+class PackedConvFilter:
+    """a Conv2d weight in the fragment order of pvo_conv_planes (conv_planes_pack); `frag` is the device buffer"""
+    __slots__ = ("frag", "ksize", "cin", "cout", "dtype")
+
+    def __init__(self, frag, ksize, cin, cout, dtype):
+        self.frag, self.ksize, self.cin, self.cout, self.dtype = frag, ksize, cin, cout, dtype
+
+
+def conv_planes_pack(weight):
+    """weight [Cout,Cin,k,k] contiguous 16-bit -> PackedConvFilter (pvo_conv_planes_pack: once per parameter version, on the device)"""
+    dev = _dev(weight)
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.dtype not in (torch.float16, torch.bfloat16) or not weight.is_contiguous():
+        raise PvoHipError("conv_planes_pack: weight must be a contiguous 16-bit [Cout,Cin,k,k] tensor")
+    Cout, Cin, k, _ = weight.shape
+    lib = _lib.load()
+    nbytes = lib.pvo_conv_planes_filter_bytes(k, Cin, Cout)
+    if nbytes == 0:
+        raise PvoHipError("conv_planes_pack: unsupported filter %d x %d, %d -> %d channels" % (k, k, Cin, Cout))
+    frag = torch.empty(nbytes // 2, dtype=weight.dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.pvo_conv_planes_pack(_ptr(weight), _ptr(frag), k, Cin, Cout, _dtype_code(weight, "weight"), _stream(dev)), "conv_planes_pack")
+    return PackedConvFilter(frag, k, Cin, Cout, weight.dtype)
+
+
+def conv_planes(x, packed, bias=None, residual=None, stride=1, relu_inner=False, relu_outer=False, out=None):
+    """Conv2d(Cin, Cout, k, stride, padding = k // 2) on a contiguous 16-bit NCHW tensor, deterministic, on the matrix cores
+    (pvo_conv_planes), and what follows it in a norm-free encoder layer: relu_outer(residual + relu_inner(conv(x) + bias[c])), every step
+    rounded to x's dtype as bias_norm_act(norm=False) rounds it.  x [N,Cin,H,W], packed = conv_planes_pack(weight), bias [Cout] or None,
+    residual [N,Cout,Ho,Wo] or None -> [N,Cout,(H-1)//stride+1,(W-1)//stride+1] (`out`, if given; it must not be x)"""
+    if not isinstance(packed, PackedConvFilter):
+        raise PvoHipError("conv_planes: packed must come from conv_planes_pack")
+    dev = _dev(x, packed.frag, bias, residual, out)
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) or not x.is_contiguous():
+        raise PvoHipError("conv_planes: x must be a contiguous 16-bit [N,Cin,H,W] tensor")
+    N, Cin, H, W = x.shape
+    stride = int(stride)
+    if packed.dtype != x.dtype or packed.cin != Cin:
+        raise PvoHipError("conv_planes: the packed filter is %s with %d input channels, x is %s with %d" % (packed.dtype, packed.cin, x.dtype, Cin))
+    Cout, k = packed.cout, packed.ksize
+    if stride < 1 or not conv_planes_supported(k, stride, Cin, Cout):
+        raise PvoHipError("conv_planes: unsupported convolution %d x %d stride %d, %d -> %d channels" % (k, k, stride, Cin, Cout))
+    shape = (N, Cout, (H - 1) // stride + 1 if H else 0, (W - 1) // stride + 1 if W else 0)
+    for t, n in ((bias, "bias"), (residual, "residual"), (out, "out")):
+        if t is not None and (t.dtype != x.dtype or not t.is_contiguous()):
+            raise PvoHipError("conv_planes: %s must be contiguous and have x's dtype" % n)
+    if bias is not None and bias.numel() != Cout or residual is not None and tuple(residual.shape) != shape \
+            or out is not None and tuple(out.shape) != shape:
+        raise PvoHipError("conv_planes: bias [Cout], residual and out of the result's shape %s" % (shape,))
+    if out is not None and out.numel() and x.numel() and out.untyped_storage().data_ptr() == x.untyped_storage().data_ptr() \
+            and out.data_ptr() < x.data_ptr() + x.numel() * 2 and x.data_ptr() < out.data_ptr() + out.numel() * 2:
+        raise PvoHipError("conv_planes: out must not alias x")
+    y = torch.empty(shape, dtype=x.dtype, device=dev) if out is None else out
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_conv_planes(_ptr(x), _ptr(packed.frag), _vp(bias), _vp(residual), _ptr(y), N, Cin, Cout, H, W, k, stride,
+                                          1 if relu_inner else 0, 1 if relu_outer else 0, _dtype_code(x, "x"), _stream(dev)), "conv_planes")
+    return y
+
+
 _FRAME_KINDS = {torch.int32: 0, torch.uint8: 1, torch.float32: 2}
 
 

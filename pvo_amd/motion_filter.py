@@ -13,16 +13,23 @@ and each encoder is ONE HIP-graph launch after its first two calls
 import torch
 
 from .geom.projective_ops import coords_grid
-from .graphs import GraphedCall
+from .graphs import GraphedCall, _version
 from .modules.corr import CorrBlock
 
 
 def _weights_guard(module):
     """what a captured graph of `module` stays valid for: the storage and dtype of its parameters (.half() / .to() re-allocate them;
-    load_state_dict copies in place, which a replay sees)"""
+    load_state_dict copies in place, which a replay sees).  An encoder with native_convs reads its filters from re-arranged copies
+    (BasicEncoder._native_filter) whose addresses a capture has baked in and which are rebuilt when a parameter's version counter moves:
+    then the switch and every parameter's version are part of the key, as for the operator below."""
     def guard():
         p = next(iter(module.parameters()), None) if hasattr(module, "parameters") else None
-        return None if p is None else (p.data_ptr(), p.dtype)
+        if p is None:
+            return None
+        if not getattr(module, "native_convs", False):
+            return (p.data_ptr(), p.dtype)
+        # (asked of the module on every call: a parameter replaced later is seen; inference tensors have no counter: None)
+        return (p.data_ptr(), p.dtype, True, tuple(_version(q) for q in module.parameters()))
     return guard
 
 
