@@ -75,7 +75,9 @@ const char* pvo_last_hip_error(void);
  * pvo_ba_pack / pvo_ba_finish_packed / pvo_ba_last_partition / pvo_proj_transform[_vjp], and pvo_ba_workspace_bytes returns more;
  * 104 -> 105: no struct changed - new entry points pvo_ba_train_workspace_bytes / pvo_ba_train_vjp_scratch_bytes /
  * pvo_ba_train / pvo_ba_train_vjp; 105 -> 106: no struct changed - new entry points pvo_conv_planes_supported /
- * pvo_conv_planes_filter_bytes / pvo_conv_planes_pack / pvo_conv_planes): a caller
+ * pvo_conv_planes_filter_bytes / pvo_conv_planes_pack / pvo_conv_planes; still 106, convex upsampling: pvo_graph_update_args grew by
+ * want_upsample / disps_up / up_frames at its END (every earlier offset unchanged; pvo_graph_update_args_size() tells the two layouts apart),
+ * new entry points pvo_cvx_upsample / pvo_cvx_upsample_vjp_scratch_bytes / pvo_cvx_upsample_vjp): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -455,6 +457,13 @@ typedef struct pvo_graph_update_args {
    * this device returned op.net as net_out; the library then uses the stored context if that call was made with context_ahead,
    * the same workspace, weight struct and weight pointers, E, H, W and net_out == this op.net - and computes it as usual if not. */
   int context_ahead, context_ready;
+  /* Full-resolution inverse depth (upstream DROID-SLAM's DepthVideo.upsample after every update).  want_upsample != 0 with a depth BA
+   * (!motion_only, itrs > 0): ONE launch of pvo_cvx_upsample's channels-last kernel on the launch stream directly behind the last
+   * back-substitution (which also applies the depth clamp) - mask = the operator's upmask (computed whether or not want_upmask is set;
+   * it still rides in the first pose solve), rows up_frames of disps in, rows up_frames of disps_up out.  up_frames (device int64 [op.K]):
+   * the frame of each aggregation row, unique(ii) ascending; disps_up [nframes, 8 H, 8 W] f32, 16-byte aligned.  Ignored in a
+   * motion-only update or one without a BA iteration; want_upsample == 0: the launch sequence is unchanged. */
+  int want_upsample; float* disps_up; const int64_t* up_frames;
 } pvo_graph_update_args;
 
 size_t pvo_graph_update_workspace_bytes(int E, int K, int R, int H, int W, int max_segments);
@@ -488,6 +497,36 @@ int pvo_probe_arm_every(int stage, int capacity, int every);
 int pvo_probe_read(float* ms_host, int max_n);
 int pvo_graph_update(const pvo_update_weights* weights, const pvo_graph_update_args* args,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Convex 8x upsampling                                                       */
+/* ------------------------------------------------------------------------- */
+
+/* cvx_upsample (VO_Module/droid_slam/droid_net.py:23-37; upsample_dim_1 / upsample_dim_x :40-54; DepthVideo.upsample, depth_video.py:139-143):
+ *   out[b][8y+dy][8x+dx][d] = sum_k softmax_k(mask logit 64 k + 8 dy + dx at (y, x)) * data[b][y+ky-1][x+kx-1][d],  k = 3 ky + kx,
+ * neighbours outside the map are ZERO (F.unfold(padding = 1)); the weights are not renormalised at the border.
+ *   data [., H, W, D] and out [., 8H, 8W, D]: data_dtype PVO_F32 or PVO_F64, D = 1 or 2; out 16-byte aligned
+ *   mask: mask_planar = 0: channels-last [B,H,W,576] (what pvo_update_operator writes to pvo_operator_args.upmask);
+ *         mask_planar = 1: [B,576,H,W] (the PyTorch module's);  mask_dtype PVO_F16 / PVO_BF16 / PVO_F32 with fp32 data, PVO_F64 with fp64
+ *         data (anything else: PVO_EUNSUPPORTED); 16-byte aligned; mask_channels must be 576 (PVO_EINVAL otherwise, as for D)
+ *   in_rows / out_rows (device int64 [B], or NULL = the identity): batch row b reads data[in_rows[b]] and writes out[out_rows[b]], so K
+ *         mask rows update K frames of the video buffers in place; n_in / n_out = rows of the data / out buffers (a table entry outside
+ *         them makes its row a no-op, it is never dereferenced).  Two batch rows must not name the same out row.
+ * Logits are converted exactly to fp32 (fp64 for fp64 operands); m = max_k, e_k = exp(l_k - m), the sums of e_k and of e_k * nbr_k run in
+ * tap order 0..8, one division, one rounding on store.  No atomics: the same operands give the same bits on every call.  Any H, W >= 0.
+ * Planar masks: B * H * W * 576 < 2^31 elements.  No allocation or synchronisation: capturable.
+ * pvo_cvx_upsample_vjp (fp32 / fp64, mask and data of that one dtype, no row tables): from gout [B,8H,8W,D] writes gmask (the mask's
+ * layout) and gdata [B,H,W,D] in full; the softmax is recomputed from `mask`, nothing of the forward is kept.  gdata is a GATHER: a first
+ * launch leaves, per coarse pixel and tap, the sum of w_k * gout over its 64 fine pixels in `scratch` (pvo_cvx_upsample_vjp_scratch_bytes,
+ * 16-byte aligned, needed only while the call's kernels run), a second sums the nine terms of every gdata element in tap order - no
+ * floating-point atomics, bit-identical from call to call. */
+int pvo_cvx_upsample(const void* data, const void* mask, void* out, const int64_t* in_rows, const int64_t* out_rows,
+                     int n_in, int n_out, int B, int H, int W, int D, int mask_channels, int mask_planar,
+                     int data_dtype, int mask_dtype, void* stream);
+size_t pvo_cvx_upsample_vjp_scratch_bytes(int B, int H, int W, int D, int dtype);
+int pvo_cvx_upsample_vjp(const void* data, const void* mask, const void* gout, void* gmask, void* gdata,
+                         int B, int H, int W, int D, int mask_channels, int mask_planar, int dtype,
+                         void* scratch, size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Reprojection helpers                                                       */

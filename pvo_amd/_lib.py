@@ -58,6 +58,9 @@ SIGNATURES = {
     "pvo_conv_planes_filter_bytes": (_sz, [_i, _i, _i]),
     "pvo_conv_planes_pack": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "pvo_conv_planes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "pvo_cvx_upsample": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "pvo_cvx_upsample_vjp_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "pvo_cvx_upsample_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "pvo_frame_normalise": (_i, [_vp, _vp, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _i, _i, _vp]),
     "pvo_segment_hist": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "pvo_graph_post": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i, _f, _i, _vp]),
@@ -134,7 +137,8 @@ class GraphUpdateArgs(_c.Structure):
                 ("n_in", _i), ("target_ba", _vp), ("weight_ba", _vp), ("ii_ba", _vp), ("jj_ba", _vp),
                 ("t0", _i), ("t1", _i), ("itrs", _i), ("motion_only", _i), ("lm", _f), ("ep", _f),
                 ("sys", _vp), ("ba_ws", _vp), ("ba_ws_bytes", _sz), ("clamp_frames", _i), ("disp_min", _f),
-                ("want_upmask", _i), ("context_ahead", _i), ("context_ready", _i)]
+                ("want_upmask", _i), ("context_ahead", _i), ("context_ready", _i),
+                ("want_upsample", _i), ("disps_up", _vp), ("up_frames", _vp)]
 
 
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4

@@ -29,6 +29,7 @@ class DroidBackend:
         self.beta, self.backend_radius = args.beta, args.backend_radius
         self.backend_nms, self.backend_thresh = args.backend_nms, args.backend_thresh
         self.corr_impl = getattr(args, "backend_corr", "auto")      # "alt" = the reference's formulation (parity runs), "auto" = the fast one that fits
+        self.upsample = bool(getattr(args, "upsample", False))      # refresh video.disps_up in every global update (resident volumes only)
         self.last_corr_impl = None                                  # what the last pass ran on ("alt" / "volume"): results record it
 
     def _volumes_fit(self, n_edges):
@@ -43,7 +44,7 @@ class DroidBackend:
         return need < 0.6 * free
 
     def _graph(self, impl):
-        return FactorGraph(self.video, self.update_op, self.device, corr_impl=impl, max_factors=_EDGE_BUDGET)
+        return FactorGraph(self.video, self.update_op, self.device, corr_impl=impl, max_factors=_EDGE_BUDGET, upsample=self.upsample)
 
     def _connect_all(self, keep=None):
         """the global graph (droid_backend.py:31-33).  keep(ii, jj) -> mask: the edges this rank keeps (edge sharding).

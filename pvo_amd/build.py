@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "se3_ops.hip",
     "encoder_ops.hip",
     "encoder_conv.hip",
+    "cvx_upsample.hip",
     "ba.hip",
     "ba_train.hip",
 ]

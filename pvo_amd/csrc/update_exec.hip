@@ -350,7 +350,10 @@ extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_upd
                            s.motion, E, H, W, dt, stream));
   a.coords = s.coords; a.corr = nullptr; a.motion = s.motion; a.heads = s.heads;
   a.eta = u->op.eta ? u->op.eta : s.eta;          // (a caller that runs the BA itself - edge sharding - supplies the buffer)
-  if (u->want_upmask && !a.upmask) a.upmask = s.upmask;
+  // full-resolution depth behind the BA (pvo_graph_update_args.want_upsample): needs the mask, whoever else wants it
+  const bool upsample = u->want_upsample && !u->motion_only && u->itrs > 0;
+  if (upsample && (!u->disps_up || !u->up_frames)) return PVO_EINVAL;
+  if ((u->want_upmask || upsample) && !a.upmask) a.upmask = s.upmask;
   // the gate context may already be in the workspace: computed ahead by the previous call, for exactly this input
   const bool ahead_off = pvo_knob(PVO_KNOB_NO_RIDERS) != 0;      // (pvo_debug_config: tests compare with and without the riders)
   ContextAhead* ca = ctx_ahead_slot();
@@ -424,6 +427,11 @@ extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_upd
                              nullptr, nullptr, 0, nullptr, u->ba_ws, u->ba_ws_bytes, &jobs, stream));
   }
   probe_mark(PVO_STAGE_BA, 1, stream);
+  // On THIS stream, behind the last back-substitution and its depth clamp: the BA's kernels must not share the device with another
+  // queue's, and the upsampling reads the depths they leave.
+  if (upsample)
+    RUN(pvo_cvx_upsample(u->disps, a.upmask, u->disps_up, u->up_frames, u->up_frames, u->nframes, u->nframes, K, H, W, 1, 576, 0,
+                         PVO_F32, dt, stream));
   if (u->clamp_frames > 0 && (u->itrs == 0 || u->motion_only)) {      // (no back-substitution ran: clamp on its own)
     const long long n = static_cast<long long>(u->clamp_frames) * HW;
     hipLaunchKernelGGL(clamp_min_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, u->disps, n, u->disp_min);

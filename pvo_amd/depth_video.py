@@ -207,12 +207,29 @@ class DepthVideo:
         self.poses[:n, :3] *= s
         self.dirty[:n] = True
 
-    def upsample(self, ix, mask):
-        """convex 8x upsampling of the inverse depth of keyframes ix (depth_video.py:139-143)"""
-        from .droid_net import cvx_upsample
+    def ensure_disps_up(self):
+        """the full-resolution inverse depths [buffer, H, W], allocated on first use (most runs never ask for them)"""
         if self.disps_up is None:
             self.disps_up = torch.zeros(self.disps.shape[0], self.ht, self.wd, dtype=torch.float, device=self.device)
-        self.disps_up[ix] = cvx_upsample(self.disps[ix].unsqueeze(-1), mask).squeeze(-1)
+        return self.disps_up
+
+    def upsample(self, ix, mask):
+        """convex 8x upsampling of the inverse depth of keyframes ix (depth_video.py:139-143): disps_up[ix] from disps[ix] and the
+        logits mask [len(ix), 576, h, w] (planar, or channels-last as the native update operator writes them).  On the device one
+        native kernel reads rows ix of disps and writes rows ix of disps_up in place (ix: a tensor or a host sequence, each frame
+        once); on the host the PyTorch formulation."""
+        up = self.ensure_disps_up()
+        if self.device.type == "cuda":
+            if isinstance(ix, torch.Tensor):
+                ix = ix.to(device=self.device, dtype=torch.long).reshape(-1).contiguous()
+            if mask.dim() == 5 and mask.shape[0] == 1:
+                mask = mask[0]
+            db.cvx_upsample(self.disps.unsqueeze(-1), mask, out=up.unsqueeze(-1), in_rows=ix, out_rows=ix)
+            return
+        from .droid_net import cvx_upsample
+        ix = torch.as_tensor(ix, dtype=torch.long, device=self.device)
+        mask = mask.reshape(-1, 576, self.ht // 8, self.wd // 8).float().contiguous()
+        up[ix] = cvx_upsample(self.disps[ix].unsqueeze(-1), mask).squeeze(-1)
 
     @staticmethod
     def format_indicies(ii, jj, device):

@@ -39,7 +39,7 @@ class Droid:
         self.frontend = DroidFrontend(self.net.update, self.video, args.device, warmup=args.warmup, beta=args.beta,
                                       frontend_nms=args.frontend_nms, keyframe_thresh=args.keyframe_thresh,
                                       frontend_window=args.frontend_window, frontend_thresh=args.frontend_thresh,
-                                      frontend_radius=args.frontend_radius)
+                                      frontend_radius=args.frontend_radius, upsample=bool(getattr(args, "upsample", False)))
         self.filterx.before_context = self.frontend.keyframe_ahead
         self.backend = DroidBackend(self.net, self.video, args)
         self.traj_filler = PoseTrajectoryFiller(self.net, self.video, args.device)
@@ -112,8 +112,14 @@ class Droid:
         self.flush()
         return SE3(self.video.poses[:self.video.counter]).data.cpu().numpy()
 
-    def get_depth(self):
+    def get_depth(self, convex=False):
+        """inverse depth of the keyframes at image resolution [counter, H, W]: bilinear enlargement of the 1/8-resolution maps, or -
+        convex=True, tracking with args.upsample - the convex upsampling the network was trained to produce (video.disps_up)"""
         self.flush()
+        if convex:
+            if not getattr(self.args, "upsample", False) or self.video.disps_up is None:
+                raise RuntimeError("get_depth(convex=True) needs tracking with args.upsample = True (video.disps_up is not maintained)")
+            return self.video.disps_up[:self.video.counter]
         d = self.video.disps[:self.video.counter]
         return upsample_inter(d[None, ..., None]).squeeze(4).squeeze(0)
 

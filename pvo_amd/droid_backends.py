@@ -1381,6 +1381,83 @@ def graph_update(weights, args, workspace):
                                            workspace.numel(), _stream(dev)), "graph_update")
 
 
+# --------------------------------------------------------------------------- convex upsampling
+def _cvx_mask_layout(mask, what):
+    """mask [B,576,H,W]: planar (contiguous) -> 1, channels-last ([B,H,W,576] in memory, what the update operator writes) -> 0"""
+    if mask.dim() != 4 or mask.shape[1] != 576:
+        raise PvoHipError("%s: mask must be [B,576,H,W] (9 taps x 8 x 8 logits); got %s" % (what, tuple(mask.shape)))
+    if mask.is_contiguous():
+        return 1
+    if mask.permute(0, 2, 3, 1).is_contiguous():
+        return 0
+    raise RuntimeError("mask must be contiguous")
+
+
+def _cvx_rows(rows, B, n, dev, name):
+    """a row table: None, a host sequence (range-checked here) or a device int64 tensor [B] (entries outside the buffer are no-ops)"""
+    if rows is None:
+        return None
+    if not isinstance(rows, torch.Tensor):
+        rows = [int(r) for r in rows]
+        if any(r < 0 or r >= n for r in rows):
+            raise PvoHipError("cvx_upsample: %s names a row outside the buffer of %d rows" % (name, n))
+        rows = to_device_async(rows, torch.long, dev)
+    _dev(rows); _long(rows, name); _contig(rows, name)
+    if rows.dim() != 1 or rows.shape[0] != B:
+        raise PvoHipError("cvx_upsample: %s must have one entry per mask row (%d)" % (name, B))
+    return rows
+
+
+def cvx_upsample(data, mask, out=None, in_rows=None, out_rows=None):
+    """droid_net.cvx_upsample as ONE kernel (pvo_cvx_upsample): data [N,H,W,D] fp32 / fp64 with D = 1 or 2, mask [B,576,H,W] logits -
+    contiguous (planar) or channels-last, fp16 / bf16 / fp32 with fp32 data, fp64 with fp64 data - -> out [N',8H,8W,D].
+    in_rows / out_rows (int64 [B] on the device, or host sequences): mask row b reads data[in_rows[b]] and writes out[out_rows[b]];
+    without them N = B and a fresh out has B rows.  Rows of `out` that no mask row names are not touched."""
+    dev = _dev(data, mask, out)
+    _contig(data, "data")
+    planar = _cvx_mask_layout(mask, "cvx_upsample")
+    if data.dim() != 4 or data.shape[3] not in (1, 2) or tuple(data.shape[1:3]) != tuple(mask.shape[2:]):
+        raise PvoHipError("cvx_upsample: data must be [N,H,W,D] with D = 1 or 2 and the mask's H, W; got %s for mask %s"
+                          % (tuple(data.shape), tuple(mask.shape)))
+    B, _, H, W = mask.shape
+    N, D = data.shape[0], data.shape[3]
+    if out is None:
+        out = torch.empty(B if out_rows is None else N, 8 * H, 8 * W, D, dtype=data.dtype, device=dev)
+    _contig(out, "out")
+    if out.dim() != 4 or tuple(out.shape[1:]) != (8 * H, 8 * W, D) or out.dtype != data.dtype:
+        raise PvoHipError("cvx_upsample: out must be [N',%d,%d,%d] %s" % (8 * H, 8 * W, D, data.dtype))
+    if (in_rows is None and N < B) or (out_rows is None and out.shape[0] < B):
+        raise PvoHipError("cvx_upsample: %d mask rows need %d rows of data and out (or row tables)" % (B, B))
+    in_rows = _cvx_rows(in_rows, B, N, dev, "in_rows")
+    out_rows = _cvx_rows(out_rows, B, out.shape[0], dev, "out_rows")
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_cvx_upsample(_ptr(data), _ptr(mask), _ptr(out), _vp(in_rows), _vp(out_rows), N, out.shape[0], B, H, W, D,
+                                           mask.shape[1], planar, _dtype_code(data, "cvx_upsample"), _dtype_code(mask, "cvx_upsample"),
+                                           _stream(dev)), "cvx_upsample")
+    return out
+
+
+def cvx_upsample_vjp(data, mask, gout):
+    """(gmask in the mask's layout, gdata) of cvx_upsample(data, mask) for the output gradient gout [B,8H,8W,D]; fp32 or fp64 throughout,
+    bit-identical from call to call (pvo_cvx_upsample_vjp)"""
+    dev = _dev(data, mask, gout)
+    _contig(data, "data"); _contig(gout, "gout")
+    planar = _cvx_mask_layout(mask, "cvx_upsample_vjp")
+    B, _, H, W = mask.shape
+    D = data.shape[-1]
+    if tuple(data.shape) != (B, H, W, D) or tuple(gout.shape) != (B, 8 * H, 8 * W, D) or not (data.dtype == mask.dtype == gout.dtype) \
+            or data.dtype not in (torch.float32, torch.float64):
+        raise PvoHipError("cvx_upsample_vjp: data [B,H,W,D], mask [B,576,H,W], gout [B,8H,8W,D], all fp32 or all fp64")
+    gmask, gdata = torch.empty_like(mask), torch.empty_like(data)         # (preserve_format: the mask's own layout)
+    lib = _lib.load()
+    dt = _DT[data.dtype]
+    scratch = torch.empty(lib.pvo_cvx_upsample_vjp_scratch_bytes(B, H, W, D, dt), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.pvo_cvx_upsample_vjp(_ptr(data), _ptr(mask), _ptr(gout), _ptr(gmask), _ptr(gdata), B, H, W, D, mask.shape[1], planar, dt,
+                                       _ptr(scratch), scratch.numel(), _stream(dev)), "cvx_upsample_vjp")
+    return gmask, gdata
+
+
 # --------------------------------------------------------------------------- SE3 element-wise operations
 SE3_OPS = {"exp": 0, "log": 1, "inv": 2, "mul": 3, "act4": 4, "act3": 5, "adj": 6, "adjT": 7}
 _SE3_OUT = {"exp": 7, "log": 6, "inv": 7, "mul": 7, "act4": 4, "act3": 3, "adj": 6, "adjT": 6}

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from .geom import projective_ops as pops
 from .geom import ba_native
+from .geom import upsample_native
 from .geom.ba import BA
 from .geom.graph_utils import graph_to_edge_list, keyframe_indicies
 from .modules.corr import CorrBlock
@@ -69,7 +70,7 @@ class DroidNet(nn.Module):
         return fmaps, torch.tanh(net), torch.relu(inp)
 
     def forward(self, Gs, images, disps, intrinsics, graph=None, num_steps=12, fixedp=2, ret_flow=False,
-                downsample=False, segments=None, corr_dtype=None, native_ba=False):
+                downsample=False, segments=None, corr_dtype=None, native_ba=False, native_upsample=False):
         """Unrolled estimation over a frame graph (droid_net.py:342-439).  Returns per-step lists
         (Gs, upsampled disps, residuals[, full flows], masks[, affine-brightness params]).
         corr_dtype (e.g. torch.bfloat16, BASELINE.json configs[4]): the all-pairs volume, its pyramid and the lookup
@@ -77,7 +78,10 @@ class DroidNet(nn.Module):
         operator and the BA stay in the module's dtype (the BA in fp32).
         native_ba: the two BA steps per update go through pvo_amd.geom.ba_native.BA (libpvo_hip, forward and backward) instead of
         the PyTorch BA; its plan is built once here, the graph being the same for every update.  Device tensors only (ValueError
-        otherwise)."""
+        otherwise).
+        native_upsample: disp_list's convex upsampling goes through pvo_amd.geom.upsample_native (one HIP kernel forward, two
+        backward, nothing but disps and the mask kept for the backward) instead of `upsample_dim_1`'s PyTorch chain.  Device tensors,
+        fp32 / fp64 (ValueError otherwise)."""
         ii, jj, _ = graph_to_edge_list(graph)
         ii = ii.to(device=images.device, dtype=torch.long)
         jj = jj.to(device=images.device, dtype=torch.long)
@@ -130,7 +134,7 @@ class DroidNet(nn.Module):
             target_all = coords1 + delta_dy
 
             Gs_list.append(Gs)
-            disp_list.append(upsample_dim_1(disps, upmask["disp"]))
+            disp_list.append((upsample_native.upsample_dim_1 if native_upsample else upsample_dim_1)(disps, upmask["disp"]))
             residual_list.append(residual)
             mask_list.append(upsample_inter(mask))
             if ret_flow:

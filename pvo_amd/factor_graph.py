@@ -100,8 +100,11 @@ _CACHE_SERIAL = itertools.count(1)
 class FactorGraph:
     _index_dirty = False             # host edge lists changed since (ii, jj, age) were last uploaded
 
-    def __init__(self, video, update_op, device="cuda:0", corr_impl="volume", max_factors=-1):
+    def __init__(self, video, update_op, device="cuda:0", corr_impl="volume", max_factors=-1, upsample=False):
         self.video, self.update_op = video, update_op
+        # upstream DROID-SLAM's constructor argument: every depth update also refreshes video.disps_up (the full-resolution inverse
+        # depth, convex upsampling with GraphAgg's mask) for the frames unique(ii).  Off: nothing is allocated, launched or uploaded.
+        self.upsample = bool(upsample)
         self.device = torch.device(device)
         self.max_factors, self.corr_impl = max_factors, corr_impl
         self.ht, self.wd = ht, wd = video.ht // 8, video.wd // 8
@@ -427,7 +430,9 @@ class FactorGraph:
         """drop keyframe ix and every edge touching it (factor_graph.py:202-225)"""
         self._corr_sync()                  # (the per-frame buffers below are read by a pending side-stream build)
         v = self.video
-        for buf in (v.poses, v.disps, v.intrinsics, v.nets, v.inps, v.fmaps) + ((v.segms,) if v.segm_filter else ()):
+        up = getattr(v, "disps_up", None)                               # (kept in step with disps where it is maintained)
+        for buf in (v.poses, v.disps, v.intrinsics, v.nets, v.inps, v.fmaps) + ((v.segms,) if v.segm_filter else ()) + \
+                ((up,) if self.upsample and up is not None else ()):
             buf[ix] = buf[ix + 1].clone()
         m = [(i == ix) or (j == ix) for i, j in zip(self._ii_h, self._jj_h)]
         for t in (self.ii_inac, self.jj_inac):                       # (masked in-place updates would synchronise)
@@ -453,6 +458,8 @@ class FactorGraph:
         (`ShardedBA.sync_disps` merges them when something needs all of them)."""
         self._corr_sync()
         from .modules.corr import AltCorrBlock
+        if self.upsample and sharded is not None:
+            raise NotImplementedError("FactorGraph(upsample=True): an edge-sharded bundle adjustment does not refresh disps_up")
         t = self.video.counter
         ht, wd = self.ht, self.wd
         if self.corr_impl == "volume" and self._fused_ok() and self.P_zr is not None:
@@ -465,6 +472,9 @@ class FactorGraph:
                 self._update_fused(1, t, itrs, False, EP, False, eta_scale=1.0, lm=1e-5, ep=1e-2, sharded=sharded, segm_vote=False)
                 self.video.dirty[:t] = True
             return
+        if self.upsample:
+            raise NotImplementedError("FactorGraph(upsample=True): update_lowmem refreshes disps_up only on resident correlation "
+                                      "volumes (corr_impl='volume' with the native update), not on its alt-corr path")
         corr_op = AltCorrBlock(self.video.fmaps[None, :t], channels_last=True)
         jmax = max(self._jj_h + self._ii_h) if sharded is not None else max(self._jj_h)
         chunks = []
@@ -705,6 +715,8 @@ class FactorGraph:
         update the host fills one argument struct.  State tensors (net, target_cam, delta_dy, raw_mask, weight,
         full_flow) are updated IN PLACE.  segm_vote=False: no panoptic vote even when the video filters by segments
         (update_lowmem: the reference's global update never votes, factor_graph.py:309-360)."""
+        if self.upsample and sharded is not None:
+            raise NotImplementedError("FactorGraph(upsample=True): an edge-sharded bundle adjustment does not refresh disps_up")
         from . import droid_backends as db
         from ._lib import GraphUpdateArgs
         from .droid_backends import to_device_packed
@@ -716,10 +728,11 @@ class FactorGraph:
             t0 = max(1, min(self._ii_h) + 1)
         if t1 is None:
             t1 = max(max(self._ii_h), max(self._jj_h)) + 1
+        up_ptr = v.ensure_disps_up().data_ptr() if self.upsample else 0
         vote = bool(segm_vote and v.segm_filter)
         S = (v.segments_bound() if hasattr(v, "segments_bound") else v.max_segments) if vote else 0
         key = (self._version, t0, t1, bool(use_inactive), bool(motion_only), E, float(eta_scale), float(lm), float(ep), sharded is not None,
-               vote, S)
+               vote, S, self.upsample, up_ptr)
         st = self._cache.get("fused")
         if st is None or st["key"] != key:
             src = sorted(set(self._ii_h))
@@ -735,6 +748,8 @@ class FactorGraph:
                      (seg_idx, torch.int32), (self.corr.slots, torch.int32), ([k for k, f in enumerate(m_l) if f], torch.long)]
             if self._index_dirty:
                 parts += [(self._ii_h, torch.long), (self._jj_h, torch.long), (self._age_h, torch.long)]
+            if self.upsample:
+                parts.append((src, torch.long))                    # the frame of each aggregation row: rows of disps / disps_up
             up = to_device_packed(parts, self.device)
             frames_t, pos_t, seg, slots_t, m = up[0], up[1], (up[2], up[3], nseg), up[4], up[5]
             if self._index_dirty:
@@ -782,6 +797,11 @@ class FactorGraph:
                 a.sys, a.ba_ws, a.ba_ws_bytes = dummy.data_ptr(), dummy.data_ptr(), dummy.numel() * 8
             a.clamp_frames, a.disp_min = v.disps.shape[0], 0.001
             a.want_upmask = 1 if self.want_upmask else 0
+            if self.upsample:
+                st["up_frames"] = up[-1]
+                a.want_upsample, a.disps_up, a.up_frames = 1, up_ptr, up[-1].data_ptr()
+            else:
+                a.want_upsample, a.disps_up, a.up_frames = 0, None, None
         a = st["args"]
         # per update: the state tensors (a caller may have re-assigned them) and the scalar arguments
         for n in ("target_cam", "delta_dy", "raw_mask", "weight"):
@@ -915,6 +935,8 @@ class FactorGraph:
         target_cam = target_cam.view(-1, ht, wd, 2).permute(0, 3, 1, 2).contiguous()
         weight = weight.view(-1, ht, wd, 2).permute(0, 3, 1, 2).contiguous()
         self.video.ba(target_cam, weight, eta, ii, jj, t0, t1, itrs=itrs, lm=1e-4, ep=0.1, motion_only=motion_only)
+        if self.upsample and not motion_only and itrs > 0:           # (as the native update: only a depth update moves disps)
+            self.video.upsample(self._cached("src", lambda: torch.tensor(src, device=self.device)), upmask["disp"])
         self.full_flow = coords1 + self.delta_dy - self.coords0
         self.age += 1
         self._age_h = [a + 1 for a in self._age_h]

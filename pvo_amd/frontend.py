@@ -14,9 +14,9 @@ from .factor_graph import FactorGraph
 
 class DroidFrontend:
     def __init__(self, update_op, video, device="cuda:0", warmup=8, beta=0.3, frontend_nms=1, keyframe_thresh=4.0,
-                 frontend_window=25, frontend_thresh=16.0, frontend_radius=2, max_factors=48):
+                 frontend_window=25, frontend_thresh=16.0, frontend_radius=2, max_factors=48, upsample=False):
         self.video, self.update_op = video, update_op
-        self.graph = FactorGraph(video, update_op, device, max_factors=max_factors)
+        self.graph = FactorGraph(video, update_op, device, max_factors=max_factors, upsample=upsample)
         self.t0 = self.t1 = 0
         self.is_initialized = False
         self.count = 0

@@ -7,7 +7,8 @@ unrolled updates, bf16 volume, fp32 operator / BA, Adam).   On the GPU box:
 Without rocprofv3 it prints the step's wall time and the host-side time of its phases (forward / loss / backward / optimizer),
 each closed by a device synchronisation.  `--native_ba True` runs the unrolled BA steps in libpvo_hip (pvo_amd.geom.ba_native),
 `--native_ba both` alternates the two forms step by step in one process (the same clips for both); PVO_TRAIN_REPS measured steps
-(default 3) follow PVO_TRAIN_WARMUP warm-up steps (default 1) per form."""
+(default 3) follow PVO_TRAIN_WARMUP warm-up steps (default 1) per form.  `--native_upsample True | both` does the same for the depth maps'
+convex upsampling (pvo_amd.geom.upsample_native); with both switches on `both` the four combinations alternate."""
 import csv, glob, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -69,7 +70,9 @@ from pvo_amd.synthetic import TrainClips
 device = torch.device("cuda:0")
 args = T.parse_args(["--device", "cuda"])
 native = sys.argv[sys.argv.index("--native_ba") + 1] if "--native_ba" in sys.argv else "False"
-forms = {"true": [True], "false": [False], "both": [False, True]}[native.lower()]
+ups = sys.argv[sys.argv.index("--native_upsample") + 1] if "--native_upsample" in sys.argv else "False"
+_sel = {"true": [True], "false": [False], "both": [False, True]}
+forms = [(b, u) for b in _sel[native.lower()] for u in _sel[ups.lower()]]          # (native_ba, native_upsample), alternating step by step
 torch.manual_seed(0)
 net = DroidNet().to(device).train()
 opt = torch.optim.Adam(net.parameters(), lr=args.lr, weight_decay=1e-5)
@@ -90,7 +93,7 @@ for k in range(reps + warm):
         Gs.data[:, 0] = Ps.data[:, 0]; Gs.data[:, 1:] = Ps.data[:, [1]]
         t0 = time.perf_counter()
         out = net(Gs, images, torch.ones_like(disps[:, :, 3::8, 3::8]), intr / 8.0, graph, num_steps=15, fixedp=2, ret_flow=True,
-                  downsample=True, segments=segments, corr_dtype=torch.bfloat16, native_ba=form)
+                  downsample=True, segments=segments, corr_dtype=torch.bfloat16, native_ba=form[0], native_upsample=form[1])
         f = lap(t0); t0 = time.perf_counter()
         loss, _ = T.objective(args, L, out, (images, Ps, disps, intr, gt_masks, gt_vals), graph, ssim, 0)
         l = lap(t0); t0 = time.perf_counter()
@@ -103,5 +106,5 @@ for k in range(reps + warm):
                 ph[form][name].append(v)
 import statistics
 for form in forms:
-    print("S-T training step, native_ba=%s (median [min, max] of %d after %d warm-up): " % (form, reps, warm) +
+    print("S-T training step, native_ba=%s native_upsample=%s (median [min, max] of %d after %d warm-up): " % (form[0], form[1], reps, warm) +
           ", ".join("%s %.1f [%.1f, %.1f] ms" % (k, statistics.median(v) * 1e3, min(v) * 1e3, max(v) * 1e3) for k, v in ph[form].items()))

@@ -74,6 +74,8 @@ def parse_args(argv=None):
     p.add_argument("--corr_dtype", default="bfloat16", choices=["float32", "bfloat16", "float16"])
     p.add_argument("--native_ba", type=str2bool, default=False,
                    help="the unrolled BA steps in libpvo_hip (pvo_amd.geom.ba_native) instead of the PyTorch BA; GPU only")
+    p.add_argument("--native_upsample", type=str2bool, default=False,
+                   help="the depth maps' convex upsampling in libpvo_hip (pvo_amd.geom.upsample_native) instead of the PyTorch chain; GPU only")
     p.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu: gloo, for the plumbing tests")
     p.add_argument("--port", type=int, default=12356)
     p.add_argument("--dist_backend", default="auto", choices=["auto", "nccl", "gloo"],
@@ -217,7 +219,7 @@ def train(rank, args, report=None):
                     want_flow = args.flow_label or args.ph_loss
                     out = ddp(Gs, images, disp0, intrinsics / 8.0, graph, num_steps=args.iters, fixedp=2, ret_flow=want_flow,
                               downsample=args.downsample, **({"segments": segments} if want_flow else {}), corr_dtype=corr_dtype,
-                              native_ba=args.native_ba)
+                              native_ba=args.native_ba, native_upsample=args.native_upsample)
                     loss, metrics = objective(args, L, out, (images, Ps, disps, intrinsics, gt_masks, gt_vals), graph, ssim, total)
                     loss.backward()
                     Gs = out[0][-1].detach()
