@@ -575,6 +575,13 @@ int pvo_reproject_motion(const float* poses, const float* disps, const float* in
                          const float* target, const float* delta_dy, const float* raw_mask, void* motn,
                          int E, int ht, int wd, int dtype, void* stream);
 
+/* RGB-D ingest (upstream DROID-SLAM's depth[3::8, 3::8] and 1 / depth): one launch.  depth [H,W] (PVO_F32 or PVO_F16, at image
+ * resolution, resized and cropped like the image), disps_sens_row [H/8, W/8] fp32 - one frame's row of the sensor map:
+ *     disps_sens_row[y][x] = 1 / d  where d = depth[8y+3][8x+3] is finite and > 0,   0 otherwise (0, negative, NaN, inf)
+ * for y < H/8, x < W/8 (integer division: any H, W; rows and columns beyond 8 * (H/8), 8 * (W/8) are not read).  The division is
+ * fp32's correctly rounded one on the value converted to fp32.  H < 8 or W < 8 writes nothing. */
+int pvo_depth_sense(const void* depth, float* disps_sens_row, int H, int W, int dtype, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */
 /* ------------------------------------------------------------------------- */
@@ -669,6 +676,35 @@ int pvo_ba(float* poses, float* disps, const float* intrinsics,
 int pvo_ba_plan(const int64_t* ii, const int64_t* jj, int E, int nframes, int HW,
                 int K_eta, int t0, int t1, void* workspace, size_t workspace_bytes,
                 void* stream);
+/* RGB-D: the sensor-depth term of the depth bundle adjustment (upstream DROID-SLAM's `disps_sens`; the reference has none).
+ * disps_sens [nframes,ht,wd] fp32 is the MEASURED inverse depth of every frame, 0 = no measurement at that pixel.  For depth frame
+ * k (frame f = kx[k]) and pixel x, with C = sum Cii and w = sum bz over the frame's out-edges and m = disps_sens[f][x] > 0:
+ *     C' = C + (m ? alpha : eta[k][x]),   w' = w - (m ? alpha * (disps[f][x] - disps_sens[f][x]) : 0),   Q = 1 / C'
+ * and everything downstream (Schur terms, right-hand side, dz = Q (w' - E^T dx)) reads Q and w' as it read Q and w.  disps[f] is
+ * the value at the start of each Gauss-Newton step.  A motion-only step has no depth phase and is untouched.
+ *   pvo_ba_depth_prior records {disps_sens, alpha} in the device-side state of a PLANNED workspace (one single-thread launch on
+ *     `stream`, no host synchronisation, capturable).  Every later pvo_ba_local on that workspace - pvo_graph_update's internal
+ *     bundle adjustment and an edge-sharded run included - applies the term; E, P, nframes, HW are the workspace's own (as for
+ *     pvo_ba_workspace_bytes).  pvo_ba_plan RESETS it to none, so call it after every plan; disps_sens == NULL clears it too.
+ *     The map is read at every step: it must stay allocated, [nframes,ht,wd], for as long as the workspace is used with it.
+ *   pvo_ba_prior is pvo_ba with the term (disps_sens == NULL: pvo_ba itself, which is this call with NULL).
+ * Limits: alpha > 0 where a map is given (PVO_EINVAL otherwise); fp32 only.
+ * Deliberate difference from upstream: the term applies to a depth frame only where that frame has at least ONE OUT-EDGE in the
+ * call's edge list.  Under edge sharding by source keyframe every rank plans all window frames as depth frames; a frame a rank
+ * does not own has C = w = 0 there and keeps dz = 0, so the sharded result stays bit-identical to the whole graph's.  On a whole
+ * graph this differs from upstream only for a window frame without out-edges, which keeps its depth map.
+ * Bit identities (selects, not blends): an all-zero map gives the bits of no map; a map equal to disps on its measured pixels
+ * (residual exactly 0) gives, for ONE step, the bits of pvo_ba with eta' = where(disps_sens > 0, alpha, eta). */
+int pvo_ba_depth_prior(void* workspace, size_t workspace_bytes, int E, int P, int nframes, int HW,
+                       const float* disps_sens, float alpha, void* stream);
+int pvo_ba_prior(float* poses, float* disps, const float* intrinsics,
+                 const float* targets, const float* weights, const float* eta,
+                 const int64_t* ii, const int64_t* jj,
+                 int E, int nframes, int ht, int wd, int K_eta,
+                 int t0, int t1, int iterations, float lm, float ep, int motion_only,
+                 float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                 void* workspace, size_t workspace_bytes,
+                 const float* disps_sens, float alpha, void* stream);
 /* The envelope pose solve beyond 29 free poses (the global bundle adjustment; the reference: Eigen's sparse LLT on the host,
  * droid_kernels.cu:1160-1198) is PARTITIONED when the system is block-banded: two workgroups eliminate the pose chain from
  * both ends at once, the separator - the poses that couple the two parts - last (ba.hip, ba_solve_twin_kernel).  Same

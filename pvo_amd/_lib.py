@@ -89,6 +89,10 @@ SIGNATURES = {
     "pvo_ba": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
                     _f, _f, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "pvo_ba_plan": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "pvo_ba_depth_prior": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _f, _vp]),
+    "pvo_ba_prior": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
+                          _f, _f, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _f, _vp]),
+    "pvo_depth_sense": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),

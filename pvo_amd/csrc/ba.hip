@@ -85,6 +85,7 @@ struct Plan {            // int region of the workspace
   int* eptr;             // [F+1] CSR over depth index -> edges (ascending edge id)
   int* eidx;             // [E]
   int* meta;             // [8]   0:K 1:status(non-SPD) 2:eta mismatch 3:row table overflow 4:non-finite / out-of-range system entry
+                         //       5,6: the sensor-depth prior's map (low / high word of a const float*, 0 = none) 7: its alpha (float bits)
   int* env;              // [P]   numeric envelope of a system for the envelope solve (ba_env_kernel; INT_MAX between solves)
 };
 
@@ -154,11 +155,31 @@ __host__ Ws carve(void* base, int E, int P, int F, int HW) {
 }
 
 // ---------------------------------------------------------------------------
+// the sensor-depth prior (pvo_ba_depth_prior): part of the plan's device-side state, read once per workgroup by the depth phase
+// ---------------------------------------------------------------------------
+struct DepthPrior { const float* sens; float alpha; };     // sens: [F][HW] measured inverse depth, 0 = no measurement; nullptr = none
+
+__device__ __forceinline__ void store_prior(int* meta, const float* sens, float alpha) {
+  const unsigned long long a = reinterpret_cast<unsigned long long>(sens);
+  meta[5] = static_cast<int>(a & 0xffffffffull);
+  meta[6] = static_cast<int>(a >> 32);
+  meta[7] = sens ? __float_as_int(alpha) : 0;
+}
+__device__ __forceinline__ DepthPrior load_prior(const int* meta) {
+  const unsigned long long a = (static_cast<unsigned long long>(static_cast<unsigned>(meta[6])) << 32) | static_cast<unsigned>(meta[5]);
+  DepthPrior pr;
+  pr.sens = reinterpret_cast<const float*>(a);
+  pr.alpha = __int_as_float(meta[7]);
+  return pr;
+}
+__global__ void ba_prior_kernel(int* meta, const float* sens, float alpha) { store_prior(meta, sens, alpha); }
+
+// ---------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ba_plan_kernel(
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, Plan pl,
-    int E, int F, int t0, int t1, int K_eta, int motion_only) {
+    int E, int F, int t0, int t1, int K_eta, int motion_only, const float* sens, float alpha) {
   __shared__ int seg[257];
   const int tid = threadIdx.x;
   for (int b = tid; b < t1 - t0; b += 256) pl.env[b] = 0x7fffffff;
@@ -212,6 +233,7 @@ __global__ __launch_bounds__(256) void ba_plan_kernel(
     // row count, so depth frames beyond it would keep stale Q / w; the solve reports failure (dx = 0, poses untouched) and the
     // back-substitution leaves every depth map alone (status_out[0] = 1, [2] = 1).
     pl.meta[2] = (!motion_only && K_eta != K && K_eta != 1) ? 1 : 0;
+    store_prior(pl.meta, sens, alpha);      // (pvo_ba_plan: none - a fresh plan runs the arithmetic without the term)
   }
 }
 
@@ -492,7 +514,8 @@ __device__ __forceinline__ RowRef row_of(int r, int k, const Plan& pl, const flo
 __device__ __forceinline__ void depth_pixel(const Plan& pl, int k, int x, const float* __restrict__ eta, int K_eta,
                                             const float* __restrict__ Eii, const float* __restrict__ Cii, const float* __restrict__ bz,
                                             float* __restrict__ Ei, float* __restrict__ Q, float* __restrict__ w, int HW, int t0, int P,
-                                            const int* __restrict__ edges, int deg, int pself) {
+                                            const int* __restrict__ edges, int deg, int pself,
+                                            const DepthPrior& pr, const float* __restrict__ disps) {
   // `edges` = this depth frame's out-edges in LDS (round 4): read from the plan in global memory inside this loop, every
   // iteration was two dependent round trips (eidx[o], then the rows of edge e) - 6 x 2 of them in front of the first product
   const bool self_in = pself >= 0 && pself < P;
@@ -510,8 +533,18 @@ __device__ __forceinline__ void depth_pixel(const Plan& pl, int k, int x, const 
   }
   // K_eta == 1 broadcasts; a row-count mismatch is flagged in meta[2] and clamped here
   const float et = eta[static_cast<long long>(k < K_eta ? k : K_eta - 1) * HW + x];
-  Q[static_cast<long long>(k) * HW + x] = 1.0f / (C + et);           // droid_kernels.cu:1376
-  w[static_cast<long long>(k) * HW + x] = ww;
+  // The sensor-depth prior (upstream DROID-SLAM's RGB-D term): where the frame has a measurement s > 0, alpha takes eta's place in C
+  // and alpha (d - s) leaves w.  SELECTS, not blends: no map, or no measurement at this pixel, is C + et and ww - 0.0f - the bits
+  // of the arithmetic without the term.  Only for a frame with out-edges in THIS call (deg > 0): an edge-sharded rank plans every
+  // window frame, and one it does not own has C = w = 0 here and must keep dz = 0, or the ranks would each apply the term.
+  float cp = et, wp = 0.0f;
+  if (pr.sens != nullptr && deg > 0) {
+    const long long fx = static_cast<long long>(pself + t0) * HW + x;      // (pself + t0 = the frame, kx[k])
+    const float s = pr.sens[fx];
+    if (s > 0.0f) { cp = pr.alpha; wp = pr.alpha * (disps[fx] - s); }
+  }
+  Q[static_cast<long long>(k) * HW + x] = 1.0f / (C + cp);           // droid_kernels.cu:1376
+  w[static_cast<long long>(k) * HW + x] = ww - wp;
   if (self_in) {
 #pragma unroll
     for (int n = 0; n < 6; ++n) Ei[(static_cast<long long>(pself) * 6 + n) * HW + x] = ei[n];
@@ -767,7 +800,8 @@ __device__ __forceinline__ void ba_schur_body(
     float* __restrict__ Ei, const float* __restrict__ Eij,
     float* __restrict__ Q, float* __restrict__ w, long long* __restrict__ sys,
     int HW, int t0, int P, const float* __restrict__ part, const int64_t* __restrict__ ii, int E, int chunksA, int deal_rows,
-    float* __restrict__ Mrg, int depth_done, int lds_floats, float* __restrict__ spart, short* __restrict__ srow, int* __restrict__ sT) {
+    float* __restrict__ Mrg, int depth_done, int lds_floats, float* __restrict__ spart, short* __restrict__ srow, int* __restrict__ sT,
+    const float* __restrict__ disps) {
   __shared__ int rowcode[kMaxRows];       // see RowTab
   __shared__ short rowout[kMaxRows];
   __shared__ int nrows_s;
@@ -842,10 +876,11 @@ __device__ __forceinline__ void ba_schur_body(
   // (S-B's launch: 18.2 us with the table in front and a 64-step follower scan, 17.3 now, 16.2 with round 4's kernel -
   // profiles/r05_schur_sweep.txt, block 6.)
   auto depth_phase = [&]() {
+    const DepthPrior pr = load_prior(pl.meta);      // (uniform: one read per workgroup, and none when ba_depth_kernel ran in front)
 #pragma unroll
     for (int h = 0; h < PIX / 256; ++h) {
       const int x = blockIdx.x * PIX + h * 256 + tid;
-      if (x < HW) depth_pixel(pl, k, x, eta, K_eta, Eii, Cii, bz, Ei, Q, w, HW, t0, P, in_lds ? s_edge : pl.eidx + e0, deg_all, pself);
+      if (x < HW) depth_pixel(pl, k, x, eta, K_eta, Eii, Cii, bz, Ei, Q, w, HW, t0, P, in_lds ? s_edge : pl.eidx + e0, deg_all, pself, pr, disps);
     }
   };
   // (every slice that gets here may have to stay - more than kFastTiles row tiles unless targets merge or are fixed - and then needs
@@ -1068,9 +1103,10 @@ __global__ __launch_bounds__(256) void ba_schur_mfma_kernel(
     float* __restrict__ Ei, const float* __restrict__ Eij,
     float* __restrict__ Q, float* __restrict__ w, long long* __restrict__ sys,
     int HW, int t0, int P, const float* __restrict__ part, const int64_t* __restrict__ ii, int E, int chunksA, int deal_rows,
-    float* __restrict__ Mrg, int depth_done, int lds_floats, float* __restrict__ spart, short* __restrict__ srow, int* __restrict__ sT) {
+    float* __restrict__ Mrg, int depth_done, int lds_floats, float* __restrict__ spart, short* __restrict__ srow, int* __restrict__ sT,
+    const float* __restrict__ disps) {
   ba_schur_body<VEC4, PIX>(pl, jj, eta, K_eta, Eii, Cii, bz, Ei, Eij, Q, w, sys, HW, t0, P, part, ii, E, chunksA, deal_rows, Mrg, depth_done, lds_floats,
-                           spart, srow, sT);
+                           spart, srow, sT, disps);
 }
 
 // second stage of the dense-window Schur sums: tile pair p of depth frame k = the sum over the frame's chunks (fixed order, fp64: the
@@ -1106,9 +1142,11 @@ __global__ __launch_bounds__(256) void ba_schur_reduce_kernel(Plan pl, const flo
 // 512- / 1024-pixel Schur grids (windows beyond ~15 poses), where the Schur kernel's z-slices would each repeat it.
 __global__ __launch_bounds__(256) void ba_depth_kernel(
     Plan pl, const float* __restrict__ eta, int K_eta, const float* __restrict__ Eii, const float* __restrict__ Cii,
-    const float* __restrict__ bz, float* __restrict__ Ei, float* __restrict__ Q, float* __restrict__ w, int HW, int t0, int P) {
+    const float* __restrict__ bz, float* __restrict__ Ei, float* __restrict__ Q, float* __restrict__ w, int HW, int t0, int P,
+    const float* __restrict__ disps) {
   const int k = blockIdx.y;
   if (k >= pl.meta[0]) return;
+  const DepthPrior pr = load_prior(pl.meta);
   __shared__ int s_edge[256];
   const int tid = threadIdx.x;
   const int e0 = pl.eptr[k], deg_all = pl.eptr[k + 1] - e0;
@@ -1117,7 +1155,7 @@ __global__ __launch_bounds__(256) void ba_depth_kernel(
   if (in_lds && tid < deg_all) s_edge[tid] = pl.eidx[e0 + tid];
   __syncthreads();
   const int x = blockIdx.x * 256 + tid;
-  if (x < HW) depth_pixel(pl, k, x, eta, K_eta, Eii, Cii, bz, Ei, Q, w, HW, t0, P, in_lds ? s_edge : pl.eidx + e0, deg_all, pself);
+  if (x < HW) depth_pixel(pl, k, x, eta, K_eta, Eii, Cii, bz, Ei, Q, w, HW, t0, P, in_lds ? s_edge : pl.eidx + e0, deg_all, pself, pr, disps);
 }
 
 // ---------------------------------------------------------------------------
@@ -3146,7 +3184,20 @@ extern "C" int pvo_ba_plan(const int64_t* ii, const int64_t* jj, int E, int nfra
   if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
   Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, pvo_stream(stream),
-                     ii, jj, w.plan, E, nframes, t0, t1, K_eta, K_eta < 0 ? 1 : 0);
+                     ii, jj, w.plan, E, nframes, t0, t1, K_eta, K_eta < 0 ? 1 : 0, static_cast<const float*>(nullptr), 0.0f);
+  PVO_CHECK_LAUNCH();
+  return PVO_OK;
+}
+
+// the sensor-depth prior of every later pvo_ba_local on this workspace: one single-thread launch that writes the plan's meta words
+// (no host synchronisation, capturable); pvo_ba_plan resets it
+extern "C" int pvo_ba_depth_prior(void* workspace, size_t workspace_bytes, int E, int P, int nframes, int HW,
+                                  const float* disps_sens, float alpha, void* stream) {
+  if (!workspace || E < 0 || P < 0 || nframes <= 0 || HW <= 0) return PVO_EINVAL;
+  if (disps_sens && !(alpha > 0.0f)) return PVO_EINVAL;      // (alpha stands in C's denominator; NaN fails here too)
+  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
+  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
+  hipLaunchKernelGGL(ba_prior_kernel, dim3(1), dim3(1), 0, pvo_stream(stream), w.plan.meta, disps_sens, alpha);
   PVO_CHECK_LAUNCH();
   return PVO_OK;
 }
@@ -3217,13 +3268,13 @@ extern "C" int pvo_ba_local(const float* poses, const float* disps, const float*
     if (dense_window && !(pvo_allow_lds<ba_schur_mfma_kernel<true, 256>>(kSchurRowsLds) && pvo_allow_lds<ba_schur_mfma_kernel<false, 256>>(kSchurRowsLds)))
       return PVO_ELAUNCH;
     if (depth_done) {
-      hipLaunchKernelGGL(ba_depth_kernel, dim3((HW + 255) / 256, Kgrid), dim3(256), 0, st, w.plan, eta, K_eta, w.Eii, w.Cii, w.bz, w.Ei, w.Q, w.w, HW, t0, P);
+      hipLaunchKernelGGL(ba_depth_kernel, dim3((HW + 255) / 256, Kgrid), dim3(256), 0, st, w.plan, eta, K_eta, w.Eii, w.Cii, w.bz, w.Ei, w.Q, w.w, HW, t0, P, disps);
       PVO_CHECK_LAUNCH();
     }
     const bool stage2 = dense_window && Kgrid <= schur_stage_frames(P);       // (the workspace holds the chunk sums of that many frames)
 #define PVO_SCHUR_LAUNCH(V, PX) hipLaunchKernelGGL((ba_schur_mfma_kernel<V, PX>), sgrid, dim3(256), (PX == 256 ? sdyn : 0), st, w.plan, jj, eta, K_eta, w.Eii, w.Cii, w.bz, w.Ei, \
                                                    w.Eij, w.Q, w.w, sys, HW, t0, P, two_stage ? w.part : nullptr, ii, E, chunksA, deal_rows, w.Mrg, depth_done, (PX == 256 ? lds_floats : 0), \
-                                                   (stage2 && PX == 256) ? w.spart : nullptr, w.srow, stage2 ? w.sT : nullptr)
+                                                   (stage2 && PX == 256) ? w.spart : nullptr, w.srow, stage2 ? w.sT : nullptr, disps)
     if ((HW & 3) == 0) { if (pix == 256) PVO_SCHUR_LAUNCH(true, 256); else if (pix == 512) PVO_SCHUR_LAUNCH(true, 512); else PVO_SCHUR_LAUNCH(true, 1024); }
     else { if (pix == 256) PVO_SCHUR_LAUNCH(false, 256); else if (pix == 512) PVO_SCHUR_LAUNCH(false, 512); else PVO_SCHUR_LAUNCH(false, 1024); }
 #undef PVO_SCHUR_LAUNCH
@@ -3458,23 +3509,25 @@ extern "C" int pvo_ba_last_partition(void* workspace, size_t workspace_bytes, in
   return PVO_OK;
 }
 
-extern "C" int pvo_ba(float* poses, float* disps, const float* intrinsics,
-                      const float* targets, const float* weights, const float* eta,
-                      const int64_t* ii, const int64_t* jj,
-                      int E, int nframes, int ht, int wd, int K_eta,
-                      int t0, int t1, int iterations, float lm, float ep, int motion_only,
-                      float* dx_out, float* dz_out, int dz_rows, int* status_out,
-                      void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int pvo_ba_prior(float* poses, float* disps, const float* intrinsics,
+                            const float* targets, const float* weights, const float* eta,
+                            const int64_t* ii, const int64_t* jj,
+                            int E, int nframes, int ht, int wd, int K_eta,
+                            int t0, int t1, int iterations, float lm, float ep, int motion_only,
+                            float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                            void* workspace, size_t workspace_bytes,
+                            const float* disps_sens, float alpha, void* stream) {
   int rc = check_common(E, nframes, ht, wd, t0, t1);
   if (rc != PVO_OK) return rc;
   if (iterations < 0) return PVO_EINVAL;
+  if (disps_sens && !(alpha > 0.0f)) return PVO_EINVAL;
   const int P = t1 - t0, HW = ht * wd;
   if (!workspace) return PVO_EINVAL;
   if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
   Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   hipStream_t st = pvo_stream(stream);
   hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, st, ii, jj, w.plan, E, nframes, t0, t1,
-                     K_eta, motion_only);
+                     K_eta, motion_only, disps_sens, alpha);
   PVO_CHECK_LAUNCH();
   for (int it = 0; it < iterations; ++it) {
     rc = pvo_ba_local(poses, disps, intrinsics, targets, weights, eta, ii, jj, E, nframes, ht, wd, K_eta,
@@ -3485,4 +3538,15 @@ extern "C" int pvo_ba(float* poses, float* disps, const float* intrinsics,
     if (rc != PVO_OK) return rc;
   }
   return PVO_OK;
+}
+
+extern "C" int pvo_ba(float* poses, float* disps, const float* intrinsics,
+                      const float* targets, const float* weights, const float* eta,
+                      const int64_t* ii, const int64_t* jj,
+                      int E, int nframes, int ht, int wd, int K_eta,
+                      int t0, int t1, int iterations, float lm, float ep, int motion_only,
+                      float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  return pvo_ba_prior(poses, disps, intrinsics, targets, weights, eta, ii, jj, E, nframes, ht, wd, K_eta, t0, t1, iterations, lm, ep,
+                      motion_only, dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, 0.0f, stream);
 }

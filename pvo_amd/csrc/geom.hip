@@ -342,3 +342,29 @@ extern "C" int pvo_reproject(const float* poses, const float* disps, const float
   PVO_CHECK_LAUNCH();
   return PVO_OK;
 }
+
+// RGB-D ingest: the sensor depth's 1/8 lattice as inverse depth, 0 where there is no measurement
+template <typename T>
+__global__ __launch_bounds__(256) void depth_sense_kernel(const typename Elem<T>::store_t* __restrict__ depth, float* __restrict__ out,
+                                                          int W, int h8, int w8) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= h8 * w8) return;
+  const int y = idx / w8, x = idx - y * w8;
+  const float d = Elem<T>::to_f32(depth[static_cast<long long>(8 * y + 3) * W + 8 * x + 3]);
+  out[idx] = (d > 0.0f && d < __builtin_inff()) ? __fdiv_rn(1.0f, d) : 0.0f;      // (NaN fails both comparisons)
+}
+
+extern "C" int pvo_depth_sense(const void* depth, float* disps_sens_row, int H, int W, int dtype, void* stream) {
+  PVO_REQ(H >= 0 && W >= 0);
+  if (dtype != PVO_F32 && dtype != PVO_F16) return PVO_EUNSUPPORTED;
+  const int h8 = H / 8, w8 = W / 8;
+  if (h8 == 0 || w8 == 0) return PVO_OK;
+  PVO_REQ(depth && disps_sens_row && static_cast<long long>(h8) * w8 < (1ll << 30));
+  return pvo_dispatch<float, pvo_half>(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(depth_sense_kernel<T>, dim3((h8 * w8 + 255) / 256), dim3(256), 0, pvo_stream(stream),
+                       static_cast<const typename Elem<T>::store_t*>(depth), disps_sens_row, W, h8, w8);
+    PVO_CHECK_LAUNCH();
+    return PVO_OK;
+  });
+}

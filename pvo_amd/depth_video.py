@@ -7,6 +7,12 @@ Differences: one process per GPU, so the counter is a plain int and there is no 
 feature maps are kept channels-last ([buf,H/8,W/8,128]) because that is the layout both
 the matrix-core volume build and AltCorr read; `reproject` is one HIP kernel instead of the
 lietorch broadcast chain.
+
+RGB-D (upstream DROID-SLAM's `disps_sens`; the reference stripped it): `append(..., depth=...)` / `video[k] = (..., depth)` store a
+keyframe's measured inverse depth at 1/8 resolution, 0 = no measurement, in `disps_sens` (allocated on first use), and from then on
+`ba()` and the factor graph's native update carry the sensor-depth prior of the bundle adjustment (include/pvo_hip.h,
+pvo_ba_depth_prior).  `has_sensor_depth` is the host-side flag everything asks; a video that never saw a depth image allocates
+nothing and computes exactly what it computed before.
 """
 import torch
 
@@ -28,6 +34,9 @@ class DepthVideo:
         self.poses[:, 6] = 1.0                                   # identity (depth_video.py:49-50)
         self.disps = torch.ones(buffer, h8, w8, dtype=torch.float, **kw)
         self.disps_up = None
+        self.disps_sens = None             # RGB-D: measured inverse depth per keyframe [buffer,H/8,W/8], 0 = none (ensure_disps_sens)
+        self.has_sensor_depth = False      # host-side: some keyframe brought a depth image
+        self.sensor_alpha = 0.05           # weight of the sensor-depth prior (upstream's alpha)
         self.intrinsics = torch.zeros(buffer, 4, dtype=torch.float, **kw)
         self.fmaps = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw)      # channels-last
         # [buffer,128,h,w] as the reference has them, stored channels-last: an edge's rows are gathered straight into the
@@ -142,9 +151,49 @@ class DepthVideo:
             b *= 2
         return max(1, min(self.max_segments, b))
 
-    def append(self, tstamp, pose, disp, intrinsics, fmap, net, inp, segm=None, image=None, channels_last=None):
-        """store one keyframe; fmap may be [128,h,w] (reference layout) or [h,w,128] (see _fmap_cl)"""
+    def ensure_disps_sens(self):
+        """the sensor inverse depths [buffer, H/8, W/8], allocated (zero = no measurement) on first use"""
+        if self.disps_sens is None:
+            self.disps_sens = torch.zeros_like(self.disps)
+        return self.disps_sens
+
+    @staticmethod
+    def sense_depth_host(depth):
+        """a host depth image [H,W] -> its inverse depth on the 1/8 lattice [H/8,W/8] fp32: 1 / depth[3::8, 3::8] where that is
+        finite and > 0, else 0 (upstream DROID-SLAM's ingest; pvo_depth_sense is the same on the device)"""
+        d = torch.as_tensor(depth)
+        h8, w8 = d.shape[-2] // 8, d.shape[-1] // 8
+        d = d[..., 3::8, 3::8][..., :h8, :w8].to(torch.float32)
+        ok = torch.isfinite(d) & (d > 0)
+        return torch.where(ok, 1.0 / torch.where(ok, d, torch.ones_like(d)), torch.zeros_like(d))
+
+    def set_depth(self, k, depth):
+        """keyframe k's sensor map from a depth image [H,W] at image resolution (None: no measurement for this keyframe)"""
+        if depth is None:
+            if self.disps_sens is not None:
+                self.disps_sens[k].zero_()
+            return
+        sens = self.ensure_disps_sens()
+        depth = torch.as_tensor(depth)
+        if depth.dim() == 3 and depth.shape[0] == 1:
+            depth = depth[0]
+        if tuple(depth.shape) != (self.ht, self.wd):
+            raise ValueError("depth image of shape %s for a %dx%d video" % (tuple(depth.shape), self.ht, self.wd))
+        if depth.is_cuda:
+            if depth.dtype not in (torch.float32, torch.float16):
+                depth = depth.float()
+            db.depth_sense(depth.contiguous(), sens[k])
+        else:
+            # a host image: sampled THERE (1/64 of its pixels) and sent up through the pinned staging ring - no blocking transfer
+            sens[k] = db.to_device_async(self.sense_depth_host(depth), torch.float32, self.device)
+        self.has_sensor_depth = True
+
+    def append(self, tstamp, pose, disp, intrinsics, fmap, net, inp, segm=None, image=None, channels_last=None, depth=None):
+        """store one keyframe; fmap may be [128,h,w] (reference layout) or [h,w,128] (see _fmap_cl).  depth: the frame's sensor
+        depth image [H,W] (RGB-D, see set_depth); None leaves the video as it is - nothing is allocated for it."""
         k = self.counter
+        if depth is not None or self.disps_sens is not None:
+            self.set_depth(k, depth)
         # (a Python number goes in with fill_ on a slice - a kernel argument.  `buf[k] = number` builds a host tensor and copies it with a
         # BLOCKING transfer queued behind everything on the stream: measured 1.3 ms per keyframe in the pipelined tracker)
         if isinstance(tstamp, torch.Tensor):
@@ -169,8 +218,13 @@ class DepthVideo:
         self.counter = k + 1
 
     def __setitem__(self, index, item):
-        """video[index] = (tstamp, image, pose, disp, intrinsics[, fmap[, net[, inp[, segm]]]]) with None = keep
-        (depth_video.py:64-101).  The counter grows to cover an int index; fmap may be NCHW or channels-last."""
+        """video[index] = (tstamp, image, pose, disp, intrinsics[, fmap[, net[, inp[, segm[, depth]]]]]) with None = keep
+        (depth_video.py:64-101).  The counter grows to cover an int index; fmap may be NCHW or channels-last.  depth (an int
+        index only): the keyframe's sensor depth image [H,W], as upstream DROID-SLAM's extra item."""
+        if len(item) > 9 and item[9] is not None:
+            if not isinstance(index, int):
+                raise ValueError("a depth image is set for one keyframe at a time")
+            self.set_depth(index, item[9])
         if isinstance(index, int) and index >= self.counter:
             self.counter = index + 1
         self.tstamp[index] = torch.as_tensor(item[0], dtype=torch.float, device=self.device)
@@ -290,6 +344,8 @@ class DepthVideo:
         if eta is None and not motion_only:
             k = torch.unique(torch.cat([ii, jj], 0)).shape[0]
             eta = 1e-7 * torch.ones([k, self.ht // 8, self.wd // 8], device=self.device)
+        # (RGB-D: the sensor-depth prior, once a keyframe has brought a depth image)
+        kw = {"disps_sens": self.disps_sens, "alpha": self.sensor_alpha} if self.has_sensor_depth and not motion_only else {}
         db.ba(self.poses, self.disps, self.intrinsics[0], target, weight, eta, ii, jj, t0, t1, itrs, lm, ep,
-              motion_only)
+              motion_only, **kw)
         self.disps.clamp_(min=0.001)

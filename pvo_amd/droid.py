@@ -24,7 +24,10 @@ def default_args(**over):
     a = dict(device="cuda:0", weights=None, buffer=1024, image_size=[240, 808], disable_vis=True, use_aff_bri=False,
              beta=0.6, filter_thresh=1.75, warmup=12, keyframe_thresh=2.25, frontend_thresh=12.0, frontend_window=25,
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
-             segm_filter=False, thresh=0.8, half_update=True, pipelined=False)
+             segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False)
+    # rgbd: use the `depth` image of track() - each keyframe's sensor depth becomes a prior of the bundle adjustment, the trajectory
+    # and the map are metric (DepthVideo, include/pvo_hip.h pvo_ba_depth_prior).  False (default): `depth` is IGNORED, nothing is
+    # allocated for it and every result is what a monocular run computes.
     a.update(over)
     return Namespace(**a)
 
@@ -36,6 +39,7 @@ class Droid:
         self.video = DepthVideo(args.image_size, args.buffer, args.device, args.segm_filter, args.thresh)
         self.filterx = MotionFilter(self.net, self.video, thresh=args.filter_thresh, device=args.device)
         self.filterx.overlap_upload = bool(getattr(args, "pipelined", False))
+        self.filterx.use_depth = bool(getattr(args, "rgbd", False))
         self.frontend = DroidFrontend(self.net.update, self.video, args.device, warmup=args.warmup, beta=args.beta,
                                       frontend_nms=args.frontend_nms, keyframe_thresh=args.keyframe_thresh,
                                       frontend_window=args.frontend_window, frontend_thresh=args.frontend_thresh,
@@ -62,7 +66,8 @@ class Droid:
             self.net.fnet.native_convs = self.net.cnet.native_convs = True
 
     def track(self, tstamp, image, depth=None, intrinsics=None, segments=None):
-        """one frame (droid.py:64-75).  args.pipelined (default False: the reference's order, the video is final for this frame when
+        """one frame (droid.py:64-75).  depth [H,W] (host or device, resized and cropped like the image; <= 0 / non-finite = no
+        measurement) is used only with args.rgbd, on every frame that brings one, and ignored otherwise.  args.pipelined (default False: the reference's order, the video is final for this frame when
         the call returns): the frame's graph is launched FIRST, then the second half of the previous keyframe's frontend update (its
         keyframe test was left in flight when the previous call returned), then the motion test is read and this frame's frontend
         work is issued up to ITS keyframe test.  Same operations on the same data in the same dependency order - poses, depths and the

@@ -490,14 +490,26 @@ def reproject(poses, disps, intrinsics, ii, jj, out=None):
 
 
 # --------------------------------------------------------------------------- bundle adjustment
+def _sens_map(disps_sens, disps, what):
+    """the sensor map of a depth BA: fp32, contiguous, disps' shape and device"""
+    _f32(disps_sens, "disps_sens")
+    _contig(disps_sens, "disps_sens")
+    if tuple(disps_sens.shape) != tuple(disps.shape) or disps_sens.device != disps.device:
+        raise PvoHipError("%s: disps_sens must have disps' shape %s and device" % (what, tuple(disps.shape)))
+
+
 def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iterations, lm, ep, motion_only,
-       status=None):
+       status=None, disps_sens=None, alpha=0.05):
     """droid.cpp:87-114 / ba_cuda droid_kernels.cu:1293-1410.
 
     poses [F,7] and disps [F,ht,wd] are updated IN PLACE; returns [dx [P,6], dz [K,ht*wd]]
     (dz is an empty tensor when motion_only, where the reference returns an undefined one).
     Fully asynchronous: no host synchronisation.  `status` (optional int32[4] device tensor)
-    receives [non-SPD seen, K, eta-row mismatch, 0]."""
+    receives [non-SPD seen, K, eta-row mismatch, 0].
+    disps_sens [F,ht,wd] (optional): measured inverse depth, 0 = no measurement - the sensor-depth prior with weight
+    `alpha` (pvo_ba_prior, include/pvo_hip.h); None is pvo_ba."""
+    if disps_sens is not None:
+        _sens_map(disps_sens, disps, "ba")
     for t, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
                  (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
         _contig(t, n)      # droid.cpp:103-109 checks exactly these
@@ -537,12 +549,16 @@ def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iteratio
     nbytes = lib.pvo_ba_workspace_bytes(E, P, F, HW)
     ws = _workspace(dev, nbytes)
     with torch.cuda.device(dev):
-        check(lib.pvo_ba(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(targets), _ptr(weights),
-                         _ptr(eta) if eta is not None else ctypes.c_void_p(0), _ptr(ii), _ptr(jj),
-                         E, F, ht, wd, K_eta, t0, t1, int(iterations), float(lm), float(ep),
-                         1 if motion_only else 0, _ptr(dx), _ptr(dz), K,
-                         _ptr(status) if status is not None else ctypes.c_void_p(0),
-                         ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "ba")
+        args = (_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(targets), _ptr(weights),
+                _ptr(eta) if eta is not None else ctypes.c_void_p(0), _ptr(ii), _ptr(jj),
+                E, F, ht, wd, K_eta, t0, t1, int(iterations), float(lm), float(ep),
+                1 if motion_only else 0, _ptr(dx), _ptr(dz), K,
+                _ptr(status) if status is not None else ctypes.c_void_p(0),
+                ctypes.c_void_p(ws.data_ptr()), ws.numel())
+        if disps_sens is None:
+            check(lib.pvo_ba(*args, _stream(dev)), "ba")
+        else:
+            check(lib.pvo_ba_prior(*args, _ptr(disps_sens), float(alpha), _stream(dev)), "ba (sensor depth)")
     return [dx, dz]
 
 
@@ -577,6 +593,36 @@ def ba_plan(ii, jj, nframes, HW, K_eta, t0, t1, workspace):
     with torch.cuda.device(dev):
         check(_lib.load().pvo_ba_plan(_ptr(ii), _ptr(jj), ii.shape[0], int(nframes), int(HW), int(K_eta), int(t0), int(t1),
                                       ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream(dev)), "ba_plan")
+
+
+def ba_depth_prior(workspace, E, P, nframes, HW, disps_sens, alpha=0.05):
+    """the sensor-depth prior of every later ba_local on this PLANNED workspace (pvo_ba_depth_prior): disps_sens [nframes,ht,wd]
+    fp32, 0 = no measurement; None clears it, and so does the next ba_plan.  The map is read at every step: keep it alive."""
+    if disps_sens is not None:
+        _f32(disps_sens, "disps_sens")
+        _contig(disps_sens, "disps_sens")
+        if disps_sens.numel() != int(nframes) * int(HW):
+            raise PvoHipError("ba_depth_prior: disps_sens must hold nframes x HW = %d x %d values" % (nframes, HW))
+    dev = _dev(workspace, disps_sens)
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_ba_depth_prior(ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), int(E), int(P), int(nframes), int(HW),
+                                             _ptr(disps_sens), float(alpha), _stream(dev)), "ba_depth_prior")
+
+
+def depth_sense(depth, out_row):
+    """RGB-D ingest (pvo_depth_sense): out_row [H/8,W/8] fp32 = 1 / depth[3::8, 3::8] where that is finite and > 0, else 0.
+    depth [H,W] fp32 / fp16 on the device; one launch."""
+    dev = _dev(depth, out_row)
+    _contig(depth, "depth"); _contig(out_row, "out_row")
+    _f32(out_row, "out_row")
+    if depth.dim() != 2 or tuple(out_row.shape) != (depth.shape[0] // 8, depth.shape[1] // 8):
+        raise PvoHipError("depth_sense: depth [H,W] and out_row [H/8,W/8] expected, got %s and %s" % (tuple(depth.shape), tuple(out_row.shape)))
+    if depth.dtype not in (torch.float32, torch.float16):
+        raise PvoHipError("depth_sense: depth must be float32 or float16")
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_depth_sense(_ptr(depth), _ptr(out_row), depth.shape[0], depth.shape[1], _DT[depth.dtype], _stream(dev)),
+              "depth_sense")
+    return out_row
 
 
 BA_SYS_DTYPE = torch.int64      # the reduced pose system is 64-bit fixed point (units of 2^-28): all-reduce it as integers

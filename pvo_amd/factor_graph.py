@@ -431,8 +431,9 @@ class FactorGraph:
         self._corr_sync()                  # (the per-frame buffers below are read by a pending side-stream build)
         v = self.video
         up = getattr(v, "disps_up", None)                               # (kept in step with disps where it is maintained)
+        sens = getattr(v, "disps_sens", None)                           # (RGB-D: the sensor map moves with its frame)
         for buf in (v.poses, v.disps, v.intrinsics, v.nets, v.inps, v.fmaps) + ((v.segms,) if v.segm_filter else ()) + \
-                ((up,) if self.upsample and up is not None else ()):
+                ((up,) if self.upsample and up is not None else ()) + ((sens,) if sens is not None else ()):
             buf[ix] = buf[ix + 1].clone()
         m = [(i == ix) or (j == ix) for i, j in zip(self._ii_h, self._jj_h)]
         for t in (self.ii_inac, self.jj_inac):                       # (masked in-place updates would synchronise)
@@ -514,11 +515,12 @@ class FactorGraph:
             if sharded is None:
                 self.video.ba(target, weight, eta, self.ii, self.jj, 1, t, itrs=itrs, lm=1e-5, ep=1e-2, motion_only=False)
             else:
+                kw = {"disps_sens": self.video.disps_sens, "alpha": self.video.sensor_alpha} if self._sensor_map() is not None else {}
                 eta_rows = torch.ones(len(rows_l), ht, wd, dtype=eta.dtype, device=self.device)
                 eta_rows[row_of_src] = eta
                 sharded.ba(self.video.poses, self.video.disps, self.video.intrinsics[0], target, weight, eta_rows,
                            self.ii.contiguous(), self.jj.contiguous(), 1, t, itrs=itrs, lm=1e-5, ep=1e-2,
-                           plan_key=(id(self), self._version, t))
+                           plan_key=(id(self), self._version, t), **kw)
                 self.video.disps.clamp_(min=0.001)                   # DepthVideo.ba's clamp (depth_video.py:214)
             self.video.dirty[:t] = True
 
@@ -686,6 +688,11 @@ class FactorGraph:
             return db.tiled_supported(self.ht, self.wd, self.video.fmaps.dtype)
         return True
 
+    def _sensor_map(self):
+        """the video's sensor inverse depths when it holds any (RGB-D), else None"""
+        v = self.video
+        return v.disps_sens if getattr(v, "has_sensor_depth", False) else None
+
     def _ba_plan(self, ii, jj, t0, t1, motion_only, n_in, R):
         """the BA's plan (unique depth frames, per-frame edge lists - the reference rebuilds these on the host in every
         iteration, droid_kernels.cu:1314-1322) depends only on the edge set and the window: built once per edge set"""
@@ -693,7 +700,8 @@ class FactorGraph:
         v = self.video
         F, ht, wd = v.disps.shape
         P = t1 - t0
-        key = (self._version, t0, t1, n_in, bool(motion_only), int(ii.shape[0]), int(R))
+        sens = None if motion_only else self._sensor_map()
+        key = (self._version, t0, t1, n_in, bool(motion_only), int(ii.shape[0]), int(R), sens.data_ptr() if sens is not None else 0)
         st = self.__dict__.get("_ba_state")
         if st is None or st["key"] != key:
             need = db.ba_workspace_bytes(int(ii.shape[0]), P, F, ht * wd)
@@ -703,6 +711,8 @@ class FactorGraph:
             sysb = st["sys"] if st is not None and st["sys"].numel() >= n6 * n6 + n6 else \
                 torch.zeros(max(n6 * n6 + n6, 1), dtype=torch.int64, device=self.device)   # zero on entry, left zero by every solve
             db.ba_plan(ii, jj, F, ht * wd, -1 if motion_only else int(R), t0, t1, ws)
+            if sens is not None:       # the plan resets the prior: set again behind every plan (a persistent video buffer: the address holds)
+                db.ba_depth_prior(ws, int(ii.shape[0]), P, F, ht * wd, sens, self.video.sensor_alpha)
             st = self.__dict__["_ba_state"] = {"key": key, "ws": ws, "sys": sysb, "ii": ii, "jj": jj}
         return st
 
@@ -729,10 +739,12 @@ class FactorGraph:
         if t1 is None:
             t1 = max(max(self._ii_h), max(self._jj_h)) + 1
         up_ptr = v.ensure_disps_up().data_ptr() if self.upsample else 0
+        sens = self._sensor_map()
+        sens_ptr = sens.data_ptr() if sens is not None else 0
         vote = bool(segm_vote and v.segm_filter)
         S = (v.segments_bound() if hasattr(v, "segments_bound") else v.max_segments) if vote else 0
         key = (self._version, t0, t1, bool(use_inactive), bool(motion_only), E, float(eta_scale), float(lm), float(ep), sharded is not None,
-               vote, S, self.upsample, up_ptr)
+               vote, S, self.upsample, up_ptr, sens_ptr)
         st = self._cache.get("fused")
         if st is None or st["key"] != key:
             src = sorted(set(self._ii_h))
@@ -837,7 +849,8 @@ class FactorGraph:
             # edge sharding: assembly + Schur on this rank's edges, ONE integer all-reduce of the reduced pose system per
             # Gauss-Newton step, identical solve on every rank (pvo_amd/parallel.py)
             sharded.ba(v.poses, v.disps, v.intrinsics[0], st["target_ba"], st["weight_ba"], st["eta"], st["ii_ba"], st["jj_ba"],
-                       t0, t1, itrs=itrs, lm=lm, ep=ep, motion_only=motion_only, plan_key=(id(self), self._version, t0, t1))
+                       t0, t1, itrs=itrs, lm=lm, ep=ep, motion_only=motion_only, plan_key=(id(self), self._version, t0, t1),
+                       **({"disps_sens": sens, "alpha": v.sensor_alpha} if sens is not None else {}))
             v.disps.clamp_(min=0.001)
         self._age_lag += 1                 # (the device copy of `age` is brought up to date when it is next read)
         self._age_h = [x + 1 for x in self._age_h]

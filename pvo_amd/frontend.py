@@ -45,6 +45,11 @@ class DroidFrontend:
             self.graph.rm_factors([a > self.max_age for a in self.graph._age_h], store=True)
         self.graph.add_proximity_factors(self.t1 - 5, max(self.t1 - self.frontend_window, 0), rad=self.frontend_radius,
                                          nms=self.frontend_nms, thresh=self.frontend_thresh, beta=self.beta, remove=True)
+        if getattr(self.video, "has_sensor_depth", False):
+            # RGB-D (upstream DROID-SLAM's frontend): the new keyframe starts from its measured inverse depth where it has one
+            k = self.t1 - 1
+            sens = self.video.disps_sens[k]
+            self.video.disps[k] = torch.where(sens > 0, sens, self.video.disps[k])
         for _ in range(self.iters1):
             self.graph.update(None, None, use_inactive=True)
         d = self.video.distance([self.t1 - 3], [self.t1 - 2], beta=self.beta, bidirectional=True)

@@ -81,6 +81,8 @@ class MotionFilter:
         self.overlap_upload = False        # asynchronous upload through pinned staging (Droid sets it in pipelined mode)
         self._up_stream, self._stage, self._stage_k, self._stage_used = None, [None, None], 0, None
         self._mag_host = self._mag_ready = None
+        self.use_depth = False             # RGB-D (Droid sets it from args.rgbd): a frame's depth image goes to video.append with its keyframe;
+        self._depth = None                 # off, the `depth` argument is ignored.  The captured frame graph reads nothing of it.
 
     def _upload(self, image):
         """host frame -> device, as it is (the reference's stream hands over int32, test_vo.py:41): NO tensor operation on the host
@@ -193,6 +195,8 @@ class MotionFilter:
         kw = {}
         if tuple(gmap.shape[-2:]) == (128, 128):      # a [128,128,128] map: the layout cannot be read off the shape
             kw["channels_last"] = False
+        if self._depth is not None:
+            kw["depth"], self._depth = self._depth, None
         self.video.append(tstamp, pose, disp, intrinsics / 8.0, gmap[0], net[0], inp[0], segm=segments, image=image, **kw)
 
     @torch.no_grad()
@@ -207,6 +211,7 @@ class MotionFilter:
         LAUNCHED; the scalar is copied to a pinned host buffer behind an event.  Nothing here reads or writes the video."""
         ht, wd = image.shape[-2] // 8, image.shape[-1] // 8
         img = self._upload(image)
+        self._depth = depth if self.use_depth else None
         self._pending = (tstamp, image, img, intrinsics, segments, None, None)
         if self.video.counter == 0:
             return
@@ -287,6 +292,7 @@ class MotionFilter:
         """every frame becomes a keyframe (motion_filter.py:89-109)"""
         ident = torch.as_tensor([0, 0, 0, 0, 0, 0, 1.0], device=self.device)
         img = self._upload(image)
+        self._depth = depth if self.use_depth else None
         gmap = self._features_g(img)
         net, inp = self._context_g(img)
         first = self.video.counter == 0
