@@ -77,7 +77,9 @@ const char* pvo_last_hip_error(void);
  * pvo_ba_train / pvo_ba_train_vjp; 105 -> 106: no struct changed - new entry points pvo_conv_planes_supported /
  * pvo_conv_planes_filter_bytes / pvo_conv_planes_pack / pvo_conv_planes; still 106, convex upsampling: pvo_graph_update_args grew by
  * want_upsample / disps_up / up_frames at its END (every earlier offset unchanged; pvo_graph_update_args_size() tells the two layouts apart),
- * new entry points pvo_cvx_upsample / pvo_cvx_upsample_vjp_scratch_bytes / pvo_cvx_upsample_vjp): a caller
+ * new entry points pvo_cvx_upsample / pvo_cvx_upsample_vjp_scratch_bytes / pvo_cvx_upsample_vjp; still 106, RGB-D and stereo: no
+ * struct changed - new entry points pvo_ba_depth_prior / pvo_ba_prior / pvo_depth_sense and pvo_ba_stereo / pvo_ba_rig /
+ * pvo_reproject_rig / pvo_reproject_motion_rig / pvo_graph_update_rig): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -497,6 +499,14 @@ int pvo_probe_arm_every(int stage, int capacity, int every);
 int pvo_probe_read(float* ms_host, int max_n);
 int pvo_graph_update(const pvo_update_weights* weights, const pvo_graph_update_args* args,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* Stereo (see pvo_ba_stereo): pvo_graph_update with a rectified rig's baseline.  pvo_graph_update_args is pinned, so the baseline is
+ * an argument of an entry point of its own, as for pvo_reproject_rig.  stereo_baseline = b > 0: every edge with ii == jj is a stereo
+ * edge - the in-update reprojection is pvo_reproject_motion_rig's, and b is recorded in the BA plan (one pvo_ba_stereo launch on the
+ * stream in front of the first assembly, when itrs > 0).  The correlation volume of such an edge is the caller's business (op.levels:
+ * left against right features).  0 IS pvo_graph_update (which forwards with 0): the launch sequence and every result are unchanged,
+ * (i, i) edges stay identity edges.  Negative, NaN or infinite: PVO_EINVAL. */
+int pvo_graph_update_rig(const pvo_update_weights* weights, const pvo_graph_update_args* args,
+                         void* workspace, size_t workspace_bytes, float stereo_baseline, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Convex 8x upsampling                                                       */
@@ -574,6 +584,19 @@ int pvo_reproject_motion(const float* poses, const float* disps, const float* in
                          const int64_t* ii, const int64_t* jj, float* coords, float* valid,
                          const float* target, const float* delta_dy, const float* raw_mask, void* motn,
                          int E, int ht, int wd, int dtype, void* stream);
+/* Stereo: the two calls above with a rectified rig's baseline.  With baseline = b > 0 an edge with ii[e] == jj[e] == i is a STEREO
+ * edge: its transform is not rel_pose(G_i, G_i) (the identity) but the fixed left -> right transform of the rig, rotation identity
+ * and translation (-b, 0, 0): [X, Y, 1, d] -> [X - b d, Y, 1, d], i.e. u_right = u - fx b d, v_right = v, with frame i's intrinsics
+ * on both sides.  b is in the units of the poses' translations.  `valid` keeps its rule; every other edge is computed exactly as by
+ * the call without baseline, and baseline == 0 IS that call (pvo_reproject / pvo_reproject_motion forward with 0).  Negative or NaN:
+ * PVO_EINVAL. */
+int pvo_reproject_rig(const float* poses, const float* disps, const float* intrinsics,
+                      const int64_t* ii, const int64_t* jj, float* coords, float* valid,
+                      int E, int ht, int wd, float baseline, void* stream);
+int pvo_reproject_motion_rig(const float* poses, const float* disps, const float* intrinsics,
+                             const int64_t* ii, const int64_t* jj, float* coords, float* valid,
+                             const float* target, const float* delta_dy, const float* raw_mask, void* motn,
+                             int E, int ht, int wd, int dtype, float baseline, void* stream);
 
 /* RGB-D ingest (upstream DROID-SLAM's depth[3::8, 3::8] and 1 / depth): one launch.  depth [H,W] (PVO_F32 or PVO_F16, at image
  * resolution, resized and cropped like the image), disps_sens_row [H/8, W/8] fp32 - one frame's row of the sensor map:
@@ -705,6 +728,30 @@ int pvo_ba_prior(float* poses, float* disps, const float* intrinsics,
                  float* dx_out, float* dz_out, int dz_rows, int* status_out,
                  void* workspace, size_t workspace_bytes,
                  const float* disps_sens, float alpha, void* stream);
+/* Stereo: fixed-baseline edges in the dense bundle adjustment.  With baseline = b > 0 recorded in a planned workspace, an edge with
+ * ii[e] == jj[e] == i is a STEREO edge: the residual between frame i's left view and its right view under the rig's fixed transform
+ * T_b (rotation identity, translation (-b, 0, 0); see pvo_reproject_rig).  The rig is rigid, so the residual depends on NO pose: the
+ * edge's 78 + 6 + 6 pose sums and its Eii / Eij rows are exactly zero (stored as zero rows, which the depth phase, the Schur kernel and
+ * the back-substitution read like any edge's), and it contributes only Cii and bz of its depth frame, by the assembly's own formula
+ * with G.t = (-b, 0, 0): Jz = fx (-b) / Z for the x residual, 0 for the y residual; same Z test, same weights.  Deliberate difference
+ * from upstream DROID-SLAM, which keeps Ji and Jj of an edge with ix == jx and adds both into pose i's block.  A motion-only step gets
+ * nothing from a stereo edge: the pose system has the bits it has without the edge.
+ *   pvo_ba_stereo records b in the device-side state of a PLANNED workspace (one single-thread launch on `stream`, no host
+ *     synchronisation, capturable); every later pvo_ba_local on it - pvo_graph_update's internal bundle adjustment, the packed / riders /
+ *     conv1x1 finish forms and an edge-sharded run included - honours it.  E, P, nframes, HW are the workspace's own.  pvo_ba_plan
+ *     RESETS it to 0, so call it after every plan.  b == 0: edges (i, i) are identity edges, as before.
+ *   pvo_ba_rig is pvo_ba_prior with the baseline (0: pvo_ba_prior itself, which is this call with 0).  The sensor-depth prior and the
+ *     stereo term are independent and both apply when both are given.
+ * Limits: b >= 0 and finite (PVO_EINVAL otherwise); fp32 only; rectified rigs (both views use frame i's intrinsics). */
+int pvo_ba_stereo(void* workspace, size_t workspace_bytes, int E, int P, int nframes, int HW, float baseline, void* stream);
+int pvo_ba_rig(float* poses, float* disps, const float* intrinsics,
+               const float* targets, const float* weights, const float* eta,
+               const int64_t* ii, const int64_t* jj,
+               int E, int nframes, int ht, int wd, int K_eta,
+               int t0, int t1, int iterations, float lm, float ep, int motion_only,
+               float* dx_out, float* dz_out, int dz_rows, int* status_out,
+               void* workspace, size_t workspace_bytes,
+               const float* disps_sens, float alpha, float baseline, void* stream);
 /* The envelope pose solve beyond 29 free poses (the global bundle adjustment; the reference: Eigen's sparse LLT on the host,
  * droid_kernels.cu:1160-1198) is PARTITIONED when the system is block-banded: two workgroups eliminate the pose chain from
  * both ends at once, the separator - the poses that couple the two parts - last (ba.hip, ba_solve_twin_kernel).  Same

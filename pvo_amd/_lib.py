@@ -68,6 +68,7 @@ SIGNATURES = {
     "pvo_update_operator": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pvo_graph_update_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "pvo_graph_update": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pvo_graph_update_rig": (_i, [_vp, _vp, _vp, _sz, _f, _vp]),
     "pvo_se3_unary": (_i, [_i, _vp, _vp, _c.c_longlong, _i, _vp]),
     "pvo_se3_binary": (_i, [_i, _vp, _c.c_longlong, _vp, _c.c_longlong, _vp, _c.c_longlong, _i, _vp]),
     "pvo_se3_unary_vjp": (_i, [_i, _vp, _vp, _vp, _c.c_longlong, _i, _vp]),
@@ -93,6 +94,11 @@ SIGNATURES = {
     "pvo_ba_prior": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
                           _f, _f, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _f, _vp]),
     "pvo_depth_sense": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "pvo_ba_stereo": (_i, [_vp, _sz, _i, _i, _i, _i, _f, _vp]),
+    "pvo_ba_rig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
+                        _f, _f, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _f, _f, _vp]),
+    "pvo_reproject_rig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "pvo_reproject_motion_rig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),

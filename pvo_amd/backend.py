@@ -2,7 +2,7 @@
 
 Role of the reference's `DroidBackend` (VO_Module/droid_slam/droid_backend.py:9-41), same constructor and call
 signature.  One pass = rescale the map to unit mean inverse depth, connect all keyframes by proximity, iterate
-`FactorGraph.update_lowmem`, drop the edges again.  A video that holds sensor depth (RGB-D) is not rescaled.
+`FactorGraph.update_lowmem`, drop the edges again.  A video that holds sensor depth (RGB-D) or right views (stereo) is not rescaled.
 
 Correlation features: `args.backend_corr = "alt"` (the reference's path: no stored volumes, features correlated on the fly
 by the alt-corr HIP kernel, operator in 8-frame chunks), `"volume"`: on MI355X the volumes of every edge of the global graph
@@ -89,7 +89,8 @@ class DroidBackend:
         n_keyframes = self.video.counter
         # (RGB-D: a video that holds sensor depth is metric - rescaling it would pull the map away from its measurements.  The
         # host-side flag set at append, not a read-back of the map.)
-        if not getattr(self.video, "has_sensor_depth", False):
+        # (stereo: likewise - the baseline fixes the scale)
+        if not getattr(self.video, "has_sensor_depth", False) and not getattr(self.video, "has_stereo", False):
             self.video.normalize()
         sharded, before, keep = None, None, None
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:

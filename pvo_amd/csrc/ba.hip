@@ -84,8 +84,9 @@ struct Plan {            // int region of the workspace
   int* kx;               // [F]   depth index -> frame
   int* eptr;             // [F+1] CSR over depth index -> edges (ascending edge id)
   int* eidx;             // [E]
-  int* meta;             // [8]   0:K 1:status(non-SPD) 2:eta mismatch 3:row table overflow 4:non-finite / out-of-range system entry
+  int* meta;             // [16]  0:K 1:status(non-SPD) 2:eta mismatch 3:row table overflow 4:non-finite / out-of-range system entry
                          //       5,6: the sensor-depth prior's map (low / high word of a const float*, 0 = none) 7: its alpha (float bits)
+                         //       8: the stereo baseline (float bits, 0 = none: an edge (i, i) is an identity edge)
   int* env;              // [P]   numeric envelope of a system for the envelope solve (ba_env_kernel; INT_MAX between solves)
 };
 
@@ -126,7 +127,7 @@ __host__ Ws carve(void* base, int E, int P, int F, int HW) {
   w.plan.kx = reinterpret_cast<int*>(take(sizeof(int) * (F + 1)));
   w.plan.eptr = reinterpret_cast<int*>(take(sizeof(int) * (F + 2)));
   w.plan.eidx = reinterpret_cast<int*>(take(sizeof(int) * (E + 1)));
-  w.plan.meta = reinterpret_cast<int*>(take(sizeof(int) * 8));
+  w.plan.meta = reinterpret_cast<int*>(take(sizeof(int) * 16));
   w.plan.env = reinterpret_cast<int*>(take(sizeof(int) * ((P > 0 ? P : 0) + 1)));
   w.Eii = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(E) * 6 * HW));
   w.Eij = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(E) * 6 * HW));
@@ -174,12 +175,16 @@ __device__ __forceinline__ DepthPrior load_prior(const int* meta) {
 }
 __global__ void ba_prior_kernel(int* meta, const float* sens, float alpha) { store_prior(meta, sens, alpha); }
 
+// the stereo baseline (pvo_ba_stereo): with b > 0 an edge (i, i) is the fixed left -> right transform of the rig.  Read once per
+// workgroup by the assembly.
+__global__ void ba_stereo_kernel(int* meta, float baseline) { meta[8] = __float_as_int(baseline); }
+
 // ---------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ba_plan_kernel(
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, Plan pl,
-    int E, int F, int t0, int t1, int K_eta, int motion_only, const float* sens, float alpha) {
+    int E, int F, int t0, int t1, int K_eta, int motion_only, const float* sens, float alpha, float baseline) {
   __shared__ int seg[257];
   const int tid = threadIdx.x;
   for (int b = tid; b < t1 - t0; b += 256) pl.env[b] = 0x7fffffff;
@@ -234,6 +239,7 @@ __global__ __launch_bounds__(256) void ba_plan_kernel(
     // back-substitution leaves every depth map alone (status_out[0] = 1, [2] = 1).
     pl.meta[2] = (!motion_only && K_eta != K && K_eta != 1) ? 1 : 0;
     store_prior(pl.meta, sens, alpha);      // (pvo_ba_plan: none - a fresh plan runs the arithmetic without the term)
+    pl.meta[8] = __float_as_int(baseline);  // (pvo_ba_plan: 0 - no stereo edges)
   }
 }
 
@@ -317,6 +323,29 @@ __device__ __forceinline__ void pixel_terms(const EdgeGeom& g, float u, float v,
   bzz += wv * rv * Jz;
 }
 
+// one pixel of a STEREO edge (i, i): g.G is the rig's fixed transform, so the residual depends on no pose - only the depth terms
+// remain.  The projection, the Z test, the weights and Jz are pixel_terms' own expressions in its own order.
+__device__ __forceinline__ void stereo_pixel_terms(const EdgeGeom& g, float u, float v, float disp,
+                                                   float tu, float tv, float wgu, float wgv, float& cii, float& bzz) {
+  float Xi[4] = {(u - g.cx) / g.fx, (v - g.cy) / g.fy, 1.0f, disp};
+  float Xj[4];
+  act4(g.G, Xi, Xj);
+  const float x = Xj[0], y = Xj[1];
+  const bool ok = !(Xj[2] < kMinDepth);
+  const float d = ok ? 1.0f / Xj[2] : 0.0f;
+  const float d2 = d * d;
+  const float wu = ok ? static_cast<float>(0.001 * static_cast<double>(wgu)) : 0.0f;
+  const float wv = ok ? static_cast<float>(0.001 * static_cast<double>(wgv)) : 0.0f;
+  const float ru = tu - (g.fx * d * x + g.cx);
+  const float rv = tv - (g.fy * d * y + g.cy);
+  float Jz = g.fx * (g.G.t.x * d - g.G.t.z * (x * d2));
+  cii = wu * Jz * Jz;
+  bzz = wu * ru * Jz;
+  Jz = g.fy * (g.G.t.y * d - g.G.t.z * (y * d2));
+  cii += wv * Jz * Jz;
+  bzz += wv * rv * Jz;
+}
+
 // Entry t of an edge's 90 sums - upper triangle of [Ji Jj]^T W [Ji Jj] (78, droid_kernels.cu:309-315 ordering), vi (6), vj (6) -
 // added to the pose system in fixed point.
 __device__ __forceinline__ void pose_block_scatter(int t, double val, int pi, int pj, int P, long long* __restrict__ sys, int* __restrict__ meta) {
@@ -392,8 +421,36 @@ __global__ __launch_bounds__(256) void ba_assemble_kernel(
   const int e = blockIdx.y;
   const int ix = static_cast<int>(ii[e]), jx = static_cast<int>(jj[e]);
   EdgeGeom g;
-  g.G = rel_pose(load_pose(poses + 7 * static_cast<long long>(ix)), load_pose(poses + 7 * static_cast<long long>(jx)));
   g.fx = intr[0]; g.fy = intr[1]; g.cx = intr[2]; g.cy = intr[3];
+  const float baseline = __int_as_float(meta[8]);
+  if (baseline != 0.0f && ix == jx) {
+    // A stereo edge (uniform over the workgroup: e is blockIdx.y).  The rig is rigid: no pose sums, so none of the reduce-scatter
+    // below; the depth terms go out with ZERO coupling rows, which the depth phase, the Schur kernel and the back-substitution read
+    // like any edge's.  Motion-only: it adds nothing at all.
+    if (motion_only) return;
+    g.G = rig_pose(baseline);
+#pragma unroll
+    for (int s = 0; s < kPPT; ++s) {
+      const int k = blockIdx.x * kChunkA + s * 256 + threadIdx.x;
+      if (k < HW) {
+        const int i = k / wd, j = k - i * wd;
+        const float* __restrict__ tg = targets + static_cast<long long>(e) * 2 * HW;
+        const float* __restrict__ wg = weights + static_cast<long long>(e) * 2 * HW;
+        float cii, bzz;
+        stereo_pixel_terms(g, static_cast<float>(j), static_cast<float>(i), disps[static_cast<long long>(ix) * HW + k], tg[k], tg[HW + k],
+                           wg[k], wg[HW + k], cii, bzz);
+        const long long eb = static_cast<long long>(e) * 6 * HW + k;
+#pragma unroll
+        for (int n = 0; n < 6; ++n) { Eii[eb + static_cast<long long>(n) * HW] = 0.0f; Eij[eb + static_cast<long long>(n) * HW] = 0.0f; }
+        Cii[static_cast<long long>(e) * HW + k] = cii;
+        bz[static_cast<long long>(e) * HW + k] = bzz;
+      }
+    }
+    // (the Schur kernel adds every edge's chunk sums into the pose system: this edge's are zero)
+    if (part && threadIdx.x < 90) part[(static_cast<long long>(e) * gridDim.x + blockIdx.x) * 90 + threadIdx.x] = 0.0f;
+    return;
+  }
+  g.G = rel_pose(load_pose(poses + 7 * static_cast<long long>(ix)), load_pose(poses + 7 * static_cast<long long>(jx)));
 
   float h[78], vi[6], vj[6];
 #pragma unroll
@@ -3184,7 +3241,7 @@ extern "C" int pvo_ba_plan(const int64_t* ii, const int64_t* jj, int E, int nfra
   if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
   Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, pvo_stream(stream),
-                     ii, jj, w.plan, E, nframes, t0, t1, K_eta, K_eta < 0 ? 1 : 0, static_cast<const float*>(nullptr), 0.0f);
+                     ii, jj, w.plan, E, nframes, t0, t1, K_eta, K_eta < 0 ? 1 : 0, static_cast<const float*>(nullptr), 0.0f, 0.0f);
   PVO_CHECK_LAUNCH();
   return PVO_OK;
 }
@@ -3198,6 +3255,18 @@ extern "C" int pvo_ba_depth_prior(void* workspace, size_t workspace_bytes, int E
   if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
   Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   hipLaunchKernelGGL(ba_prior_kernel, dim3(1), dim3(1), 0, pvo_stream(stream), w.plan.meta, disps_sens, alpha);
+  PVO_CHECK_LAUNCH();
+  return PVO_OK;
+}
+
+// the stereo baseline of every later pvo_ba_local on this workspace: one single-thread launch that writes the plan's meta word
+// (no host synchronisation, capturable); pvo_ba_plan resets it to 0
+extern "C" int pvo_ba_stereo(void* workspace, size_t workspace_bytes, int E, int P, int nframes, int HW, float baseline, void* stream) {
+  if (!workspace || E < 0 || P < 0 || nframes <= 0 || HW <= 0) return PVO_EINVAL;
+  if (!(baseline >= 0.0f) || !(baseline < __builtin_inff())) return PVO_EINVAL;      // (NaN fails the first comparison)
+  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
+  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
+  hipLaunchKernelGGL(ba_stereo_kernel, dim3(1), dim3(1), 0, pvo_stream(stream), w.plan.meta, baseline);
   PVO_CHECK_LAUNCH();
   return PVO_OK;
 }
@@ -3509,25 +3578,26 @@ extern "C" int pvo_ba_last_partition(void* workspace, size_t workspace_bytes, in
   return PVO_OK;
 }
 
-extern "C" int pvo_ba_prior(float* poses, float* disps, const float* intrinsics,
-                            const float* targets, const float* weights, const float* eta,
-                            const int64_t* ii, const int64_t* jj,
-                            int E, int nframes, int ht, int wd, int K_eta,
-                            int t0, int t1, int iterations, float lm, float ep, int motion_only,
-                            float* dx_out, float* dz_out, int dz_rows, int* status_out,
-                            void* workspace, size_t workspace_bytes,
-                            const float* disps_sens, float alpha, void* stream) {
+extern "C" int pvo_ba_rig(float* poses, float* disps, const float* intrinsics,
+                          const float* targets, const float* weights, const float* eta,
+                          const int64_t* ii, const int64_t* jj,
+                          int E, int nframes, int ht, int wd, int K_eta,
+                          int t0, int t1, int iterations, float lm, float ep, int motion_only,
+                          float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                          void* workspace, size_t workspace_bytes,
+                          const float* disps_sens, float alpha, float baseline, void* stream) {
   int rc = check_common(E, nframes, ht, wd, t0, t1);
   if (rc != PVO_OK) return rc;
   if (iterations < 0) return PVO_EINVAL;
   if (disps_sens && !(alpha > 0.0f)) return PVO_EINVAL;
+  if (!(baseline >= 0.0f) || !(baseline < __builtin_inff())) return PVO_EINVAL;
   const int P = t1 - t0, HW = ht * wd;
   if (!workspace) return PVO_EINVAL;
   if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
   Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   hipStream_t st = pvo_stream(stream);
   hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, st, ii, jj, w.plan, E, nframes, t0, t1,
-                     K_eta, motion_only, disps_sens, alpha);
+                     K_eta, motion_only, disps_sens, alpha, baseline);
   PVO_CHECK_LAUNCH();
   for (int it = 0; it < iterations; ++it) {
     rc = pvo_ba_local(poses, disps, intrinsics, targets, weights, eta, ii, jj, E, nframes, ht, wd, K_eta,
@@ -3538,6 +3608,18 @@ extern "C" int pvo_ba_prior(float* poses, float* disps, const float* intrinsics,
     if (rc != PVO_OK) return rc;
   }
   return PVO_OK;
+}
+
+extern "C" int pvo_ba_prior(float* poses, float* disps, const float* intrinsics,
+                            const float* targets, const float* weights, const float* eta,
+                            const int64_t* ii, const int64_t* jj,
+                            int E, int nframes, int ht, int wd, int K_eta,
+                            int t0, int t1, int iterations, float lm, float ep, int motion_only,
+                            float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                            void* workspace, size_t workspace_bytes,
+                            const float* disps_sens, float alpha, void* stream) {
+  return pvo_ba_rig(poses, disps, intrinsics, targets, weights, eta, ii, jj, E, nframes, ht, wd, K_eta, t0, t1, iterations, lm, ep,
+                    motion_only, dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, disps_sens, alpha, 0.0f, stream);
 }
 
 extern "C" int pvo_ba(float* poses, float* disps, const float* intrinsics,

@@ -176,18 +176,25 @@ __global__ __launch_bounds__(256) void depth_filter_kernel(
   counter[static_cast<long long>(b) * HW + k] = votes;
 }
 
+// the relative transform of edge (ix, jx).  Stereo (baseline != 0): an edge of a frame with itself is the fixed left -> right
+// transform of the rig, not the identity rel_pose would give.  baseline == 0: rel_pose for every edge, as before.
+__device__ __forceinline__ Pose edge_pose(const float* __restrict__ poses, int ix, int jx, float baseline) {
+  if (baseline != 0.0f && ix == jx) return rig_pose(baseline);
+  return rel_pose(load_pose(poses + 7 * static_cast<long long>(ix)), load_pose(poses + 7 * static_cast<long long>(jx)));
+}
+
 // projective_ops.py:102-130 with jacobian=False; per-frame intrinsics [nframes,4]
 __global__ __launch_bounds__(256) void reproject_kernel(
     const float* __restrict__ poses, const float* __restrict__ disps, const float* __restrict__ intrinsics,
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj,
-    float* __restrict__ coords, float* __restrict__ valid, int HW, int wd) {
+    float* __restrict__ coords, float* __restrict__ valid, int HW, int wd, float baseline) {
   const int e = blockIdx.y;
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= HW) return;
   const int ix = static_cast<int>(ii[e]), jx = static_cast<int>(jj[e]);
   const Intr Ki = load_intr(intrinsics + 4 * static_cast<long long>(ix));
   const Intr Kj = load_intr(intrinsics + 4 * static_cast<long long>(jx));
-  const Pose G = rel_pose(load_pose(poses + 7 * static_cast<long long>(ix)), load_pose(poses + 7 * static_cast<long long>(jx)));
+  const Pose G = edge_pose(poses, ix, jx, baseline);
   const int i = k / wd, j = k - i * wd;
   float X0[4] = {(static_cast<float>(j) - Ki.cx) / Ki.fx, (static_cast<float>(i) - Ki.cy) / Ki.fy, 1.0f,
                  disps[static_cast<long long>(ix) * HW + k]};
@@ -276,7 +283,7 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj,
     float* __restrict__ coords, float* __restrict__ valid,
     const float2* __restrict__ target, const float2* __restrict__ delta_dy, const float2* __restrict__ raw_mask,
-    uint16_t* __restrict__ motn, int HW, int wd) {
+    uint16_t* __restrict__ motn, int HW, int wd, float baseline) {
   const int e = blockIdx.y;
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= HW) return;
@@ -285,7 +292,7 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(
   const int ix = static_cast<int>(ii[e]), jx = static_cast<int>(jj[e]);
   const Intr Ki = load_intr(intrinsics + 4 * static_cast<long long>(ix));
   const Intr Kj = load_intr(intrinsics + 4 * static_cast<long long>(jx));
-  const Pose G = rel_pose(load_pose(poses + 7 * static_cast<long long>(ix)), load_pose(poses + 7 * static_cast<long long>(jx)));
+  const Pose G = edge_pose(poses, ix, jx, baseline);
   const int i = k / wd, j = k - i * wd;
   float X0[4] = {(static_cast<float>(j) - Ki.cx) / Ki.fx, (static_cast<float>(i) - Ki.cy) / Ki.fy, 1.0f,
                  disps[static_cast<long long>(ix) * HW + k]};
@@ -311,11 +318,11 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(
   *reinterpret_cast<uint4*>(motn + idx * 8) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-extern "C" int pvo_reproject_motion(const float* poses, const float* disps, const float* intrinsics,
-                                    const int64_t* ii, const int64_t* jj, float* coords, float* valid,
-                                    const float* target, const float* delta_dy, const float* raw_mask, void* motn,
-                                    int E, int ht, int wd, int dtype, void* stream) {
-  PVO_REQ(E >= 0 && ht >= 0 && wd >= 0);
+extern "C" int pvo_reproject_motion_rig(const float* poses, const float* disps, const float* intrinsics,
+                                        const int64_t* ii, const int64_t* jj, float* coords, float* valid,
+                                        const float* target, const float* delta_dy, const float* raw_mask, void* motn,
+                                        int E, int ht, int wd, int dtype, float baseline, void* stream) {
+  PVO_REQ(E >= 0 && ht >= 0 && wd >= 0 && baseline >= 0.0f);
   if (E == 0 || ht * wd == 0) return PVO_OK;
   PVO_REQ(poses && disps && intrinsics && ii && jj && coords && valid && target && delta_dy && raw_mask && motn && E <= 65535);
   PVO_REQ(!pvo_misaligned16(motn) && !((reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(delta_dy) |
@@ -325,22 +332,36 @@ extern "C" int pvo_reproject_motion(const float* poses, const float* disps, cons
   return pvo_dispatch16(dtype, [&](auto tag) -> int {
     using T = decltype(tag);
     hipLaunchKernelGGL(reproject_motion_kernel<T>, grid, dim3(256), 0, pvo_stream(stream), poses, disps, intrinsics, ii, jj, coords, valid,
-                       f2(target), f2(delta_dy), f2(raw_mask), static_cast<uint16_t*>(motn), ht * wd, wd);
+                       f2(target), f2(delta_dy), f2(raw_mask), static_cast<uint16_t*>(motn), ht * wd, wd, baseline);
     PVO_CHECK_LAUNCH();
     return PVO_OK;
   });
 }
 
-extern "C" int pvo_reproject(const float* poses, const float* disps, const float* intrinsics,
-                             const int64_t* ii, const int64_t* jj, float* coords, float* valid,
-                             int E, int ht, int wd, void* stream) {
-  PVO_REQ(E >= 0 && ht >= 0 && wd >= 0);
+extern "C" int pvo_reproject_motion(const float* poses, const float* disps, const float* intrinsics,
+                                    const int64_t* ii, const int64_t* jj, float* coords, float* valid,
+                                    const float* target, const float* delta_dy, const float* raw_mask, void* motn,
+                                    int E, int ht, int wd, int dtype, void* stream) {
+  return pvo_reproject_motion_rig(poses, disps, intrinsics, ii, jj, coords, valid, target, delta_dy, raw_mask, motn, E, ht, wd, dtype, 0.0f, stream);
+}
+
+// stereo: baseline > 0 makes every edge (i, i) the rig's left -> right transform (se3.h rig_pose); 0 is pvo_reproject
+extern "C" int pvo_reproject_rig(const float* poses, const float* disps, const float* intrinsics,
+                                 const int64_t* ii, const int64_t* jj, float* coords, float* valid,
+                                 int E, int ht, int wd, float baseline, void* stream) {
+  PVO_REQ(E >= 0 && ht >= 0 && wd >= 0 && baseline >= 0.0f);
   if (E == 0 || ht * wd == 0) return PVO_OK;
   PVO_REQ(poses && disps && intrinsics && ii && jj && coords && valid && E <= 65535);
   hipLaunchKernelGGL(reproject_kernel, dim3((ht * wd + 255) / 256, E), dim3(256), 0, pvo_stream(stream),
-                     poses, disps, intrinsics, ii, jj, coords, valid, ht * wd, wd);
+                     poses, disps, intrinsics, ii, jj, coords, valid, ht * wd, wd, baseline);
   PVO_CHECK_LAUNCH();
   return PVO_OK;
+}
+
+extern "C" int pvo_reproject(const float* poses, const float* disps, const float* intrinsics,
+                             const int64_t* ii, const int64_t* jj, float* coords, float* valid,
+                             int E, int ht, int wd, void* stream) {
+  return pvo_reproject_rig(poses, disps, intrinsics, ii, jj, coords, valid, E, ht, wd, 0.0f, stream);
 }
 
 // RGB-D ingest: the sensor depth's 1/8 lattice as inverse depth, 0 where there is no measurement

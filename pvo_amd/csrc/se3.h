@@ -46,6 +46,15 @@ __device__ __forceinline__ Pose rel_pose(const Pose Gi, const Pose Gj) {
   return G;
 }
 
+// the fixed transform of a rectified stereo rig, left camera -> right camera: no rotation, the right camera sits `baseline` to the
+// right, so a point moves by (-baseline, 0, 0) d.  Stands in for rel_pose on a stereo edge (i, i).
+__device__ __forceinline__ Pose rig_pose(float baseline) {
+  Pose G;
+  G.t = {-baseline, 0.0f, 0.0f};
+  G.q = {0.0f, 0.0f, 0.0f, 1.0f};
+  return G;
+}
+
 // homogeneous point action [X,Y,Z,d] -> [R X + d t, d]  (droid_kernels.cu:70-77 actSE3)
 __device__ __forceinline__ void act4(const Pose G, const float X[4], float Y[4]) {
   const Vec3 r = rotate(G.q, {X[0], X[1], X[2]});

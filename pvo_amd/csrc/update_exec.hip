@@ -321,9 +321,10 @@ extern "C" size_t pvo_graph_update_workspace_bytes(int E, int K, int R, int H, i
   return carve_up(nullptr, E, K, R, H, W, max_segments, pvo_operator_workspace_bytes(E, K, H, W)).bytes + 256;
 }
 
-extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_update_args* u,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int pvo_graph_update_rig(const pvo_update_weights* w, const pvo_graph_update_args* u,
+                                    void* workspace, size_t workspace_bytes, float stereo_baseline, void* stream) {
   if (!w || !u) return PVO_EINVAL;
+  if (!(stereo_baseline >= 0.0f) || !(stereo_baseline < __builtin_inff())) return PVO_EINVAL;      // (NaN fails the first comparison)
   pvo_operator_args a = u->op;
   a.net_out = a.net_out ? a.net_out : const_cast<void*>(a.net);
   a.heads = reinterpret_cast<void*>(1);        // supplied from the workspace below
@@ -346,8 +347,9 @@ extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_upd
   probe_mark(PVO_STAGE_UPDATE, 0, stream);
   // factor_graph.py:231-237: reprojection and motion features
   // (the motion features ride on the reprojection: 20-24 us of the side chain beside the lookup otherwise)
-  RUN(pvo_reproject_motion(u->poses, u->disps, u->intrinsics, u->ii, u->jj, s.coords, s.valid, u->target, u->delta_dy, u->raw_mask,
-                           s.motion, E, H, W, dt, stream));
+  // (stereo: with stereo_baseline > 0 an edge (i, i) is the rig's fixed left -> right transform; 0 is pvo_reproject_motion)
+  RUN(pvo_reproject_motion_rig(u->poses, u->disps, u->intrinsics, u->ii, u->jj, s.coords, s.valid, u->target, u->delta_dy, u->raw_mask,
+                               s.motion, E, H, W, dt, stereo_baseline, stream));
   a.coords = s.coords; a.corr = nullptr; a.motion = s.motion; a.heads = s.heads;
   a.eta = u->op.eta ? u->op.eta : s.eta;          // (a caller that runs the BA itself - edge sharding - supplies the buffer)
   // full-resolution depth behind the BA (pvo_graph_update_args.want_upsample): needs the mask, whoever else wants it
@@ -404,6 +406,9 @@ extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_upd
   if (!mask_rides) RUN(run_upmask(w, &a, b, stream));
   // :302 dense bundle adjustment on [inactive | active] edges, planned by the caller (pvo_ba_plan) for this edge set
   const int Eb = u->n_in + E;
+  // (stereo: the baseline goes into the plan on this stream, in front of the first assembly; off, no launch is added)
+  if (stereo_baseline != 0.0f && u->itrs > 0)
+    RUN(pvo_ba_stereo(u->ba_ws, u->ba_ws_bytes, Eb, u->t1 - u->t0, u->nframes, HW, stereo_baseline, stream));
   probe_mark(PVO_STAGE_BA, 0, stream);
   // `sys` is zero on entry (contract, see the header) and every solve leaves it zero: no memset between updates.  The
   // depth clamp of depth_video.py:214 rides on the last back-substitution.
@@ -444,6 +449,11 @@ extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_upd
     *ca = ContextAhead{workspace, w, w->glo_w, w->gate_wt, a.net_out, E, H, W, dt, true};
   probe_mark(PVO_STAGE_UPDATE, 1, stream);
   return PVO_OK;
+}
+
+extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_update_args* u,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  return pvo_graph_update_rig(w, u, workspace, workspace_bytes, 0.0f, stream);
 }
 
 extern "C" int pvo_side_stream(void** stream_out) {

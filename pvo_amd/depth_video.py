@@ -13,6 +13,13 @@ keyframe's measured inverse depth at 1/8 resolution, 0 = no measurement, in `dis
 `ba()` and the factor graph's native update carry the sensor-depth prior of the bundle adjustment (include/pvo_hip.h,
 pvo_ba_depth_prior).  `has_sensor_depth` is the host-side flag everything asks; a video that never saw a depth image allocates
 nothing and computes exactly what it computed before.
+
+Stereo: `append(..., right_fmap=...)` stores the feature map of a keyframe's RIGHT view in `fmaps_right` (allocated on first use).  On
+such a video (`has_stereo`: a right view was seen and `stereo_baseline` > 0) an edge (i, i) is a stereo edge - the fixed left -> right
+transform of a rectified rig, u_right = u - fx b d - in `reproject`, `reproject_into`, `ba` and the factor graph's native update
+(include/pvo_hip.h, pvo_ba_stereo); the factor graph correlates it against the right map.  Every keyframe of a stereo video is expected
+to bring its right view (one that does not gets a zero map).  A video that never saw a right view allocates nothing and computes
+exactly what it computed before, (i, i) edges included.
 """
 import torch
 
@@ -39,6 +46,8 @@ class DepthVideo:
         self.sensor_alpha = 0.05           # weight of the sensor-depth prior (upstream's alpha)
         self.intrinsics = torch.zeros(buffer, 4, dtype=torch.float, **kw)
         self.fmaps = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw)      # channels-last
+        self.fmaps_right = None            # stereo: the right views' feature maps [buffer,H/8,W/8,128] channels-last (ensure_fmaps_right)
+        self.stereo_baseline = 0.1         # the rig's baseline in the units of the poses' translations (upstream's constant)
         # [buffer,128,h,w] as the reference has them, stored channels-last: an edge's rows are gathered straight into the
         # layout the update operator reads (factor_graph.py add_factors)
         self.nets = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw).permute(0, 3, 1, 2)
@@ -151,6 +160,21 @@ class DepthVideo:
             b *= 2
         return max(1, min(self.max_segments, b))
 
+    @property
+    def has_stereo(self):
+        """host-side: some keyframe brought a right view and the baseline is positive - edges (i, i) are stereo edges"""
+        return self.fmaps_right is not None and self.stereo_baseline > 0
+
+    def rig_baseline(self):
+        """the baseline the native calls get: stereo_baseline on a stereo video, else 0 (no stereo edges)"""
+        return float(self.stereo_baseline) if self.has_stereo else 0.0
+
+    def ensure_fmaps_right(self):
+        """the right views' feature maps [buffer, H/8, W/8, 128] fp16 channels-last, allocated on first use"""
+        if self.fmaps_right is None:
+            self.fmaps_right = torch.zeros_like(self.fmaps)
+        return self.fmaps_right
+
     def ensure_disps_sens(self):
         """the sensor inverse depths [buffer, H/8, W/8], allocated (zero = no measurement) on first use"""
         if self.disps_sens is None:
@@ -188,10 +212,16 @@ class DepthVideo:
             sens[k] = db.to_device_async(self.sense_depth_host(depth), torch.float32, self.device)
         self.has_sensor_depth = True
 
-    def append(self, tstamp, pose, disp, intrinsics, fmap, net, inp, segm=None, image=None, channels_last=None, depth=None):
+    def append(self, tstamp, pose, disp, intrinsics, fmap, net, inp, segm=None, image=None, channels_last=None, depth=None,
+               right_fmap=None):
         """store one keyframe; fmap may be [128,h,w] (reference layout) or [h,w,128] (see _fmap_cl).  depth: the frame's sensor
-        depth image [H,W] (RGB-D, see set_depth); None leaves the video as it is - nothing is allocated for it."""
+        depth image [H,W] (RGB-D, see set_depth); None leaves the video as it is - nothing is allocated for it.  right_fmap: the
+        feature map of the frame's right view (stereo), in fmap's layouts; None likewise allocates nothing."""
         k = self.counter
+        if right_fmap is not None:
+            self.ensure_fmaps_right()[k] = self._fmap_cl(right_fmap, channels_last)
+        elif self.fmaps_right is not None:
+            self.fmaps_right[k].zero_()        # (a stale row, as rm_keyframe leaves one)
         if depth is not None or self.disps_sens is not None:
             self.set_depth(k, depth)
         # (a Python number goes in with fill_ on a slice - a kernel argument.  `buf[k] = number` builds a host tensor and copies it with a
@@ -298,13 +328,17 @@ class DepthVideo:
     def reproject(self, ii, jj):
         """project points ii -> jj (depth_video.py:154-163): coords [1,E,h,w,2], valid [1,E,h,w,1]"""
         ii, jj = self.format_indicies(ii, jj, self.device)
-        coords, valid = db.reproject(self.poses, self.disps, self.intrinsics, ii, jj)
+        coords, valid = db.reproject(self.poses, self.disps, self.intrinsics, ii, jj, **self._rig_kw("baseline"))
         return coords[None], valid[None]
 
     def reproject_into(self, ii, jj, coords_out):
         """reproject(ii, jj)[0][0] written into coords_out [E,h,w,2] (device tensors only)"""
         ii, jj = self.format_indicies(ii, jj, self.device)
-        db.reproject(self.poses, self.disps, self.intrinsics, ii, jj, out=coords_out)
+        db.reproject(self.poses, self.disps, self.intrinsics, ii, jj, out=coords_out, **self._rig_kw("baseline"))
+
+    def _rig_kw(self, name):
+        """{name: baseline} on a stereo video, {} otherwise: the native call is then exactly the one a monocular video makes"""
+        return {name: float(self.stereo_baseline)} if self.has_stereo else {}
 
     def distance(self, ii=None, jj=None, beta=0.3, bidirectional=True):
         """frame distance metric (depth_video.py:165-195)"""
@@ -346,6 +380,7 @@ class DepthVideo:
             eta = 1e-7 * torch.ones([k, self.ht // 8, self.wd // 8], device=self.device)
         # (RGB-D: the sensor-depth prior, once a keyframe has brought a depth image)
         kw = {"disps_sens": self.disps_sens, "alpha": self.sensor_alpha} if self.has_sensor_depth and not motion_only else {}
+        kw.update(self._rig_kw("stereo_baseline"))      # (stereo: edges (i, i) under the rig's fixed transform)
         db.ba(self.poses, self.disps, self.intrinsics[0], target, weight, eta, ii, jj, t0, t1, itrs, lm, ep,
               motion_only, **kw)
         self.disps.clamp_(min=0.001)

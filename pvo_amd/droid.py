@@ -24,10 +24,13 @@ def default_args(**over):
     a = dict(device="cuda:0", weights=None, buffer=1024, image_size=[240, 808], disable_vis=True, use_aff_bri=False,
              beta=0.6, filter_thresh=1.75, warmup=12, keyframe_thresh=2.25, frontend_thresh=12.0, frontend_window=25,
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
-             segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False)
+             segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1)
     # rgbd: use the `depth` image of track() - each keyframe's sensor depth becomes a prior of the bundle adjustment, the trajectory
     # and the map are metric (DepthVideo, include/pvo_hip.h pvo_ba_depth_prior).  False (default): `depth` is IGNORED, nothing is
     # allocated for it and every result is what a monocular run computes.
+    # stereo: use the `right` image of track() - each keyframe's right view gives the graph a stereo edge (i, i) with the fixed baseline
+    # stereo_baseline (in the units the trajectory is wanted in: metres give a metric trajectory; 0.1 is upstream's constant).  False
+    # (default): `right` is IGNORED, nothing is allocated for it and every result is what a monocular run computes.
     a.update(over)
     return Namespace(**a)
 
@@ -40,6 +43,8 @@ class Droid:
         self.filterx = MotionFilter(self.net, self.video, thresh=args.filter_thresh, device=args.device)
         self.filterx.overlap_upload = bool(getattr(args, "pipelined", False))
         self.filterx.use_depth = bool(getattr(args, "rgbd", False))
+        self.filterx.use_stereo = bool(getattr(args, "stereo", False))
+        self.video.stereo_baseline = float(getattr(args, "stereo_baseline", 0.1))
         self.frontend = DroidFrontend(self.net.update, self.video, args.device, warmup=args.warmup, beta=args.beta,
                                       frontend_nms=args.frontend_nms, keyframe_thresh=args.keyframe_thresh,
                                       frontend_window=args.frontend_window, frontend_thresh=args.frontend_thresh,
@@ -65,8 +70,9 @@ class Droid:
             # the encoders' 3 x 3 / 7 x 7 convolutions on the library's own deterministic kernel instead of the vendor library (opt-in)
             self.net.fnet.native_convs = self.net.cnet.native_convs = True
 
-    def track(self, tstamp, image, depth=None, intrinsics=None, segments=None):
-        """one frame (droid.py:64-75).  depth [H,W] (host or device, resized and cropped like the image; <= 0 / non-finite = no
+    def track(self, tstamp, image, depth=None, intrinsics=None, segments=None, right=None):
+        """one frame (droid.py:64-75).  right [3,H,W]: the right view of a rectified stereo pair, prepared like `image`; used only
+        with args.stereo and ignored otherwise.  depth [H,W] (host or device, resized and cropped like the image; <= 0 / non-finite = no
         measurement) is used only with args.rgbd, on every frame that brings one, and ignored otherwise.  args.pipelined (default False: the reference's order, the video is final for this frame when
         the call returns): the frame's graph is launched FIRST, then the second half of the previous keyframe's frontend update (its
         keyframe test was left in flight when the previous call returned), then the motion test is read and this frame's frontend
@@ -76,10 +82,10 @@ class Droid:
         completes it."""
         with torch.no_grad():
             if not getattr(self.args, "pipelined", False):
-                self.filterx.track(tstamp, image, depth, intrinsics, segments)
+                self.filterx.track(tstamp, image, depth, intrinsics, segments, right=right)
                 self.frontend()
                 return
-            self.filterx.begin(tstamp, image, depth, intrinsics, segments)
+            self.filterx.begin(tstamp, image, depth, intrinsics, segments, right=right)
             self.frontend.finish()
             self.filterx.finish()
             self.frontend.begin()

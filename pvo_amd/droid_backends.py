@@ -467,10 +467,20 @@ def depth_filter(poses, disps, intrinsics, ix, thresh):
     return counter
 
 
-def reproject(poses, disps, intrinsics, ii, jj, out=None):
+def _baseline(baseline, what):
+    """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
+    b = float(baseline)
+    if not (0.0 <= b < float("inf")):
+        raise PvoHipError("%s: the stereo baseline must be finite and >= 0, got %r" % (what, baseline))
+    return b
+
+
+def reproject(poses, disps, intrinsics, ii, jj, out=None, baseline=0.0):
     """DepthVideo.reproject (depth_video.py:154-163): poses [F,7], disps [F,ht,wd],
     intrinsics [F,4] -> coords [E,ht,wd,2], valid [E,ht,wd,1].  out: a contiguous fp32 [E,ht,wd,2] tensor to write the
-    coordinates into (e.g. the rows of a state buffer)."""
+    coordinates into (e.g. the rows of a state buffer).  baseline > 0 (pvo_reproject_rig): an edge (i, i) is a stereo edge,
+    u_right = u - fx b d; 0 is pvo_reproject."""
+    baseline = _baseline(baseline, "reproject")
     for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
         _contig(t, n)
     dev = _dev(poses, disps, intrinsics, ii, jj)
@@ -484,8 +494,12 @@ def reproject(poses, disps, intrinsics, ii, jj, out=None):
         coords = torch.empty(E, ht, wd, 2, dtype=torch.float32, device=dev)
     valid = torch.empty(E, ht, wd, 1, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        check(_lib.load().pvo_reproject(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj),
-                                        _ptr(coords), _ptr(valid), E, ht, wd, _stream(dev)), "reproject")
+        if baseline == 0.0:
+            check(_lib.load().pvo_reproject(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj),
+                                            _ptr(coords), _ptr(valid), E, ht, wd, _stream(dev)), "reproject")
+        else:
+            check(_lib.load().pvo_reproject_rig(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj),
+                                                _ptr(coords), _ptr(valid), E, ht, wd, baseline, _stream(dev)), "reproject (stereo)")
     return coords, valid
 
 
@@ -499,7 +513,7 @@ def _sens_map(disps_sens, disps, what):
 
 
 def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iterations, lm, ep, motion_only,
-       status=None, disps_sens=None, alpha=0.05):
+       status=None, disps_sens=None, alpha=0.05, stereo_baseline=0.0):
     """droid.cpp:87-114 / ba_cuda droid_kernels.cu:1293-1410.
 
     poses [F,7] and disps [F,ht,wd] are updated IN PLACE; returns [dx [P,6], dz [K,ht*wd]]
@@ -507,7 +521,9 @@ def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iteratio
     Fully asynchronous: no host synchronisation.  `status` (optional int32[4] device tensor)
     receives [non-SPD seen, K, eta-row mismatch, 0].
     disps_sens [F,ht,wd] (optional): measured inverse depth, 0 = no measurement - the sensor-depth prior with weight
-    `alpha` (pvo_ba_prior, include/pvo_hip.h); None is pvo_ba."""
+    `alpha` (pvo_ba_prior, include/pvo_hip.h); None is pvo_ba.
+    stereo_baseline > 0 (pvo_ba_rig): an edge (i, i) is a stereo edge of a rectified rig with that baseline; 0 changes nothing."""
+    stereo_baseline = _baseline(stereo_baseline, "ba")
     if disps_sens is not None:
         _sens_map(disps_sens, disps, "ba")
     for t, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
@@ -555,7 +571,10 @@ def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iteratio
                 1 if motion_only else 0, _ptr(dx), _ptr(dz), K,
                 _ptr(status) if status is not None else ctypes.c_void_p(0),
                 ctypes.c_void_p(ws.data_ptr()), ws.numel())
-        if disps_sens is None:
+        if stereo_baseline != 0.0:
+            check(lib.pvo_ba_rig(*args, _ptr(disps_sens) if disps_sens is not None else ctypes.c_void_p(0), float(alpha), stereo_baseline,
+                                 _stream(dev)), "ba (stereo)")
+        elif disps_sens is None:
             check(lib.pvo_ba(*args, _stream(dev)), "ba")
         else:
             check(lib.pvo_ba_prior(*args, _ptr(disps_sens), float(alpha), _stream(dev)), "ba (sensor depth)")
@@ -607,6 +626,15 @@ def ba_depth_prior(workspace, E, P, nframes, HW, disps_sens, alpha=0.05):
     with torch.cuda.device(dev):
         check(_lib.load().pvo_ba_depth_prior(ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), int(E), int(P), int(nframes), int(HW),
                                              _ptr(disps_sens), float(alpha), _stream(dev)), "ba_depth_prior")
+
+
+def ba_stereo(workspace, E, P, nframes, HW, baseline):
+    """the stereo baseline of every later ba_local on this PLANNED workspace (pvo_ba_stereo): with baseline > 0 an edge (i, i) is a
+    stereo edge; 0 clears it, and so does the next ba_plan."""
+    dev = _dev(workspace)
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_ba_stereo(ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), int(E), int(P), int(nframes), int(HW),
+                                        _baseline(baseline, "ba_stereo"), _stream(dev)), "ba_stereo")
 
 
 def depth_sense(depth, out_row):
@@ -1035,8 +1063,10 @@ def graph_motion(target, coords1, delta_dy, raw_mask, dtype):
     return motn.permute(0, 3, 1, 2)[None]
 
 
-def reproject_motion(poses, disps, intrinsics, ii, jj, target, delta_dy, raw_mask, dtype):
-    """reproject + graph_motion in one pass (pvo_reproject_motion) -> coords [E,ht,wd,2], valid [E,ht,wd,1], motion [1,E,8,H,W]"""
+def reproject_motion(poses, disps, intrinsics, ii, jj, target, delta_dy, raw_mask, dtype, baseline=0.0):
+    """reproject + graph_motion in one pass (pvo_reproject_motion) -> coords [E,ht,wd,2], valid [E,ht,wd,1], motion [1,E,8,H,W].
+    baseline > 0: pvo_reproject_motion_rig (stereo edges, see reproject)."""
+    baseline = _baseline(baseline, "reproject_motion")
     for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj"), (target, "target"),
                  (delta_dy, "delta_dy"), (raw_mask, "raw_mask")):
         _contig(t, n)
@@ -1049,9 +1079,12 @@ def reproject_motion(poses, disps, intrinsics, ii, jj, target, delta_dy, raw_mas
     valid = torch.empty(E, ht, wd, 1, dtype=torch.float32, device=dev)
     motn = torch.empty(E, ht, wd, 8, dtype=dtype, device=dev)
     with torch.cuda.device(dev):
-        check(_lib.load().pvo_reproject_motion(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj), _ptr(coords), _ptr(valid),
-                                               _ptr(target), _ptr(delta_dy), _ptr(raw_mask), _ptr(motn), E, ht, wd, _DT[dtype],
-                                               _stream(dev)), "reproject_motion")
+        a = (_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj), _ptr(coords), _ptr(valid),
+             _ptr(target), _ptr(delta_dy), _ptr(raw_mask), _ptr(motn), E, ht, wd, _DT[dtype])
+        if baseline == 0.0:
+            check(_lib.load().pvo_reproject_motion(*a, _stream(dev)), "reproject_motion")
+        else:
+            check(_lib.load().pvo_reproject_motion_rig(*a, baseline, _stream(dev)), "reproject_motion (stereo)")
     return coords, valid, motn.permute(0, 3, 1, 2)[None]
 
 
@@ -1418,13 +1451,19 @@ def graph_update_workspace(E, K, R, H, W, max_segments, device):
     return _op_workspace(("up", torch.device(device).index), torch.device(device), n)
 
 
-def graph_update(weights, args, workspace):
+def graph_update(weights, args, workspace, stereo_baseline=0.0):
     """FactorGraph.update (factor_graph.py:227-307) as ONE call: `args` is a filled _lib.GraphUpdateArgs (the caller -
-    pvo_amd.factor_graph - keeps every tensor it points to alive); see include/pvo_hip.h pvo_graph_update."""
+    pvo_amd.factor_graph - keeps every tensor it points to alive); see include/pvo_hip.h pvo_graph_update.
+    stereo_baseline > 0 (pvo_graph_update_rig): edges (i, i) are stereo edges of a rectified rig with that baseline."""
     dev = workspace.device
+    stereo_baseline = _baseline(stereo_baseline, "graph_update")
     with torch.cuda.device(dev):
-        check(_lib.load().pvo_graph_update(ctypes.byref(weights.struct), ctypes.byref(args), ctypes.c_void_p(workspace.data_ptr()),
-                                           workspace.numel(), _stream(dev)), "graph_update")
+        if stereo_baseline == 0.0:
+            check(_lib.load().pvo_graph_update(ctypes.byref(weights.struct), ctypes.byref(args), ctypes.c_void_p(workspace.data_ptr()),
+                                               workspace.numel(), _stream(dev)), "graph_update")
+        else:
+            check(_lib.load().pvo_graph_update_rig(ctypes.byref(weights.struct), ctypes.byref(args), ctypes.c_void_p(workspace.data_ptr()),
+                                                   workspace.numel(), stereo_baseline, _stream(dev)), "graph_update (stereo)")
 
 
 # --------------------------------------------------------------------------- convex upsampling

@@ -187,6 +187,27 @@ class FactorGraph:
     def _to_list(x):
         return [int(v) for v in (x.tolist() if isinstance(x, torch.Tensor) else x)]
 
+    def _rig_baseline(self):
+        """the stereo baseline of the video's rig when it is a stereo video (an edge (i, i) is then a stereo edge), else 0"""
+        v = self.video
+        return float(v.stereo_baseline) if getattr(v, "has_stereo", False) else 0.0
+
+    def _stereo_edges(self, t0, t1):
+        """stereo: the stereo edge (i, i) of every keyframe in [t0, t1), requested IN FRONT of a call's other edges (add_factors drops
+        the ones that exist as active or inactive edges); nothing on a video without a right view"""
+        if self._rig_baseline() == 0.0:
+            return []
+        return list(range(max(t0, 0), t1))
+
+    def _fmap2(self, ii_l, jj_l, jj):
+        """the second feature map of each new edge: frame jj's - for a stereo edge (i, i) of a stereo video the RIGHT view of frame i"""
+        f2 = self.video.fmaps[jj]
+        pos = [k for k, (i, j) in enumerate(zip(ii_l, jj_l)) if i == j] if self._rig_baseline() != 0.0 else []
+        if pos:
+            both = self._idx(pos + [ii_l[k] for k in pos])
+            f2.index_copy_(0, both[:len(pos)], self.video.fmaps_right.index_select(0, both[len(pos):]))
+        return f2
+
     def add_factors(self, ii, jj, remove=False):
         """add edges (factor_graph.py:106-161)"""
         ii_l, jj_l = self._filter_repeated(self._to_list(ii), self._to_list(jj))
@@ -230,9 +251,9 @@ class FactorGraph:
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             if self.corr_impl == "volume":
                 if pool_path:
-                    self.corr.add(self.video.fmaps[ii], self.video.fmaps[jj], new_slots)
+                    self.corr.add(self.video.fmaps[ii], self._fmap2(ii_l, jj_l, jj), new_slots)
                 else:
-                    corr = CorrBlock(self.video.fmaps[ii][None], self.video.fmaps[jj][None], channels_last=True)
+                    corr = CorrBlock(self.video.fmaps[ii][None], self._fmap2(ii_l, jj_l, jj)[None], channels_last=True)
                     self.corr = corr if self.corr is None else self.corr.cat(corr)
                 inp = self._frame_rows(self.video.inps, ii)[None]
                 if not by_slot:
@@ -432,8 +453,10 @@ class FactorGraph:
         v = self.video
         up = getattr(v, "disps_up", None)                               # (kept in step with disps where it is maintained)
         sens = getattr(v, "disps_sens", None)                           # (RGB-D: the sensor map moves with its frame)
+        right = getattr(v, "fmaps_right", None)                         # (stereo: and so does the right view's feature map)
         for buf in (v.poses, v.disps, v.intrinsics, v.nets, v.inps, v.fmaps) + ((v.segms,) if v.segm_filter else ()) + \
-                ((up,) if self.upsample and up is not None else ()) + ((sens,) if sens is not None else ()):
+                ((up,) if self.upsample and up is not None else ()) + ((sens,) if sens is not None else ()) + \
+                ((right,) if right is not None else ()):
             buf[ix] = buf[ix + 1].clone()
         m = [(i == ix) or (j == ix) for i, j in zip(self._ii_h, self._jj_h)]
         for t in (self.ii_inac, self.jj_inac):                       # (masked in-place updates would synchronise)
@@ -476,7 +499,13 @@ class FactorGraph:
         if self.upsample:
             raise NotImplementedError("FactorGraph(upsample=True): update_lowmem refreshes disps_up only on resident correlation "
                                       "volumes (corr_impl='volume' with the native update), not on its alt-corr path")
-        corr_op = AltCorrBlock(self.video.fmaps[None, :t], channels_last=True)
+        rig = self._rig_baseline()
+        if rig != 0.0:
+            # stereo: the block holds [left maps of [0, t) | right maps of [0, t)], and a stereo edge (i, i) looks up frame t + i
+            corr_op = AltCorrBlock(torch.cat([self.video.fmaps[:t], self.video.fmaps_right[:t]])[None], channels_last=True)
+            jj_corr = self._idx([j + t if i == j else j for i, j in zip(self._ii_h, self._jj_h)])
+        else:
+            corr_op, jj_corr = AltCorrBlock(self.video.fmaps[None, :t], channels_last=True), None
         jmax = max(self._jj_h + self._ii_h) if sharded is not None else max(self._jj_h)
         chunks = []
         for i in range(0, jmax + 1, 8):
@@ -497,7 +526,7 @@ class FactorGraph:
             motn = motn.permute(0, 1, 4, 2, 3).clamp(-64.0, 64.0)
             for v, srcs in chunks:
                 iis, jjs = self.ii[v], self.jj[v]
-                corr1 = corr_op(coords1[:, v], iis, jjs)
+                corr1 = corr_op(coords1[:, v], iis, jjs if jj_corr is None else jj_corr[v])
                 with torch.autocast("cuda", dtype=torch.float16, enabled=self._autocast and self.device.type == "cuda"):
                     net, delta, weight, damping, _, delta_m = self.update_op(
                         self.net[:, v], self.video.inps[iis][None], corr1, motn[:, v], iis, jjs, False)
@@ -516,6 +545,8 @@ class FactorGraph:
                 self.video.ba(target, weight, eta, self.ii, self.jj, 1, t, itrs=itrs, lm=1e-5, ep=1e-2, motion_only=False)
             else:
                 kw = {"disps_sens": self.video.disps_sens, "alpha": self.video.sensor_alpha} if self._sensor_map() is not None else {}
+                if rig != 0.0:
+                    kw["stereo_baseline"] = rig
                 eta_rows = torch.ones(len(rows_l), ht, wd, dtype=eta.dtype, device=self.device)
                 eta_rows[row_of_src] = eta
                 sharded.ba(self.video.poses, self.video.disps, self.video.intrinsics[0], target, weight, eta_rows,
@@ -526,7 +557,8 @@ class FactorGraph:
 
     def add_neighborhood_factors(self, t0, t1, r=3):
         """edges between frames within temporal radius r (factor_graph.py:362-370)"""
-        ii, jj = [], []
+        ii = self._stereo_edges(t0, t1)          # (stereo: every keyframe's left -> right edge first)
+        jj = list(ii)
         for i in range(t0, t1):
             for j in range(t0, t1):
                 if i != j and abs(i - j) <= r:
@@ -598,8 +630,9 @@ class FactorGraph:
             have_i = np.array(list(self._ii_h) + self.ii_bad.tolist() + list(self._ii_inac_h), dtype=np.int64)
             have_j = np.array(list(self._jj_h) + self.jj_bad.tolist() + list(self._jj_inac_h), dtype=np.int64)
             ei, ej = db.proximity_select(D32, t0, t1, rad, nms, thresh, have_i, have_j)
-            if ei:
-                self.add_factors(ei, ej, remove)
+            st_e = self._stereo_edges(t0, t)     # (stereo: every keyframe's left -> right edge, in front of the selected ones)
+            if ei or st_e:
+                self.add_factors(st_e + list(ei), st_e + list(ej), remove)
             return
         D = D32.astype(np.float64)
         I = np.arange(t0, t)[:, None]
@@ -632,7 +665,7 @@ class FactorGraph:
         far = np.abs(have_i - have_j) > 2
         if far.any():
             suppress_many(have_i[far], have_j[far])
-        es = []
+        es = [(i, i) for i in self._stereo_edges(t0, t)]
         for i in range(t0, t):
             for j in range(i + 1, min(i + rad + 1, t)):
                 es += [(i, j), (j, i)]
@@ -701,7 +734,8 @@ class FactorGraph:
         F, ht, wd = v.disps.shape
         P = t1 - t0
         sens = None if motion_only else self._sensor_map()
-        key = (self._version, t0, t1, n_in, bool(motion_only), int(ii.shape[0]), int(R), sens.data_ptr() if sens is not None else 0)
+        rig = self._rig_baseline()
+        key = (self._version, t0, t1, n_in, bool(motion_only), int(ii.shape[0]), int(R), sens.data_ptr() if sens is not None else 0, rig)
         st = self.__dict__.get("_ba_state")
         if st is None or st["key"] != key:
             need = db.ba_workspace_bytes(int(ii.shape[0]), P, F, ht * wd)
@@ -713,6 +747,8 @@ class FactorGraph:
             db.ba_plan(ii, jj, F, ht * wd, -1 if motion_only else int(R), t0, t1, ws)
             if sens is not None:       # the plan resets the prior: set again behind every plan (a persistent video buffer: the address holds)
                 db.ba_depth_prior(ws, int(ii.shape[0]), P, F, ht * wd, sens, self.video.sensor_alpha)
+            if rig != 0.0:             # ... and so is the stereo baseline
+                db.ba_stereo(ws, int(ii.shape[0]), P, F, ht * wd, rig)
             st = self.__dict__["_ba_state"] = {"key": key, "ws": ws, "sys": sysb, "ii": ii, "jj": jj}
         return st
 
@@ -741,10 +777,11 @@ class FactorGraph:
         up_ptr = v.ensure_disps_up().data_ptr() if self.upsample else 0
         sens = self._sensor_map()
         sens_ptr = sens.data_ptr() if sens is not None else 0
+        rig = self._rig_baseline()
         vote = bool(segm_vote and v.segm_filter)
         S = (v.segments_bound() if hasattr(v, "segments_bound") else v.max_segments) if vote else 0
         key = (self._version, t0, t1, bool(use_inactive), bool(motion_only), E, float(eta_scale), float(lm), float(ep), sharded is not None,
-               vote, S, self.upsample, up_ptr, sens_ptr)
+               vote, S, self.upsample, up_ptr, sens_ptr, rig)
         st = self._cache.get("fused")
         if st is None or st["key"] != key:
             src = sorted(set(self._ii_h))
@@ -843,14 +880,16 @@ class FactorGraph:
         token = (net.data_ptr(), net._version, st.setdefault("serial", next(_CACHE_SERIAL)), weights.serial)
         a.context_ahead = 1
         a.context_ready = 1 if getattr(self, "_ctx_token", None) == token else 0
-        db.graph_update(weights, a, st["ws"])
+        # (stereo: the baseline goes to the in-update reprojection and the BA plan - pvo_graph_update_rig; any other video makes today's call)
+        db.graph_update(weights, a, st["ws"], **({"stereo_baseline": rig} if rig != 0.0 else {}))
         self._ctx_token = token
         if sharded is not None:
             # edge sharding: assembly + Schur on this rank's edges, ONE integer all-reduce of the reduced pose system per
             # Gauss-Newton step, identical solve on every rank (pvo_amd/parallel.py)
             sharded.ba(v.poses, v.disps, v.intrinsics[0], st["target_ba"], st["weight_ba"], st["eta"], st["ii_ba"], st["jj_ba"],
                        t0, t1, itrs=itrs, lm=lm, ep=ep, motion_only=motion_only, plan_key=(id(self), self._version, t0, t1),
-                       **({"disps_sens": sens, "alpha": v.sensor_alpha} if sens is not None else {}))
+                       **({"disps_sens": sens, "alpha": v.sensor_alpha} if sens is not None else {}),
+                       **({"stereo_baseline": rig} if rig != 0.0 else {}))
             v.disps.clamp_(min=0.001)
         self._age_lag += 1                 # (the device copy of `age` is brought up to date when it is next read)
         self._age_h = [x + 1 for x in self._age_h]

@@ -83,6 +83,8 @@ class MotionFilter:
         self._mag_host = self._mag_ready = None
         self.use_depth = False             # RGB-D (Droid sets it from args.rgbd): a frame's depth image goes to video.append with its keyframe;
         self._depth = None                 # off, the `depth` argument is ignored.  The captured frame graph reads nothing of it.
+        self.use_stereo = False            # stereo (Droid sets it from args.stereo): the RIGHT image of a frame that becomes a keyframe goes
+        self._right = None                 # through the fnet graph and its map to video.append; a non-keyframe's right image costs nothing
 
     def _upload(self, image):
         """host frame -> device, as it is (the reference's stream hands over int32, test_vo.py:41): NO tensor operation on the host
@@ -197,21 +199,28 @@ class MotionFilter:
             kw["channels_last"] = False
         if self._depth is not None:
             kw["depth"], self._depth = self._depth, None
+        if self._right is not None:
+            # stereo: the same fnet graph on the right image.  Its output is a static buffer - the one `gmap` may live in (first frame,
+            # track_vo) - so the left map is copied out before the graph runs again, and the right map before anyone else reuses it
+            right, self._right = self._right, None
+            gmap = gmap.clone()
+            kw["right_fmap"] = self._features_g(upload_frame(right, self.device)).clone()[0]
         self.video.append(tstamp, pose, disp, intrinsics / 8.0, gmap[0], net[0], inp[0], segm=segments, image=image, **kw)
 
     @torch.no_grad()
-    def track(self, tstamp, image, depth=None, intrinsics=None, segments=None):
-        """run on every incoming frame (motion_filter.py:46-87); image [3,H,W] BGR 0..255"""
-        self.begin(tstamp, image, depth, intrinsics, segments)
+    def track(self, tstamp, image, depth=None, intrinsics=None, segments=None, right=None):
+        """run on every incoming frame (motion_filter.py:46-87); image [3,H,W] BGR 0..255; right: the right view (use_stereo)"""
+        self.begin(tstamp, image, depth, intrinsics, segments, right=right)
         return self.finish()
 
     @torch.no_grad()
-    def begin(self, tstamp, image, depth=None, intrinsics=None, segments=None):
+    def begin(self, tstamp, image, depth=None, intrinsics=None, segments=None, right=None):
         """first half of track(): the frame goes up and its graph (encoder, 1-edge volume, lookup, one operator pass, mean flow norm) is
         LAUNCHED; the scalar is copied to a pinned host buffer behind an event.  Nothing here reads or writes the video."""
         ht, wd = image.shape[-2] // 8, image.shape[-1] // 8
         img = self._upload(image)
         self._depth = depth if self.use_depth else None
+        self._right = right if self.use_stereo else None         # (held on the host until the frame is known to be a keyframe)
         self._pending = (tstamp, image, img, intrinsics, segments, None, None)
         if self.video.counter == 0:
             return
@@ -272,6 +281,7 @@ class MotionFilter:
             self._append(tstamp, image, None, None, self._small_to_device(intrinsics), gmap, net, inp, segments)
             return True
         self.count += 1
+        self._right = None                                                     # (not a keyframe: its right view is never looked at)
         return False
 
     def _small_to_device(self, t):
@@ -288,11 +298,12 @@ class MotionFilter:
             self.video.remember_features(tstamp, gmap, image)
 
     @torch.no_grad()
-    def track_vo(self, tstamp, image, depth=None, intrinsics=None, segments=None):
+    def track_vo(self, tstamp, image, depth=None, intrinsics=None, segments=None, right=None):
         """every frame becomes a keyframe (motion_filter.py:89-109)"""
         ident = torch.as_tensor([0, 0, 0, 0, 0, 0, 1.0], device=self.device)
         img = self._upload(image)
         self._depth = depth if self.use_depth else None
+        self._right = right if self.use_stereo else None
         gmap = self._features_g(img)
         net, inp = self._context_g(img)
         first = self.video.counter == 0

@@ -113,7 +113,8 @@ class ShardedBA:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
 
     def ba(self, poses, disps, intrinsics, targets, weights, eta_local, ii_local, jj_local, t0, t1,
-           itrs=2, lm=1e-4, ep=0.1, motion_only=False, plan_key=None, structure=None, disps_sens=None, alpha=0.05):
+           itrs=2, lm=1e-4, ep=0.1, motion_only=False, plan_key=None, structure=None, disps_sens=None, alpha=0.05,
+           stereo_baseline=0.0):
         """poses/disps updated in place (disps: only the maps this rank owns change).
         targets/weights/ii/jj/eta_local describe THIS RANK's edges (see partition_by_source,
         local_eta_rows).  Returns dx [P,6] of the last step.
@@ -123,7 +124,8 @@ class ShardedBA:
         from them).  When given, only the envelope of the pose system is all-reduced (`envelope_index`) instead of the
         dense (6P)^2 matrix; the result is bit-identical.
         disps_sens [F,ht,wd] (every rank holds the whole map): the sensor-depth prior of a depth BA (`ba_depth_prior`).  It acts
-        on a frame only on the rank that holds the frame's out-edges, so the result stays bit-identical to the whole graph's."""
+        on a frame only on the rank that holds the frame's out-edges, so the result stays bit-identical to the whole graph's.
+        stereo_baseline > 0: an edge (i, i) is a stereo edge (`ba_stereo`); it lives on the rank that owns frame i, like any out-edge."""
         F, ht, wd = disps.shape
         P = t1 - t0
         E = ii_local.shape[0]
@@ -142,10 +144,14 @@ class ShardedBA:
             self._plan_key, self._plan_edges = key, (ii_local, jj_local)
             self._env_idx = None
             self._prior_key = None                      # (a fresh plan carries no prior)
+            self._rig_key = 0.0                         # (... and no stereo baseline)
         prior_key = None if disps_sens is None or motion_only else (disps_sens.data_ptr(), float(alpha))
         if prior_key != getattr(self, "_prior_key", None):
             self.db.ba_depth_prior(ws, E, P, F, ht * wd, disps_sens if prior_key is not None else None, alpha)
             self._prior_key = prior_key
+        if float(stereo_baseline) != getattr(self, "_rig_key", 0.0):
+            self.db.ba_stereo(ws, E, P, F, ht * wd, float(stereo_baseline))
+            self._rig_key = float(stereo_baseline)
         multi = self._world() > 1 or (self.collective_at_one and self.communicate and dist.is_available() and dist.is_initialized())
         native = hasattr(self.db, "ba_pack") and not self.torch_pack      # the HIP library packs / unpacks the message itself
         if getattr(self, "_env_native", native) != native:                # (torch_pack / db changed between two calls on one plan:
