@@ -79,7 +79,9 @@ const char* pvo_last_hip_error(void);
  * want_upsample / disps_up / up_frames at its END (every earlier offset unchanged; pvo_graph_update_args_size() tells the two layouts apart),
  * new entry points pvo_cvx_upsample / pvo_cvx_upsample_vjp_scratch_bytes / pvo_cvx_upsample_vjp; still 106, RGB-D and stereo: no
  * struct changed - new entry points pvo_ba_depth_prior / pvo_ba_prior / pvo_depth_sense and pvo_ba_stereo / pvo_ba_rig /
- * pvo_reproject_rig / pvo_reproject_motion_rig / pvo_graph_update_rig): a caller
+ * pvo_reproject_rig / pvo_reproject_motion_rig / pvo_graph_update_rig; still 106, map export: no existing struct changed - new struct
+ * pvo_map_points_args (pvo_map_points_args_size() reports its size) and new entry points pvo_map_points_args_size /
+ * pvo_map_points_workspace_bytes / pvo_map_points): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -604,6 +606,71 @@ int pvo_reproject_motion_rig(const float* poses, const float* disps, const float
  * for y < H/8, x < W/8 (integer division: any H, W; rows and columns beyond 8 * (H/8), 8 * (W/8) are not read).  The division is
  * fp32's correctly rounded one on the value converted to fp32.  H < 8 or W < 8 writes nothing. */
 int pvo_depth_sense(const void* depth, float* disps_sens_row, int H, int W, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Dense map export                                                           */
+/* ------------------------------------------------------------------------- */
+
+/* The filtered, coloured, labelled point cloud of N keyframes - what the reference's viewer loop computes for every keyframe whose
+ * pose or depth changed (droid_slam/visualization.py:92-107,127-129: depth_filter, iproj on the inverted poses, the mask
+ * count >= 2 & disp > 0.5 * mean(disp), and three boolean-index gathers), without its [N,HW] vote and [N,HW,3] point tensors and
+ * without a host round trip.  All pointers are device pointers, dense, row-major.
+ *
+ *   poses [nframes,7] world-to-camera; disps [nframes,ht,wd] fp32 inverse depth at ANY resolution (the 1/8 maps, or the
+ *   full-resolution ones with the intrinsics times 8); intrinsics [4] for that resolution; ix [N] int64: the frames to export;
+ *   thresh [N]: pvo_depth_filter's threshold per exported frame; min_votes (the reference: 2), mean_frac (the reference: 0.5).
+ *   images  uint8 [nframes,3,IH,IW] BGR planes or NULL: the colour of map pixel (y,x) is images[f][c][s*y+o][s*x+o] with
+ *           s = img_stride, o = img_offset ((8,3) is the reference's [3::8,3::8], (1,0) a full-resolution map), written as RGB.
+ *           s*(ht-1)+o >= IH or s*(wd-1)+o >= IW: PVO_EINVAL.
+ *   labels  int32 [nframes,LH,LW] or NULL: the label of map pixel (y,x) is labels[f][y/label_div][x/label_div].
+ *   reject  uint8 [nframes,LH,LW] or NULL, indexed like labels: a nonzero cell drops the pixel (dynamic objects, "thing" classes;
+ *           the caller computes the mask).  (ht-1)/label_div >= LH or (wd-1)/label_div >= LW: PVO_EINVAL.
+ *
+ * Keep rule.  Slot b, frame f = ix[b], pixel k = y*wd+x, d = disps[f][k] is kept if and only if
+ *   votes >= min_votes, votes being exactly what pvo_depth_filter writes for (ix[b], thresh[b]);
+ *   d > mean_frac * mean_f in fp32, mean_f = the frame's mean inverse depth, summed in fp64 in a fixed order, rounded to fp32 once;
+ *   d is finite and > 0 (an addition to the reference: no effect with a positive mean, and no division by 0 / NaN otherwise);
+ *   reject is NULL or zero at the pixel.
+ * A frame id outside [0, nframes) contributes no point and is never dereferenced.
+ *
+ * Outputs, compacted: exported frames in the order of ix, inside a frame pixels in raster order.
+ *   xyz   f32 [capacity,3]  R^T (Xc - t), Xc = ((x-cx)/fx, (y-cy)/fy, 1) / d, (t, q) the frame's pose: iproj on the inverted pose,
+ *                           the inverse formed in the kernel; each component within 12 * 2^-24 * (|t|_1 + |Xc|_1) of the exact value
+ *   rgba  uint8 [capacity,4] or NULL: the colour (0,0,0 without images), a = votes; 4-byte aligned
+ *   label int32 [capacity] or NULL (needs labels)
+ *   src   int32 [capacity,2] or NULL: (f, k); 8-byte aligned
+ *   frame_start int32 [N+1], ALWAYS written in full: frame_start[b] = index of slot b's first point, frame_start[N] = the number
+ *                           of points the call found, NOT clamped by capacity.
+ * A point whose index is >= capacity is written nowhere: the caller sees frame_start[N] > capacity and calls again with more room.
+ *
+ * Four launches (frame means; votes + keep bits + per-workgroup counts; one exclusive scan; emit) and no atomics: the same operands
+ * give the same bytes in the same order.  No allocation, no host synchronisation: capturable.  workspace: at least
+ * pvo_map_points_workspace_bytes(N, ht, wd) bytes (PVO_EWORKSPACE otherwise), 8-byte aligned, needed only while the kernels run.
+ * Limits: N <= 65535, N*ht*wd < 2^31 (PVO_EINVAL).  N == 0 or ht*wd == 0 writes frame_start (zeros) and returns PVO_OK. */
+typedef struct pvo_map_points_args {
+  const float* poses;
+  const float* disps;
+  const float* intrinsics;
+  const int64_t* ix;
+  const float* thresh;
+  int N, nframes, ht, wd;
+  int min_votes;
+  float mean_frac;
+  const uint8_t* images;
+  int IH, IW, img_stride, img_offset;
+  const int32_t* labels;
+  const uint8_t* reject;
+  int LH, LW, label_div;
+  int capacity;
+  float* xyz;
+  uint8_t* rgba;
+  int32_t* label;
+  int32_t* src;
+  int32_t* frame_start;
+} pvo_map_points_args;
+size_t pvo_map_points_args_size(void);
+size_t pvo_map_points_workspace_bytes(int N, int ht, int wd);
+int pvo_map_points(const pvo_map_points_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

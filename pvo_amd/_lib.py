@@ -99,6 +99,9 @@ SIGNATURES = {
                         _f, _f, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _f, _f, _vp]),
     "pvo_reproject_rig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "pvo_reproject_motion_rig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "pvo_map_points_args_size": (_sz, []),
+    "pvo_map_points_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pvo_map_points": (_i, [_vp, _vp, _sz, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -151,6 +154,15 @@ class GraphUpdateArgs(_c.Structure):
                 ("want_upsample", _i), ("disps_up", _vp), ("up_frames", _vp)]
 
 
+class MapPointsArgs(_c.Structure):
+    """pvo_map_points_args"""
+    _fields_ = [("poses", _vp), ("disps", _vp), ("intrinsics", _vp), ("ix", _vp), ("thresh", _vp),
+                ("N", _i), ("nframes", _i), ("ht", _i), ("wd", _i), ("min_votes", _i), ("mean_frac", _f),
+                ("images", _vp), ("IH", _i), ("IW", _i), ("img_stride", _i), ("img_offset", _i),
+                ("labels", _vp), ("reject", _vp), ("LH", _i), ("LW", _i), ("label_div", _i), ("capacity", _i),
+                ("xyz", _vp), ("rgba", _vp), ("label", _vp), ("src", _vp), ("frame_start", _vp)]
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 
@@ -183,6 +195,9 @@ def load():
         raise PvoHipError("libpvo_hip.so is ABI version %d with a %d-byte pvo_graph_update_args; this binding is written for version %d / %d bytes - "
                           "rebuild with `python -m pvo_amd.build`" % (lib.pvo_version(), lib.pvo_graph_update_args_size(), PVO_ABI_VERSION,
                                                                      ctypes.sizeof(GraphUpdateArgs)))
+    if lib.pvo_map_points_args_size() != ctypes.sizeof(MapPointsArgs):
+        raise PvoHipError("libpvo_hip.so has a %d-byte pvo_map_points_args; this binding is written for %d bytes - rebuild with "
+                          "`python -m pvo_amd.build`" % (lib.pvo_map_points_args_size(), ctypes.sizeof(MapPointsArgs)))
     _lib = lib
     return lib
 

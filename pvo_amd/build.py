@@ -22,6 +22,7 @@ HIP_SOURCES = [
     "corr_build.hip",
     "altcorr.hip",
     "geom.hip",
+    "map_points.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",
@@ -50,7 +51,8 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 # is compiled WITHOUT multiply-add contraction: its kernels then perform exactly the roundings the reference's text states, and
 # projmap / iproj / the depth filter's integer counts equal the kernel-text fixtures bit for bit (tests/test_kernel_text_goldens.py;
 # until round 5 the counts differed in ~0.5 % of the pixels, where |1/dj - 1/d| sat within a contraction's rounding of the threshold)
-EXTRA_FLAGS = {"geom.hip": ["-ffp-contract=off"]}
+# map_points.hip shares the depth filter's vote (csrc/depth_vote.h) and must get pvo_depth_filter's counts: the same flag
+EXTRA_FLAGS = {"geom.hip": ["-ffp-contract=off"], "map_points.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src):

@@ -12,14 +12,12 @@
 // frame_distance keeps one workgroup per pair but reduces with wave shuffles.
 #include "operand16.h"
 #include "se3.h"
+#include "depth_vote.h"
 
 namespace {
 
 constexpr float kMinDepthNative = 0.25f;  // droid_kernels.cu:26  MIN_DEPTH
 constexpr float kMinDepthPy = 0.2f;       // projective_ops.py:6  MIN_DEPTH
-
-struct Intr { float fx, fy, cx, cy; };
-__device__ __forceinline__ Intr load_intr(const float* p) { return {p[0], p[1], p[2], p[3]}; }
 
 // one direction of the frame distance for the pair (ix -> jx), computed by the 256 threads `tid` of one group; `red` is
 // that group's [3][4] reduction buffer.  Returns the distance in the group's thread 0 (droid_kernels.cu:497-636).
@@ -140,39 +138,8 @@ __global__ __launch_bounds__(256) void depth_filter_kernel(
   const int b = blockIdx.z;
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= HW) return;
-  const int ix = static_cast<int>(inds[b]);
-  const Intr K = load_intr(intrinsics);
-  const Pose Gi = load_pose(poses + 7 * static_cast<long long>(ix));
-  const float t = thresh[b];
-  const int i = k / wd, j = k - i * wd;
-  const float di = disps[static_cast<long long>(ix) * HW + k];
-  const float Xi[4] = {(static_cast<float>(j) - K.cx) / K.fx, (static_cast<float>(i) - K.cy) / K.fy, 1.0f, di};
-  // the reference votes with one atomicAdd per neighbour view (grid.y = 6); the six
-  // votes are summed in a register here and stored once.
-  float votes = 0.f;
-#pragma unroll
-  for (int neigh = 0; neigh < 6; ++neigh) {
-    const int jx = (neigh < 3) ? ix - neigh - 1 : ix + neigh;   // droid_kernels.cu:674
-    if (jx < 0 || jx >= nframes) continue;
-    const Pose G = rel_pose(Gi, load_pose(poses + 7 * static_cast<long long>(jx)));
-    float Xj[4];
-    act4(G, Xi, Xj);
-    const float uj = K.fx * (Xj[0] / Xj[2]) + K.cx;
-    const float vj = K.fy * (Xj[1] / Xj[2]) + K.cy;
-    const float dj = Xj[3] / Xj[2];
-    const int u0 = pvo_floor_to_int(uj), v0 = pvo_floor_to_int(vj);
-    if (u0 >= 0 && v0 >= 0 && u0 < wd - 1 && v0 < ht - 1) {
-      const float* dm = disps + static_cast<long long>(jx) * HW;
-      const float d00 = dm[v0 * wd + u0], d01 = dm[v0 * wd + u0 + 1];
-      const float d10 = dm[(v0 + 1) * wd + u0], d11 = dm[(v0 + 1) * wd + u0 + 1];
-      // droid_kernels.cu:748-751: double-precision reciprocal differences
-      const double idj = 1.0 / static_cast<double>(dj);
-      if (fabs(idj - 1.0 / static_cast<double>(d00)) < t) votes += 1.0f;
-      else if (fabs(idj - 1.0 / static_cast<double>(d01)) < t) votes += 1.0f;
-      else if (fabs(idj - 1.0 / static_cast<double>(d10)) < t) votes += 1.0f;
-      else if (fabs(idj - 1.0 / static_cast<double>(d11)) < t) votes += 1.0f;
-    }
-  }
+  // the vote itself: depth_vote.h, shared with the map export (map_points.hip)
+  const float votes = depth_votes(poses, disps, load_intr(intrinsics), static_cast<int>(inds[b]), thresh[b], nframes, ht, wd, k);
   counter[static_cast<long long>(b) * HW + k] = votes;
 }
 

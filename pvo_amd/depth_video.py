@@ -370,6 +370,34 @@ class DepthVideo:
             d = db.frame_distance(self.poses, self.disps, self.intrinsics[0], ii, jj, beta)
         return d.reshape(N, N) if return_matrix else d
 
+    def map_points(self, ix=None, thresh=0.005, full_res=False, dirty_only=False, reject=None):
+        """the dense map of keyframes ix (default: all stored ones) as db.map_points returns it - the reference's viewer loop
+        (visualization.py:76-134) without the viewer: points confirmed by two neighbouring keyframes within `thresh` (the viewer's
+        filter_thresh) and nearer than twice the frame's mean depth, with colours when the video stores images (`store_images`; RGB
+        zero otherwise) and the per-frame dense labels of `segms`.  full_res: from disps_up (tracking with args.upsample) with
+        8 * intrinsics, colours at every pixel and labels at (y // 8, x // 8); otherwise from the 1/8 maps with the colours of
+        [3::8, 3::8].  dirty_only: export where(dirty[:counter]) and clear those flags (the viewer's semantics).  reject: bool / uint8
+        [buffer, H/8, W/8] or [buffer, 1, H/8, W/8]; nonzero cells are left out (dynamic objects, "thing" classes)."""
+        n = self.counter
+        if dirty_only:
+            if ix is not None:
+                raise ValueError("dirty_only exports the dirty keyframes: no ix")
+            ix = torch.where(self.dirty[:n])[0]
+            self.dirty[ix] = False
+        elif ix is None:
+            ix = torch.arange(n, device=self.device)
+        ix = torch.as_tensor(ix, dtype=torch.long, device=self.device).reshape(-1).contiguous()
+        th = torch.full((ix.shape[0],), float(thresh), dtype=torch.float, device=self.device)
+        if full_res:
+            if self.disps_up is None:
+                raise RuntimeError("map_points(full_res=True) needs the full-resolution depths of tracking with args.upsample = True "
+                                   "(video.disps_up is not maintained)")
+            disps, intr, stride, offset, div = self.disps_up, 8.0 * self.intrinsics[0], 1, 0, 8
+        else:
+            disps, intr, stride, offset, div = self.disps, self.intrinsics[0], 8, 3, 1
+        return db.map_points(self.poses, disps, intr.contiguous(), ix, th, images=self.images, img_stride=stride, img_offset=offset,
+                             labels=self.segms, label_div=div, reject=reject)
+
     def ba(self, target, weight, eta, ii, jj, t0=1, t1=None, itrs=2, lm=1e-4, ep=0.1, motion_only=False,
            t1_hint=None):
         """dense bundle adjustment (depth_video.py:197-214); in place on poses / disps"""

@@ -24,13 +24,16 @@ def default_args(**over):
     a = dict(device="cuda:0", weights=None, buffer=1024, image_size=[240, 808], disable_vis=True, use_aff_bri=False,
              beta=0.6, filter_thresh=1.75, warmup=12, keyframe_thresh=2.25, frontend_thresh=12.0, frontend_window=25,
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
-             segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1)
+             segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1,
+             store_images=False)
     # rgbd: use the `depth` image of track() - each keyframe's sensor depth becomes a prior of the bundle adjustment, the trajectory
     # and the map are metric (DepthVideo, include/pvo_hip.h pvo_ba_depth_prior).  False (default): `depth` is IGNORED, nothing is
     # allocated for it and every result is what a monocular run computes.
     # stereo: use the `right` image of track() - each keyframe's right view gives the graph a stereo edge (i, i) with the fixed baseline
     # stereo_baseline (in the units the trajectory is wanted in: metres give a metric trajectory; 0.1 is upstream's constant).  False
     # (default): `right` is IGNORED, nothing is allocated for it and every result is what a monocular run computes.
+    # store_images: keep every keyframe's image on the device (DepthVideo.images, uint8 [buffer,3,H,W]) so that get_map() can colour
+    # its points.  False (default): nothing is allocated, no result changes, and get_map() returns points without colours.
     a.update(over)
     return Namespace(**a)
 
@@ -39,7 +42,8 @@ class Droid:
     def __init__(self, args):
         self.args = args
         self.load_weights(args.weights, args.use_aff_bri)
-        self.video = DepthVideo(args.image_size, args.buffer, args.device, args.segm_filter, args.thresh)
+        self.video = DepthVideo(args.image_size, args.buffer, args.device, args.segm_filter, args.thresh,
+                                store_images=bool(getattr(args, "store_images", False)))
         self.filterx = MotionFilter(self.net, self.video, thresh=args.filter_thresh, device=args.device)
         self.filterx.overlap_upload = bool(getattr(args, "pipelined", False))
         self.filterx.use_depth = bool(getattr(args, "rgbd", False))
@@ -133,6 +137,12 @@ class Droid:
             return self.video.disps_up[:self.video.counter]
         d = self.video.disps[:self.video.counter]
         return upsample_inter(d[None, ..., None]).squeeze(4).squeeze(0)
+
+    def get_map(self, **kw):
+        """the dense map of the keyframes: DepthVideo.map_points(ix=None, thresh=0.005, full_res=False, dirty_only=False, reject=None) -
+        a dict of xyz [n,3], rgba [n,4] (colours with args.store_images, else 0; a = votes), label [n], src [n,2], frame_start"""
+        self.flush()
+        return self.video.map_points(**kw)
 
     def get_flow(self):
         self.flush()

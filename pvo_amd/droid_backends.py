@@ -467,6 +467,83 @@ def depth_filter(poses, disps, intrinsics, ix, thresh):
     return counter
 
 
+def map_points(poses, disps, intrinsics, ix, thresh, images=None, img_stride=8, img_offset=3, labels=None, label_div=1, reject=None,
+               min_votes=2, mean_frac=0.5, capacity=None):
+    """The filtered point cloud of keyframes ix (include/pvo_hip.h pvo_map_points; the reference's viewer loop,
+    visualization.py:92-107,127-129): pixels confirmed by >= min_votes neighbouring keyframes (depth_filter's votes for thresh [N])
+    whose inverse depth exceeds mean_frac of their frame's mean, back-projected into the world, compacted in the order of ix and, inside
+    a frame, in raster order.  images uint8 [nframes,3,IH,IW] (BGR) give colours from [img_offset::img_stride] in both directions,
+    labels int32 [nframes,LH,LW] labels at (y // label_div, x // label_div), reject (bool / uint8, shaped like labels; labels' shape
+    if both are given) drops the pixels of its nonzero cells.
+
+    Returns a dict: xyz f32 [n,3], rgba uint8 [n,4] (a = votes; rgb 0 without images), src int32 [n,2] = (frame, pixel), label
+    int32 [n] (only with labels), frame_start int32 [N+1] (frame_start[N] = the number of points found).
+    capacity=None allocates the upper bound N*ht*wd, reads the total back ONCE - the call's one host synchronisation - and returns
+    the tensors sliced to it.  An explicit capacity returns the unsliced [capacity, ...] buffers and never synchronises: points
+    beyond it are dropped, which frame_start[N] > capacity tells."""
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ix, "ix"), (thresh, "thresh"), (images, "images"),
+                 (labels, "labels"), (reject, "reject")):
+        if t is not None:
+            _contig(t, n)
+    dev = _dev(poses, disps, intrinsics, ix, thresh, images, labels, reject)
+    _long(ix, "ix"); _f32(thresh, "thresh"); _f32(poses, "poses"); _f32(disps, "disps"); _f32(intrinsics, "intrinsics")
+    N, (nf, ht, wd) = ix.shape[0], disps.shape
+    if thresh.shape[0] != N:
+        raise PvoHipError("map_points: thresh must have one entry per exported frame")
+    a = _lib.MapPointsArgs()
+    if images is not None:
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < nf or images.shape[1] != 3:
+            raise PvoHipError("map_points: images must be uint8 [nframes,3,IH,IW]")
+        a.images, a.IH, a.IW, a.img_stride, a.img_offset = _ptr(images), images.shape[2], images.shape[3], int(img_stride), int(img_offset)
+    if labels is not None:
+        labels = labels.reshape(labels.shape[0], labels.shape[-2], labels.shape[-1])
+        if labels.dtype != torch.int32 or labels.shape[0] < nf:
+            raise PvoHipError("map_points: labels must be int32 [nframes,LH,LW]")
+    if reject is not None:
+        reject = reject.reshape(reject.shape[0], reject.shape[-2], reject.shape[-1])
+        if reject.dtype == torch.bool:
+            reject = reject.view(torch.uint8)
+        if reject.dtype != torch.uint8 or reject.shape[0] < nf or (labels is not None and reject.shape[1:] != labels.shape[1:]):
+            raise PvoHipError("map_points: reject must be bool / uint8 [nframes,LH,LW], the shape of labels")
+    grid = labels if labels is not None else reject
+    if grid is not None:
+        a.labels, a.reject, a.LH, a.LW, a.label_div = _ptr(labels), _ptr(reject), grid.shape[1], grid.shape[2], int(label_div)
+    cap = N * ht * wd if capacity is None else int(capacity)
+    xyz = torch.empty(cap, 3, dtype=torch.float32, device=dev)
+    rgba = torch.empty(cap, 4, dtype=torch.uint8, device=dev)
+    src = torch.empty(cap, 2, dtype=torch.int32, device=dev)
+    label = torch.empty(cap, dtype=torch.int32, device=dev) if labels is not None else None
+    frame_start = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    out = {"xyz": xyz, "rgba": rgba, "src": src, "frame_start": frame_start}
+    if label is not None:
+        out["label"] = label
+    map_points_into(a, poses, disps, intrinsics, ix, thresh, out, min_votes, mean_frac)
+    if capacity is None:
+        n = int(frame_start[N].item())                  # the one synchronisation
+        for k in ("xyz", "rgba", "src", "label"):
+            if k in out:
+                out[k] = out[k][:n]
+    return out
+
+
+def map_points_into(a, poses, disps, intrinsics, ix, thresh, out, min_votes=2, mean_frac=0.5):
+    """map_points' native call on caller-owned output buffers (out: xyz [capacity,3], frame_start [N+1], optional rgba / label / src;
+    the capacity is xyz's first dimension); `a`: a _lib.MapPointsArgs with the image / label / reject fields already set.  Buffers
+    keep whatever they held beyond the points written.  No allocation beyond the cached workspace, no synchronisation."""
+    dev = poses.device
+    N, (nf, ht, wd) = ix.shape[0], disps.shape
+    a.poses, a.disps, a.intrinsics, a.ix, a.thresh = _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ix), _ptr(thresh)
+    a.N, a.nframes, a.ht, a.wd, a.min_votes, a.mean_frac = N, nf, ht, wd, int(min_votes), float(mean_frac)
+    a.capacity = out["xyz"].shape[0]
+    a.xyz, a.rgba, a.label, a.src = _ptr(out["xyz"]), _ptr(out.get("rgba")), _ptr(out.get("label")), _ptr(out.get("src"))
+    a.frame_start = ctypes.c_void_p(out["frame_start"].data_ptr())
+    lib = _lib.load()
+    nbytes = lib.pvo_map_points_workspace_bytes(N, ht, wd)
+    ws = _workspace(dev, nbytes)
+    with torch.cuda.device(dev):
+        check(lib.pvo_map_points(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "map_points")
+
+
 def _baseline(baseline, what):
     """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
     b = float(baseline)

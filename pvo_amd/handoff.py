@@ -42,3 +42,54 @@ def write_kitti_trajectory(path, traj):
     with open(path, "w") as f:
         for m in T:
             f.write(" ".join("%.9e" % v for v in m[:3].reshape(-1)) + "\n")
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def write_ply(path, xyz, rgb=None, label=None):
+    """a point cloud as binary little-endian PLY: x y z float, then red green blue uchar (rgb [n,3] or [n,4], the first three columns;
+    omitted when None), then an int label (omitted when None).  numpy only; returns the number of points written."""
+    xyz = _host(xyz)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    props = ["property float x", "property float y", "property float z"]
+    if rgb is not None:
+        rgb = _host(rgb)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    if label is not None:
+        label = _host(label)
+        fields.append(("label", "<i4"))
+        props.append("property int label")
+    n = int(xyz.shape[0])
+    rec = np.zeros(n, dtype=np.dtype(fields))
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if rgb is not None:
+        rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    if label is not None:
+        rec["label"] = label
+    header = "\n".join(["ply", "format binary_little_endian 1.0", "element vertex %d" % n] + props + ["end_header"]) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+    return n
+
+
+def save_reconstruction(root, video):
+    """upstream DROID-SLAM's reconstruction folder (demo.py save_reconstruction): tstamps / disps / poses / intrinsics as .npy of
+    the stored keyframes, and images when the video keeps them.  disps are the full-resolution maps where the video maintains them
+    (tracking with args.upsample, as upstream saves disps_up), else the 1/8 maps; intrinsics are the stored ones, for the 1/8 maps.
+    Returns the paths written."""
+    n = video.counter
+    os.makedirs(root, exist_ok=True)
+    items = [("tstamps", video.tstamp[:n]), ("disps", (video.disps if video.disps_up is None else video.disps_up)[:n]),
+             ("poses", video.poses[:n]), ("intrinsics", video.intrinsics[:n])]
+    if video.images is not None:
+        items.append(("images", video.images[:n]))
+    paths = []
+    for name, t in items:
+        paths.append(os.path.join(root, name + ".npy"))
+        np.save(paths[-1], _host(t))
+    return paths

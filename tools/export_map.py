@@ -1,0 +1,61 @@
+"""Run the VO system over an image sequence like tools/test_vo.py (same arguments and data layout) and export the dense map.
+
+    python tools/export_map.py --datapath <.../SceneXX> --weights <checkpoint.pth> --map out.ply [--full_res] [--filter_thresh_map 0.005]
+                               [--reconstruction_path DIR]
+
+--map writes the filtered point cloud of all keyframes after the global bundle adjustment (Droid.get_map: points confirmed by two
+neighbouring keyframes, pvo_map_points) as a binary little-endian PLY: x y z float, red green blue uchar, int label (the per-frame
+dense panoptic label, with --segm_filter True).  --full_res tracks with the convex upsampling and exports every pixel of the
+full-resolution depth maps instead of the 1/8 lattice.  --reconstruction_path DIR also writes upstream DROID-SLAM's
+tstamps / disps / poses / intrinsics / images .npy files.
+"""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import test_vo  # noqa: E402  (tools/test_vo.py: the driver this one extends)
+
+
+def parse_args(argv=None):
+    import argparse
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--map", required=True, help="output .ply")
+    p.add_argument("--full_res", action="store_true")
+    p.add_argument("--filter_thresh_map", "--map_filter_thresh", type=float, default=0.005,
+                   help="the depth filter's threshold (the reference viewer's filter_thresh; test_vo.py's --filter_thresh is the motion filter's)")
+    p.add_argument("--reconstruction_path", default=None)
+    own, rest = p.parse_known_args(argv)
+    args = test_vo.parse_args(rest)
+    for k, v in vars(own).items():
+        setattr(args, k, v)
+    return args
+
+
+def main(argv=None):
+    from pvo_amd.droid import Droid
+    from pvo_amd.handoff import save_reconstruction, write_kitti_trajectory, write_ply
+    args = parse_args(argv)
+    args.half_update = True
+    args.store_images = True
+    args.upsample = bool(args.full_res)
+    if args.datapath.endswith("20"):
+        args.thresh = 0.9
+    droid = Droid(args)
+    for t, image, intr, segm in test_vo.image_stream(args.datapath, args.image_size, "val", args.segm_filter):
+        droid.track(t, image, intrinsics=intr, segments=segm)
+    print("video frames:", droid.video.counter)
+    traj = droid.terminate(test_vo.image_stream(args.datapath, args.image_size, "val", args.segm_filter), need_inv=True)
+    out_dir = os.path.join(args.out, os.path.basename(args.datapath.rstrip("/")), test_vo.SPLIT["val"])
+    write_kitti_trajectory(os.path.join(out_dir, "pvo_traj.txt"), traj)
+    m = droid.get_map(thresh=args.filter_thresh_map, full_res=args.full_res)
+    n = write_ply(args.map, m["xyz"], m["rgba"], m.get("label") if args.segm_filter else None)
+    print("map: %d points of %d keyframes written to %s" % (n, droid.video.counter, args.map))
+    if args.reconstruction_path:
+        for p in save_reconstruction(args.reconstruction_path, droid.video):
+            print("wrote", p)
+
+
+if __name__ == "__main__":
+    main()
