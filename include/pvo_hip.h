@@ -81,7 +81,8 @@ const char* pvo_last_hip_error(void);
  * struct changed - new entry points pvo_ba_depth_prior / pvo_ba_prior / pvo_depth_sense and pvo_ba_stereo / pvo_ba_rig /
  * pvo_reproject_rig / pvo_reproject_motion_rig / pvo_graph_update_rig; still 106, map export: no existing struct changed - new struct
  * pvo_map_points_args (pvo_map_points_args_size() reports its size) and new entry points pvo_map_points_args_size /
- * pvo_map_points_workspace_bytes / pvo_map_points): a caller
+ * pvo_map_points_workspace_bytes / pvo_map_points; still 106, uncertainty: no struct changed - new entry points pvo_ba_sigma /
+ * pvo_ba_uncertainty): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -839,6 +840,47 @@ int pvo_ba_finish(float* poses, float* disps, void* sys,
                   float lm, float ep, int motion_only, int clamp_frames, float disp_min,
                   float* dx_out, float* dz_out, int dz_rows, int* status_out,
                   void* workspace, size_t workspace_bytes, void* stream);
+/* Depth and pose uncertainty from the normal equations of ONE depth-BA Gauss-Newton step (no reference counterpart).  With the
+ * notation of that step - P = t1 - t0, kx = unique([t0, t1) U ii), C the summed depth blocks, add = eta (alpha on pixels the
+ * sensor-depth prior measures), Q = 1 / (C + add), the rows of depth frame k = its own pose row Ei[kx[k] - t0] and Eij[e] at pose
+ * jj[e] - t0 for every out-edge e, a row LIVE iff its pose p satisfies 0 <= p < P:
+ *   S_d      = (A - sum_k M_k Q_k M_k^T) + diag(ep + lm diag(A - ...))      the matrix the step factorises, damping included
+ *   pose_cov = S_d^-1                       [6P, 6P] fp64, row-major, symmetric BIT FOR BIT; tangent order that of dx
+ *   var_cond[kx[k], x] = Q                  the inverse depth's variance GIVEN the poses
+ *   var_pose[kx[k], x] = Q^2 max(m^T S_d^-1 m, 0)     what pose uncertainty adds; m in R^6P = the pixel's live rows at their poses
+ * var_cond + var_pose is the marginal variance: the diagonal of the inverse of the full information matrix
+ * [[A + D, B], [B^T, diag(C + add)]].  The two parts are separate outputs because var_pose is typically 0.1 - 10 % of var_cond.
+ *   - Window pose 0 TAKES PART: the back-substitution skips it (EvT6x1's quirk), the Schur complement does not, and this is the
+ *     covariance of the Schur system.
+ *   - These are the variances of the DAMPED model with the network's confidences as weights: relative, not calibrated - good for
+ *     ranking, thresholds and fusion weights up to one global factor.
+ *   - var_cond / var_pose: [nframes, ht, wd] fp32, either may be NULL; only the rows kx[k] are written, other frames are untouched.
+ *   - A frame whose rows are all fixed poses (a source frame in front of the window whose targets are all < t0) gets var_pose 0.0f.
+ *   - Factorisation failure (S_d not positive definite, or the step's own failure flags): status_out[0] = 1, var_cond is still
+ *     written, var_pose = +inf on the rows of kx, pose_cov = +inf on the diagonal and 0 elsewhere.  status_out (int[4], may be
+ *     NULL) = [failed, K, eta-row mismatch, row-table overflow].  The last is pvo_ba_local's own limit - a depth frame with more than
+ *     169 out-edges to FREE poses - and counts as a failure here: the eliminated system is incomplete.
+ *   - Nothing of poses, disps, sys or the plan is modified (sys is NOT zeroed: pvo_ba_finish may still follow).  The workspace's
+ *     factorisation scratch is overwritten.  No allocation, no host synchronisation, capturable, no atomics; same operands, same bytes.
+ *   - Limits: P <= 64 (PVO_EUNSUPPORTED beyond: the frontend's window; the backend's global graph is out of scope), P == 0 is a
+ *     depth-only window (var_pose = 0, pose_cov untouched and may be NULL); E >= 1 (PVO_EINVAL: without an edge nothing is
+ *     assembled); fp32 only.  The quadratic form is accumulated in fp64 (Ei ~ -sum Eij: it cancels heavily).
+ * pvo_ba_sigma runs on a PLANNED workspace after a pvo_ba_local with motion_only = 0 on the same operands; `sys` is the buffer that
+ *   call filled, E / P / nframes / ht / wd / t0 the workspace's own, lm / ep the damping the step's solve would apply.
+ * pvo_ba_uncertainty is the one-call form: plan + sensor-depth prior + stereo baseline + pvo_ba_local + pvo_ba_sigma on the
+ *   workspace's own system buffer; pvo_ba_rig's operands with the three outputs in place of iterations / dx_out / dz_out. */
+int pvo_ba_sigma(const void* sys, void* workspace, size_t workspace_bytes,
+                 const int64_t* ii, const int64_t* jj,
+                 int E, int P, int nframes, int ht, int wd, int t0, float lm, float ep,
+                 double* pose_cov, float* var_cond, float* var_pose, int* status_out, void* stream);
+int pvo_ba_uncertainty(const float* poses, const float* disps, const float* intrinsics,
+                       const float* targets, const float* weights, const float* eta,
+                       const int64_t* ii, const int64_t* jj,
+                       int E, int nframes, int ht, int wd, int K_eta,
+                       int t0, int t1, float lm, float ep,
+                       double* pose_cov, float* var_cond, float* var_pose, int* status_out,
+                       void* workspace, size_t workspace_bytes,
+                       const float* disps_sens, float alpha, float baseline, void* stream);
 /* The message of an edge-sharded step, packed by the library (round 4): first_s (device, int[P]) is the
  * STRUCTURAL envelope of the pose system - first_s[b] = lowest free pose block row b can couple with, derived from the whole
  * graph's edge list, the same table on every rank (pvo_amd/parallel.py: envelope_structure).

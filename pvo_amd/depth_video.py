@@ -20,6 +20,12 @@ transform of a rectified rig, u_right = u - fx b d - in `reproject`, `reproject_
 (include/pvo_hip.h, pvo_ba_stereo); the factor graph correlates it against the right map.  Every keyframe of a stereo video is expected
 to bring its right view (one that does not gets a zero map).  A video that never saw a right view allocates nothing and computes
 exactly what it computed before, (i, i) edges included.
+
+Uncertainty: `uncertainty(...)`, beside `ba(...)` and on its operands, writes every optimised keyframe's inverse-depth variances -
+`disps_var_cond` (given the poses) and `disps_var_pose` (what pose uncertainty adds) - and the diagonal 6 x 6 blocks of the window's
+pose covariance `poses_cov` (include/pvo_hip.h, pvo_ba_uncertainty).  The three buffers are allocated on first use
+(`ensure_uncertainty`, +inf = never estimated) and travel with their keyframe; a video that never asks allocates nothing.
+`map_points(max_rel_sigma=...)` filters the map by them and returns each point's sigma.
 """
 import torch
 
@@ -44,6 +50,9 @@ class DepthVideo:
         self.disps_sens = None             # RGB-D: measured inverse depth per keyframe [buffer,H/8,W/8], 0 = none (ensure_disps_sens)
         self.has_sensor_depth = False      # host-side: some keyframe brought a depth image
         self.sensor_alpha = 0.05           # weight of the sensor-depth prior (upstream's alpha)
+        # uncertainty (ensure_uncertainty): inverse-depth variance given the poses / added by the poses [buffer,H/8,W/8], +inf = never
+        # estimated, and the diagonal blocks of the window's pose covariance [buffer,6,6] fp64
+        self.disps_var_cond = self.disps_var_pose = self.poses_cov = None
         self.intrinsics = torch.zeros(buffer, 4, dtype=torch.float, **kw)
         self.fmaps = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw)      # channels-last
         self.fmaps_right = None            # stereo: the right views' feature maps [buffer,H/8,W/8,128] channels-last (ensure_fmaps_right)
@@ -181,6 +190,23 @@ class DepthVideo:
             self.disps_sens = torch.zeros_like(self.disps)
         return self.disps_sens
 
+    def ensure_uncertainty(self):
+        """the variance maps [buffer, H/8, W/8] (+inf: never estimated) and the pose covariance blocks [buffer, 6, 6] fp64 (+inf on
+        the diagonals), allocated on first use -> (disps_var_cond, disps_var_pose, poses_cov)"""
+        if self.disps_var_cond is None:
+            self.disps_var_cond = torch.full_like(self.disps, float("inf"))
+            self.disps_var_pose = torch.full_like(self.disps, float("inf"))
+            self.poses_cov = torch.zeros(self.disps.shape[0], 6, 6, dtype=torch.float64, device=self.device)
+            self.poses_cov.diagonal(dim1=1, dim2=2).fill_(float("inf"))
+        return self.disps_var_cond, self.disps_var_pose, self.poses_cov
+
+    def reset_uncertainty(self, index):
+        """keyframe(s) `index` got a new depth map: what was estimated for the old one no longer holds"""
+        if self.disps_var_cond is not None:
+            self.disps_var_cond[index] = float("inf")
+            self.disps_var_pose[index] = float("inf")
+            self.poses_cov[index] = torch.diag(torch.full((6,), float("inf"), dtype=torch.float64, device=self.device))
+
     @staticmethod
     def sense_depth_host(depth):
         """a host depth image [H,W] -> its inverse depth on the 1/8 lattice [H/8,W/8] fp32: 1 / depth[3::8, 3::8] where that is
@@ -224,6 +250,7 @@ class DepthVideo:
             self.fmaps_right[k].zero_()        # (a stale row, as rm_keyframe leaves one)
         if depth is not None or self.disps_sens is not None:
             self.set_depth(k, depth)
+        self.reset_uncertainty(slice(k, k + 1))
         # (a Python number goes in with fill_ on a slice - a kernel argument.  `buf[k] = number` builds a host tensor and copies it with a
         # BLOCKING transfer queued behind everything on the stream: measured 1.3 ms per keyframe in the pipelined tracker)
         if isinstance(tstamp, torch.Tensor):
@@ -263,6 +290,8 @@ class DepthVideo:
         for buf, val in ((self.poses, item[2]), (self.disps, item[3]), (self.intrinsics, item[4])):
             if val is not None:
                 buf[index] = val
+        if item[3] is not None:
+            self.reset_uncertainty(slice(index, index + 1) if isinstance(index, int) else index)
         if len(item) > 5 and item[5] is not None:
             self.fmaps[index] = self._fmap_cl(item[5], None)
         if len(item) > 6:
@@ -370,14 +399,34 @@ class DepthVideo:
             d = db.frame_distance(self.poses, self.disps, self.intrinsics[0], ii, jj, beta)
         return d.reshape(N, N) if return_matrix else d
 
-    def map_points(self, ix=None, thresh=0.005, full_res=False, dirty_only=False, reject=None):
+    def sigma_disp(self):
+        """sqrt(var_cond + var_pose) [buffer, H/8, W/8]: the standard deviation of the inverse depths (+inf where never estimated)"""
+        if self.disps_var_cond is None:
+            raise RuntimeError("no uncertainty has been estimated on this video (DepthVideo.uncertainty / args.uncertainty = True)")
+        return torch.sqrt(self.disps_var_cond + self.disps_var_pose)
+
+    @staticmethod
+    def rel_sigma_reject(sigma, disps, max_rel_sigma, reject=None):
+        """the map export's reject mask [.., H/8, W/8] (bool) of a bound on the RELATIVE standard deviation: sigma / disp >
+        max_rel_sigma (relative depth error = relative inverse-depth error to first order; a never-estimated +inf cell is rejected),
+        OR a caller's own mask ([buffer, H/8, W/8] or [buffer, 1, H/8, W/8], nonzero = reject)"""
+        m = ~(sigma <= float(max_rel_sigma) * disps)              # (NaN and +inf reject)
+        if reject is not None:
+            r = reject if reject.dim() == m.dim() else reject.reshape(m.shape)
+            m = m | (r != 0)
+        return m
+
+    def map_points(self, ix=None, thresh=0.005, full_res=False, dirty_only=False, reject=None, max_rel_sigma=None):
         """the dense map of keyframes ix (default: all stored ones) as db.map_points returns it - the reference's viewer loop
         (visualization.py:76-134) without the viewer: points confirmed by two neighbouring keyframes within `thresh` (the viewer's
         filter_thresh) and nearer than twice the frame's mean depth, with colours when the video stores images (`store_images`; RGB
         zero otherwise) and the per-frame dense labels of `segms`.  full_res: from disps_up (tracking with args.upsample) with
         8 * intrinsics, colours at every pixel and labels at (y // 8, x // 8); otherwise from the 1/8 maps with the colours of
         [3::8, 3::8].  dirty_only: export where(dirty[:counter]) and clear those flags (the viewer's semantics).  reject: bool / uint8
-        [buffer, H/8, W/8] or [buffer, 1, H/8, W/8]; nonzero cells are left out (dynamic objects, "thing" classes)."""
+        [buffer, H/8, W/8] or [buffer, 1, H/8, W/8]; nonzero cells are left out (dynamic objects, "thing" classes).
+        max_rel_sigma (needs the variances of `uncertainty`): cells whose relative standard deviation sigma / disp exceeds it are
+        left out as well - at 1/8 resolution, for full_res through the same (y // 8, x // 8) rule as the labels - and the result gains
+        `sigma` [n], each point's standard deviation of the inverse depth (of its 1/8 cell)."""
         n = self.counter
         if dirty_only:
             if ix is not None:
@@ -395,8 +444,24 @@ class DepthVideo:
             disps, intr, stride, offset, div = self.disps_up, 8.0 * self.intrinsics[0], 1, 0, 8
         else:
             disps, intr, stride, offset, div = self.disps, self.intrinsics[0], 8, 3, 1
-        return db.map_points(self.poses, disps, intr.contiguous(), ix, th, images=self.images, img_stride=stride, img_offset=offset,
-                             labels=self.segms, label_div=div, reject=reject)
+        sigma = None
+        if max_rel_sigma is not None:
+            sigma = self.sigma_disp()
+            reject = self.rel_sigma_reject(sigma, self.disps, max_rel_sigma, reject).to(torch.uint8)
+        out = db.map_points(self.poses, disps, intr.contiguous(), ix, th, images=self.images, img_stride=stride, img_offset=offset,
+                            labels=self.segms, label_div=div, reject=reject)
+        if sigma is not None:
+            out["sigma"] = self.gather_sigma(sigma, out["src"], self.wd // 8, div)
+        return out
+
+    @staticmethod
+    def gather_sigma(sigma, src, w8, div):
+        """per map point the sigma of its 1/8 cell: src [n,2] = (keyframe, pixel index in the map the points were taken from -
+        the 1/8 map, or for div = 8 the full-resolution one)"""
+        frame, pix = src[:, 0].long(), src[:, 1].long()
+        wd = w8 * div
+        y, x = torch.div(pix, wd, rounding_mode="floor") // div, (pix % wd) // div
+        return sigma[frame, y, x]
 
     def ba(self, target, weight, eta, ii, jj, t0=1, t1=None, itrs=2, lm=1e-4, ep=0.1, motion_only=False,
            t1_hint=None):
@@ -412,3 +477,19 @@ class DepthVideo:
         db.ba(self.poses, self.disps, self.intrinsics[0], target, weight, eta, ii, jj, t0, t1, itrs, lm, ep,
               motion_only, **kw)
         self.disps.clamp_(min=0.001)
+
+    def uncertainty(self, target, weight, eta, ii, jj, t0=1, t1=None, lm=1e-4, ep=0.1):
+        """depth and pose uncertainty of the depth-BA step `ba(target, weight, eta, ii, jj, t0, t1, lm=lm, ep=ep)` would take from the
+        present state, read only (pvo_ba_uncertainty): writes disps_var_cond / disps_var_pose on the optimised keyframes'
+        rows and the diagonal blocks of the pose covariance into poses_cov[t0:t1]; returns the whole covariance [P,6,P,6] fp64.
+        Honours the sensor-depth prior and the rig's baseline exactly as `ba` does."""
+        if t1 is None:
+            t1 = int(max(ii.max().item(), jj.max().item())) + 1
+        vc, vp, pc = self.ensure_uncertainty()
+        kw = {"disps_sens": self.disps_sens, "alpha": self.sensor_alpha} if self.has_sensor_depth else {}
+        kw.update(self._rig_kw("stereo_baseline"))
+        cov = db.ba_uncertainty(self.poses, self.disps, self.intrinsics[0], target, weight, eta, ii, jj, t0, t1, lm, ep,
+                                var_cond=vc, var_pose=vp, **kw)
+        if t1 > t0:
+            pc[t0:t1] = torch.diagonal(cov, dim1=0, dim2=2).permute(2, 0, 1)
+        return cov

@@ -25,7 +25,11 @@ def default_args(**over):
              beta=0.6, filter_thresh=1.75, warmup=12, keyframe_thresh=2.25, frontend_thresh=12.0, frontend_window=25,
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
              segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1,
-             store_images=False)
+             store_images=False, uncertainty=False)
+    # uncertainty: after every keyframe's last frontend update, estimate the window's inverse-depth variances and pose covariance from
+    # the bundle adjustment's normal equations (DepthVideo.uncertainty; get_uncertainty(), get_map(max_rel_sigma=...)).  Read only: the
+    # trajectory and the depths are bit for bit those of a run without it.  A window of more than 64 poses (frontend_window above 64) is
+    # not estimated: its keyframes keep +inf.  False (default): nothing is allocated, no launch is added.
     # rgbd: use the `depth` image of track() - each keyframe's sensor depth becomes a prior of the bundle adjustment, the trajectory
     # and the map are metric (DepthVideo, include/pvo_hip.h pvo_ba_depth_prior).  False (default): `depth` is IGNORED, nothing is
     # allocated for it and every result is what a monocular run computes.
@@ -52,7 +56,8 @@ class Droid:
         self.frontend = DroidFrontend(self.net.update, self.video, args.device, warmup=args.warmup, beta=args.beta,
                                       frontend_nms=args.frontend_nms, keyframe_thresh=args.keyframe_thresh,
                                       frontend_window=args.frontend_window, frontend_thresh=args.frontend_thresh,
-                                      frontend_radius=args.frontend_radius, upsample=bool(getattr(args, "upsample", False)))
+                                      frontend_radius=args.frontend_radius, upsample=bool(getattr(args, "upsample", False)),
+                                      uncertainty=bool(getattr(args, "uncertainty", False)))
         self.filterx.before_context = self.frontend.keyframe_ahead
         self.backend = DroidBackend(self.net, self.video, args)
         self.traj_filler = PoseTrajectoryFiller(self.net, self.video, args.device)
@@ -138,9 +143,19 @@ class Droid:
         d = self.video.disps[:self.video.counter]
         return upsample_inter(d[None, ..., None]).squeeze(4).squeeze(0)
 
+    def get_uncertainty(self):
+        """(sigma_disp = sqrt(var_cond + var_pose), var_cond, var_pose [counter, H/8, W/8], poses_cov [counter, 6, 6] fp64) of the
+        keyframes, from tracking with args.uncertainty = True; +inf where a keyframe was never estimated"""
+        self.flush()
+        v, n = self.video, self.video.counter
+        if not getattr(self.args, "uncertainty", False) or v.disps_var_cond is None:
+            raise RuntimeError("get_uncertainty() needs tracking with args.uncertainty = True (the variances are not maintained)")
+        return v.sigma_disp()[:n], v.disps_var_cond[:n], v.disps_var_pose[:n], v.poses_cov[:n]
+
     def get_map(self, **kw):
-        """the dense map of the keyframes: DepthVideo.map_points(ix=None, thresh=0.005, full_res=False, dirty_only=False, reject=None) -
-        a dict of xyz [n,3], rgba [n,4] (colours with args.store_images, else 0; a = votes), label [n], src [n,2], frame_start"""
+        """the dense map of the keyframes: DepthVideo.map_points(ix=None, thresh=0.005, full_res=False, dirty_only=False, reject=None,
+        max_rel_sigma=None) - a dict of xyz [n,3], rgba [n,4] (colours with args.store_images, else 0; a = votes), label [n], src [n,2],
+        frame_start, and with max_rel_sigma (args.uncertainty) sigma [n]"""
         self.flush()
         return self.video.map_points(**kw)
 

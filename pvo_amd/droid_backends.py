@@ -714,6 +714,82 @@ def ba_stereo(workspace, E, P, nframes, HW, baseline):
                                         _baseline(baseline, "ba_stereo"), _stream(dev)), "ba_stereo")
 
 
+BA_SIGMA_MAX_POSES = 64      # pvo_ba_sigma / pvo_ba_uncertainty: the frontend's window (include/pvo_hip.h)
+
+
+def _sigma_outputs(P, disps, var_cond, var_pose, status, what):
+    """pose_cov [6P,6P] fp64 (fresh) and the two caller-provided variance maps checked: fp32, contiguous, disps' shape"""
+    if P > BA_SIGMA_MAX_POSES:
+        raise PvoHipError("%s: at most %d window poses (got %d)" % (what, BA_SIGMA_MAX_POSES, P))
+    for t, n in ((var_cond, "var_cond"), (var_pose, "var_pose")):
+        if t is None:
+            continue
+        _f32(t, n)
+        _contig(t, n)
+        if tuple(t.shape) != tuple(disps.shape) or t.device != disps.device:
+            raise PvoHipError("%s: %s must have disps' shape %s and device" % (what, n, tuple(disps.shape)))
+    if status is not None and (status.dtype != torch.int32 or status.numel() < 4):
+        raise PvoHipError("%s: status must be int32 with 4 elements" % what)
+    return torch.zeros(6 * P, 6 * P, dtype=torch.float64, device=disps.device)
+
+
+def ba_sigma(sys, workspace, ii, jj, disps, t0, t1, lm, ep, var_cond=None, var_pose=None, status=None):
+    """depth and pose uncertainty of the step `ba_local(..., motion_only=False, sys, workspace)` has just assembled on a planned
+    workspace (pvo_ba_sigma, include/pvo_hip.h).  disps [F,ht,wd] gives the shapes only.  var_cond / var_pose [F,ht,wd] fp32
+    (optional) are written IN PLACE on the rows unique([t0,t1) U ii); returns pose_cov as a [P,6,P,6] fp64 view of the symmetric
+    [6P,6P] inverse of the damped pose system.  Nothing of sys or the plan is modified.  No host synchronisation."""
+    for t, n in ((ii, "ii"), (jj, "jj"), (sys, "sys")):
+        _contig(t, n)
+    _long(ii, "ii"); _long(jj, "jj")
+    dev = _dev(sys, workspace, ii, jj, disps, var_cond, var_pose, status)
+    F, ht, wd = disps.shape
+    t0, t1 = int(t0), int(t1)
+    P = t1 - t0
+    if P < 0 or t0 < 0 or t1 > F:
+        raise PvoHipError("ba_sigma: pose window [%d,%d) exceeds the %d depth maps" % (t0, t1, F))
+    if sys.dtype != torch.int64 or sys.numel() < (6 * P) ** 2 + 6 * P:
+        raise PvoHipError("ba_sigma: sys must be int64 with (6P)^2 + 6P elements")
+    cov = _sigma_outputs(P, disps, var_cond, var_pose, status, "ba_sigma")
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_ba_sigma(_ptr(sys), ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _ptr(ii), _ptr(jj),
+                                       ii.shape[0], P, F, ht, wd, t0, float(lm), float(ep), _ptr(cov), _vp(var_cond), _vp(var_pose),
+                                       _vp(status), _stream(dev)), "ba_sigma")
+    return cov.view(P, 6, P, 6)
+
+
+def ba_uncertainty(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, lm, ep, var_cond=None, var_pose=None,
+                   status=None, disps_sens=None, alpha=0.05, stereo_baseline=0.0):
+    """the one-call form (pvo_ba_uncertainty): `ba`'s operands of ONE depth-BA step, read only.  var_cond / var_pose [F,ht,wd]
+    fp32 (optional) are written IN PLACE on the rows unique([t0,t1) U ii); returns pose_cov [P,6,P,6] fp64.  disps_sens / alpha /
+    stereo_baseline as in `ba`.  status (optional int32[4]) receives [failed, K, eta-row mismatch, row-table overflow of the elimination].  No host synchronisation."""
+    stereo_baseline = _baseline(stereo_baseline, "ba_uncertainty")
+    if disps_sens is not None:
+        _sens_map(disps_sens, disps, "ba_uncertainty")
+    for t, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
+                 (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
+        _contig(t, n)
+    dev = _dev(poses, disps, intrinsics, targets, weights, eta, ii, jj, var_cond, var_pose, status)
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (targets, "targets"), (weights, "weights"), (eta, "eta")):
+        _f32(t, n)
+    _long(ii, "ii"); _long(jj, "jj")
+    F, ht, wd = disps.shape
+    HW, E = ht * wd, ii.shape[0]
+    t0, t1 = int(t0), int(t1)
+    P = t1 - t0
+    if P < 0 or t0 < 0 or poses.shape[0] < t1 or F < t1:
+        raise PvoHipError("ba_uncertainty: pose window [%d,%d) exceeds the buffers (%d poses, %d depth maps)" % (t0, t1, poses.shape[0], F))
+    eta = eta.contiguous().view(-1, HW)
+    cov = _sigma_outputs(P, disps, var_cond, var_pose, status, "ba_uncertainty")
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_ba_workspace_bytes(E, P, F, HW))
+    with torch.cuda.device(dev):
+        check(lib.pvo_ba_uncertainty(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(targets), _ptr(weights), _ptr(eta), _ptr(ii), _ptr(jj),
+                                     E, F, ht, wd, eta.shape[0], t0, t1, float(lm), float(ep), _ptr(cov), _vp(var_cond), _vp(var_pose),
+                                     _vp(status), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _vp(disps_sens), float(alpha),
+                                     stereo_baseline, _stream(dev)), "ba_uncertainty")
+    return cov.view(P, 6, P, 6)
+
+
 def depth_sense(depth, out_row):
     """RGB-D ingest (pvo_depth_sense): out_row [H/8,W/8] fp32 = 1 / depth[3::8, 3::8] where that is finite and > 0, else 0.
     depth [H,W] fp32 / fp16 on the device; one launch."""

@@ -454,9 +454,11 @@ class FactorGraph:
         up = getattr(v, "disps_up", None)                               # (kept in step with disps where it is maintained)
         sens = getattr(v, "disps_sens", None)                           # (RGB-D: the sensor map moves with its frame)
         right = getattr(v, "fmaps_right", None)                         # (stereo: and so does the right view's feature map)
+        # (uncertainty: the variances and the pose covariance block of a keyframe are its own)
+        unc = tuple(b for b in (getattr(v, n, None) for n in ("disps_var_cond", "disps_var_pose", "poses_cov")) if b is not None)
         for buf in (v.poses, v.disps, v.intrinsics, v.nets, v.inps, v.fmaps) + ((v.segms,) if v.segm_filter else ()) + \
                 ((up,) if self.upsample and up is not None else ()) + ((sens,) if sens is not None else ()) + \
-                ((right,) if right is not None else ()):
+                ((right,) if right is not None else ()) + unc:
             buf[ix] = buf[ix + 1].clone()
         m = [(i == ix) or (j == ix) for i, j in zip(self._ii_h, self._jj_h)]
         for t in (self.ii_inac, self.jj_inac):                       # (masked in-place updates would synchronise)
@@ -936,9 +938,45 @@ class FactorGraph:
         self._age_dev, self._age_lag = t, 0
 
     @torch.no_grad()
+    def uncertainty(self, t0=None, t1=None, use_inactive=False, sharded=None):
+        """depth and pose uncertainty of the window from the operands the last `update`'s bundle adjustment read - on the native and on
+        the composed path the same `target_cam`, `weight`, eta = 0.2 damping + EP (one row per depth frame the BA optimises), t0 / t1
+        rule and lm = 1e-4, ep = 0.1 - at the present poses and depths: DepthVideo.uncertainty (read only; returns the pose
+        covariance [P,6,P,6] fp64 and fills the video's variance maps).  A window of more than 64 poses (the stage's limit, the frontend's
+        window is a user argument) is NOT estimated: returns None and the variances keep what they hold (+inf: never estimated).
+        sharded: an edge-sharded bundle adjustment (pvo_amd/parallel.py) has no such stage - NotImplementedError."""
+        if sharded is not None:
+            sharded.uncertainty()
+        self._corr_sync()
+        ht, wd = self.ht, self.wd
+        if t0 is None:
+            t0 = max(1, min(self._ii_h) + 1)
+        if t1 is None:
+            t1 = max(max(self._ii_h), max(self._jj_h)) + 1
+        from . import droid_backends as db
+        if t1 - t0 > db.BA_SIGMA_MAX_POSES:
+            return None
+        m_l = [(i >= t0 - 3) and (j >= t0 - 3) for i, j in zip(self._ii_inac_h, self._jj_inac_h)] if use_inactive else []
+        if any(m_l):
+            m = self._cached(("inac_ix", t0), lambda: torch.tensor([k for k, f in enumerate(m_l) if f], dtype=torch.long, device=self.device))
+            ii, jj = torch.cat([self.ii_inac[m], self.ii]), torch.cat([self.jj_inac[m], self.jj])
+            target_cam = torch.cat([self.target_cam_inac[:, m], self.target_cam], 1)
+            weight = torch.cat([self.weight_inac[:, m], self.weight], 1)
+        else:
+            ii, jj, target_cam, weight = self.ii, self.jj, self.target_cam, self.weight
+        # one eta row per depth map the BA optimises, in the order of unique([t0, t1) U ii) - as the native update lays them out
+        rows = sorted(set(self._ii_h) | {i for i, k in zip(self._ii_inac_h, m_l) if k} | set(range(t0, t1)))
+        rows_t = self._cached(("unc_rows", t0, t1, bool(use_inactive)), lambda: torch.tensor(rows, device=self.device))
+        eta = 0.2 * self.damping[rows_t] + getattr(self, "_last_EP", 1e-7)
+        target_cam = target_cam.reshape(-1, ht, wd, 2).permute(0, 3, 1, 2).float().contiguous()
+        weight = weight.reshape(-1, ht, wd, 2).permute(0, 3, 1, 2).float().contiguous()
+        return self.video.uncertainty(target_cam, weight, eta, ii.contiguous(), jj.contiguous(), t0, t1, lm=1e-4, ep=0.1)
+
+    @torch.no_grad()
     def update(self, t0=None, t1=None, itrs=2, use_inactive=False, EP=1e-7, motion_only=False):
         """one update of the factor graph (factor_graph.py:227-307)"""
         self._corr_sync()
+        self._last_EP = float(EP)                                      # (uncertainty() reads the operands of the last update's BA)
         if self._fused_ok() and self.P_zr is not None:
             return self._update_fused(t0, t1, itrs, use_inactive, EP, motion_only)
         ht, wd = self.ht, self.wd

@@ -14,7 +14,7 @@ from .factor_graph import FactorGraph
 
 class DroidFrontend:
     def __init__(self, update_op, video, device="cuda:0", warmup=8, beta=0.3, frontend_nms=1, keyframe_thresh=4.0,
-                 frontend_window=25, frontend_thresh=16.0, frontend_radius=2, max_factors=48, upsample=False):
+                 frontend_window=25, frontend_thresh=16.0, frontend_radius=2, max_factors=48, upsample=False, uncertainty=False):
         self.video, self.update_op = video, update_op
         self.graph = FactorGraph(video, update_op, device, max_factors=max_factors, upsample=upsample)
         self.t0 = self.t1 = 0
@@ -28,6 +28,9 @@ class DroidFrontend:
         self.keyframes_removed = 0
         self.update_pending = False                 # a keyframe update whose second half has not run yet (pipelined Droid)
         self.prefetch = True                        # launch an update's proximity distances ahead of the keyframe's context encoder
+        # uncertainty: after a keyframe's LAST graph update, the window's depth variances and pose covariance (FactorGraph.uncertainty:
+        # read only, nothing of the trajectory changes).  False: nothing is allocated and no launch is added.
+        self.uncertainty = bool(uncertainty)
         self._dist = self._dist_host = self._dist_ready = None
 
     def _update(self):
@@ -86,6 +89,8 @@ class DroidFrontend:
         else:
             for _ in range(self.iters2):
                 self.graph.update(None, None, use_inactive=True)
+            if getattr(self, "uncertainty", False):
+                self.graph.uncertainty(None, None, use_inactive=True)
         self.video.poses[self.t1] = self.video.poses[self.t1 - 1]
         self.video.disps[self.t1] = self.video.disps[self.t1 - 1].mean()
         self.video.dirty[min(self.graph._ii_h):self.t1] = True
@@ -99,6 +104,8 @@ class DroidFrontend:
         self.graph.add_proximity_factors(0, 0, rad=2, nms=2, thresh=self.frontend_thresh)
         for _ in range(12):
             self.graph.update(1, use_inactive=True)
+        if getattr(self, "uncertainty", False):
+            self.graph.uncertainty(1, use_inactive=True)
         self.video.poses[self.t1] = self.video.poses[self.t1 - 1].clone()
         self.video.disps[self.t1] = self.video.disps[self.t1 - 4:self.t1].mean()
         self.is_initialized = True

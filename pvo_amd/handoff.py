@@ -48,9 +48,11 @@ def _host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
-def write_ply(path, xyz, rgb=None, label=None):
+def write_ply(path, xyz, rgb=None, label=None, sigma=None):
     """a point cloud as binary little-endian PLY: x y z float, then red green blue uchar (rgb [n,3] or [n,4], the first three columns;
-    omitted when None), then an int label (omitted when None).  numpy only; returns the number of points written."""
+    omitted when None), then an int label (omitted when None), then a float sigma - the point's standard deviation of the inverse
+    depth (omitted when None: the file is then byte for byte what it was without the argument).  numpy only; returns the number of
+    points written."""
     xyz = _host(xyz)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     props = ["property float x", "property float y", "property float z"]
@@ -62,6 +64,10 @@ def write_ply(path, xyz, rgb=None, label=None):
         label = _host(label)
         fields.append(("label", "<i4"))
         props.append("property int label")
+    if sigma is not None:
+        sigma = _host(sigma)
+        fields.append(("sigma", "<f4"))
+        props.append("property float sigma")
     n = int(xyz.shape[0])
     rec = np.zeros(n, dtype=np.dtype(fields))
     rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
@@ -69,6 +75,8 @@ def write_ply(path, xyz, rgb=None, label=None):
         rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     if label is not None:
         rec["label"] = label
+    if sigma is not None:
+        rec["sigma"] = sigma
     header = "\n".join(["ply", "format binary_little_endian 1.0", "element vertex %d" % n] + props + ["end_header"]) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as f:

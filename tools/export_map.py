@@ -1,13 +1,16 @@
 """Run the VO system over an image sequence like tools/test_vo.py (same arguments and data layout) and export the dense map.
 
     python tools/export_map.py --datapath <.../SceneXX> --weights <checkpoint.pth> --map out.ply [--full_res] [--filter_thresh_map 0.005]
-                               [--reconstruction_path DIR]
+                               [--reconstruction_path DIR] [--uncertainty [--max_rel_sigma X]]
 
 --map writes the filtered point cloud of all keyframes after the global bundle adjustment (Droid.get_map: points confirmed by two
 neighbouring keyframes, pvo_map_points) as a binary little-endian PLY: x y z float, red green blue uchar, int label (the per-frame
 dense panoptic label, with --segm_filter True).  --full_res tracks with the convex upsampling and exports every pixel of the
 full-resolution depth maps instead of the 1/8 lattice.  --reconstruction_path DIR also writes upstream DROID-SLAM's
-tstamps / disps / poses / intrinsics / images .npy files.
+tstamps / disps / poses / intrinsics / images .npy files.  --uncertainty tracks with args.uncertainty (every keyframe's inverse-depth
+variances from the frontend's bundle adjustment, estimated after the keyframe's last local update - the global bundle adjustment
+does not refresh them) and adds `property float sigma` to the PLY; --max_rel_sigma X also leaves out the cells whose relative
+standard deviation sigma / disp exceeds X.
 """
 import os
 import sys
@@ -26,10 +29,14 @@ def parse_args(argv=None):
     p.add_argument("--filter_thresh_map", "--map_filter_thresh", type=float, default=0.005,
                    help="the depth filter's threshold (the reference viewer's filter_thresh; test_vo.py's --filter_thresh is the motion filter's)")
     p.add_argument("--reconstruction_path", default=None)
+    p.add_argument("--uncertainty", action="store_true", help="estimate depth variances while tracking and write a sigma column")
+    p.add_argument("--max_rel_sigma", type=float, default=None, help="with --uncertainty: drop cells with sigma / disp above this")
     own, rest = p.parse_known_args(argv)
     args = test_vo.parse_args(rest)
     for k, v in vars(own).items():
         setattr(args, k, v)
+    if args.max_rel_sigma is not None and not args.uncertainty:
+        p.error("--max_rel_sigma needs --uncertainty")
     return args
 
 
@@ -49,8 +56,9 @@ def main(argv=None):
     traj = droid.terminate(test_vo.image_stream(args.datapath, args.image_size, "val", args.segm_filter), need_inv=True)
     out_dir = os.path.join(args.out, os.path.basename(args.datapath.rstrip("/")), test_vo.SPLIT["val"])
     write_kitti_trajectory(os.path.join(out_dir, "pvo_traj.txt"), traj)
-    m = droid.get_map(thresh=args.filter_thresh_map, full_res=args.full_res)
-    n = write_ply(args.map, m["xyz"], m["rgba"], m.get("label") if args.segm_filter else None)
+    kw = {"max_rel_sigma": args.max_rel_sigma if args.max_rel_sigma is not None else float("inf")} if args.uncertainty else {}
+    m = droid.get_map(thresh=args.filter_thresh_map, full_res=args.full_res, **kw)
+    n = write_ply(args.map, m["xyz"], m["rgba"], m.get("label") if args.segm_filter else None, **({"sigma": m["sigma"]} if args.uncertainty else {}))
     print("map: %d points of %d keyframes written to %s" % (n, droid.video.counter, args.map))
     if args.reconstruction_path:
         for p in save_reconstruction(args.reconstruction_path, droid.video):
