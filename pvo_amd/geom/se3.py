@@ -19,7 +19,28 @@ differentiable Python path (geom/ba.py, DroidNet.forward) and host-side bookkeep
 """
 import torch
 
-EPS = 1e-6  # lietorch include/common.h:7
+EPS = 1e-6  # lietorch include/common.h:7: log's |w| -> 0 branch only
+
+# Below CUTOFF[dtype] on the rotation angle, exp's and log's coefficients are series in theta^2 of TERMS[dtype] terms; above it, closed
+# forms.  lietorch's single switch at theta < 1e-6 left (1 - cos) / theta^2 and (theta - sin) / theta^3 to cancel catastrophically in
+# fp32 up to theta ~ 1e-2, and their derivatives up to ~ 1e-1.  csrc/se3_dual.h holds the same constants and the derivation of the
+# cutoffs and term counts; the kernels and this formulation share every formula and cutoff.  The cancellation that sets the cutoff is a
+# multiple of eps / theta, so in units of eps it is the same for both types; the term count is what differs.
+PI = 3.14159265358979323846
+CUTOFF = {torch.float32: 0.5, torch.float64: 0.5}                     # on theta
+TERMS = {torch.float32: 5, torch.float64: 8}
+Q_CUTOFF = {torch.float32: 0.125, torch.float64: 0.0125}              # log's quaternion coefficient: on |v| = sin(theta / 2), five terms
+S_IMAG = (1.0 / 2.0, -1.0 / 48.0, 1.0 / 3840.0, -1.0 / 645120.0, 1.0 / 185794560.0, -1.0 / 81749606400.0,
+          1.0 / 51011754393600.0, -1.0 / 42849873690624000.0)                                             # sin(theta / 2) / theta
+S_REAL = (1.0, -1.0 / 8.0, 1.0 / 384.0, -1.0 / 46080.0, 1.0 / 10321920.0, -1.0 / 3715891200.0, 1.0 / 1961990553600.0,
+          -1.0 / 1428329123020800.0)                                                                      # cos(theta / 2)
+S_C1 = (1.0 / 2.0, -1.0 / 24.0, 1.0 / 720.0, -1.0 / 40320.0, 1.0 / 3628800.0, -1.0 / 479001600.0, 1.0 / 87178291200.0,
+        -1.0 / 20922789888000.0)                                                                          # (1 - cos theta) / theta^2
+S_C2 = (1.0 / 6.0, -1.0 / 120.0, 1.0 / 5040.0, -1.0 / 362880.0, 1.0 / 39916800.0, -1.0 / 6227020800.0, 1.0 / 1307674368000.0,
+        -1.0 / 355687428096000.0)                                                                         # (theta - sin theta) / theta^3
+S_LOG_C2 = (1.0 / 12.0, 1.0 / 720.0, 1.0 / 30240.0, 1.0 / 1209600.0, 1.0 / 47900160.0, 691.0 / 1307674368000.0, 1.0 / 74724249600.0,
+            3617.0 / 10670622842880000.0)                                            # (1 - (theta / 2) cot(theta / 2)) / theta^2
+S_ATAN = (1.0, -1.0 / 3.0, 1.0 / 5.0, -1.0 / 7.0, 1.0 / 9.0)                         # atan(u) / u in u^2
 
 
 FORCE_TORCH = False      # tests: the torch formulation everywhere (also pvo_amd.config "se3_torch"; nothing is read from the environment)
@@ -139,37 +160,59 @@ def _qrot(q, v):
     return v + q[..., 3:] * uv + _cross(qv, uv)
 
 
+def _cutoff(x):
+    """the rotation angle below which the coefficients are series in theta^2 (csrc/se3_dual.h: Cut<F>, with the derivation)"""
+    return CUTOFF.get(x.dtype, CUTOFF[torch.float32])
+
+
+def _series(x, coefs):
+    """sum_k coefs[k] x^k over the type's term count, by Horner's rule"""
+    coefs = coefs[:TERMS.get(x.dtype, TERMS[torch.float32])]
+    y = torch.full_like(x, coefs[-1])
+    for c in reversed(coefs[:-1]):
+        y = y * x + c
+    return y
+
+
+def _theta(th2, cut):
+    """-> (small, theta, theta^2) with theta = theta^2 = 1 on the series branch: the closed forms stay finite where they are not
+    selected, and sqrt is never differentiated at 0 (phi = 0 exactly: the fixed poses of geom/ba.py)"""
+    small = th2 < cut * cut
+    th2s = torch.where(small, torch.ones_like(th2), th2)
+    return small, torch.sqrt(th2s), th2s
+
+
 def _so3_exp(phi):
     th2 = (phi * phi).sum(-1, keepdim=True)
-    th = torch.sqrt(th2)
-    small = th < EPS
-    th_safe = torch.where(small, torch.ones_like(th), th)
-    imag = torch.where(small, 0.5 - th2 / 48.0 + th2 * th2 / 3840.0, torch.sin(0.5 * th_safe) / th_safe)
-    real = torch.where(small, 1.0 - th2 / 8.0 + th2 * th2 / 384.0, torch.cos(0.5 * th_safe))
+    small, ths, _ = _theta(th2, _cutoff(phi))
+    imag = torch.where(small, _series(th2, S_IMAG), torch.sin(0.5 * ths) / ths)
+    real = torch.where(small, _series(th2, S_REAL), torch.cos(0.5 * ths))
     return torch.cat([imag * phi, real], dim=-1)
 
 
 def _so3_log(q):
     v, w = q[..., :3], q[..., 3:]
     n2 = (v * v).sum(-1, keepdim=True)
-    small = n2 < EPS * EPS
+    cut = Q_CUTOFF.get(q.dtype, Q_CUTOFF[torch.float32])
+    small = n2 < cut * cut
     n = torch.sqrt(torch.where(small, torch.ones_like(n2), n2))
-    w_safe = torch.where(w.abs() < EPS, torch.full_like(w, EPS), w)
+    flat = w.abs() < EPS
+    w_safe = torch.where(flat, torch.full_like(w, EPS), w)
     big = 2.0 * torch.atan(n / w_safe) / n
-    near_pi = torch.where(w > 0, 3.14159265358979323846 / n, -3.14159265358979323846 / n)
-    big = torch.where(w.abs() < EPS, near_pi, big)
-    sm = 2.0 / w - (2.0 / 3.0) * n2 / (w * w * w)
+    # 2 atan(n / w) = +-pi - 2 atan(w / n): exact on both sides of w = 0, where n / w overflows
+    near_pi = (torch.where(w > 0, torch.full_like(w, PI), torch.full_like(w, -PI)) - 2.0 * torch.atan(w / n)) / n
+    big = torch.where(flat, near_pi, big)
+    ws = torch.where(small, w, torch.ones_like(w))
+    sm = 2.0 / ws * _series(n2 / (ws * ws), S_ATAN)
     return torch.where(small, sm, big) * v
 
 
 def _left_jacobian_coefs(phi):
     th2 = (phi * phi).sum(-1, keepdim=True)
-    th = torch.sqrt(th2)
-    small = th < EPS
-    th2s = torch.where(small, torch.ones_like(th2), th2)
-    ths = torch.where(small, torch.ones_like(th), th)
-    c1 = torch.where(small, 0.5 - th2 / 24.0, (1.0 - torch.cos(ths)) / th2s)
-    c2 = torch.where(small, 1.0 / 6.0 - th2 / 120.0, (ths - torch.sin(ths)) / (th2s * ths))
+    small, ths, th2s = _theta(th2, _cutoff(phi))
+    sh = torch.sin(0.5 * ths) / ths
+    c1 = torch.where(small, _series(th2, S_C1), 2.0 * sh * sh)               # (1 - cos) / theta^2 by the half angle: no cancellation
+    c2 = torch.where(small, _series(th2, S_C2), (ths - torch.sin(ths)) / (th2s * ths))
     return c1, c2
 
 
@@ -247,12 +290,9 @@ class SE3:
         t, q = self.data[..., :3], self.data[..., 3:]
         phi = _so3_log(q)
         th2 = (phi * phi).sum(-1, keepdim=True)
-        th = torch.sqrt(th2)
-        small = th < EPS
-        ths = torch.where(small, torch.ones_like(th), th)
+        small, ths, th2s = _theta(th2, _cutoff(phi))
         half = 0.5 * ths
-        c2 = torch.where(small, torch.full_like(th, 1.0 / 12.0),
-                         (1.0 - ths * torch.cos(half) / (2.0 * torch.sin(half))) / (ths * ths))
+        c2 = torch.where(small, _series(th2, S_LOG_C2), (1.0 - ths * torch.cos(half) / (2.0 * torch.sin(half))) / th2s)
         pt = _cross(phi, t)
         tau = t - 0.5 * pt + c2 * _cross(phi, pt)
         return torch.cat([tau, phi], dim=-1)
