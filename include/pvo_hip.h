@@ -82,7 +82,7 @@ const char* pvo_last_hip_error(void);
  * pvo_reproject_rig / pvo_reproject_motion_rig / pvo_graph_update_rig; still 106, map export: no existing struct changed - new struct
  * pvo_map_points_args (pvo_map_points_args_size() reports its size) and new entry points pvo_map_points_args_size /
  * pvo_map_points_workspace_bytes / pvo_map_points; still 106, uncertainty: no struct changed - new entry points pvo_ba_sigma /
- * pvo_ba_uncertainty): a caller
+ * pvo_ba_uncertainty; still 106, calibration: no struct changed - new entry points pvo_ba_calib_workspace_bytes / pvo_ba_calib): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -881,6 +881,47 @@ int pvo_ba_uncertainty(const float* poses, const float* disps, const float* intr
                        double* pose_cov, float* var_cond, float* var_pose, int* status_out,
                        void* workspace, size_t workspace_bytes,
                        const float* disps_sens, float alpha, float baseline, void* stream);
+/* Online intrinsics calibration: the depth BA's Gauss-Newton step (pvo_ba, motion_only = 0) with four more unknowns c = (fx, fy, cx, cy),
+ * shared by all frames (upstream DROID-SLAM's `opt_intr`; the reference has none).  Notation as for pvo_ba_sigma: P, kx, C, w (with
+ * the depth phase's w'), Q = 1 / (C + eta), M_k the live rows of depth frame k, A / b the pose blocks and right-hand side.  Per edge
+ * e = (i -> j), pixel and residual row, with the assembly's own weight (0.001 * weight formed in double, 0 where Z < 0.25), residual r,
+ * Ji, Jj, Jz and Jc [1 x 4] = d(projection) / dc:
+ *     Hcc += w Jc^T Jc        Hc[i] += w Ji^T Jc,  Hc[j] += w Jj^T Jc   (live poses only)        vc += w r Jc^T
+ *     gc[e][x] += w Jz Jc^T,  Gc_k = sum over the out-edges of depth frame k of gc[e]
+ * and after the elimination of the depths
+ *     Sc = Hc - sum_k sum_x M_k Q Gc_k^T  [6P x 4]      Scc = Hcc - sum_k sum_x Q Gc Gc^T      rc = vc - sum_k sum_x Q w' Gc
+ * The bordered system [[S, Sc], [Sc^T, Scc]] is damped by diag(ep + lm diag(S)) on the poses (pvo_ba's rule) and by
+ * diag(ep_c + lm diag(Scc)) on the intrinsics, and solved in fp64 (S_d^-1 by the kernels of pvo_ba_sigma, then the 4 x 4 complement).
+ * A parameter whose bit of free_mask is clear is HELD: its row and column are removed, its dc is exactly 0 and its bytes stay.
+ * Back-substitution dz = Q (w' - M^T dx - Gc^T dc) over the live rows pvo_ba's uses, the skip of window pose 0 included;
+ * retraction of poses and depths as pvo_ba_finish (no clamp), c += dc in fp32.  free_mask = 0 is pvo_ba's step.
+ * Jc in closed form, with R, (X, Y, Z) the rotation of G_ij and the point in frame j, d = 1 / Z, px = (u - cx) / fx, py = (v - cy) / fy,
+ * a_n = fx (d R0n - X d^2 R2n), b_n = fy (d R1n - Y d^2 R2n):
+ *     du/dc = [X d - a0 px / fx, -a1 py / fy, 1 - a0 / fx, -a1 / fy]      dv/dc = [-b0 px / fx, Y d - b1 py / fy, -b0 / fx, 1 - b1 / fy]
+ * evaluated in fp64 from the stored fp32 poses, depths and intrinsics (an identity edge gets Jc = 0).
+ *   - intrinsics [4] is UPDATED IN PLACE; dc_out [4] (may be NULL) and dx_out / dz_out receive the LAST step.
+ *   - A step is REJECTED AS A WHOLE when the factorisation (of S_d or of the 4 x 4 complement) fails, a non-finite entry appears,
+ *     fx + dfx <= 0 or fy + dfy <= 0, or one of the step's own flags is raised (eta-row mismatch, row-table overflow, a sum out of
+ *     the fixed-point range).  A rejected step changes NOTHING in poses, disps or intrinsics; dx_out, dz_out (rows of kx) and dc_out
+ *     are zeros; status_out (int[4], may be NULL) = [1 if any step was rejected, K, eta-row mismatch, row-table overflow].  A status,
+ *     never a fault.
+ *   - ep_c = 0 is legal and the caller's risk: a motion that leaves a parameter unobservable makes the complement singular (rejected)
+ *     or the step wild.
+ *   - calib_workspace: pvo_ba_calib_workspace_bytes(E, P, nframes, HW) bytes of caller-owned scratch beside the BA workspace (gc, Gc,
+ *     the border, S_d^-1), needed only while the kernels run.  The BA workspace is PLANNED by this call: the sensor-depth prior and the
+ *     stereo baseline are not set - both are OUT OF SCOPE for calibration for now (an edge (i, i) is an identity edge).
+ *   - No allocation, no host synchronisation, capturable.  The border's sums are 64-bit fixed point like `sys` (units of 2^-32), the
+ *     rest fixed-order: same operands, same bytes.  pvo_ba on the same BA workspace afterwards gives the bits of pvo_ba alone.
+ *   - Limits: 1 <= P <= 64 (PVO_EUNSUPPORTED otherwise; the backend's global graph is out of scope); E >= 1, ep_c >= 0, free_mask in
+ *     [0, 15] (bit n frees c[n]), iterations >= 0 (PVO_EINVAL otherwise); fp32 only. */
+size_t pvo_ba_calib_workspace_bytes(int E, int P, int nframes, int HW);
+int pvo_ba_calib(float* poses, float* disps, float* intrinsics,
+                 const float* targets, const float* weights, const float* eta,
+                 const int64_t* ii, const int64_t* jj,
+                 int E, int nframes, int ht, int wd, int K_eta,
+                 int t0, int t1, int iterations, float lm, float ep, float ep_c, int free_mask,
+                 float* dx_out, float* dz_out, int dz_rows, float* dc_out, int* status_out,
+                 void* workspace, size_t workspace_bytes, void* calib_workspace, size_t calib_bytes, void* stream);
 /* The message of an edge-sharded step, packed by the library (round 4): first_s (device, int[P]) is the
  * STRUCTURAL envelope of the pose system - first_s[b] = lowest free pose block row b can couple with, derived from the whole
  * graph's edge list, the same table on every rank (pvo_amd/parallel.py: envelope_structure).

@@ -100,6 +100,9 @@ SIGNATURES = {
     "pvo_ba_sigma": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "pvo_ba_uncertainty": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp, _f, _f, _vp]),
+    "pvo_ba_calib_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pvo_ba_calib": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i,
+                          _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "pvo_reproject_rig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "pvo_reproject_motion_rig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "pvo_map_points_args_size": (_sz, []),

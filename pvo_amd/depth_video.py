@@ -26,6 +26,14 @@ Uncertainty: `uncertainty(...)`, beside `ba(...)` and on its operands, writes ev
 pose covariance `poses_cov` (include/pvo_hip.h, pvo_ba_uncertainty).  The three buffers are allocated on first use
 (`ensure_uncertainty`, +inf = never estimated) and travel with their keyframe; a video that never asks allocates nothing.
 `map_points(max_rel_sigma=...)` filters the map by them and returns each point's sigma.
+
+Calibration: `ba_calib(...)`, on `ba(...)`'s operands, is the depth BA with the four intrinsics as unknowns shared by all frames
+(include/pvo_hip.h, pvo_ba_calib).  It runs on `intrinsics[0]`; once a step has been ACCEPTED - decided on the device, without a host
+synchronisation: row 0 moved - the result is copied into every row IN PLACE (captured graphs and the native update hold the buffer's
+pointer) and the device flag `calibrated_dev` is set: from then on `append` and `video[k] = ...` keep the calibrated vector instead of
+the caller's, whose stale guess `reproject` would otherwise read per frame.  While every step was rejected the rows and the flag stay
+as they were and the caller's vectors are still written.  `calibrated` is the host-side "ba_calib has run": a video that never
+calibrates launches nothing more and behaves as before.
 """
 import torch
 
@@ -54,6 +62,8 @@ class DepthVideo:
         # estimated, and the diagonal blocks of the window's pose covariance [buffer,6,6] fp64
         self.disps_var_cond = self.disps_var_pose = self.poses_cov = None
         self.intrinsics = torch.zeros(buffer, 4, dtype=torch.float, **kw)
+        self.calibrated = False            # host side: ba_calib has run on this video (calibrated_dev says whether a step was accepted)
+        self.calibrated_dev = None         # device bool [1]: a calibrating step was accepted - every row holds the calibrated vector and keeps it
         self.fmaps = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw)      # channels-last
         self.fmaps_right = None            # stereo: the right views' feature maps [buffer,H/8,W/8,128] channels-last (ensure_fmaps_right)
         self.stereo_baseline = 0.1         # the rig's baseline in the units of the poses' translations (upstream's constant)
@@ -264,7 +274,7 @@ class DepthVideo:
                 self.disps[k] = disp
             else:
                 self.disps[k:k + 1].fill_(float(disp))
-        self.intrinsics[k] = intrinsics
+        self.intrinsics[k] = self._kept_intrinsics(intrinsics)
         self.fmaps[k] = self._fmap_cl(fmap, channels_last)
         self.nets[k] = net
         self.inps[k] = inp
@@ -289,7 +299,7 @@ class DepthVideo:
             self.images[index] = item[1].to(self.images.dtype)
         for buf, val in ((self.poses, item[2]), (self.disps, item[3]), (self.intrinsics, item[4])):
             if val is not None:
-                buf[index] = val
+                buf[index] = self._kept_intrinsics(val) if buf is self.intrinsics else val
         if item[3] is not None:
             self.reset_uncertainty(slice(index, index + 1) if isinstance(index, int) else index)
         if len(item) > 5 and item[5] is not None:
@@ -304,6 +314,14 @@ class DepthVideo:
                 self.segms[index] = self._dense_segments(seg).reshape(self.segms[index].shape)
             else:                                           # several frames at once: labels are per frame
                 self.segms[index] = torch.stack([self._dense_segments(x) for x in seg]).reshape(self.segms[index].shape)
+
+    def _kept_intrinsics(self, value):
+        """what `append` / `video[k] = ...` store for a caller's intrinsics: the caller's, or - on a video whose calibration was
+        accepted (the device flag; no host synchronisation) - the calibrated vector"""
+        if not self.calibrated:
+            return value
+        value = torch.as_tensor(value, dtype=torch.float, device=self.device)
+        return torch.where(self.calibrated_dev, self.intrinsics[0], value)
 
     def __getitem__(self, index):
         """(pose, disp, intrinsics, fmap, net, inp) of a keyframe; negative ints count from the end (:103-121)"""
@@ -477,6 +495,33 @@ class DepthVideo:
         db.ba(self.poses, self.disps, self.intrinsics[0], target, weight, eta, ii, jj, t0, t1, itrs, lm, ep,
               motion_only, **kw)
         self.disps.clamp_(min=0.001)
+
+    def ba_calib(self, target, weight, eta, ii, jj, t0=1, t1=None, itrs=2, lm=1e-4, ep=0.1, ep_c=0.1, free="all"):
+        """online intrinsics calibration: `itrs` steps of the depth BA `ba(target, weight, eta, ii, jj, t0, t1, lm=lm, ep=ep)` with
+        (fx, fy, cx, cy) free (free="all") or the focal lengths only ("focal"), damped by ep_c (pvo_ba_calib).  In place on poses, disps
+        and - through row 0, then copied to every row once a step was accepted - intrinsics; a step the library rejects changes nothing.  Returns
+        [dx, dz, dc, status] of the last step (device tensors; status[0] = 1: a step was rejected).  No host synchronisation.
+        Not with the sensor-depth prior or stereo edges: the calibrating step has neither."""
+        if self.has_sensor_depth or self._rig_kw("stereo_baseline"):
+            raise NotImplementedError("DepthVideo.ba_calib: calibration together with the sensor-depth prior or stereo edges is not supported")
+        if free not in ("all", "focal"):
+            raise ValueError("free must be 'all' or 'focal', got %r" % (free,))
+        if t1 is None:
+            t1 = int(max(ii.max().item(), jj.max().item())) + 1
+        status = torch.zeros(4, dtype=torch.int32, device=self.device)
+        before = self.intrinsics[0].clone()
+        out = db.ba_calib(self.poses, self.disps, self.intrinsics[0], target, weight, eta, ii, jj, t0, t1, itrs, lm, ep, ep_c,
+                          db.BA_CALIB_FREE[free], status=status)
+        self.disps.clamp_(min=0.001)
+        # accepted = row 0 moved (status[0] says "some step was rejected", which an earlier accepted step of the same call survives).
+        # In place and on the device: the same storage; every row the calibrated vector, or every row what it was
+        moved = (self.intrinsics[0] != before).any().reshape(1)
+        if self.intrinsics.shape[0] > 1:
+            rest = self.intrinsics[1:]
+            rest.copy_(torch.where(moved, self.intrinsics[0:1].expand_as(rest), rest))
+        self.calibrated_dev = moved if self.calibrated_dev is None else (self.calibrated_dev | moved)
+        self.calibrated = True
+        return out + [status]
 
     def uncertainty(self, target, weight, eta, ii, jj, t0=1, t1=None, lm=1e-4, ep=0.1):
         """depth and pose uncertainty of the depth-BA step `ba(target, weight, eta, ii, jj, t0, t1, lm=lm, ep=ep)` would take from the

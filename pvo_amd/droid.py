@@ -25,11 +25,15 @@ def default_args(**over):
              beta=0.6, filter_thresh=1.75, warmup=12, keyframe_thresh=2.25, frontend_thresh=12.0, frontend_window=25,
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
              segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1,
-             store_images=False, uncertainty=False)
+             store_images=False, uncertainty=False, opt_intr=False, opt_intr_free="all")
     # uncertainty: after every keyframe's last frontend update, estimate the window's inverse-depth variances and pose covariance from
     # the bundle adjustment's normal equations (DepthVideo.uncertainty; get_uncertainty(), get_map(max_rel_sigma=...)).  Read only: the
     # trajectory and the depths are bit for bit those of a run without it.  A window of more than 64 poses (frontend_window above 64) is
     # not estimated: its keyframes keep +inf.  False (default): nothing is allocated, no launch is added.
+    # opt_intr: online intrinsics calibration for a video without (or with a wrong) calibration - after initialisation and after every
+    # kept keyframe's last frontend update the window's bundle adjustment runs two more steps with (fx, fy, cx, cy) as unknowns shared by
+    # all frames (opt_intr_free = "all") or the focal lengths only ("focal"); DepthVideo.ba_calib, get_intrinsics().  Windows of more than
+    # 64 poses are not calibrated.  Not with rgbd / stereo.  False (default): no launch is added, every result is what it was.
     # rgbd: use the `depth` image of track() - each keyframe's sensor depth becomes a prior of the bundle adjustment, the trajectory
     # and the map are metric (DepthVideo, include/pvo_hip.h pvo_ba_depth_prior).  False (default): `depth` is IGNORED, nothing is
     # allocated for it and every result is what a monocular run computes.
@@ -45,6 +49,11 @@ def default_args(**over):
 class Droid:
     def __init__(self, args):
         self.args = args
+        if getattr(args, "opt_intr", False) and (getattr(args, "rgbd", False) or getattr(args, "stereo", False)):
+            raise ValueError("args.opt_intr together with args.rgbd or args.stereo is not supported: the calibrating bundle adjustment has "
+                             "neither the sensor-depth prior nor stereo edges")
+        if getattr(args, "opt_intr_free", "all") not in ("all", "focal"):
+            raise ValueError("args.opt_intr_free must be 'all' or 'focal', got %r" % (args.opt_intr_free,))
         self.load_weights(args.weights, args.use_aff_bri)
         self.video = DepthVideo(args.image_size, args.buffer, args.device, args.segm_filter, args.thresh,
                                 store_images=bool(getattr(args, "store_images", False)))
@@ -57,7 +66,9 @@ class Droid:
                                       frontend_nms=args.frontend_nms, keyframe_thresh=args.keyframe_thresh,
                                       frontend_window=args.frontend_window, frontend_thresh=args.frontend_thresh,
                                       frontend_radius=args.frontend_radius, upsample=bool(getattr(args, "upsample", False)),
-                                      uncertainty=bool(getattr(args, "uncertainty", False)))
+                                      uncertainty=bool(getattr(args, "uncertainty", False)),
+                                      opt_intr=bool(getattr(args, "opt_intr", False)),
+                                      opt_intr_free=getattr(args, "opt_intr_free", "all"))
         self.filterx.before_context = self.frontend.keyframe_ahead
         self.backend = DroidBackend(self.net, self.video, args)
         self.traj_filler = PoseTrajectoryFiller(self.net, self.video, args.device)
@@ -142,6 +153,12 @@ class Droid:
             return self.video.disps_up[:self.video.counter]
         d = self.video.disps[:self.video.counter]
         return upsample_inter(d[None, ..., None]).squeeze(4).squeeze(0)
+
+    def get_intrinsics(self):
+        """(fx, fy, cx, cy) at image resolution: 8 x the vector the video stores - the calibrated one after tracking with
+        args.opt_intr = True, else the first keyframe's"""
+        self.flush()
+        return 8.0 * self.video.intrinsics[0]
 
     def get_uncertainty(self):
         """(sigma_disp = sqrt(var_cond + var_pose), var_cond, var_pose [counter, H/8, W/8], poses_cov [counter, 6, 6] fp64) of the

@@ -790,6 +790,56 @@ def ba_uncertainty(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, 
     return cov.view(P, 6, P, 6)
 
 
+BA_CALIB_MAX_POSES = 64      # pvo_ba_calib: the frontend's window (include/pvo_hip.h)
+BA_CALIB_FREE = {"all": 15, "focal": 3}
+_calib_ws_cache = {}
+
+
+def ba_calib(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iterations, lm, ep, ep_c=0.1, free_mask=15, status=None):
+    """the calibrating depth BA (pvo_ba_calib, include/pvo_hip.h): `ba`'s operands with intrinsics [4] fp32 UPDATED IN PLACE beside
+    poses and disps.  free_mask: bit n frees (fx, fy, cx, cy)[n]; a held parameter keeps its bytes.  Returns [dx [P,6], dz [K,ht*wd],
+    dc [4]] of the last step (zeros when it was rejected).  status (optional int32[4]) receives [a step was rejected, K, eta-row
+    mismatch, row-table overflow].  1 <= P <= BA_CALIB_MAX_POSES.  Runs on the workspace `ba` uses.  No host synchronisation."""
+    for t, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
+                 (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
+        _contig(t, n)
+    dev = _dev(poses, disps, intrinsics, targets, weights, eta, ii, jj, status)
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (targets, "targets"), (weights, "weights"), (eta, "eta")):
+        _f32(t, n)
+    _long(ii, "ii"); _long(jj, "jj")
+    F, ht, wd = disps.shape
+    HW, E = ht * wd, ii.shape[0]
+    t0, t1 = int(t0), int(t1)
+    P = t1 - t0
+    if P < 0 or t0 < 0 or poses.shape[0] < t1 or F < t1:
+        raise PvoHipError("ba_calib: pose window [%d,%d) exceeds the buffers (%d poses, %d depth maps)" % (t0, t1, poses.shape[0], F))
+    if P > BA_CALIB_MAX_POSES:
+        raise PvoHipError("ba_calib: at most %d window poses (got %d)" % (BA_CALIB_MAX_POSES, P))
+    if intrinsics.numel() != 4:
+        raise PvoHipError("ba_calib: intrinsics must hold the 4 values fx, fy, cx, cy")
+    if status is not None and (status.dtype != torch.int32 or status.numel() < 4):
+        raise PvoHipError("ba_calib: status must be int32 with 4 elements")
+    eta = eta.contiguous().view(-1, HW)
+    K_eta = eta.shape[0]
+    K = K_eta if K_eta > 1 else int(torch.unique(torch.cat([torch.arange(t0, t1, device=dev), ii])).numel())
+    dx = torch.zeros(max(P, 0), 6, dtype=torch.float32, device=dev)
+    dz = torch.zeros(K, HW, dtype=torch.float32, device=dev)
+    dc = torch.zeros(4, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_ba_workspace_bytes(E, P, F, HW))
+    nb = lib.pvo_ba_calib_workspace_bytes(E, P, F, HW)
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    cws = _calib_ws_cache.get(key)
+    if cws is None or cws.numel() < nb:
+        cws = _calib_ws_cache[key] = torch.empty(int(nb) + (int(nb) >> 3), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.pvo_ba_calib(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(targets), _ptr(weights), _ptr(eta), _ptr(ii), _ptr(jj),
+                               E, F, ht, wd, K_eta, t0, t1, int(iterations), float(lm), float(ep), float(ep_c), int(free_mask),
+                               _ptr(dx), _ptr(dz), K, _ptr(dc), _vp(status), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                               ctypes.c_void_p(cws.data_ptr()), cws.numel(), _stream(dev)), "ba_calib")
+    return [dx, dz, dc]
+
+
 def depth_sense(depth, out_row):
     """RGB-D ingest (pvo_depth_sense): out_row [H/8,W/8] fp32 = 1 / depth[3::8, 3::8] where that is finite and > 0, else 0.
     depth [H,W] fp32 / fp16 on the device; one launch."""

@@ -937,24 +937,16 @@ class FactorGraph:
             self._sync_edge_index()
         self._age_dev, self._age_lag = t, 0
 
-    @torch.no_grad()
-    def uncertainty(self, t0=None, t1=None, use_inactive=False, sharded=None):
-        """depth and pose uncertainty of the window from the operands the last `update`'s bundle adjustment read - on the native and on
-        the composed path the same `target_cam`, `weight`, eta = 0.2 damping + EP (one row per depth frame the BA optimises), t0 / t1
-        rule and lm = 1e-4, ep = 0.1 - at the present poses and depths: DepthVideo.uncertainty (read only; returns the pose
-        covariance [P,6,P,6] fp64 and fills the video's variance maps).  A window of more than 64 poses (the stage's limit, the frontend's
-        window is a user argument) is NOT estimated: returns None and the variances keep what they hold (+inf: never estimated).
-        sharded: an edge-sharded bundle adjustment (pvo_amd/parallel.py) has no such stage - NotImplementedError."""
-        if sharded is not None:
-            sharded.uncertainty()
+    def _last_ba_operands(self, t0, t1, use_inactive, max_poses):
+        """the operands the last `update`'s bundle adjustment read, as DepthVideo.ba takes them: (target [E,2,ht,wd], weight, eta [one row
+        per depth frame], ii, jj, t0, t1) - shared by `uncertainty` and `calibrate`; None for a window of more than max_poses poses"""
         self._corr_sync()
         ht, wd = self.ht, self.wd
         if t0 is None:
             t0 = max(1, min(self._ii_h) + 1)
         if t1 is None:
             t1 = max(max(self._ii_h), max(self._jj_h)) + 1
-        from . import droid_backends as db
-        if t1 - t0 > db.BA_SIGMA_MAX_POSES:
+        if t1 - t0 > max_poses:
             return None
         m_l = [(i >= t0 - 3) and (j >= t0 - 3) for i, j in zip(self._ii_inac_h, self._jj_inac_h)] if use_inactive else []
         if any(m_l):
@@ -970,7 +962,37 @@ class FactorGraph:
         eta = 0.2 * self.damping[rows_t] + getattr(self, "_last_EP", 1e-7)
         target_cam = target_cam.reshape(-1, ht, wd, 2).permute(0, 3, 1, 2).float().contiguous()
         weight = weight.reshape(-1, ht, wd, 2).permute(0, 3, 1, 2).float().contiguous()
-        return self.video.uncertainty(target_cam, weight, eta, ii.contiguous(), jj.contiguous(), t0, t1, lm=1e-4, ep=0.1)
+        return target_cam, weight, eta, ii.contiguous(), jj.contiguous(), t0, t1
+
+    @torch.no_grad()
+    def uncertainty(self, t0=None, t1=None, use_inactive=False, sharded=None):
+        """depth and pose uncertainty of the window from the operands the last `update`'s bundle adjustment read - on the native and on
+        the composed path the same `target_cam`, `weight`, eta = 0.2 damping + EP (one row per depth frame the BA optimises), t0 / t1
+        rule and lm = 1e-4, ep = 0.1 - at the present poses and depths: DepthVideo.uncertainty (read only; returns the pose
+        covariance [P,6,P,6] fp64 and fills the video's variance maps).  A window of more than 64 poses (the stage's limit, the frontend's
+        window is a user argument) is NOT estimated: returns None and the variances keep what they hold (+inf: never estimated).
+        sharded: an edge-sharded bundle adjustment (pvo_amd/parallel.py) has no such stage - NotImplementedError."""
+        if sharded is not None:
+            sharded.uncertainty()
+        from . import droid_backends as db
+        ops = self._last_ba_operands(t0, t1, use_inactive, db.BA_SIGMA_MAX_POSES)
+        if ops is None:
+            return None
+        return self.video.uncertainty(*ops, lm=1e-4, ep=0.1)
+
+    @torch.no_grad()
+    def calibrate(self, t0=None, t1=None, use_inactive=False, itrs=2, lm=1e-4, ep=0.1, ep_c=0.1, free="all", sharded=None):
+        """online intrinsics calibration on the operands `uncertainty` reconstructs - the last update's `target_cam`, `weight`, eta rows
+        and t0 / t1 rule: DepthVideo.ba_calib (`itrs` calibrating Gauss-Newton steps; poses, depths and the video's intrinsics are
+        updated in place).  Returns its [dx, dz, dc, status]; None, and nothing done, for a window of more than 64 poses.  sharded: an
+        edge-sharded bundle adjustment has no such step - NotImplementedError."""
+        if sharded is not None:
+            sharded.calibrate()
+        from . import droid_backends as db
+        ops = self._last_ba_operands(t0, t1, use_inactive, db.BA_CALIB_MAX_POSES)
+        if ops is None:
+            return None
+        return self.video.ba_calib(*ops, itrs=itrs, lm=lm, ep=ep, ep_c=ep_c, free=free)
 
     @torch.no_grad()
     def update(self, t0=None, t1=None, itrs=2, use_inactive=False, EP=1e-7, motion_only=False):

@@ -14,7 +14,8 @@ from .factor_graph import FactorGraph
 
 class DroidFrontend:
     def __init__(self, update_op, video, device="cuda:0", warmup=8, beta=0.3, frontend_nms=1, keyframe_thresh=4.0,
-                 frontend_window=25, frontend_thresh=16.0, frontend_radius=2, max_factors=48, upsample=False, uncertainty=False):
+                 frontend_window=25, frontend_thresh=16.0, frontend_radius=2, max_factors=48, upsample=False, uncertainty=False,
+                 opt_intr=False, opt_intr_free="all"):
         self.video, self.update_op = video, update_op
         self.graph = FactorGraph(video, update_op, device, max_factors=max_factors, upsample=upsample)
         self.t0 = self.t1 = 0
@@ -31,6 +32,9 @@ class DroidFrontend:
         # uncertainty: after a keyframe's LAST graph update, the window's depth variances and pose covariance (FactorGraph.uncertainty:
         # read only, nothing of the trajectory changes).  False: nothing is allocated and no launch is added.
         self.uncertainty = bool(uncertainty)
+        # opt_intr: online intrinsics calibration at the same two places, BEFORE the uncertainty - FactorGraph.calibrate on the last
+        # update's operands, (fx, fy, cx, cy) free ("all") or the focal lengths only ("focal").  False: no launch is added.
+        self.opt_intr, self.opt_intr_free = bool(opt_intr), opt_intr_free
         self._dist = self._dist_host = self._dist_ready = None
 
     def _update(self):
@@ -89,6 +93,8 @@ class DroidFrontend:
         else:
             for _ in range(self.iters2):
                 self.graph.update(None, None, use_inactive=True)
+            if getattr(self, "opt_intr", False):
+                self.graph.calibrate(None, None, use_inactive=True, free=self.opt_intr_free)
             if getattr(self, "uncertainty", False):
                 self.graph.uncertainty(None, None, use_inactive=True)
         self.video.poses[self.t1] = self.video.poses[self.t1 - 1]
@@ -104,6 +110,8 @@ class DroidFrontend:
         self.graph.add_proximity_factors(0, 0, rad=2, nms=2, thresh=self.frontend_thresh)
         for _ in range(12):
             self.graph.update(1, use_inactive=True)
+        if getattr(self, "opt_intr", False):
+            self.graph.calibrate(1, use_inactive=True, free=self.opt_intr_free)
         if getattr(self, "uncertainty", False):
             self.graph.uncertainty(1, use_inactive=True)
         self.video.poses[self.t1] = self.video.poses[self.t1 - 1].clone()

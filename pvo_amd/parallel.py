@@ -200,6 +200,11 @@ class ShardedBA:
         raise NotImplementedError("ShardedBA: depth and pose uncertainty (pvo_ba_sigma) is not available for an edge-sharded bundle "
                                   "adjustment - use FactorGraph.uncertainty / DepthVideo.uncertainty on one GPU")
 
+    def calibrate(self, *args, **kw):
+        """not for an edge-sharded run: the calibrating step reads ONE rank's eliminated system and depth rows"""
+        raise NotImplementedError("ShardedBA: online intrinsics calibration (pvo_ba_calib) is not available for an edge-sharded bundle "
+                                  "adjustment - use FactorGraph.calibrate / DepthVideo.ba_calib on one GPU")
+
     def sync_disps(self, disps, disps_before):
         """make the depth replicas identical again (only needed when something reads maps a rank does
         not own, e.g. writing results): all-reduce of the per-rank updates."""
