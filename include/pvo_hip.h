@@ -730,6 +730,20 @@ size_t pvo_ba_workspace_bytes(int E, int P, int nframes, int HW);
  * status_out (device int[4], may be NULL): [0]=0 ok / 1 non-SPD in some iteration
  * (that step's dx is 0, as droid_kernels.cu:1186-1189), [1]=K found on device,
  * [2]=1 if K_eta mismatched K (the call then updates NOTHING and [0] is 1 as well), [3] reserved.
+ * A REJECTED POSE STEP.  The reduced pose system is summed in 64-bit fixed point (units of 2^-28).  An addend that is not
+ * finite, or not below 3e10 in magnitude - a NaN or Inf in a target, weight, depth or pose, or a weight so large that one
+ * edge's or one pixel chunk's sum leaves the range - is not added; it raises a flag, and the solve of that step then takes the
+ * path of a factorisation that failed: status_out[0] = 1, dx = 0 (dx_out too, if this was the last step), every pose keeps
+ * its bytes.  The DEPTHS of that step are not held back: as in the reference, the back-substitution runs with dx = 0, i.e.
+ * every optimised depth map takes the depth-only step dz = Q w, Q = 1 / (sum Cii + eta), w = sum bz over the frame's own
+ * out-edges.  A non-finite operand therefore reaches the depth maps only where it entered them: the pixels of the SOURCE frame
+ * of the poisoned edge (a target or weight pixel: that pixel; a pose or a depth: every pixel it projects).  Every depth pixel of a
+ * frame whose own out-edges are clean stays finite.  The flag and the fixed-point system are cleared by the solve that consumed
+ * them: the next step of the same call, and the next call on the same workspace, compute what they compute on a fresh one.
+ * (status_out[0] is sticky over the iterations of one call.)  The range check is per addend; the SUMS must stay below 2^35 in
+ * magnitude (2^63 units).  A diagonal entry of the reduced system in [2^35, 2^36) - weights and eta about 2^29 times those of a
+ * tracked window - wraps to a negative number, the factorisation fails on it and the step is rejected like the above
+ * (tests/test_ba_fp64_gpu.py); beyond 2^36 nothing is promised.
  * The depth back-substitution reproduces EvT6x1_kernel's skip of window pose 0
  * (droid_kernels.cu:1084).  expSE3 uses xi[5] where the reference reads xi[45] (:154).
  * No host synchronisation: the factor-graph index structures are built on the

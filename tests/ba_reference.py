@@ -1,0 +1,462 @@
+"""The plain dense bundle adjustment (pvo_ba) against fp64: regimes, the reduced pose system and its error bound, admission of a case.
+
+Everything the calibration tests' yardstick already has is reused from tests/calib_reference.py: the closed-form fp64 Jacobians
+(`pixel_jacobians`), the fp64 assembly (`fields(..., assembly="fp64")`), the step (`step` with free_mask = 0 is the plain step), and
+the comparison with a bound derived from the case's own sensitivity (`sensitivity`, `within`, `relchange`, `floors`).  Added here:
+
+    regime_window      window_general's recipe with ONE property changed per regime (REGIMES), on any graph (GRAPHS)
+    reduced_system     (S, rhs): the undamped A - E Q E^T and its right-hand side in fp64 - the first half of rgbd_reference.gn_step
+    reduced_abs        the same sums with every addend replaced by its magnitude: T, what a summation error is relative to
+    decode_sys         the device's 64-bit fixed-point system -> fp64
+    sys_bound          (n_add + 16) 2^-24 T + n_fix 2^-29 per entry, n_add and n_fix read off pvo_amd/csrc/ba.hip (see n_add)
+    case / admission   a (graph, regime, damping) triple with its fp64 step, s_case and the conditions it must meet to be used on the GPU
+
+ADMISSION (tests/test_ba_fp64_host.py asserts it for every name in ADMITTED, tests/test_ba_fp64_gpu.py runs exactly those):
+  * 4 s_case <= 2e-3 for dx and for dz - the cap of tests/test_ba_calib_gpu.py; a case this sensitive is replaced, not loosened;
+  * in `behind` no pixel of any edge has fp64 |Z - MIN_DEPTH| < 1e-3, so that the fp32 and the fp64 mask coincide (the generator
+    nudges the starting disparities until the count is 0);
+  * the fp32 restatement (fields(..., assembly="oracle") -> step) lies within HALF of the bound 4 s_case + floors, and its reduced
+    system within sys_bound of the fp64 one - room for a device that sums in another order.
+
+Regimes and cases LEFT OUT, by that rule or by the issue's trials (no cap is raised for any of them):
+  * a far scene (disparities ~0.01): s_case(dz) = 0 under the floor while the fp32 restatement is above it - no bound to hold to;
+  * fx = 725 / 8 on a 9 x 12 map (a 7 degree field of view): s_case(dx) = 4e-3;
+  * the S-A sized window (10 x 30 x 101, radius 3): s_case(dx) = 1.0e-3, four times that misses the cap;
+  * `light` (weights and eta x 2^-10) under either damping: the reduced entries (7e-2) lie under ep, s_case(dz) = 0 under the
+    floor, and the fp32 restatement uses 0.97 - 0.99 of the bound where half is allowed;
+  * `behind` on the one-chain (32 frames), global-memory (64) and blocked (40, radius 6) graphs: s_case(dx) >= 5.4e-4, 1.4e-3 and
+    1.5e-3 over the seeds tried (1..30, 1..9, 1..9) - the backward chain's scale is barely held; `behind` runs on the dense solve
+    at 5 and 29 free poses and on the partitioned one (seeds 8 and 27 of the 29- and 39-pose chains, the ones that meet the cap);
+  * `control` under the GLOBAL damping at 29 / 31 / 39 free poses (s_case(dx) 5.7e-4, 2.0e-3, 5.2e-4) and on the blocked graph
+    (6.4e-4): those run under (1e-4, 0.1); the global damping is held on the tiny windows, at 5 poses, at 63 poses and at S-B size;
+  * `behind` at S-B size: s_case(dx) = 9e-3;
+  * `behind` under the GLOBAL damping (tiny window and 5 poses): it meets the cap, but the mutation lm = 0 stays inside the bound
+    (0.6 and 0.3 of it) - steps of 0.7 on which lm = 1e-5 cannot be seen; `behind` runs under (1e-4, 0.1);
+  * two chained `behind` steps at seed 7: the chain's s_case(dx) = 1.1e-3; seed 9 of the same window meets the cap (3.7e-4) and
+    keeps every pixel 2.7e-3 away from the mask after the first step."""
+import numpy as np
+
+import calib_reference as C
+from oracle import oracle as O
+
+DAMPINGS = {"local": (1e-4, 0.1), "global": (1e-5, 1e-2)}      # the frontend's and the global BA's (factor_graph.py: lm=1e-5, ep=1e-2)
+CAP = 2e-3
+NEAR = 1e-3
+
+# regime -> the motion between frames (None: GENERAL_XI); the other changes are in regime_window
+REGIMES = {
+    "control": None,
+    "rotation_only": (1e-3, 5e-4, 1e-3, 0.02, 0.03, 0.01),      # Jz is tiny: Q ~ 1 / eta
+    "big_rotation": (0.05, 0.02, 0.02, 0.1, 0.25, 0.15),        # steps of ~0.4
+    "sideways": (0.3, 0.1, 0.0, 0.0, 0.02, 0.0),
+    "behind": (0.0, 0.0, -0.35, 0.0, 0.0, 0.0),                 # ground-truth disparities 0.5 - 2.5: some Z < MIN_DEPTH
+    "sparse_weights": None,                                     # half the weights exactly 0, a quarter x 1e-3
+    "eta_wide": None,                                           # eta = 10^U(-6, 0) per pixel
+    "heavy": None,                                              # weights and eta x 2^26
+    "light": None,                                              # weights and eta x 2^-10
+}
+
+
+CLOSURE_WEIGHT = 0.2
+
+
+def _closures(far):
+    far = list(far)
+    return [1] * len(far) + far, far + [1] * len(far)
+
+
+# graph -> regime_window's shape arguments; the sizes at which pvo_ba_finish picks each solve form (solve_form, ba.hip) are the ones
+# tests/test_geom_ba_gpu.py reaches them with
+GRAPHS = {
+    "tiny": dict(F=6, ht=9, wd=12, radius=2),
+    "hw264": dict(F=6, ht=12, wd=22, radius=2),                 # a partial second chunk
+    "hw273": dict(F=6, ht=13, wd=21, radius=2),                 # HW & 3 != 0
+    "dense5": dict(F=6, ht=8, wd=10, radius=2),                 # dense matrix-core solve, 5 free poses
+    "dense29": dict(F=30, ht=8, wd=10, radius=2),               # ... and its limit, 29
+    "chain31": dict(F=32, ht=8, wd=10, radius=2, closures=_closures(range(18, 31))),      # a separator too wide: one chain
+    "twin39": dict(F=40, ht=8, wd=10, radius=2),                # partitioned
+    "gmem63": dict(F=64, ht=8, wd=10, radius=2, closures=_closures(range(52, 62))),       # envelope beyond LDS: global memory
+    "blocked39": dict(F=40, ht=8, wd=10, radius=6),             # E > 8 P: dense in 48 x 48 blocks
+    "sb": dict(F=8, ht=48, wd=64, radius=3),                    # S-B: 36 edges
+    # `behind` on a long chain: the seeds (of 1..30 tried) at which the window meets the cap
+    "dense29_s8": dict(F=30, ht=8, wd=10, radius=2, seed=8),
+    "twin39_s27": dict(F=40, ht=8, wd=10, radius=2, seed=27),
+    "tiny_s9": dict(F=6, ht=9, wd=12, radius=2, seed=9),        # `behind`, two chained steps: the seed (of 1..24) whose chain meets the cap
+}
+
+
+def regime_window(name, seed=7, F=6, ht=9, wd=12, radius=2, t0=1, closures=None, scale=None):
+    """calib_reference.window_general's recipe (the same draws in the same order: `control` IS window_general) with the one change
+    the regime names; closures = (ii, jj) appends edges to the radius graph, with CLOSURE_WEIGHT of the recipe's weight (the
+    loop-closure edges of tests/test_geom_ba_gpu.py carry 0.2 rand: a wide-baseline edge at full weight makes the window's step
+    too sensitive to admit, s_case(dx) = 1.9e-3 at 32 frames); scale: weights and eta times it (a power of two).  Same dict."""
+    import torch
+    import rgbd_reference as R
+    from pvo_amd.geom.se3 import SE3
+    g = torch.Generator().manual_seed(seed)
+    intr = torch.tensor([wd * 0.625, wd * 0.7, wd / 2.0 - 0.3, ht / 2.0 + 0.4])
+    xi = torch.tensor(REGIMES[name] or C.GENERAL_XI)
+    poses_gt = torch.stack([SE3.exp(k * xi).data for k in range(F)], 0)
+    lo, span = (0.5, 2.0) if name == "behind" else (0.2, 0.8)
+    low = torch.rand(1, 1, 6, 8, generator=g) * span + lo
+    disps_gt = torch.nn.functional.interpolate(low, size=(ht, wd), mode="bilinear", align_corners=True)[0, 0][None].repeat(F, 1, 1)
+    ii, jj = R.radius_graph(F, radius)
+    if closures is not None:
+        ii, jj = np.concatenate([ii, np.asarray(closures[0], np.int64)]), np.concatenate([jj, np.asarray(closures[1], np.int64)])
+    ii, jj = torch.as_tensor(ii), torch.as_tensor(jj)
+    E = ii.shape[0]
+    c, _ = O.reproject(poses_gt.numpy(), disps_gt.numpy(), intr[None].repeat(F, 1).numpy(), ii.numpy(), jj.numpy())
+    target = torch.from_numpy(c) + 0.1 * torch.randn(E, ht, wd, 2, generator=g)
+    weight = torch.rand(E, ht, wd, 2, generator=g) + 0.5
+    poses0 = torch.stack([poses_gt[max(k - 1, 0)] for k in range(F)], 0)
+    disps0 = torch.ones(F, ht, wd) + 0.2 * torch.rand(F, ht, wd, generator=g)
+    K = int(np.unique(np.concatenate([np.arange(t0, F), ii.numpy()])).shape[0])
+    eta = torch.full((K, ht, wd), 1e-4) + 0.01 * torch.rand(K, ht, wd, generator=g)
+    # the regime's own draws come after the recipe's
+    if name == "sparse_weights":
+        u = torch.rand(E, ht, wd, 2, generator=g)
+        weight = torch.where(u < 0.5, torch.zeros_like(weight), torch.where(u < 0.75, weight * 1e-3, weight))
+    if name == "eta_wide":
+        eta = 10.0 ** (-6.0 * torch.rand(K, ht, wd, generator=g))
+    if closures is not None:
+        weight[E - len(closures[0]):] *= CLOSURE_WEIGHT
+    if name in ("heavy", "light") or scale is not None:
+        k = scale if scale is not None else (2.0 ** 26 if name == "heavy" else 2.0 ** -10)
+        weight, eta = weight * k, eta * k
+    s = dict(intr=intr, poses=poses0, disps=disps0, target=target.permute(0, 3, 1, 2).contiguous(),
+             weight=weight.permute(0, 3, 1, 2).contiguous(), eta=eta, ii=ii.contiguous(), jj=jj.contiguous(), t0=t0, t1=F)
+    # no pixel on the fence between the fp32 and the fp64 mask: in `behind`, and wherever a long loop-closure edge looks backwards
+    # (a window without such pixels - every tiny regime but `behind` - is left as drawn)
+    for _ in range(64):
+        near = np.abs(edge_depths(s) - C.MIN_DEPTH) < NEAR
+        if not near.any():
+            break
+        d = s["disps"].reshape(F, -1)
+        for e, x in zip(*np.nonzero(near)):
+            d[int(ii[e]), int(x)] += 2.0 ** -6
+    assert near_count(s) == 0
+    return s
+
+
+def edge_depths(s):
+    """Z of every edge's pixels in the target frame, fp64 from the stored fp32 operands [E,HW] (pixel_jacobians' expression)"""
+    a = C.scene_args(s)
+    poses, disps = a[0].astype(np.float64), a[1].astype(np.float64)
+    fx, fy, cx, cy = (float(v) for v in a[2].astype(np.float64))
+    F, ht, wd = disps.shape
+    v_, u_ = np.meshgrid(np.arange(ht, dtype=np.float64), np.arange(wd, dtype=np.float64), indexing="ij")
+    px, py = (u_.reshape(-1) - cx) / fx, (v_.reshape(-1) - cy) / fy
+    Z = np.zeros((len(a[6]), ht * wd))
+    for e, (i, j) in enumerate(zip(a[6], a[7])):
+        Rm, t = C.rel_pose(poses[int(i)], poses[int(j)])
+        Z[e] = Rm[2, 0] * px + Rm[2, 1] * py + Rm[2, 2] + disps[int(i)].reshape(-1) * t[2]
+    return Z
+
+
+def near_count(s):
+    return int((np.abs(edge_depths(s) - C.MIN_DEPTH) < NEAR).sum())
+
+
+def masked_fraction(s):
+    return float((edge_depths(s) < C.MIN_DEPTH).mean())
+
+
+# ------------------------------------------------------------------------------------------------ the reduced system
+def _reduce(f, eta, ii, jj, t0, t1, magnitudes=False, q_from=None, stats=None):
+    """calib_reference.step up to its damping line -> (A [6P,6P], b [6P]).  magnitudes: the fields are sums of magnitudes and the
+    Schur part is ADDED (every addend of A - E Q E^T by its absolute value); q_from: the Cii that Q is formed from"""
+    ii, jj = np.asarray(ii, np.int64), np.asarray(jj, np.int64)
+    Hs, vs, Eii, Eij, Cii, bz = (f[k] for k in C.FIELDS[:6])
+    HW, E, P = Cii.shape[1], ii.shape[0], t1 - t0
+    n6 = 6 * P
+    A, b = np.zeros((n6, n6)), np.zeros(n6)
+    blk = lambda p: slice(6 * p, 6 * p + 6)
+    for e in range(E):
+        pi, pj = int(ii[e]) - t0, int(jj[e]) - t0
+        iok, jok = 0 <= pi < P, 0 <= pj < P
+        if iok:
+            A[blk(pi), blk(pi)] += Hs[0, e]; b[blk(pi)] += vs[0, e]
+        if jok:
+            A[blk(pj), blk(pj)] += Hs[3, e]; b[blk(pj)] += vs[1, e]
+        if iok and jok:
+            A[blk(pi), blk(pj)] += Hs[1, e]; A[blk(pj), blk(pi)] += Hs[2, e]
+    kx = np.unique(np.concatenate([np.arange(t0, t1, dtype=np.int64), ii]))
+    K = kx.shape[0]
+    kidx = {int(fr): k for k, fr in enumerate(kx)}
+    Cq = Cii if q_from is None else q_from
+    Cs, w, Ei = np.zeros((K, HW)), np.zeros((K, HW)), np.zeros((P, 6, HW))
+    for e in range(E):
+        k = kidx[int(ii[e])]
+        Cs[k] += Cq[e]; w[k] += bz[e]
+        if 0 <= int(ii[e]) - t0 < P:
+            Ei[int(ii[e]) - t0] += Eii[e]
+    eta = np.asarray(eta, np.float64).reshape(-1, HW)
+    add = np.broadcast_to(eta, (K, HW)).copy() if eta.shape[0] == 1 else eta.copy()
+    assert add.shape == (K, HW)
+    Q = 1.0 / (Cs + add)
+    rows = [[] for _ in range(K)]
+    for p in range(P):
+        rows[kidx[t0 + p]].append((p, Ei[p]))
+    for e in range(E):
+        rows[kidx[int(ii[e])]].append((int(jj[e]) - t0, Eij[e]))
+    sign = 1.0 if magnitudes else -1.0
+    if stats is not None:
+        stats["largest"] = max(float(np.abs(Hs).max()), float(np.abs(vs).max()))
+    for k in range(K):
+        live = [(p, M) for p, M in rows[k] if 0 <= p < P]
+        if not live:
+            continue
+        M = np.concatenate([m_ for _, m_ in live], 0)
+        S = (M * Q[k]) @ M.T
+        v = M @ (Q[k] * w[k])
+        if stats is not None:                                                  # (a frame's Schur sums: no chunk's addend is larger while HW <= 256)
+            stats["largest"] = max(stats.get("largest", 0.0), float(np.abs(S).max()), float(np.abs(v).max()))
+        for x, (pa, _) in enumerate(live):
+            b[blk(pa)] += sign * v[6 * x:6 * x + 6]
+            for y, (pb, _) in enumerate(live):
+                A[blk(pa), blk(pb)] += sign * S[6 * x:6 * x + 6, 6 * y:6 * y + 6]
+    return A, b
+
+
+def reduced_system(f, s, stats=None):
+    """(S [6P,6P], rhs [6P]) of the window `s` from the assembled fields `f`: the undamped A - E Q E^T and v - E Q w in fp64.
+    stats (a dict) receives "largest": the largest magnitude of one fixed-point addend (an edge's pose sums, a frame's Schur sums)"""
+    a = C.scene_args(s)
+    return _reduce(f, a[5], a[6], a[7], a[8], a[9], stats=stats)
+
+
+def reduced_abs(f, s):
+    """T = (T_S, T_rhs): reduced_system's sums with every addend replaced by its absolute value, for the pose part (per edge,
+    residual row and pixel: |w Ja Jb|, |w r Ja|) and the Schur part (|E| Q |E|^T and |E| Q |w| with |E|, |w| the per-frame sums of
+    per-row magnitudes |w Jz J|, |w r Jz|; Q itself, a sum of non-negative terms, is the one of `f`)."""
+    a = C.scene_args(s)
+    J = C.pixel_jacobians(a[0], a[1], a[2], a[3], a[4], a[6], a[7])
+    w, r, Ji, Jj, Jz = J["w"], np.abs(J["r"]), np.abs(J["Ji"]), np.abs(J["Jj"]), np.abs(J["Jz"])
+    es = lambda spec, *ops: np.einsum(spec, *ops, optimize=True)
+    m = dict(Hs=np.stack([es("ecx,ecax,ecbx->eab", w, A, B) for A, B in ((Ji, Ji), (Ji, Jj), (Jj, Ji), (Jj, Jj))]),
+             vs=np.stack([es("ecx,ecx,ecax->ea", w, r, A) for A in (Ji, Jj)]),
+             Eii=es("ecx,ecx,ecax->eax", w, Jz, Ji), Eij=es("ecx,ecx,ecax->eax", w, Jz, Jj),
+             Cii=es("ecx,ecx,ecx->ex", w, Jz, Jz), bz=es("ecx,ecx,ecx->ex", w, r, Jz))
+    return _reduce(m, a[5], a[6], a[7], a[8], a[9], magnitudes=True, q_from=f["Cii"])
+
+
+def block_support(s):
+    """[P,P] bool, lower block triangle: the 6 x 6 blocks of the reduced system some addend reaches - the diagonal, the pose pairs an
+    edge joins, and the pairs of poses that meet in one depth frame's rows (the frame's own pose and its out-edges' targets)"""
+    ii, jj, t0, t1 = s["ii"].numpy(), s["jj"].numpy(), s["t0"], s["t1"]
+    P = t1 - t0
+    sup = np.eye(P, dtype=bool)
+    by_frame = {}
+    for i, j in zip(ii, jj):
+        by_frame.setdefault(int(i), {int(i) - t0}).add(int(j) - t0)
+    for ps in by_frame.values():
+        ps = [p for p in ps if 0 <= p < P]
+        for a in ps:
+            for b in ps:
+                sup[max(a, b), min(a, b)] = True
+    return sup
+
+
+def fix_addends(s):
+    """n_fix per block (S [P,P]) and per pose (rhs [P]): the fixed-point addends behind an entry - one per edge that reaches it (the
+    assembly's chunk sums are added in fp64 and quantised once per edge, ba.hip:891-893) and one per (depth frame, 256-pixel chunk)
+    whose rows hold both poses (scatter_tile, ba.hip:678-681)"""
+    ii, jj, t0, t1 = s["ii"].numpy(), s["jj"].numpy(), s["t0"], s["t1"]
+    P, HW = t1 - t0, s["disps"].shape[1] * s["disps"].shape[2]
+    chunks = (HW + SCHUR_CHUNK - 1) // SCHUR_CHUNK
+    nS, nr = np.zeros((P, P)), np.zeros(P)
+    by_frame = {}
+    for i, j in zip(ii, jj):
+        pi, pj = int(i) - t0, int(j) - t0
+        for p in (pi, pj):
+            if 0 <= p < P:
+                nS[p, p] += 1; nr[p] += 1
+        if 0 <= pi < P and 0 <= pj < P:
+            nS[max(pi, pj), min(pi, pj)] += 1
+        by_frame.setdefault(int(i), {pi}).add(pj)
+    for ps in by_frame.values():
+        ps = [p for p in ps if 0 <= p < P]
+        for a in ps:
+            nr[a] += chunks
+            for b in ps:
+                if a >= b:
+                    nS[a, b] += chunks
+    return nS, nr
+
+
+def max_out_degree(s):
+    return int(np.bincount(s["ii"].numpy()).max())
+
+
+# fp32 additions behind one fixed-point addend, read off pvo_amd/csrc/ba.hip:
+ASSEMBLE_CHUNK = 512      # kChunkA = 256 kPPT, kPPT = 2 pixels per thread (ba.hip:61-62)
+SCHUR_CHUNK = 256         # kSchurPix (ba.hip:622); pvo_ba_local keeps 256-pixel chunks while (HW / 256) (P + 1) <= 192 (ba.hip:3974-3983)
+
+
+def n_add(deg):
+    """the longest chain of fp32 additions behind one fixed-point addend, for a window whose frames have at most `deg` out-edges:
+      pose part   2 kPPT = 4 per thread (two pixels, rows u and v: pixel_terms, ba.hip:287,312) + 6 steps of the wave's reduce-scatter
+                  (ba.hip:499-526) + 2 across the four waves (ba.hip:538) = 12; the chunks of an edge are then added in fp64 (ba.hip:891);
+      Schur part  64 per wave - a quarter of a 256-pixel chunk, 16 MFMAs of K = 4 (schur_pass, ba.hip:700-717) - + 2 across the waves
+                  (ba.hip:733-734) = 66, on operands that are sums over the frame's out-edges themselves: Ei on either side, or w
+                  (deg - 1 each, depth_pixel ba.hip:582-589), C + eta (deg, ba.hip:584,603), the division and the product E Q (2)."""
+    return max(12, 66 + 2 * (deg - 1) + deg + 2)
+
+
+def sys_bound(s, T):
+    """per entry of (S, rhs): (n_add + 16) 2^-24 T + n_fix 2^-29.  16 units cover the per-pixel products - the 2^-20 relative
+    perturbation s_case is defined with; 2^-29 is half a unit of the 2^-28 fixed-point grid (fix_add, ba.hip:52-58)."""
+    TS, Tr = T
+    nS, nr = fix_addends(s)
+    k = (n_add(max_out_degree(s)) + 16) * 2.0 ** -24
+    return k * TS + np.kron(nS, np.ones((6, 6))) * 2.0 ** -29, k * Tr + np.repeat(nr, 6) * 2.0 ** -29
+
+
+def decode_sys(sys, P):
+    """the device's fixed-point system, int64 [(6P)^2 + 6P] (row-major S, then rhs; units of 2^-28) -> (S [6P,6P], rhs [6P]) in fp64.
+    Only the LOWER BLOCK TRIANGLE of `sys` is ever written - confirmed in the code: pose_block_scatter adds an edge's (i, j) block at
+    (max, min) only (ba.hip:364-371) and scatter_tile keeps an entry only if its block row is not above its block column
+    (ba.hip:675-679); inside a diagonal block both triangles are written.  So S is read from the lower block triangle and mirrored;
+    the words above it are not read here: tests/test_ba_fp64_gpu.py asserts that they are 0."""
+    v = np.asarray(sys.cpu().numpy() if hasattr(sys, "cpu") else sys, np.int64)
+    n6 = 6 * P
+    S = v[:n6 * n6].astype(np.float64).reshape(n6, n6) * 2.0 ** -28
+    low = np.kron(np.tril(np.ones((P, P))), np.ones((6, 6))) > 0
+    strict = np.kron(np.tril(np.ones((P, P)), -1), np.ones((6, 6))) > 0
+    L = np.where(low, S, 0.0)
+    return L + np.where(strict, S, 0.0).T, v[n6 * n6:n6 * n6 + n6].astype(np.float64) * 2.0 ** -28
+
+
+def lower_blocks(P):
+    """[6P,6P] bool: the entries of the lower block triangle"""
+    return np.kron(np.tril(np.ones((P, P))), np.ones((6, 6))) > 0
+
+
+# ------------------------------------------------------------------------------------------------ cases
+_windows, _cases = {}, {}
+
+
+def window_of(graph, regime):
+    """-> (window, fp64 fields); built once, shared, never modified"""
+    if (graph, regime) not in _windows:
+        s = regime_window(regime, **GRAPHS[graph])
+        a = C.scene_args(s)
+        _windows[(graph, regime)] = (s, C.fields(a[0], a[1], a[2], a[3], a[4], a[6], a[7], assembly="fp64"))
+    return _windows[(graph, regime)]
+
+
+def case(graph, regime, damping):
+    """-> dict(s, f [fp64 fields], base [the fp64 step], sc [s_case], lm, ep); once per triple"""
+    key = (graph, regime, damping)
+    if key not in _cases:
+        s, f = window_of(graph, regime)
+        lm, ep = DAMPINGS[damping]
+        base = C.scene_step(s, lm, ep, 0.1, 0, f)
+        _cases[key] = dict(s=s, f=f, base=base, sc=C.sensitivity(s, base, f, lm, ep, 0.1, 0), lm=lm, ep=ep)
+    return _cases[key]
+
+
+def share(name, got, c, frac=1.0):
+    """-> (inside, share): `got` against the case's fp64 step on dx or dz, unit by unit, within frac (4 s_case + floors); share = the
+    largest |difference| / bound over the units"""
+    base, rel = c["base"][name], 4 * c["sc"][name]
+    intr = c["s"]["intr"].numpy()
+    if not np.isfinite(np.asarray(got, np.float64)).all():
+        return False, float("inf")
+    a, b = C.units(name, got), C.units(name, base)
+    d, m, fl = np.abs(a - b).max(1), np.abs(b).max(1), C.floors(name, base, intr)
+    bound = rel * m + fl
+    ok, _ = C.within(name, got, base, rel, intr)
+    sh = float((d / np.where(bound > 0, bound, 1.0)).max())
+    return bool(ok and np.all(d <= frac * bound)), sh
+
+
+def restatement(c):
+    """the fp32 restatement's step for the case: fields(..., assembly="oracle") -> step"""
+    a = C.scene_args(c["s"])
+    f = C.fields(a[0], a[1], a[2], a[3], a[4], a[6], a[7], assembly="oracle")
+    return f, C.scene_step(c["s"], c["lm"], c["ep"], 0.1, 0, f)
+
+
+def mutations(c):
+    """name -> the fp64 step of a deliberately wrong variant of the case, each of a kind the 1e-4 tolerance of the fp32 oracle tests
+    lets through: Eij x 1.001, the ij blocks of Hs x 1.001 (Hs[1] and its mirror Hs[2]), lm = 0, the last pixel of Cii / bz zeroed"""
+    s, f, lm, ep = c["s"], c["f"], c["lm"], c["ep"]
+    step = lambda g, lm_=lm: C.scene_step(s, lm_, ep, 0.1, 0, g)
+    Hs = f["Hs"].copy()
+    Hs[1] *= 1.001
+    Hs[2] = np.swapaxes(Hs[1], 1, 2)
+    Cz, bz = f["Cii"].copy(), f["bz"].copy()
+    Cz[:, -1], bz[:, -1] = 0.0, 0.0
+    return dict(Eij=step(dict(f, Eij=f["Eij"] * 1.001)), Hs_ij=step(dict(f, Hs=Hs)), lm0=step(f, 0.0), last_pixel=step(dict(f, Cii=Cz, bz=bz)))
+
+
+def unmasked_step(c):
+    """the case's step with MIN_DEPTH disabled: every pixel counts, whatever its Z"""
+    a = C.scene_args(c["s"])
+    keep = C.MIN_DEPTH
+    C.MIN_DEPTH = -np.inf
+    try:
+        f = C.fields(a[0], a[1], a[2], a[3], a[4], a[6], a[7], assembly="fp64")
+    finally:
+        C.MIN_DEPTH = keep
+    return C.scene_step(c["s"], c["lm"], c["ep"], 0.1, 0, f)
+
+
+_chains = {}
+
+
+def chain(graph, regime, damping, iters=2):
+    """`iters` chained fp64 steps (poses and depths pass through fp32 between them, as the device's do) with the chain's own
+    sensitivity: every step's fields perturbed, four seeded draws -> case's dict"""
+    key = (graph, regime, damping, iters)
+    if key not in _chains:
+        s, _ = window_of(graph, regime)
+        a = C.scene_args(s)
+        lm, ep = DAMPINGS[damping]
+        base = C.ba_calib(*a, iters, lm, ep, 0.1, 0, assembly="fp64")
+        sc = dict(dx=0.0, dz=0.0)
+        for seed in (0, 10, 20, 30):
+            r = C.ba_calib(*a, iters, lm, ep, 0.1, 0, perturb_seed=seed, assembly="fp64")
+            for k in sc:
+                sc[k] = max(sc[k], C.relchange(k, r[k], base[k], a[2]))
+        mid = C.ba_calib(*a, iters - 1, lm, ep, 0.1, 0, assembly="fp64")      # the state the last step starts from
+        import torch
+        near = near_count(dict(s, poses=torch.from_numpy(mid["poses"]), disps=torch.from_numpy(mid["disps"])))
+        _chains[key] = dict(s=s, base=base, sc=sc, lm=lm, ep=ep, near_mid=near)
+    return _chains[key]
+
+
+FIX_LIMIT = 3.0e10      # fix_add's range check per addend (ba.hip:54); the sums live in int64 units of 2^-28: |sum| < 2^35
+
+
+def overflow_window():
+    """the `control` window with weights and eta times 2^k, k chosen BY THE REFERENCE such that the largest fp64 diagonal entry of S
+    lies in [2^35, 2^36) - beyond what the fixed-point sum can hold - while every single addend stays below fix_add's limit
+    -> (window, k, largest diagonal entry, largest addend)"""
+    for k in range(20, 40):
+        s = regime_window("control", scale=2.0 ** k, **GRAPHS["tiny"])
+        a = C.scene_args(s)
+        st = {}
+        S, _ = reduced_system(C.fields(a[0], a[1], a[2], a[3], a[4], a[6], a[7], assembly="fp64"), s, st)
+        d = float(np.diag(S).max())
+        if 2.0 ** 35 <= d < 2.0 ** 36:
+            assert st["largest"] < FIX_LIMIT
+            return s, k, d, st["largest"]
+    raise AssertionError("no scale puts the diagonal into [2^35, 2^36)")
+
+
+# ------------------------------------------------------------------------------------------------ what runs on the GPU
+# (graph, regime, damping) triples that meet the admission rule; tests/test_ba_fp64_host.py asserts it for every one of them.
+TINY = [("tiny", r, d) for r in REGIMES if r != "light" for d in DAMPINGS if (r, d) != ("behind", "global")]
+SHAPES = [(g, "control", d) for g in ("hw264", "hw273") for d in DAMPINGS]
+# cut C under every solve form, at the graph that selects it (GRAPHS): the global BA's damping where the case meets the cap under it
+FORMS = [("dense5", "control", "global"), ("dense5", "behind", "local"),
+         ("dense29", "control", "local"), ("dense29_s8", "behind", "local"),
+         ("chain31", "control", "local"),
+         ("twin39", "control", "local"), ("twin39_s27", "behind", "local"),
+         ("gmem63", "control", "global"),
+         ("blocked39", "control", "local"),
+         ("sb", "control", "global")]
+ADMITTED = TINY + SHAPES + FORMS
+TWO_STEPS = [("tiny", "control", "local"), ("tiny_s9", "behind", "local")]

@@ -225,12 +225,13 @@ def gn_step_calib(poses, disps, intr, target, weight, eta, ii, jj, t0, t1, lm, e
     return step(f, poses, disps, intr, eta, ii, jj, t0, t1, lm, ep, ep_c, free_mask)
 
 
-def ba_calib(poses, disps, intr, target, weight, eta, ii, jj, t0, t1, iters, lm, ep, ep_c=0.1, free_mask=15, perturb_seed=None):
+def ba_calib(poses, disps, intr, target, weight, eta, ii, jj, t0, t1, iters, lm, ep, ep_c=0.1, free_mask=15, perturb_seed=None, assembly="oracle"):
     """`iters` steps; poses, disps and intrinsics pass through fp32 between steps, as the device's do -> the last step's dict.
-    perturb_seed: every step's assembled fields are `perturbed` (seed + step index) - the sensitivity of a chain of steps"""
+    perturb_seed: every step's assembled fields are `perturbed` (seed + step index) - the sensitivity of a chain of steps.
+    assembly: `fields`' (the default is the oracle's fp32 pixel arithmetic; "fp64" with free_mask = 0 is a chain of plain fp64 steps)"""
     out = None
     for it in range(iters):
-        f = fields(poses, disps, intr, target, weight, ii, jj)
+        f = fields(poses, disps, intr, target, weight, ii, jj, assembly)
         if perturb_seed is not None:
             f = perturbed(f, perturb_seed + it)
         out = step(f, poses, disps, intr, eta, ii, jj, t0, t1, lm, ep, ep_c, free_mask)
