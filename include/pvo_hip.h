@@ -82,7 +82,9 @@ const char* pvo_last_hip_error(void);
  * pvo_reproject_rig / pvo_reproject_motion_rig / pvo_graph_update_rig; still 106, map export: no existing struct changed - new struct
  * pvo_map_points_args (pvo_map_points_args_size() reports its size) and new entry points pvo_map_points_args_size /
  * pvo_map_points_workspace_bytes / pvo_map_points; still 106, uncertainty: no struct changed - new entry points pvo_ba_sigma /
- * pvo_ba_uncertainty; still 106, calibration: no struct changed - new entry points pvo_ba_calib_workspace_bytes / pvo_ba_calib): a caller
+ * pvo_ba_uncertainty; still 106, calibration: no struct changed - new entry points pvo_ba_calib_workspace_bytes / pvo_ba_calib; still 106, surface
+ * reconstruction: no existing struct changed - new structs pvo_tsdf_integrate_args / pvo_tsdf_mesh_args (their *_args_size() report the
+ * sizes) and new entry points pvo_tsdf_integrate[_args_size, _workspace_bytes] / pvo_tsdf_mesh[_args_size, _workspace_bytes]): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -672,6 +674,105 @@ typedef struct pvo_map_points_args {
 size_t pvo_map_points_args_size(void);
 size_t pvo_map_points_workspace_bytes(int N, int ht, int wd);
 int pvo_map_points(const pvo_map_points_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Dense surface reconstruction: TSDF fusion and mesh extraction              */
+/* ------------------------------------------------------------------------- */
+
+/* pvo_tsdf_integrate: the keyframes ix[0..N), IN THAT ORDER, accumulated into a caller-owned truncated signed distance volume
+ * (no counterpart in the reference, which stops at the viewer's point cloud).  All pointers are device pointers, dense, row-major.
+ *
+ *   Volume, updated in place; a zeroed volume is an empty one:
+ *     tsdf f32 [nz,ny,nx]   the weighted mean of the truncated distances, in [-1, 1] (units of trunc)
+ *     wsum f32 [nz,ny,nx]   the sum of the weights
+ *     rgb  f32 [nz,ny,nx,3] or NULL: the weighted mean colour (needs images)
+ *   The centre of voxel (z,y,x) is X = origin + voxel * (x, y, z).
+ *   poses [nframes,7] world-to-camera; disps [nframes,ht,wd] fp32 inverse depth at ANY resolution with intrinsics [4] for that
+ *   resolution; ix [N] int64, an id outside [0, nframes) is skipped and never dereferenced; weight f32 [nframes,ht,wd] or NULL (= 1);
+ *   images uint8 [nframes,3,IH,IW] BGR planes or NULL, img_stride / img_offset exactly as in pvo_map_points (PVO_EINVAL where
+ *   s*(ht-1)+o >= IH or s*(wd-1)+o >= IW); trunc > 0; z_near >= 0; w_max >= 0, 0 = no cap.
+ *
+ * Per voxel, for every frame f of ix in turn, with (R, t) the frame's pose (R the matrix of the quaternion as stored):
+ *   (xc,yc,zc) = R X + t;                                   skip unless zc > z_near
+ *   u = fx*(xc/zc)+cx, v = fy*(yc/zc)+cy; ui = floor(u+0.5), vi = floor(v+0.5) (the nearest pixel);
+ *                                                           skip unless 0 <= ui < wd and 0 <= vi < ht
+ *   d = disps[f][vi][ui]                                    skip unless d is finite and > 0
+ *   w = weight[f][vi][ui]                                   skip unless w is finite and > 0
+ *   sdf = 1/d - zc, along the optical axis                  skip if sdf < -trunc
+ *   val = min(1, sdf/trunc);  Wn = W + w, rounded to fp32;  tsdf = (tsdf*W + val*w) / Wn, rgb likewise from the pixel's colour
+ *   images[f][2,1,0][s*vi+o][s*ui+o] (written as RGB);      W = Wn, or w_max where w_max > 0 and Wn > w_max.
+ * A voxel no frame contributes to is not written.  Frames apply in the order of ix and a voxel is one thread's sequential loop, so
+ * two calls with [0,1,2] and then [3,4] leave the bytes of one call with [0..4], and the same operands give the same bytes.
+ * Arithmetic is fp32 with multiply-add contraction; tests/tsdf_reference.py derives the error bound from it.
+ *
+ * Two launches (per-slot constants  voxel * R  and  R origin + t  into the workspace; one thread per voxel, x fastest, with the
+ * frame loop inside: the volume is read and written once per call whatever N is), no atomics, no allocation, no host
+ * synchronisation: capturable.  workspace: pvo_tsdf_integrate_workspace_bytes(N) bytes (PVO_EWORKSPACE otherwise), 16-byte aligned.
+ * Limits: nz*ny*nx < 2^31, ht*wd < 2^31, voxel > 0, trunc > 0, z_near >= 0, w_max >= 0, all finite, a NULL tsdf / wsum / poses / disps /
+ * intrinsics / ix, rgb without images (PVO_EINVAL).  An empty volume, N == 0 or ht*wd == 0 returns PVO_OK and does nothing. */
+typedef struct pvo_tsdf_integrate_args {
+  float* tsdf;
+  float* wsum;
+  float* rgb;
+  int nz, ny, nx;
+  float origin[3];
+  float voxel, trunc, z_near, w_max;
+  const float* poses;
+  const float* disps;
+  const float* intrinsics;
+  const int64_t* ix;
+  const float* weight;
+  int N, nframes, ht, wd;
+  const uint8_t* images;
+  int IH, IW, img_stride, img_offset;
+} pvo_tsdf_integrate_args;
+size_t pvo_tsdf_integrate_args_size(void);
+size_t pvo_tsdf_integrate_workspace_bytes(int N);
+int pvo_tsdf_integrate(const pvo_tsdf_integrate_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pvo_tsdf_mesh: a triangle mesh of the volume's zero level by naive surface nets (one vertex per cell the surface passes through,
+ * one quad per sign-changing lattice edge; no case tables).
+ *
+ *   A voxel is VALID if wsum >= min_weight and INSIDE if tsdf < 0 (exact fp32 comparisons).  Cell (cz,cy,cx), each index < dim-1,
+ *   with corners (cz+{0,1}, cy+{0,1}, cx+{0,1}), is ACTIVE if and only if all eight corners are valid and not all on one side.
+ *   Vertices, one per active cell, in raster order of the cells:
+ *     verts   f32 [vcap,3]  origin + voxel * (cell index + m), m the mean of the crossing points of the cell's sign-changing edges
+ *                           (of its 12), each linear: t = sa / (sa - sb) from corner a toward corner b
+ *     normals f32 [vcap,3] or NULL: the normalised central gradient of the eight corner values (toward increasing tsdf: outward);
+ *                           a zero gradient gives (0,0,0)
+ *     rgba    uint8 [vcap,4] or NULL: the mean of the eight corners' rgb, floor(mean + 0.5) clamped to [0,255]; (0,0,0) without an
+ *                           rgb volume; a = 255; 4-byte aligned
+ *   Faces: every active cell c in raster order, then every axis a in the order x, y, z, with (b,c') the other two taken cyclically
+ *   (x -> (y,z), y -> (z,x), z -> (x,y)), A = the cell's corner 0 and B = A + e_a: a quad is emitted if inside(A) != inside(B), the
+ *   cell's indices along b and c' are both >= 1 and the four cells Q = [c, c-e_b, c-e_b-e_c', c-e_c'] are all active.  With A inside it
+ *   becomes the triangles (Q0,Q1,Q2), (Q0,Q2,Q3), with B inside (Q0,Q2,Q1), (Q0,Q3,Q2): geometric normals point from inside to outside.
+ *     faces   int32 [fcap,3] vertex indices
+ *     counts  int32 [2], ALWAYS written: the vertices and the faces found, NOT clamped by the capacities.
+ *   A vertex or face whose index is >= its capacity is written nowhere (the protocol of pvo_map_points' frame_start[N]): the caller
+ *   sees counts > capacity and calls again with more room.
+ *
+ * Four launches (classify + per-workgroup counts; one scan; vertices, which also record cell -> vertex index in the workspace;
+ * faces), no atomics, no allocation, no host synchronisation: capturable; the same operands give the same bytes.  workspace:
+ * pvo_tsdf_mesh_workspace_bytes(nz, ny, nx) bytes (five bytes per cell; PVO_EWORKSPACE otherwise), 8-byte aligned.
+ * Limits: nz*ny*nx < 2^31, voxel > 0 and finite, min_weight not NaN, a NULL counts / tsdf / wsum, NULL verts with vcap > 0 or NULL
+ * faces with fcap > 0 (PVO_EINVAL).  A dimension < 2 has no cell: counts = (0,0), PVO_OK. */
+typedef struct pvo_tsdf_mesh_args {
+  const float* tsdf;
+  const float* wsum;
+  const float* rgb;
+  int nz, ny, nx;
+  float origin[3];
+  float voxel, min_weight;
+  int vcap, fcap;
+  float* verts;
+  float* normals;
+  uint8_t* rgba;
+  int32_t* faces;
+  int32_t* counts;
+} pvo_tsdf_mesh_args;
+size_t pvo_tsdf_mesh_args_size(void);
+size_t pvo_tsdf_mesh_workspace_bytes(int nz, int ny, int nx);
+int pvo_tsdf_mesh(const pvo_tsdf_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

@@ -23,6 +23,7 @@ HIP_SOURCES = [
     "altcorr.hip",
     "geom.hip",
     "map_points.hip",
+    "tsdf.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",

@@ -1,0 +1,436 @@
+// tsdf.hip — dense surface reconstruction: keyframe depth maps fused into a truncated signed distance volume, and a triangle mesh
+// extracted from it by naive surface nets.  Contracts: include/pvo_hip.h (pvo_tsdf_integrate, pvo_tsdf_mesh); yardstick:
+// tests/tsdf_reference.py.
+//
+//   integrate  (a) tsdf_frames_kernel     one thread per slot of ix: the frame's twelve pre-multiplied constants  voxel * R  and
+//                                         R origin + t  (so that Xc = A (x, y, z) + b for the INTEGER voxel index) and its frame id,
+//                                         -1 for an id outside [0, nframes): sixteen floats per slot in the workspace
+//              (b) tsdf_integrate_kernel  one thread per voxel, x fastest; the frame loop runs inside, so the volume is read and
+//                                         written once per call whatever N is.  The slot's constants are wave-uniform loads; a wave none
+//                                         of whose voxels projects into a frame skips its gathers.
+//   mesh       (a) mesh_classify_kernel   one thread per cell: active bit, the three quad bits, per-workgroup counts
+//              (b) mesh_scan_kernel       one workgroup: exclusive scans of both counts in index order, the two totals
+//              (c) mesh_verts_kernel      vertex of every active cell (and cell -> vertex index in the workspace)
+//              (d) mesh_faces_kernel      two triangles per quad
+//
+// No atomics anywhere: every output index is a function of the classification bits alone, and a voxel's running average is one
+// thread's sequential loop - the same operands give the same bytes.
+#include "depth_vote.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kScanThreads = 1024;
+constexpr int kFrameFloats = 16;      // per slot: A[9] row-major, b[3], frame id (as int bits), 3 unused
+
+__device__ __forceinline__ int lanes_below(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mask), 0));
+}
+
+// ------------------------------------------------------------------------------------------------------------ integrate
+
+struct Vol { float ox, oy, oz, voxel; };
+
+__global__ __launch_bounds__(64) void tsdf_frames_kernel(const float* __restrict__ poses, const int64_t* __restrict__ ix,
+                                                         float* __restrict__ fc, int N, int nframes, const Vol vol) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= N) return;
+  float* o = fc + static_cast<long long>(kFrameFloats) * b;
+  const long long f = ix[b];
+  if (f < 0 || f >= nframes) {            // never dereferenced
+    o[12] = __int_as_float(-1);
+    return;
+  }
+  const Pose G = load_pose(poses + 7 * f);
+  const Quat q = G.q;
+  // R(q) of the quaternion as stored (the matrix map_points.hip transposes)
+  const float r[9] = {1.0f - 2.0f * (q.y * q.y + q.z * q.z), 2.0f * (q.x * q.y - q.z * q.w), 2.0f * (q.x * q.z + q.y * q.w),
+                      2.0f * (q.x * q.y + q.z * q.w), 1.0f - 2.0f * (q.x * q.x + q.z * q.z), 2.0f * (q.y * q.z - q.x * q.w),
+                      2.0f * (q.x * q.z - q.y * q.w), 2.0f * (q.y * q.z + q.x * q.w), 1.0f - 2.0f * (q.x * q.x + q.y * q.y)};
+#pragma unroll
+  for (int k = 0; k < 9; ++k) o[k] = vol.voxel * r[k];
+  o[9] = (r[0] * vol.ox + r[1] * vol.oy) + r[2] * vol.oz + G.t.x;
+  o[10] = (r[3] * vol.ox + r[4] * vol.oy) + r[5] * vol.oz + G.t.y;
+  o[11] = (r[6] * vol.ox + r[7] * vol.oy) + r[8] * vol.oz + G.t.z;
+  o[12] = __int_as_float(static_cast<int>(f));
+}
+
+struct Fuse {
+  const float* disps; const float* weight; const uint8_t* images;
+  int ht, wd, IH, IW, stride, offset;
+  float trunc, z_near, w_max;
+};
+
+template <bool RGB>
+__global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(float* __restrict__ tsdf, float* __restrict__ wsum, float* __restrict__ rgb,
+                                                               const float* __restrict__ fc, const float* __restrict__ intrinsics,
+                                                               const Fuse in, int N, int nz, int ny, int nx) {
+  const long long total = static_cast<long long>(nz) * ny * nx;
+  const long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  const bool live = i < total;
+  const int x = static_cast<int>(i % nx), y = static_cast<int>((i / nx) % ny), z = static_cast<int>(i / (static_cast<long long>(nx) * ny));
+  const float xf = static_cast<float>(x), yf = static_cast<float>(y), zf = static_cast<float>(z);
+  const Intr K = load_intr(intrinsics);
+  const long long HW = static_cast<long long>(in.ht) * in.wd;
+  const long long plane = static_cast<long long>(in.IH) * in.IW;
+  float T = 0.0f, W = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+  if (live) {
+    T = tsdf[i]; W = wsum[i];
+    if (RGB) { cr = rgb[3 * i]; cg = rgb[3 * i + 1]; cb = rgb[3 * i + 2]; }
+  }
+  bool touched = false;
+  for (int b = 0; b < N; ++b) {
+    const float* __restrict__ c = fc + static_cast<long long>(kFrameFloats) * b;      // wave-uniform
+    const int f = __float_as_int(c[12]);
+    if (f < 0) continue;
+    const float zc = c[6] * xf + c[7] * yf + c[8] * zf + c[11];
+    const float xc = c[0] * xf + c[1] * yf + c[2] * zf + c[9];
+    const float yc = c[3] * xf + c[4] * yf + c[5] * zf + c[10];
+    const float u = K.fx * (xc / zc) + K.cx, v = K.fy * (yc / zc) + K.cy;
+    const int ui = pvo_floor_to_int(u + 0.5f), vi = pvo_floor_to_int(v + 0.5f);       // (saturating, NaN -> 0)
+    const bool hit = live && zc > in.z_near && ui >= 0 && ui < in.wd && vi >= 0 && vi < in.ht;
+    if (!hit) continue;                                  // (a wave without a hit branches over the gathers)
+    const long long pix = f * HW + static_cast<long long>(vi) * in.wd + ui;
+    const float d = in.disps[pix];
+    const float w = in.weight ? in.weight[pix] : 1.0f;
+    if (!(d > 0.0f && d < __builtin_inff() && w > 0.0f && w < __builtin_inff())) continue;   // (NaN fails every comparison)
+    const float sdf = 1.0f / d - zc;
+    if (sdf < -in.trunc) continue;
+    const float val = fminf(1.0f, sdf / in.trunc);
+    const float Wn = W + w;
+    T = (T * W + val * w) / Wn;
+    if (RGB) {                                           // BGR planes -> RGB
+      const uint8_t* im = in.images + 3 * plane * f + static_cast<long long>(in.stride * vi + in.offset) * in.IW + (in.stride * ui + in.offset);
+      cr = (cr * W + static_cast<float>(im[2 * plane]) * w) / Wn;
+      cg = (cg * W + static_cast<float>(im[plane]) * w) / Wn;
+      cb = (cb * W + static_cast<float>(im[0]) * w) / Wn;
+    }
+    W = (in.w_max > 0.0f && Wn > in.w_max) ? in.w_max : Wn;
+    touched = true;
+  }
+  if (touched) {
+    tsdf[i] = T; wsum[i] = W;
+    if (RGB) { rgb[3 * i] = cr; rgb[3 * i + 1] = cg; rgb[3 * i + 2] = cb; }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ mesh
+
+// flag byte of a cell: bit 0 active, bits 1-3 a quad around the edge corner 0 -> corner 0 + e_a (a = x, y, z), bit 4 corner 0 inside
+constexpr int kActive = 1, kInsideA = 16;
+
+struct Grid {
+  const float* tsdf; const float* wsum; const float* rgb;
+  int nz, ny, nx;
+  float ox, oy, oz, voxel, min_weight;
+};
+
+__device__ __forceinline__ void cell_coords(long long k, const Grid g, int& cz, int& cy, int& cx) {
+  const int mx = g.nx - 1, my = g.ny - 1;
+  cx = static_cast<int>(k % mx); cy = static_cast<int>((k / mx) % my); cz = static_cast<int>(k / (static_cast<long long>(mx) * my));
+}
+
+__device__ __forceinline__ long long voxel_index(const Grid g, int z, int y, int x) {
+  return (static_cast<long long>(z) * g.ny + y) * g.nx + x;
+}
+
+// all eight corners of the cell at (cz, cy, cx) valid; the caller keeps the cell's indices in [0, dim - 1)
+__device__ __forceinline__ bool cell_valid(const Grid g, int cz, int cy, int cx) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ok = ok && g.wsum[voxel_index(g, cz + (j >> 2), cy + ((j >> 1) & 1), cx + (j & 1))] >= g.min_weight;
+  return ok;
+}
+
+__global__ __launch_bounds__(kBlock) void mesh_classify_kernel(const Grid g, long long cells, uint8_t* __restrict__ flags,
+                                                              int* __restrict__ vcount, int* __restrict__ qcount) {
+  const int tid = threadIdx.x;
+  const long long k = static_cast<long long>(blockIdx.x) * kBlock + tid;
+  int flag = 0;
+  if (k < cells) {                        // (no early return: every wave reaches the ballots and the barrier)
+    int cz, cy, cx;
+    cell_coords(k, g, cz, cy, cx);
+    bool valid = true;
+    int inside = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const long long v = voxel_index(g, cz + (j >> 2), cy + ((j >> 1) & 1), cx + (j & 1));
+      valid = valid && g.wsum[v] >= g.min_weight;
+      inside |= (g.tsdf[v] < 0.0f ? 1 : 0) << j;
+    }
+    if (valid && inside != 0 && inside != 255) {
+      flag = kActive | ((inside & 1) ? kInsideA : 0);
+      const int c[3] = {cx, cy, cz};
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const int b = (a + 1) % 3, cc = (a + 2) % 3;
+        if ((((inside >> (1 << a)) ^ inside) & 1) == 0 || c[b] < 1 || c[cc] < 1) continue;
+        // the three other cells around the edge share it, so they are not all on one side: active = all corners valid
+        int eb[3] = {0, 0, 0}, ec[3] = {0, 0, 0};
+        eb[b] = 1; ec[cc] = 1;
+        if (cell_valid(g, cz - eb[2], cy - eb[1], cx - eb[0]) && cell_valid(g, cz - eb[2] - ec[2], cy - eb[1] - ec[1], cx - eb[0] - ec[0]) &&
+            cell_valid(g, cz - ec[2], cy - ec[1], cx - ec[0]))
+          flag |= 2 << a;
+      }
+    }
+    flags[k] = static_cast<uint8_t>(flag);
+  }
+  const unsigned long long ma = __ballot(flag & kActive);
+  const int quads = __popcll(__ballot(flag & 2)) + __popcll(__ballot(flag & 4)) + __popcll(__ballot(flag & 8));
+  __shared__ int wave_v[kBlock / 64], wave_q[kBlock / 64];
+  if ((tid & 63) == 0) { wave_v[tid >> 6] = __popcll(ma); wave_q[tid >> 6] = quads; }
+  __syncthreads();
+  if (tid == 0) {
+    vcount[blockIdx.x] = (wave_v[0] + wave_v[1]) + (wave_v[2] + wave_v[3]);
+    qcount[blockIdx.x] = (wave_q[0] + wave_q[1]) + (wave_q[2] + wave_q[3]);
+  }
+}
+
+// exclusive scans of vcount and qcount [M] in index order (thread t owns a contiguous chunk, map_points.hip's scan);
+// counts = (vertices, faces = 2 * quads), not clamped by any capacity
+__global__ __launch_bounds__(kScanThreads) void mesh_scan_kernel(const int* __restrict__ vcount, const int* __restrict__ qcount,
+                                                                 int* __restrict__ vbase, int* __restrict__ qbase,
+                                                                 int32_t* __restrict__ counts, int M) {
+  const int tid = threadIdx.x;
+  const int chunk = (M + kScanThreads - 1) / kScanThreads;
+  const int lo = static_cast<int>(min(static_cast<long long>(tid) * chunk, static_cast<long long>(M))), hi = min(lo + chunk, M);
+  __shared__ int buf[2][kScanThreads];
+  for (int pass = 0; pass < 2; ++pass) {
+    const int* __restrict__ cnt = pass ? qcount : vcount;
+    int* __restrict__ base = pass ? qbase : vbase;
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += cnt[i];
+    int cur = 0;
+    buf[0][tid] = s;
+    __syncthreads();
+#pragma unroll
+    for (int off = 1; off < kScanThreads; off <<= 1) {      // Hillis-Steele, inclusive
+      buf[cur ^ 1][tid] = buf[cur][tid] + (tid >= off ? buf[cur][tid - off] : 0);
+      cur ^= 1;
+      __syncthreads();
+    }
+    int run = buf[cur][tid] - s;
+    for (int i = lo; i < hi; ++i) { base[i] = run; run += cnt[i]; }
+    if (tid == kScanThreads - 1) counts[pass] = pass ? 2 * buf[cur][tid] : buf[cur][tid];
+    __syncthreads();                                        // buf is reused by the second pass
+  }
+}
+
+struct MeshOut { float* verts; float* normals; uint8_t* rgba; int32_t* faces; int vcap, fcap; };
+
+__global__ __launch_bounds__(kBlock) void mesh_verts_kernel(const Grid g, long long cells, const uint8_t* __restrict__ flags,
+                                                           const int* __restrict__ vbase, int32_t* __restrict__ vidx, const MeshOut out) {
+  const int tid = threadIdx.x;
+  const long long k = static_cast<long long>(blockIdx.x) * kBlock + tid;
+  const bool active = k < cells && (flags[k] & kActive);
+  const unsigned long long m = __ballot(active);
+  __shared__ int wave_n[kBlock / 64];
+  if ((tid & 63) == 0) wave_n[tid >> 6] = __popcll(m);
+  __syncthreads();
+  if (!active) return;
+  int idx = vbase[blockIdx.x] + lanes_below(m);
+  for (int w = 0; w < (tid >> 6); ++w) idx += wave_n[w];
+  vidx[k] = idx;                          // (also beyond the capacity: the faces name the vertex by its index)
+  if (idx >= out.vcap) return;            // written nowhere; the caller sees counts[0] > vcap
+  int cz, cy, cx;
+  cell_coords(k, g, cz, cy, cx);
+  float s[8];
+  long long at[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    at[j] = voxel_index(g, cz + (j >> 2), cy + ((j >> 1) & 1), cx + (j & 1));
+    s[j] = g.tsdf[at[j]];
+  }
+  // mean of the crossings of the sign-changing edges, in cell coordinates; edges in the order x (from corners 0, 2, 4, 6),
+  // y (0, 1, 4, 5), z (0, 1, 2, 3)
+  float p[3] = {0.0f, 0.0f, 0.0f};
+  int n = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j & (1 << a)) continue;
+      const float sa = s[j], sb = s[j | (1 << a)];
+      if ((sa < 0.0f) == (sb < 0.0f)) continue;
+      const float t = sa / (sa - sb);     // opposite sides: |sa - sb| = |sa| + |sb| > 0
+#pragma unroll
+      for (int e = 0; e < 3; ++e) p[e] += (e == a) ? t : static_cast<float>((j >> e) & 1);
+      ++n;
+    }
+  }
+  const float nf = static_cast<float>(n);
+  float* o = out.verts + 3ll * idx;
+  o[0] = g.ox + g.voxel * (static_cast<float>(cx) + p[0] / nf);
+  o[1] = g.oy + g.voxel * (static_cast<float>(cy) + p[1] / nf);
+  o[2] = g.oz + g.voxel * (static_cast<float>(cz) + p[2] / nf);
+  if (out.normals) {                      // central gradient of the eight corners, toward increasing tsdf
+    const float gx = ((s[1] - s[0]) + (s[3] - s[2])) + ((s[5] - s[4]) + (s[7] - s[6]));
+    const float gy = ((s[2] - s[0]) + (s[3] - s[1])) + ((s[6] - s[4]) + (s[7] - s[5]));
+    const float gz = ((s[4] - s[0]) + (s[5] - s[1])) + ((s[6] - s[2]) + (s[7] - s[3]));
+    const float len = sqrtf(gx * gx + gy * gy + gz * gz);
+    float* q = out.normals + 3ll * idx;
+    const bool zero = !(len > 0.0f);
+    q[0] = zero ? 0.0f : gx / len; q[1] = zero ? 0.0f : gy / len; q[2] = zero ? 0.0f : gz / len;
+  }
+  if (out.rgba) {
+    uchar4 c = make_uchar4(0, 0, 0, 255);
+    if (g.rgb) {
+      float acc[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+#pragma unroll
+        for (int e = 0; e < 3; ++e) acc[e] += g.rgb[3 * at[j] + e];
+      }
+      // mean + 0.5, floored, clamped to [0, 255] (NaN -> 0)
+      c.x = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[0] * 0.125f + 0.5f))));
+      c.y = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[1] * 0.125f + 0.5f))));
+      c.z = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[2] * 0.125f + 0.5f))));
+    }
+    reinterpret_cast<uchar4*>(out.rgba)[idx] = c;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void mesh_faces_kernel(const Grid g, long long cells, const uint8_t* __restrict__ flags,
+                                                           const int* __restrict__ qbase, const int32_t* __restrict__ vidx, const MeshOut out) {
+  const int tid = threadIdx.x;
+  const long long k = static_cast<long long>(blockIdx.x) * kBlock + tid;
+  const int flag = k < cells ? flags[k] : 0;
+  // quads are numbered cell by cell, inside a cell by axis: the quads of the lower lanes, whatever their axis, come first
+  const unsigned long long mx = __ballot(flag & 2), my = __ballot(flag & 4), mz = __ballot(flag & 8);
+  __shared__ int wave_n[kBlock / 64];
+  if ((tid & 63) == 0) wave_n[tid >> 6] = __popcll(mx) + __popcll(my) + __popcll(mz);
+  __syncthreads();
+  if (!(flag & 14)) return;
+  int q = qbase[blockIdx.x] + lanes_below(mx) + lanes_below(my) + lanes_below(mz);
+  for (int w = 0; w < (tid >> 6); ++w) q += wave_n[w];
+  const long long mxc = g.nx - 1, mxy = mxc * (g.ny - 1);
+  const long long step[3] = {1, mxc, mxy};              // cell index strides along x, y, z
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (!(flag & (2 << a))) continue;
+    const long long sb = step[(a + 1) % 3], sc = step[(a + 2) % 3];
+    const int q0 = vidx[k], q1 = vidx[k - sb], q2 = vidx[k - sb - sc], q3 = vidx[k - sc];
+    const bool fwd = (flag & kInsideA) != 0;            // corner 0 inside; otherwise its neighbour is: reversed winding
+    const int f0 = 2 * q, f1 = 2 * q + 1;
+    if (f0 < out.fcap) {
+      int32_t* o = out.faces + 3ll * f0;
+      o[0] = q0; o[1] = fwd ? q1 : q2; o[2] = fwd ? q2 : q1;
+    }
+    if (f1 < out.fcap) {
+      int32_t* o = out.faces + 3ll * f1;
+      o[0] = q0; o[1] = fwd ? q2 : q3; o[2] = fwd ? q3 : q2;
+    }
+    ++q;
+  }
+}
+
+constexpr size_t kAlign = 256;
+inline size_t aligned(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+
+struct MeshLayout { size_t vcount, qcount, vbase, qbase, vidx, flags, total; long long cells, blocks; };
+inline MeshLayout mesh_layout(int nz, int ny, int nx) {
+  MeshLayout L;
+  L.cells = static_cast<long long>(nz - 1) * (ny - 1) * (nx - 1);
+  L.blocks = (L.cells + kBlock - 1) / kBlock;
+  const size_t per = aligned(sizeof(int) * L.blocks);
+  L.vcount = 0; L.qcount = per; L.vbase = 2 * per; L.qbase = 3 * per;
+  L.vidx = 4 * per;
+  L.flags = L.vidx + aligned(sizeof(int32_t) * L.cells);
+  L.total = L.flags + aligned(L.cells);
+  return L;
+}
+
+inline bool volume_ok(int nz, int ny, int nx) {
+  return nz >= 0 && ny >= 0 && nx >= 0 && static_cast<long long>(nz) * ny < (1ll << 31) && static_cast<long long>(nz) * ny * nx < (1ll << 31);
+}
+inline bool finite_f(float v) { return v - v == 0.0f; }
+
+}  // namespace
+
+#define PVO_REQ(c) do { if (!(c)) return PVO_EINVAL; } while (0)
+
+extern "C" size_t pvo_tsdf_integrate_args_size(void) { return sizeof(pvo_tsdf_integrate_args); }
+extern "C" size_t pvo_tsdf_mesh_args_size(void) { return sizeof(pvo_tsdf_mesh_args); }
+
+extern "C" size_t pvo_tsdf_integrate_workspace_bytes(int N) {
+  return N <= 0 ? 0 : aligned(sizeof(float) * kFrameFloats * static_cast<size_t>(N));
+}
+
+extern "C" size_t pvo_tsdf_mesh_workspace_bytes(int nz, int ny, int nx) {
+  if (nz < 2 || ny < 2 || nx < 2 || !volume_ok(nz, ny, nx)) return 0;
+  return mesh_layout(nz, ny, nx).total;
+}
+
+extern "C" int pvo_tsdf_integrate(const pvo_tsdf_integrate_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  PVO_REQ(a);
+  PVO_REQ(volume_ok(a->nz, a->ny, a->nx));
+  PVO_REQ(a->N >= 0 && a->nframes >= 0 && a->ht >= 0 && a->wd >= 0 && static_cast<long long>(a->ht) * a->wd < (1ll << 31));
+  PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->trunc > 0.0f && finite_f(a->trunc));
+  PVO_REQ(a->z_near >= 0.0f && finite_f(a->z_near) && a->w_max >= 0.0f && finite_f(a->w_max));
+  PVO_REQ(finite_f(a->origin[0]) && finite_f(a->origin[1]) && finite_f(a->origin[2]));
+  const long long total = static_cast<long long>(a->nz) * a->ny * a->nx;
+  if (total == 0 || a->N == 0 || a->ht * a->wd == 0) return PVO_OK;       // nothing to fuse
+  PVO_REQ(a->tsdf && a->wsum && a->poses && a->disps && a->intrinsics && a->ix);
+  PVO_REQ(!a->rgb || a->images);                 // a colour volume needs the images
+  if (a->images) {
+    PVO_REQ(a->img_stride >= 1 && a->img_offset >= 0 && a->IH > 0 && a->IW > 0);
+    PVO_REQ(static_cast<long long>(a->img_stride) * (a->ht - 1) + a->img_offset < a->IH);
+    PVO_REQ(static_cast<long long>(a->img_stride) * (a->wd - 1) + a->img_offset < a->IW);
+  }
+  if (!workspace || workspace_bytes < pvo_tsdf_integrate_workspace_bytes(a->N)) return PVO_EWORKSPACE;
+  PVO_REQ(!(reinterpret_cast<uintptr_t>(workspace) & 15));
+  hipStream_t s = pvo_stream(stream);
+  float* fc = static_cast<float*>(workspace);
+  const Vol vol = {a->origin[0], a->origin[1], a->origin[2], a->voxel};
+  hipLaunchKernelGGL(tsdf_frames_kernel, dim3((a->N + 63) / 64), dim3(64), 0, s, a->poses, a->ix, fc, a->N, a->nframes, vol);
+  PVO_CHECK_LAUNCH();
+  const Fuse in = {a->disps, a->weight, a->images, a->ht, a->wd, a->IH, a->IW, a->img_stride, a->img_offset, a->trunc, a->z_near, a->w_max};
+  const dim3 grid(static_cast<unsigned>((total + kBlock - 1) / kBlock));
+  if (a->rgb)
+    hipLaunchKernelGGL(tsdf_integrate_kernel<true>, grid, dim3(kBlock), 0, s, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N,
+                       a->nz, a->ny, a->nx);
+  else
+    hipLaunchKernelGGL(tsdf_integrate_kernel<false>, grid, dim3(kBlock), 0, s, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N,
+                       a->nz, a->ny, a->nx);
+  PVO_CHECK_LAUNCH();
+  return PVO_OK;
+}
+
+extern "C" int pvo_tsdf_mesh(const pvo_tsdf_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  PVO_REQ(a);
+  PVO_REQ(volume_ok(a->nz, a->ny, a->nx));
+  PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->min_weight == a->min_weight);
+  PVO_REQ(finite_f(a->origin[0]) && finite_f(a->origin[1]) && finite_f(a->origin[2]));
+  PVO_REQ(a->vcap >= 0 && a->fcap >= 0 && a->counts);
+  PVO_REQ(!((reinterpret_cast<uintptr_t>(a->rgba) & 3)));
+  hipStream_t s = pvo_stream(stream);
+  if (a->nz < 2 || a->ny < 2 || a->nx < 2) {     // no cell: the counts alone
+    const hipError_t e = hipMemsetAsync(a->counts, 0, 2 * sizeof(int32_t), s);
+    if (e != hipSuccess) { pvo_note_hip_error(static_cast<int>(e)); return PVO_ELAUNCH; }
+    return PVO_OK;
+  }
+  PVO_REQ(a->tsdf && a->wsum);
+  PVO_REQ((a->vcap == 0 || a->verts) && (a->fcap == 0 || a->faces));
+  const MeshLayout L = mesh_layout(a->nz, a->ny, a->nx);
+  if (!workspace || workspace_bytes < L.total) return PVO_EWORKSPACE;
+  PVO_REQ(!(reinterpret_cast<uintptr_t>(workspace) & 7));
+  char* ws = static_cast<char*>(workspace);
+  int* vcount = reinterpret_cast<int*>(ws + L.vcount);
+  int* qcount = reinterpret_cast<int*>(ws + L.qcount);
+  int* vbase = reinterpret_cast<int*>(ws + L.vbase);
+  int* qbase = reinterpret_cast<int*>(ws + L.qbase);
+  int32_t* vidx = reinterpret_cast<int32_t*>(ws + L.vidx);
+  uint8_t* flags = reinterpret_cast<uint8_t*>(ws + L.flags);
+  const Grid g = {a->tsdf, a->wsum, a->rgb, a->nz, a->ny, a->nx, a->origin[0], a->origin[1], a->origin[2], a->voxel, a->min_weight};
+  const MeshOut out = {a->verts, a->normals, a->rgba, a->faces, a->vcap, a->fcap};
+  const dim3 grid(static_cast<unsigned>(L.blocks));
+  hipLaunchKernelGGL(mesh_classify_kernel, grid, dim3(kBlock), 0, s, g, L.cells, flags, vcount, qcount);
+  PVO_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, vcount, qcount, vbase, qbase, a->counts, static_cast<int>(L.blocks));
+  PVO_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mesh_verts_kernel, grid, dim3(kBlock), 0, s, g, L.cells, flags, vbase, vidx, out);
+  PVO_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mesh_faces_kernel, grid, dim3(kBlock), 0, s, g, L.cells, flags, qbase, vidx, out);
+  PVO_CHECK_LAUNCH();
+  return PVO_OK;
+}

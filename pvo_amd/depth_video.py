@@ -34,7 +34,13 @@ pointer) and the device flag `calibrated_dev` is set: from then on `append` and 
 the caller's, whose stale guess `reproject` would otherwise read per frame.  While every step was rejected the rows and the flag stay
 as they were and the caller's vectors are still written.  `calibrated` is the host-side "ba_calib has run": a video that never
 calibrates launches nothing more and behaves as before.
+
+Surface: `tsdf(voxel, ...)` fuses the pixels `map_points` would keep into a truncated signed distance volume, weighted by
+`fusion_weights` (the per-cell sigma as a weight, not a threshold), and returns its surface-nets mesh (include/pvo_hip.h,
+pvo_tsdf_integrate / pvo_tsdf_mesh).  Read only: the video is unchanged.
 """
+import math
+
 import torch
 
 from . import droid_backends as db
@@ -480,6 +486,73 @@ class DepthVideo:
         wd = w8 * div
         y, x = torch.div(pix, wd, rounding_mode="floor") // div, (pix % wd) // div
         return sigma[frame, y, x]
+
+    @staticmethod
+    def fusion_weights(keep, disps, sigma=None, rel0=0.05):
+        """the TSDF fusion's per-pixel weights (f32, the shape of keep): `keep` itself, or with sigma - the standard deviation of the
+        inverse depths, shaped like disps - keep / (1 + (sigma / (rel0 * disps))^2): a pixel whose relative standard deviation is rel0
+        counts half, a confident one fully.  A non-finite sigma (a never-estimated cell) gives 0.  Works on CPU tensors."""
+        w = keep.to(torch.float32)
+        if sigma is None:
+            return w
+        w = w / (1.0 + (sigma / (float(rel0) * disps)) ** 2)
+        return torch.where(torch.isfinite(sigma) & torch.isfinite(w), w, torch.zeros_like(w))
+
+    @staticmethod
+    def tsdf_bounds(xyz, voxel, trunc):
+        """a volume around the points xyz [n,3]: per axis the 1st and 99th percentile - s[floor(0.01 (m-1))] and s[ceil(0.99 (m-1))] of
+        the sorted values s of the strided subsample xyz[::ceil(n / 2^20)] (m points) - widened by trunc on both sides.  Returns
+        (origin [x,y,z] as floats, (nz,ny,nx)) with dim = ceil((hi - lo + 2 trunc) / voxel) + 1.  Works on CPU tensors."""
+        n = int(xyz.shape[0])
+        if n == 0:
+            raise ValueError("tsdf_bounds: no points")
+        sub = xyz[::max(1, -(-n // (1 << 20)))].to(torch.float64)
+        m = sub.shape[0]
+        s = torch.sort(sub, dim=0).values
+        lo, hi = s[int(math.floor(0.01 * (m - 1)))], s[int(math.ceil(0.99 * (m - 1)))]
+        origin = [float(v) - float(trunc) for v in lo]
+        dims = [int(math.ceil((float(h) - float(l) + 2.0 * float(trunc)) / float(voxel))) + 1 for l, h in zip(lo, hi)]
+        return origin, (dims[2], dims[1], dims[0])
+
+    def tsdf(self, voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None, use_sigma=False, origin=None, dims=None,
+             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05):
+        """the fused surface of keyframes ix (default: all stored ones; fuse after `terminate` - poses that move later are not
+        de-integrated): a TSDF volume of `voxel`-sized cells, truncation `trunc` (default 3 voxels), integrated natively
+        (pvo_tsdf_integrate) from exactly the pixels map_points(ix, thresh, full_res, reject, max_rel_sigma) keeps, and its surface-nets
+        mesh (pvo_tsdf_mesh).  use_sigma (needs the variances of `uncertainty`): pixels are weighted by fusion_weights(keep, disps,
+        sigma, rel0), sigma at the 1/8 cell for full_res.  origin [x,y,z] / dims (nz,ny,nx): the volume; default tsdf_bounds of the map's
+        points.  Returns a dict: verts, normals, rgba, faces (the mesh; min_weight = the least wsum of a usable voxel), tsdf, wsum
+        (the volume), origin, voxel."""
+        trunc = 3.0 * float(voxel) if trunc is None else float(trunc)
+        n = self.counter
+        m = self.map_points(ix=ix, thresh=thresh, full_res=full_res, reject=reject, max_rel_sigma=max_rel_sigma)
+        if full_res:
+            disps, intr, stride, offset, div = self.disps_up[:n], 8.0 * self.intrinsics[0], 1, 0, 8
+        else:
+            disps, intr, stride, offset, div = self.disps[:n], self.intrinsics[0], 8, 3, 1
+        ix = torch.arange(n, device=self.device) if ix is None else torch.as_tensor(ix, dtype=torch.long, device=self.device).reshape(-1)
+        ix = ix[(ix >= 0) & (ix < n)].contiguous()
+        keep = torch.zeros(disps.shape, dtype=torch.bool, device=self.device)
+        src = m["src"].long()
+        keep.view(n, -1)[src[:, 0], src[:, 1]] = True
+        sigma = None
+        if use_sigma:
+            sigma = self.sigma_disp()[:n]
+            if div > 1:
+                sigma = sigma.repeat_interleave(div, 1).repeat_interleave(div, 2)
+        weight = self.fusion_weights(keep, disps, sigma, rel0).contiguous()
+        if origin is None or dims is None:
+            origin, dims = self.tsdf_bounds(m["xyz"], voxel, trunc)
+        nz, ny, nx = [int(v) for v in dims]
+        vol = torch.zeros(nz, ny, nx, dtype=torch.float32, device=self.device)
+        wsum = torch.zeros_like(vol)
+        rgb = torch.zeros(nz, ny, nx, 3, dtype=torch.float32, device=self.device) if self.images is not None else None
+        db.tsdf_integrate(vol, wsum, rgb, self.poses[:n], disps.contiguous(), intr.contiguous(), ix, origin, voxel, trunc, weight=weight,
+                          images=self.images, img_stride=stride, img_offset=offset, w_max=w_max)
+        out = db.tsdf_mesh(vol, wsum, rgb, origin, voxel, min_weight=min_weight)
+        out.pop("counts")
+        out.update(tsdf=vol, wsum=wsum, origin=[float(v) for v in origin], voxel=float(voxel))
+        return out
 
     def ba(self, target, weight, eta, ii, jj, t0=1, t1=None, itrs=2, lm=1e-4, ep=0.1, motion_only=False,
            t1_hint=None):

@@ -176,6 +176,14 @@ class Droid:
         self.flush()
         return self.video.map_points(**kw)
 
+    def get_mesh(self, **kw):
+        """the fused surface of the keyframes: DepthVideo.tsdf(voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None,
+        use_sigma=False, origin=None, dims=None, min_weight=1.0, w_max=0) - a dict of the mesh verts [V,3], normals [V,3], rgba [V,4],
+        faces [F,3] and the volume tsdf, wsum [nz,ny,nx], origin, voxel.  Call it after terminate(): poses that move later are not
+        de-integrated."""
+        self.flush()
+        return self.video.tsdf(**kw)
+
     def get_flow(self):
         self.flush()
         return upsample_inter(self.video.full_flow[:self.video.counter][None] * 8)

@@ -544,6 +544,94 @@ def map_points_into(a, poses, disps, intrinsics, ix, thresh, out, min_votes=2, m
         check(lib.pvo_map_points(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "map_points")
 
 
+def tsdf_integrate(tsdf, wsum, rgb, poses, disps, intrinsics, ix, origin, voxel, trunc, weight=None, images=None, img_stride=8,
+                   img_offset=3, z_near=0.0, w_max=0.0):
+    """Fuse keyframes ix, in that order, into the caller's volume in place (include/pvo_hip.h pvo_tsdf_integrate): tsdf / wsum f32
+    [nz,ny,nx], rgb f32 [nz,ny,nx,3] or None (needs images); a zeroed volume is an empty one.  The centre of voxel (z,y,x) is
+    origin + voxel * (x,y,z); poses [nframes,7] world-to-camera, disps [nframes,ht,wd] at any resolution with intrinsics [4] for it,
+    weight f32 [nframes,ht,wd] or None (= 1), images uint8 [nframes,3,IH,IW] BGR sampled at [img_offset::img_stride], w_max 0 = no
+    cap.  No allocation beyond the cached workspace, no synchronisation."""
+    for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb"), (poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"),
+                 (ix, "ix"), (weight, "weight"), (images, "images")):
+        if t is not None:
+            _contig(t, n)
+    dev = _dev(tsdf, wsum, rgb, poses, disps, intrinsics, ix, weight, images)
+    _long(ix, "ix")
+    for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb"), (poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"),
+                 (weight, "weight")):
+        if t is not None:
+            _f32(t, n)
+    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
+        raise PvoHipError("tsdf_integrate: tsdf and wsum must be [nz,ny,nx], rgb [nz,ny,nx,3]")
+    N, (nf, ht, wd) = ix.shape[0], disps.shape
+    if poses.shape[0] < nf or (weight is not None and weight.shape != disps.shape):
+        raise PvoHipError("tsdf_integrate: poses must cover the frames of disps, weight must have the shape of disps")
+    a = _lib.TsdfIntegrateArgs()
+    if images is not None:
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < nf or images.shape[1] != 3:
+            raise PvoHipError("tsdf_integrate: images must be uint8 [nframes,3,IH,IW]")
+        a.images, a.IH, a.IW, a.img_stride, a.img_offset = _ptr(images), images.shape[2], images.shape[3], int(img_stride), int(img_offset)
+    a.tsdf, a.wsum, a.rgb = _ptr(tsdf), _ptr(wsum), _ptr(rgb)
+    a.nz, a.ny, a.nx = tsdf.shape
+    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
+    a.voxel, a.trunc, a.z_near, a.w_max = float(voxel), float(trunc), float(z_near), float(w_max)
+    a.poses, a.disps, a.intrinsics, a.ix, a.weight = _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ix), _ptr(weight)
+    a.N, a.nframes, a.ht, a.wd = N, nf, ht, wd
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_integrate_workspace_bytes(N))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_integrate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_integrate")
+
+
+def tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out):
+    """pvo_tsdf_mesh on caller-owned buffers (out: verts [vcap,3], faces [fcap,3], counts [2], optional normals / rgba).  Buffers keep
+    whatever they held beyond the elements written.  No allocation beyond the cached workspace, no synchronisation."""
+    dev = tsdf.device
+    a = _lib.TsdfMeshArgs()
+    a.tsdf, a.wsum, a.rgb = _ptr(tsdf), _ptr(wsum), _ptr(rgb)
+    a.nz, a.ny, a.nx = tsdf.shape
+    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
+    a.voxel, a.min_weight = float(voxel), float(min_weight)
+    a.vcap, a.fcap = out["verts"].shape[0], out["faces"].shape[0]
+    a.verts, a.normals, a.rgba, a.faces = _ptr(out["verts"]), _ptr(out.get("normals")), _ptr(out.get("rgba")), _ptr(out["faces"])
+    a.counts = ctypes.c_void_p(out["counts"].data_ptr())
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_mesh_workspace_bytes(a.nz, a.ny, a.nx))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_mesh(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_mesh")
+
+
+def tsdf_mesh(tsdf, wsum, rgb, origin, voxel, min_weight=1.0, vcap=None, fcap=None):
+    """The surface-nets mesh of a TSDF volume (include/pvo_hip.h pvo_tsdf_mesh).  Returns a dict: verts f32 [V,3], normals f32 [V,3],
+    rgba uint8 [V,4] (rgb 0 without a colour volume), faces int32 [F,3], counts int32 [2] = (V, F).  Calls once with room for vcap
+    vertices and fcap faces (default: a guess from the volume's faces), reads counts back - the call's one host synchronisation - and
+    calls again with exactly the room needed if a capacity was exceeded."""
+    for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")):
+        if t is not None:
+            _contig(t, n)
+            _f32(t, n)
+    dev = _dev(tsdf, wsum, rgb)
+    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
+        raise PvoHipError("tsdf_mesh: tsdf and wsum must be [nz,ny,nx], rgb [nz,ny,nx,3]")
+    nz, ny, nx = tsdf.shape
+    cells = max(nz - 1, 0) * max(ny - 1, 0) * max(nx - 1, 0)
+    vcap = min(cells, 8 * (nz * ny + ny * nx + nz * nx)) if vcap is None else int(vcap)
+    fcap = 2 * vcap if fcap is None else int(fcap)
+    while True:
+        out = {"verts": torch.empty(vcap, 3, dtype=torch.float32, device=dev), "normals": torch.empty(vcap, 3, dtype=torch.float32, device=dev),
+               "rgba": torch.empty(vcap, 4, dtype=torch.uint8, device=dev), "faces": torch.empty(fcap, 3, dtype=torch.int32, device=dev),
+               "counts": torch.empty(2, dtype=torch.int32, device=dev)}
+        tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out)
+        nv, nf = out["counts"].tolist()                 # the one synchronisation
+        if nv <= vcap and nf <= fcap:
+            break
+        vcap, fcap = max(nv, vcap), max(nf, fcap)
+    for k in ("verts", "normals", "rgba"):
+        out[k] = out[k][:nv]
+    out["faces"] = out["faces"][:nf]
+    return out
+
+
 def _baseline(baseline, what):
     """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
     b = float(baseline)

@@ -85,6 +85,40 @@ def write_ply(path, xyz, rgb=None, label=None, sigma=None):
     return n
 
 
+def write_ply_mesh(path, verts, faces, rgb=None, normals=None):
+    """a triangle mesh as binary little-endian PLY: per vertex x y z float, then nx ny nz float (omitted when normals is None), then
+    red green blue uchar (rgb [n,3] or [n,4], the first three columns; omitted when None); per face `property list uchar int
+    vertex_indices`: the byte 3 and three int32 indices.  numpy only; returns (vertices, faces) written."""
+    verts, faces = _host(verts), _host(faces)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    props = ["property float x", "property float y", "property float z"]
+    if normals is not None:
+        normals = _host(normals)
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        props += ["property float nx", "property float ny", "property float nz"]
+    if rgb is not None:
+        rgb = _host(rgb)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    n, m = int(verts.shape[0]), int(faces.shape[0])
+    rec = np.zeros(n, dtype=np.dtype(fields))
+    rec["x"], rec["y"], rec["z"] = verts[:, 0], verts[:, 1], verts[:, 2]
+    if normals is not None:
+        rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
+    if rgb is not None:
+        rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    tri = np.zeros(m, dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    tri["n"], tri["v"] = 3, faces.reshape(m, 3)
+    header = "\n".join(["ply", "format binary_little_endian 1.0", "element vertex %d" % n] + props +
+                       ["element face %d" % m, "property list uchar int vertex_indices", "end_header"]) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+        f.write(tri.tobytes())
+    return n, m
+
+
 def save_reconstruction(root, video):
     """upstream DROID-SLAM's reconstruction folder (demo.py save_reconstruction): tstamps / disps / poses / intrinsics as .npy of
     the stored keyframes, and images when the video keeps them.  disps are the full-resolution maps where the video maintains them

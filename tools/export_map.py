@@ -2,6 +2,7 @@
 
     python tools/export_map.py --datapath <.../SceneXX> --weights <checkpoint.pth> --map out.ply [--full_res] [--filter_thresh_map 0.005]
                                [--reconstruction_path DIR] [--uncertainty [--max_rel_sigma X]]
+                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight]]
 
 --map writes the filtered point cloud of all keyframes after the global bundle adjustment (Droid.get_map: points confirmed by two
 neighbouring keyframes, pvo_map_points) as a binary little-endian PLY: x y z float, red green blue uchar, int label (the per-frame
@@ -10,7 +11,10 @@ full-resolution depth maps instead of the 1/8 lattice.  --reconstruction_path DI
 tstamps / disps / poses / intrinsics / images .npy files.  --uncertainty tracks with args.uncertainty (every keyframe's inverse-depth
 variances from the frontend's bundle adjustment, estimated after the keyframe's last local update - the global bundle adjustment
 does not refresh them) and adds `property float sigma` to the PLY; --max_rel_sigma X also leaves out the cells whose relative
-standard deviation sigma / disp exceeds X.
+standard deviation sigma / disp exceeds X.  --mesh also fuses the same pixels into a TSDF volume of --voxel sized cells (truncation
+--trunc, default three voxels) and writes its surface-nets mesh (Droid.get_mesh: pvo_tsdf_integrate / pvo_tsdf_mesh) as a binary PLY
+with vertex normals, colours and triangle faces; --sigma_weight (with --uncertainty) weights every pixel by its inverse-depth
+variance instead of counting all alike.  Without --mesh the output is what it was without the option.
 """
 import os
 import sys
@@ -31,18 +35,26 @@ def parse_args(argv=None):
     p.add_argument("--reconstruction_path", default=None)
     p.add_argument("--uncertainty", action="store_true", help="estimate depth variances while tracking and write a sigma column")
     p.add_argument("--max_rel_sigma", type=float, default=None, help="with --uncertainty: drop cells with sigma / disp above this")
+    p.add_argument("--mesh", default=None, help="also write the fused surface's triangle mesh to this .ply (needs --voxel)")
+    p.add_argument("--voxel", type=float, default=None, help="with --mesh: the TSDF volume's voxel size, in the units of the poses")
+    p.add_argument("--trunc", type=float, default=None, help="with --mesh: the truncation distance (default: 3 voxels)")
+    p.add_argument("--sigma_weight", action="store_true", help="with --mesh and --uncertainty: weight pixels by their variance")
     own, rest = p.parse_known_args(argv)
     args = test_vo.parse_args(rest)
     for k, v in vars(own).items():
         setattr(args, k, v)
     if args.max_rel_sigma is not None and not args.uncertainty:
         p.error("--max_rel_sigma needs --uncertainty")
+    if args.mesh is not None and not (args.voxel is not None and args.voxel > 0):
+        p.error("--mesh needs --voxel V with V > 0")
+    if args.sigma_weight and not (args.mesh is not None and args.uncertainty):
+        p.error("--sigma_weight needs --mesh and --uncertainty")
     return args
 
 
 def main(argv=None):
     from pvo_amd.droid import Droid
-    from pvo_amd.handoff import save_reconstruction, write_kitti_trajectory, write_ply
+    from pvo_amd.handoff import save_reconstruction, write_kitti_trajectory, write_ply, write_ply_mesh
     args = parse_args(argv)
     args.half_update = True
     args.store_images = True
@@ -60,6 +72,12 @@ def main(argv=None):
     m = droid.get_map(thresh=args.filter_thresh_map, full_res=args.full_res, **kw)
     n = write_ply(args.map, m["xyz"], m["rgba"], m.get("label") if args.segm_filter else None, **({"sigma": m["sigma"]} if args.uncertainty else {}))
     print("map: %d points of %d keyframes written to %s" % (n, droid.video.counter, args.map))
+    if args.mesh is not None:
+        g = droid.get_mesh(voxel=args.voxel, trunc=args.trunc, thresh=args.filter_thresh_map, full_res=args.full_res,
+                           use_sigma=args.sigma_weight, max_rel_sigma=args.max_rel_sigma)
+        nv, nf = write_ply_mesh(args.mesh, g["verts"], g["faces"], g["rgba"], g["normals"])
+        print("mesh: %d vertices, %d triangles from a %s volume of %g-sized voxels written to %s"
+              % (nv, nf, "x".join(str(d) for d in g["tsdf"].shape), args.voxel, args.mesh))
     if args.reconstruction_path:
         for p in save_reconstruction(args.reconstruction_path, droid.video):
             print("wrote", p)
