@@ -84,7 +84,9 @@ const char* pvo_last_hip_error(void);
  * pvo_map_points_workspace_bytes / pvo_map_points; still 106, uncertainty: no struct changed - new entry points pvo_ba_sigma /
  * pvo_ba_uncertainty; still 106, calibration: no struct changed - new entry points pvo_ba_calib_workspace_bytes / pvo_ba_calib; still 106, surface
  * reconstruction: no existing struct changed - new structs pvo_tsdf_integrate_args / pvo_tsdf_mesh_args (their *_args_size() report the
- * sizes) and new entry points pvo_tsdf_integrate[_args_size, _workspace_bytes] / pvo_tsdf_mesh[_args_size, _workspace_bytes]): a caller
+ * sizes) and new entry points pvo_tsdf_integrate[_args_size, _workspace_bytes] / pvo_tsdf_mesh[_args_size, _workspace_bytes]; still 106,
+ * sparse surface reconstruction: no existing struct changed - new structs pvo_tsdf_sparse_{allocate,integrate,mesh}_args and new entry
+ * points pvo_tsdf_sparse_{allocate,integrate,mesh}[_args_size, _workspace_bytes]): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -773,6 +775,134 @@ typedef struct pvo_tsdf_mesh_args {
 size_t pvo_tsdf_mesh_args_size(void);
 size_t pvo_tsdf_mesh_workspace_bytes(int nz, int ny, int nx);
 int pvo_tsdf_mesh(const pvo_tsdf_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Sparse surface reconstruction: a brick volume with per-brick frame culling  */
+/* ------------------------------------------------------------------------- */
+
+/* The brick volume: the dense volume's contract on a world too large to store.  Only blocks of B x B x B voxels near observed surfaces
+ * exist.  All memory is the caller's, device, dense, row-major:
+ *   the world is a grid of gz x gy x gx bricks (gz*gy*gx < 2^31, each of 8gz, 8gy, 8gx <= 2^21 so that indices are exact in fp32);
+ *   the centre of GLOBAL voxel (z,y,x), 0 <= x < 8gx ..., is origin + voxel * (x, y, z), as in pvo_tsdf_integrate; brick (bz,by,bx)
+ *   holds the voxels 8b .. 8b+7 of each axis, local voxel (lz,ly,lx) at offset 64 lz + 8 ly + lx;
+ *     grid  int32 [gz,gy,gx]    the pool slot of a brick, or -1 (the caller fills it with -1 when it creates the volume)
+ *     tsdf  f32 [cap,8,8,8], wsum f32 [cap,8,8,8], rgb f32 [cap,8,8,8,3] or NULL: the pool of cap bricks (cap*512 < 2^31), ZEROED by
+ *           the caller when it creates it; coord int32 [cap,3] = (bz,by,bx) of every slot in use
+ *     bricks int32 [1]          the number of bricks the volume WANTS, never clamped by cap (the protocol of pvo_tsdf_mesh's counts
+ *                               and pvo_map_points' frame_start[N]): slots [0, min(bricks[0], cap)) are in use.  Zero at creation.
+ *   Bricks are never freed.  A brick holds the frames integrated since it was allocated: allocate for all keyframes, then integrate. */
+#define PVO_TSDF_BRICK 8
+
+/* pvo_tsdf_sparse_allocate: marks the bricks near the surfaces seen by the keyframes ix[0..N) and appends the new ones to the pool.
+ *   Marking, per pixel (vi,ui) of every frame f of ix in [0, nframes), valid under pvo_tsdf_integrate's tests (d and w finite and > 0):
+ *     S = ceil(trunc / voxel) + 1 samples at the camera depths z_k = lo + (hi - lo) * (k / (S-1)), k = 0..S-1, lo = max(z_near,
+ *     1/d - trunc), hi = 1/d + trunc (none if hi < lo): consecutive depths are at most 2 voxels apart, so consecutive samples are at
+ *     most 4 voxels apart along every ray within 60 degrees of the optical axis.  Sample k in the world:
+ *       Xc = (z_k (ui - cx) / fx, z_k (vi - cy) / fy, z_k);  X = R^T (Xc - t);  p = (X - origin) / voxel  (in voxels)
+ *     and every brick that contains one of the 8 corners p + margin * (+-1, +-1, +-1) is marked: the brick index of a coordinate c is
+ *     floor((c + 0.5) / 8) (voxel x covers [x - 0.5, x + 0.5)).  A sample whose own p lies outside the grid, and a corner outside
+ *     it, mark nothing.  margin is in voxels, 0 <= margin <= 8.  Marks are same-value byte stores: no atomics.
+ *   Appending: one scan over the grid in raster order.  A marked brick with grid == -1 gets the slot  n + rank,  n the number of
+ *     bricks the grid already holds (= min(bricks[0], cap) of the call before; recounted from the grid, so that after an overflow
+ *     the caller only has to come back with a larger pool) and rank its raster rank among the new ones.  A slot >= cap is written
+ *     nowhere and its grid entry stays -1.  bricks[0] = n + the number of new ones, unclamped.  The call is idempotent; called
+ *     again with a larger pool (the old pool, coord and grid copied in) it finishes the job, and one-shot allocation and allocation
+ *     after an overflow give the same grid / coord.
+ * Six launches (marks cleared; inverse frame constants; marks; per-workgroup counts; one scan; slots), no atomics, no allocation, no
+ * host synchronisation: capturable; the same operands give the same bytes.  workspace: pvo_tsdf_sparse_allocate_workspace_bytes(gz,
+ * gy, gx, N) (one byte per brick of the grid plus twelve per 256; PVO_EWORKSPACE otherwise), 16-byte aligned.
+ * Limits (PVO_EINVAL): the grid limits above, cap >= 0 with cap*512 < 2^31, N, nframes, ht, wd >= 0, ht*wd < 2^31, voxel > 0, trunc > 0,
+ * trunc / voxel <= 4096, z_near >= 0, 0 <= margin <= 8, all finite; a NULL grid / bricks / poses / disps / intrinsics / ix, a NULL
+ * coord with cap > 0.  An empty grid, N == 0 or ht*wd == 0 returns PVO_OK and does nothing. */
+typedef struct pvo_tsdf_sparse_allocate_args {
+  int32_t* grid;
+  int32_t* coord;
+  int32_t* bricks;
+  int gz, gy, gx, cap;
+  float origin[3];
+  float voxel, trunc, z_near, margin;
+  const float* poses;
+  const float* disps;
+  const float* intrinsics;
+  const int64_t* ix;
+  const float* weight;
+  int N, nframes, ht, wd;
+} pvo_tsdf_sparse_allocate_args;
+size_t pvo_tsdf_sparse_allocate_args_size(void);
+size_t pvo_tsdf_sparse_allocate_workspace_bytes(int gz, int gy, int gx, int N);
+int pvo_tsdf_sparse_allocate(const pvo_tsdf_sparse_allocate_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pvo_tsdf_sparse_integrate: pvo_tsdf_integrate on every voxel of every brick in use - the same operands (poses .. img_offset), the
+ * same per-(voxel, frame) sequence in the order of ix, the same per-slot constants and the voxel's GLOBAL integer index converted to
+ * float, by the same inline function (csrc/tsdf_fuse.h): a voxel of a brick ends with the bytes the dense call leaves at that voxel
+ * of an [8gz,8gy,8gx] volume.  A voxel no frame contributes to is not written.
+ *   One workgroup per slot (the launch is sized by cap; workgroups at or beyond min(bricks[0], cap) exit).  Per chunk of 512 slots of
+ *   ix, every slot is tested ONCE against the brick and dropped only when no voxel of the brick can contribute: an id outside
+ *   [0, nframes); a frame without a valid pixel; the bounding sphere of the brick's voxel centres, its radius inflated against
+ *   rounding, behind z_near, outside one of the four sides of the image's frustum (widened by half a pixel), or beyond
+ *   zfar[f] + trunc, zfar[f] the largest 1/d over the frame's valid pixels (a max, so order-independent).  The survivors, compacted
+ *   in slot order, are then applied to the brick's 512 voxels.  kept int32 [cap] or NULL: per brick in use, the number of slots of ix
+ *   that survived (a diagnostic: tools/tsdf_sparse_bench.py reports the share of (brick, frame) pairs the cull removes).
+ * Two launches (per-slot constants and zfar; the bricks), no atomics, no allocation, no host synchronisation: capturable; the same
+ * operands give the same bytes.  workspace: pvo_tsdf_sparse_integrate_workspace_bytes(N), 16-byte aligned.
+ * Limits (PVO_EINVAL): as pvo_tsdf_integrate with the grid limits above; a NULL tsdf / wsum / coord with cap > 0, a NULL bricks / poses /
+ * disps / intrinsics / ix, rgb without images.  cap == 0, N == 0 or ht*wd == 0 returns PVO_OK and does nothing. */
+typedef struct pvo_tsdf_sparse_integrate_args {
+  float* tsdf;
+  float* wsum;
+  float* rgb;
+  const int32_t* coord;
+  const int32_t* bricks;
+  int gz, gy, gx, cap;
+  float origin[3];
+  float voxel, trunc, z_near, w_max;
+  const float* poses;
+  const float* disps;
+  const float* intrinsics;
+  const int64_t* ix;
+  const float* weight;
+  int N, nframes, ht, wd;
+  const uint8_t* images;
+  int IH, IW, img_stride, img_offset;
+  int32_t* kept;
+} pvo_tsdf_sparse_integrate_args;
+size_t pvo_tsdf_sparse_integrate_args_size(void);
+size_t pvo_tsdf_sparse_integrate_workspace_bytes(int N);
+int pvo_tsdf_sparse_integrate(const pvo_tsdf_sparse_integrate_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pvo_tsdf_sparse_mesh: the surface-nets rules of pvo_tsdf_mesh on the GLOBAL lattice [8gz,8gy,8gx].  A voxel of a brick that is not
+ * allocated is INVALID whatever min_weight is; a last global index has no cell.  A cell belongs to the brick that holds its corner 0;
+ * corners and neighbour cells in other bricks are reached through grid.  Vertices are ordered by (slot, raster order of the cell's
+ * corner 0 inside the brick); faces by that cell order, then axis x, y, z, with pvo_tsdf_mesh's quad rule and winding.  Position,
+ * normal and colour of a vertex are pvo_tsdf_mesh's, computed by the same inline function from the cell's global integer index: the
+ * bytes the dense call gives for that cell.  counts int32 [2] is ALWAYS written and NOT clamped; a vertex or face at or beyond its
+ * capacity is written nowhere.
+ * Four launches (classify + per-brick counts; one scan; vertices; faces), no atomics, no allocation, no host synchronisation:
+ * capturable; the same operands give the same bytes.  workspace: pvo_tsdf_sparse_mesh_workspace_bytes(cap) (five bytes per pool
+ * voxel; PVO_EWORKSPACE otherwise), 8-byte aligned.
+ * Limits (PVO_EINVAL): the grid limits above, voxel > 0 and finite, min_weight not NaN, a NULL counts / bricks, a NULL grid / tsdf /
+ * wsum / coord with cap > 0 and a grid that is not empty, NULL verts with vcap > 0 or NULL faces with fcap > 0, rgba not 4-byte
+ * aligned.  cap == 0 or an empty grid: counts = (0,0), PVO_OK. */
+typedef struct pvo_tsdf_sparse_mesh_args {
+  const int32_t* grid;
+  const int32_t* coord;
+  const int32_t* bricks;
+  const float* tsdf;
+  const float* wsum;
+  const float* rgb;
+  int gz, gy, gx, cap;
+  float origin[3];
+  float voxel, min_weight;
+  int vcap, fcap;
+  float* verts;
+  float* normals;
+  uint8_t* rgba;
+  int32_t* faces;
+  int32_t* counts;
+} pvo_tsdf_sparse_mesh_args;
+size_t pvo_tsdf_sparse_mesh_args_size(void);
+size_t pvo_tsdf_sparse_mesh_workspace_bytes(int cap);
+int pvo_tsdf_sparse_mesh(const pvo_tsdf_sparse_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

@@ -114,6 +114,15 @@ SIGNATURES = {
     "pvo_tsdf_mesh_args_size": (_sz, []),
     "pvo_tsdf_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
     "pvo_tsdf_mesh": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_sparse_allocate_args_size": (_sz, []),
+    "pvo_tsdf_sparse_allocate_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pvo_tsdf_sparse_allocate": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_sparse_integrate_args_size": (_sz, []),
+    "pvo_tsdf_sparse_integrate_workspace_bytes": (_sz, [_i]),
+    "pvo_tsdf_sparse_integrate": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_sparse_mesh_args_size": (_sz, []),
+    "pvo_tsdf_sparse_mesh_workspace_bytes": (_sz, [_i]),
+    "pvo_tsdf_sparse_mesh": (_i, [_vp, _vp, _sz, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -191,6 +200,35 @@ class TsdfMeshArgs(_c.Structure):
                 ("verts", _vp), ("normals", _vp), ("rgba", _vp), ("faces", _vp), ("counts", _vp)]
 
 
+TSDF_BRICK = 8                             # PVO_TSDF_BRICK
+
+
+class TsdfSparseAllocateArgs(_c.Structure):
+    """pvo_tsdf_sparse_allocate_args"""
+    _fields_ = [("grid", _vp), ("coord", _vp), ("bricks", _vp), ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i), ("origin", _f * 3),
+                ("voxel", _f), ("trunc", _f), ("z_near", _f), ("margin", _f),
+                ("poses", _vp), ("disps", _vp), ("intrinsics", _vp), ("ix", _vp), ("weight", _vp),
+                ("N", _i), ("nframes", _i), ("ht", _i), ("wd", _i)]
+
+
+class TsdfSparseIntegrateArgs(_c.Structure):
+    """pvo_tsdf_sparse_integrate_args"""
+    _fields_ = [("tsdf", _vp), ("wsum", _vp), ("rgb", _vp), ("coord", _vp), ("bricks", _vp),
+                ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i), ("origin", _f * 3),
+                ("voxel", _f), ("trunc", _f), ("z_near", _f), ("w_max", _f),
+                ("poses", _vp), ("disps", _vp), ("intrinsics", _vp), ("ix", _vp), ("weight", _vp),
+                ("N", _i), ("nframes", _i), ("ht", _i), ("wd", _i),
+                ("images", _vp), ("IH", _i), ("IW", _i), ("img_stride", _i), ("img_offset", _i), ("kept", _vp)]
+
+
+class TsdfSparseMeshArgs(_c.Structure):
+    """pvo_tsdf_sparse_mesh_args"""
+    _fields_ = [("grid", _vp), ("coord", _vp), ("bricks", _vp), ("tsdf", _vp), ("wsum", _vp), ("rgb", _vp),
+                ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i), ("origin", _f * 3),
+                ("voxel", _f), ("min_weight", _f), ("vcap", _i), ("fcap", _i),
+                ("verts", _vp), ("normals", _vp), ("rgba", _vp), ("faces", _vp), ("counts", _vp)]
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 
@@ -226,7 +264,10 @@ def load():
     if lib.pvo_map_points_args_size() != ctypes.sizeof(MapPointsArgs):
         raise PvoHipError("libpvo_hip.so has a %d-byte pvo_map_points_args; this binding is written for %d bytes - rebuild with "
                           "`python -m pvo_amd.build`" % (lib.pvo_map_points_args_size(), ctypes.sizeof(MapPointsArgs)))
-    for fn, struct in ((lib.pvo_tsdf_integrate_args_size, TsdfIntegrateArgs), (lib.pvo_tsdf_mesh_args_size, TsdfMeshArgs)):
+    for fn, struct in ((lib.pvo_tsdf_integrate_args_size, TsdfIntegrateArgs), (lib.pvo_tsdf_mesh_args_size, TsdfMeshArgs),
+                       (lib.pvo_tsdf_sparse_allocate_args_size, TsdfSparseAllocateArgs),
+                       (lib.pvo_tsdf_sparse_integrate_args_size, TsdfSparseIntegrateArgs),
+                       (lib.pvo_tsdf_sparse_mesh_args_size, TsdfSparseMeshArgs)):
         if fn() != ctypes.sizeof(struct):
             raise PvoHipError("libpvo_hip.so has a %d-byte %s; this binding is written for %d bytes - rebuild with "
                               "`python -m pvo_amd.build`" % (fn(), struct.__doc__, ctypes.sizeof(struct)))

@@ -24,6 +24,7 @@ HIP_SOURCES = [
     "geom.hip",
     "map_points.hip",
     "tsdf.hip",
+    "tsdf_sparse.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",

@@ -14,22 +14,16 @@
 //              (d) mesh_faces_kernel      two triangles per quad
 //
 // No atomics anywhere: every output index is a function of the classification bits alone, and a voxel's running average is one
-// thread's sequential loop - the same operands give the same bytes.
-#include "depth_vote.h"
+// thread's sequential loop - the same operands give the same bytes.  The slot constants, the update of a voxel by one frame and the
+// vertex of a cell are the inline functions of tsdf_fuse.h, which the brick volume (tsdf_sparse.hip) calls as well.
+#include "tsdf_fuse.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kScanThreads = 1024;
-constexpr int kFrameFloats = 16;      // per slot: A[9] row-major, b[3], frame id (as int bits), 3 unused
-
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mask), 0));
-}
 
 // ------------------------------------------------------------------------------------------------------------ integrate
-
-struct Vol { float ox, oy, oz, voxel; };
 
 __global__ __launch_bounds__(64) void tsdf_frames_kernel(const float* __restrict__ poses, const int64_t* __restrict__ ix,
                                                          float* __restrict__ fc, int N, int nframes, const Vol vol) {
@@ -41,25 +35,8 @@ __global__ __launch_bounds__(64) void tsdf_frames_kernel(const float* __restrict
     o[12] = __int_as_float(-1);
     return;
   }
-  const Pose G = load_pose(poses + 7 * f);
-  const Quat q = G.q;
-  // R(q) of the quaternion as stored (the matrix map_points.hip transposes)
-  const float r[9] = {1.0f - 2.0f * (q.y * q.y + q.z * q.z), 2.0f * (q.x * q.y - q.z * q.w), 2.0f * (q.x * q.z + q.y * q.w),
-                      2.0f * (q.x * q.y + q.z * q.w), 1.0f - 2.0f * (q.x * q.x + q.z * q.z), 2.0f * (q.y * q.z - q.x * q.w),
-                      2.0f * (q.x * q.z - q.y * q.w), 2.0f * (q.y * q.z + q.x * q.w), 1.0f - 2.0f * (q.x * q.x + q.y * q.y)};
-#pragma unroll
-  for (int k = 0; k < 9; ++k) o[k] = vol.voxel * r[k];
-  o[9] = (r[0] * vol.ox + r[1] * vol.oy) + r[2] * vol.oz + G.t.x;
-  o[10] = (r[3] * vol.ox + r[4] * vol.oy) + r[5] * vol.oz + G.t.y;
-  o[11] = (r[6] * vol.ox + r[7] * vol.oy) + r[8] * vol.oz + G.t.z;
-  o[12] = __int_as_float(static_cast<int>(f));
+  tsdf_frame_constants(poses, f, vol, o);
 }
-
-struct Fuse {
-  const float* disps; const float* weight; const uint8_t* images;
-  int ht, wd, IH, IW, stride, offset;
-  float trunc, z_near, w_max;
-};
 
 template <bool RGB>
 __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(float* __restrict__ tsdf, float* __restrict__ wsum, float* __restrict__ rgb,
@@ -73,51 +50,24 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(float* __restric
   const Intr K = load_intr(intrinsics);
   const long long HW = static_cast<long long>(in.ht) * in.wd;
   const long long plane = static_cast<long long>(in.IH) * in.IW;
-  float T = 0.0f, W = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+  Voxel a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, false};
   if (live) {
-    T = tsdf[i]; W = wsum[i];
-    if (RGB) { cr = rgb[3 * i]; cg = rgb[3 * i + 1]; cb = rgb[3 * i + 2]; }
+    a.T = tsdf[i]; a.W = wsum[i];
+    if (RGB) { a.cr = rgb[3 * i]; a.cg = rgb[3 * i + 1]; a.cb = rgb[3 * i + 2]; }
   }
-  bool touched = false;
   for (int b = 0; b < N; ++b) {
     const float* __restrict__ c = fc + static_cast<long long>(kFrameFloats) * b;      // wave-uniform
     const int f = __float_as_int(c[12]);
     if (f < 0) continue;
-    const float zc = c[6] * xf + c[7] * yf + c[8] * zf + c[11];
-    const float xc = c[0] * xf + c[1] * yf + c[2] * zf + c[9];
-    const float yc = c[3] * xf + c[4] * yf + c[5] * zf + c[10];
-    const float u = K.fx * (xc / zc) + K.cx, v = K.fy * (yc / zc) + K.cy;
-    const int ui = pvo_floor_to_int(u + 0.5f), vi = pvo_floor_to_int(v + 0.5f);       // (saturating, NaN -> 0)
-    const bool hit = live && zc > in.z_near && ui >= 0 && ui < in.wd && vi >= 0 && vi < in.ht;
-    if (!hit) continue;                                  // (a wave without a hit branches over the gathers)
-    const long long pix = f * HW + static_cast<long long>(vi) * in.wd + ui;
-    const float d = in.disps[pix];
-    const float w = in.weight ? in.weight[pix] : 1.0f;
-    if (!(d > 0.0f && d < __builtin_inff() && w > 0.0f && w < __builtin_inff())) continue;   // (NaN fails every comparison)
-    const float sdf = 1.0f / d - zc;
-    if (sdf < -in.trunc) continue;
-    const float val = fminf(1.0f, sdf / in.trunc);
-    const float Wn = W + w;
-    T = (T * W + val * w) / Wn;
-    if (RGB) {                                           // BGR planes -> RGB
-      const uint8_t* im = in.images + 3 * plane * f + static_cast<long long>(in.stride * vi + in.offset) * in.IW + (in.stride * ui + in.offset);
-      cr = (cr * W + static_cast<float>(im[2 * plane]) * w) / Wn;
-      cg = (cg * W + static_cast<float>(im[plane]) * w) / Wn;
-      cb = (cb * W + static_cast<float>(im[0]) * w) / Wn;
-    }
-    W = (in.w_max > 0.0f && Wn > in.w_max) ? in.w_max : Wn;
-    touched = true;
+    tsdf_fuse_frame<RGB>(a, c, f, xf, yf, zf, live, K, in, HW, plane);
   }
-  if (touched) {
-    tsdf[i] = T; wsum[i] = W;
-    if (RGB) { rgb[3 * i] = cr; rgb[3 * i + 1] = cg; rgb[3 * i + 2] = cb; }
+  if (a.touched) {
+    tsdf[i] = a.T; wsum[i] = a.W;
+    if (RGB) { rgb[3 * i] = a.cr; rgb[3 * i + 1] = a.cg; rgb[3 * i + 2] = a.cb; }
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------ mesh
-
-// flag byte of a cell: bit 0 active, bits 1-3 a quad around the edge corner 0 -> corner 0 + e_a (a = x, y, z), bit 4 corner 0 inside
-constexpr int kActive = 1, kInsideA = 16;
 
 struct Grid {
   const float* tsdf; const float* wsum; const float* rgb;
@@ -216,8 +166,6 @@ __global__ __launch_bounds__(kScanThreads) void mesh_scan_kernel(const int* __re
   }
 }
 
-struct MeshOut { float* verts; float* normals; uint8_t* rgba; int32_t* faces; int vcap, fcap; };
-
 __global__ __launch_bounds__(kBlock) void mesh_verts_kernel(const Grid g, long long cells, const uint8_t* __restrict__ flags,
                                                            const int* __restrict__ vbase, int32_t* __restrict__ vidx, const MeshOut out) {
   const int tid = threadIdx.x;
@@ -241,53 +189,7 @@ __global__ __launch_bounds__(kBlock) void mesh_verts_kernel(const Grid g, long l
     at[j] = voxel_index(g, cz + (j >> 2), cy + ((j >> 1) & 1), cx + (j & 1));
     s[j] = g.tsdf[at[j]];
   }
-  // mean of the crossings of the sign-changing edges, in cell coordinates; edges in the order x (from corners 0, 2, 4, 6),
-  // y (0, 1, 4, 5), z (0, 1, 2, 3)
-  float p[3] = {0.0f, 0.0f, 0.0f};
-  int n = 0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (j & (1 << a)) continue;
-      const float sa = s[j], sb = s[j | (1 << a)];
-      if ((sa < 0.0f) == (sb < 0.0f)) continue;
-      const float t = sa / (sa - sb);     // opposite sides: |sa - sb| = |sa| + |sb| > 0
-#pragma unroll
-      for (int e = 0; e < 3; ++e) p[e] += (e == a) ? t : static_cast<float>((j >> e) & 1);
-      ++n;
-    }
-  }
-  const float nf = static_cast<float>(n);
-  float* o = out.verts + 3ll * idx;
-  o[0] = g.ox + g.voxel * (static_cast<float>(cx) + p[0] / nf);
-  o[1] = g.oy + g.voxel * (static_cast<float>(cy) + p[1] / nf);
-  o[2] = g.oz + g.voxel * (static_cast<float>(cz) + p[2] / nf);
-  if (out.normals) {                      // central gradient of the eight corners, toward increasing tsdf
-    const float gx = ((s[1] - s[0]) + (s[3] - s[2])) + ((s[5] - s[4]) + (s[7] - s[6]));
-    const float gy = ((s[2] - s[0]) + (s[3] - s[1])) + ((s[6] - s[4]) + (s[7] - s[5]));
-    const float gz = ((s[4] - s[0]) + (s[5] - s[1])) + ((s[6] - s[2]) + (s[7] - s[3]));
-    const float len = sqrtf(gx * gx + gy * gy + gz * gz);
-    float* q = out.normals + 3ll * idx;
-    const bool zero = !(len > 0.0f);
-    q[0] = zero ? 0.0f : gx / len; q[1] = zero ? 0.0f : gy / len; q[2] = zero ? 0.0f : gz / len;
-  }
-  if (out.rgba) {
-    uchar4 c = make_uchar4(0, 0, 0, 255);
-    if (g.rgb) {
-      float acc[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int e = 0; e < 3; ++e) acc[e] += g.rgb[3 * at[j] + e];
-      }
-      // mean + 0.5, floored, clamped to [0, 255] (NaN -> 0)
-      c.x = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[0] * 0.125f + 0.5f))));
-      c.y = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[1] * 0.125f + 0.5f))));
-      c.z = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[2] * 0.125f + 0.5f))));
-    }
-    reinterpret_cast<uchar4*>(out.rgba)[idx] = c;
-  }
+  surface_net_vertex(s, g.rgb, at, cx, cy, cz, g.ox, g.oy, g.oz, g.voxel, out, idx);
 }
 
 __global__ __launch_bounds__(kBlock) void mesh_faces_kernel(const Grid g, long long cells, const uint8_t* __restrict__ flags,

@@ -514,15 +514,40 @@ class DepthVideo:
         dims = [int(math.ceil((float(h) - float(l) + 2.0 * float(trunc)) / float(voxel))) + 1 for l, h in zip(lo, hi)]
         return origin, (dims[2], dims[1], dims[0])
 
+    @staticmethod
+    def tsdf_sparse_bounds(xyz, voxel, trunc):
+        """the brick world around the points xyz [n,3]: tsdf_bounds with the 0.1st and 99.9th percentile - the map's full extent but for
+        stray points - and every axis rounded up to whole 8-voxel bricks.  Returns (origin [x,y,z] as floats, (gz,gy,gx) bricks); a
+        ValueError where that is over the brick grid's limit (2^21 voxels per axis, fewer than 2^31 bricks).  Works on CPU tensors."""
+        from .tsdf_sparse import AXIS_LIMIT, BRICK, GRID_LIMIT
+        n = int(xyz.shape[0])
+        if n == 0:
+            raise ValueError("tsdf_sparse_bounds: no points")
+        sub = xyz[::max(1, -(-n // (1 << 20)))].to(torch.float64)
+        m = sub.shape[0]
+        s = torch.sort(sub, dim=0).values
+        lo, hi = s[int(math.floor(0.001 * (m - 1)))], s[int(math.ceil(0.999 * (m - 1)))]
+        origin = [float(v) - float(trunc) for v in lo]
+        dims = [int(math.ceil((float(h) - float(l) + 2.0 * float(trunc)) / float(voxel))) + 1 for l, h in zip(lo, hi)]
+        g = [-(-d // BRICK) for d in dims]
+        if max(g) > AXIS_LIMIT or g[0] * g[1] * g[2] >= GRID_LIMIT:
+            raise ValueError("tsdf_sparse_bounds: %d x %d x %d voxels of %g are over the brick grid's limit (2^21 voxels per axis, fewer "
+                             "than 2^31 bricks of 8^3): use a larger voxel" % (dims[0], dims[1], dims[2], float(voxel)))
+        return origin, (g[2], g[1], g[0])
+
     def tsdf(self, voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None, use_sigma=False, origin=None, dims=None,
-             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05):
+             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05, sparse=False, margin=2):
         """the fused surface of keyframes ix (default: all stored ones; fuse after `terminate` - poses that move later are not
         de-integrated): a TSDF volume of `voxel`-sized cells, truncation `trunc` (default 3 voxels), integrated natively
         (pvo_tsdf_integrate) from exactly the pixels map_points(ix, thresh, full_res, reject, max_rel_sigma) keeps, and its surface-nets
         mesh (pvo_tsdf_mesh).  use_sigma (needs the variances of `uncertainty`): pixels are weighted by fusion_weights(keep, disps,
         sigma, rel0), sigma at the 1/8 cell for full_res.  origin [x,y,z] / dims (nz,ny,nx): the volume; default tsdf_bounds of the map's
         points.  Returns a dict: verts, normals, rgba, faces (the mesh; min_weight = the least wsum of a usable voxel), tsdf, wsum
-        (the volume), origin, voxel."""
+        (the volume), origin, voxel.
+        sparse=True: the same pixels and weights into a brick volume (pvo_amd.tsdf_sparse.SparseTSDF: bricks allocated within `margin`
+        voxels of the samples along every kept pixel's ray, pvo_tsdf_sparse_allocate / _integrate / _mesh) - for maps a dense volume
+        cannot hold.  The world defaults to tsdf_sparse_bounds of the map's points; given dims are rounded up to bricks.  Returns the
+        mesh, origin, voxel and `volume`, the SparseTSDF, in place of tsdf / wsum."""
         trunc = 3.0 * float(voxel) if trunc is None else float(trunc)
         n = self.counter
         m = self.map_points(ix=ix, thresh=thresh, full_res=full_res, reject=reject, max_rel_sigma=max_rel_sigma)
@@ -541,6 +566,20 @@ class DepthVideo:
             if div > 1:
                 sigma = sigma.repeat_interleave(div, 1).repeat_interleave(div, 2)
         weight = self.fusion_weights(keep, disps, sigma, rel0).contiguous()
+        if sparse:
+            from .tsdf_sparse import BRICK, SparseTSDF
+            if origin is None or dims is None:
+                origin, gdims = self.tsdf_sparse_bounds(m["xyz"], voxel, trunc)
+            else:
+                gdims = [-(-int(v) // BRICK) for v in dims]
+            vol = SparseTSDF(origin, gdims, voxel, trunc, colours=self.images is not None, device=self.device)
+            frames = (self.poses[:n], disps.contiguous(), intr.contiguous(), ix)
+            vol.allocate(*frames, weight=weight, margin=margin)
+            vol.integrate(*frames, weight=weight, images=self.images, img_stride=stride, img_offset=offset, w_max=w_max)
+            out = vol.mesh(min_weight=min_weight)
+            out.pop("counts")
+            out.update(volume=vol, origin=[float(v) for v in origin], voxel=float(voxel))
+            return out
         if origin is None or dims is None:
             origin, dims = self.tsdf_bounds(m["xyz"], voxel, trunc)
         nz, ny, nx = [int(v) for v in dims]

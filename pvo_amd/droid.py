@@ -179,8 +179,8 @@ class Droid:
     def get_mesh(self, **kw):
         """the fused surface of the keyframes: DepthVideo.tsdf(voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None,
         use_sigma=False, origin=None, dims=None, min_weight=1.0, w_max=0) - a dict of the mesh verts [V,3], normals [V,3], rgba [V,4],
-        faces [F,3] and the volume tsdf, wsum [nz,ny,nx], origin, voxel.  Call it after terminate(): poses that move later are not
-        de-integrated."""
+        faces [F,3] and the volume tsdf, wsum [nz,ny,nx], origin, voxel.  sparse=True (with margin=2): a brick volume in place of the dense
+        one, returned as `volume` (DepthVideo.tsdf).  Call it after terminate(): poses that move later are not de-integrated."""
         self.flush()
         return self.video.tsdf(**kw)
 

@@ -632,6 +632,131 @@ def tsdf_mesh(tsdf, wsum, rgb, origin, voxel, min_weight=1.0, vcap=None, fcap=No
     return out
 
 
+def _sparse_world(a, vol):
+    """the brick volume's fields every sparse call shares.  vol: a dict (pvo_amd.tsdf_sparse.SparseTSDF.volume()) with grid int32
+    [gz,gy,gx], coord int32 [cap,3], counts int32 [1], tsdf / wsum f32 [cap,8,8,8], rgb f32 [cap,8,8,8,3] or None, origin, voxel"""
+    grid, coord, counts, tsdf, wsum, rgb = vol["grid"], vol["coord"], vol["counts"], vol["tsdf"], vol["wsum"], vol.get("rgb")
+    for t, n in ((grid, "grid"), (coord, "coord"), (counts, "counts"), (tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")):
+        if t is not None:
+            _contig(t, n)
+    dev = _dev(grid, coord, counts, tsdf, wsum, rgb)
+    B = _lib.TSDF_BRICK
+    cap = tsdf.shape[0]
+    if grid.dtype != torch.int32 or coord.dtype != torch.int32 or counts.dtype != torch.int32 or grid.dim() != 3 or counts.numel() < 1:
+        raise PvoHipError("sparse tsdf: grid [gz,gy,gx], coord [cap,3] and counts [1] must be int32")
+    if (tuple(tsdf.shape) != (cap, B, B, B) or wsum.shape != tsdf.shape or tuple(coord.shape) != (cap, 3)
+            or (rgb is not None and tuple(rgb.shape) != (cap, B, B, B, 3))):
+        raise PvoHipError("sparse tsdf: the pool must be tsdf / wsum [cap,8,8,8], rgb [cap,8,8,8,3], coord [cap,3]")
+    for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")):
+        if t is not None:
+            _f32(t, n)
+    a.gz, a.gy, a.gx = grid.shape
+    a.cap = cap
+    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in vol["origin"]]
+    a.voxel = float(vol["voxel"])
+    a.coord, a.bricks = _ptr(coord), _ptr(counts)
+    return dev
+
+
+def _sparse_frames(a, what, poses, disps, intrinsics, ix, weight):
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ix, "ix"), (weight, "weight")):
+        if t is not None:
+            _contig(t, n)
+    _long(ix, "ix")
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (weight, "weight")):
+        if t is not None:
+            _f32(t, n)
+    N, (nf, ht, wd) = ix.shape[0], disps.shape
+    if poses.shape[0] < nf or (weight is not None and weight.shape != disps.shape):
+        raise PvoHipError("%s: poses must cover the frames of disps, weight must have the shape of disps" % what)
+    a.poses, a.disps, a.intrinsics, a.ix, a.weight = _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ix), _ptr(weight)
+    a.N, a.nframes, a.ht, a.wd = N, nf, ht, wd
+
+
+def tsdf_sparse_allocate(vol, poses, disps, intrinsics, ix, trunc, weight=None, z_near=0.0, margin=2.0):
+    """Mark the bricks near the surfaces keyframes ix see and append the new ones to the pool of the brick volume `vol` (a dict, see
+    _sparse_world; include/pvo_hip.h pvo_tsdf_sparse_allocate).  vol["counts"][0] becomes the number of bricks the volume wants, NOT
+    clamped by the pool's capacity: the caller reads it and comes back with a larger pool (SparseTSDF.allocate does).  No allocation
+    beyond the cached workspace, no synchronisation."""
+    a = _lib.TsdfSparseAllocateArgs()
+    dev = _sparse_world(a, vol)
+    _dev(vol["grid"], poses, disps, intrinsics, ix, weight)
+    _sparse_frames(a, "tsdf_sparse_allocate", poses, disps, intrinsics, ix, weight)
+    a.grid = _ptr(vol["grid"])
+    a.trunc, a.z_near, a.margin = float(trunc), float(z_near), float(margin)
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_sparse_allocate_workspace_bytes(a.gz, a.gy, a.gx, a.N))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_sparse_allocate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_allocate")
+
+
+def tsdf_sparse_integrate(vol, poses, disps, intrinsics, ix, trunc, weight=None, images=None, img_stride=8, img_offset=3, z_near=0.0,
+                          w_max=0.0, kept=None):
+    """tsdf_integrate on the bricks in use of the brick volume `vol` (include/pvo_hip.h pvo_tsdf_sparse_integrate): every voxel of a
+    brick gets the bytes the dense call leaves at that voxel; a frame is tested once per brick, not once per voxel.  kept: int32
+    [cap] or None, per brick in use the number of slots of ix that survived the cull.  No allocation beyond the cached workspace, no
+    synchronisation."""
+    a = _lib.TsdfSparseIntegrateArgs()
+    dev = _sparse_world(a, vol)
+    _dev(vol["grid"], poses, disps, intrinsics, ix, weight, images)
+    _sparse_frames(a, "tsdf_sparse_integrate", poses, disps, intrinsics, ix, weight)
+    if images is not None:
+        _contig(images, "images")
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < a.nframes or images.shape[1] != 3:
+            raise PvoHipError("tsdf_sparse_integrate: images must be uint8 [nframes,3,IH,IW]")
+        a.images, a.IH, a.IW, a.img_stride, a.img_offset = _ptr(images), images.shape[2], images.shape[3], int(img_stride), int(img_offset)
+    a.tsdf, a.wsum, a.rgb = _ptr(vol["tsdf"]), _ptr(vol["wsum"]), _ptr(vol.get("rgb"))
+    a.trunc, a.z_near, a.w_max = float(trunc), float(z_near), float(w_max)
+    if kept is not None:
+        _contig(kept, "kept")
+        if kept.dtype != torch.int32 or kept.numel() < a.cap or kept.device != dev:
+            raise PvoHipError("tsdf_sparse_integrate: kept must be an int32 device tensor of at least cap elements")
+        a.kept = _ptr(kept)
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_sparse_integrate_workspace_bytes(a.N))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_sparse_integrate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_integrate")
+
+
+def tsdf_sparse_mesh_into(vol, min_weight, out):
+    """pvo_tsdf_sparse_mesh on caller-owned buffers (out as for tsdf_mesh_into).  No allocation beyond the cached workspace, no
+    synchronisation."""
+    a = _lib.TsdfSparseMeshArgs()
+    dev = _sparse_world(a, vol)
+    a.grid = _ptr(vol["grid"])
+    a.tsdf, a.wsum, a.rgb = _ptr(vol["tsdf"]), _ptr(vol["wsum"]), _ptr(vol.get("rgb"))
+    a.min_weight = float(min_weight)
+    a.vcap, a.fcap = out["verts"].shape[0], out["faces"].shape[0]
+    a.verts, a.normals, a.rgba, a.faces = _ptr(out["verts"]), _ptr(out.get("normals")), _ptr(out.get("rgba")), _ptr(out["faces"])
+    a.counts = ctypes.c_void_p(out["counts"].data_ptr())
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_sparse_mesh_workspace_bytes(a.cap))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_sparse_mesh(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_mesh")
+
+
+def tsdf_sparse_mesh(vol, min_weight=1.0, vcap=None, fcap=None):
+    """The surface-nets mesh of a brick volume (include/pvo_hip.h pvo_tsdf_sparse_mesh), the dict of tsdf_mesh; vertices in the order
+    (slot, raster order inside the brick).  One host synchronisation (the counts), a second call if a capacity was exceeded."""
+    dev = vol["tsdf"].device
+    cap = vol["tsdf"].shape[0]
+    vcap = min(cap * _lib.TSDF_BRICK ** 3, max(1024, 96 * cap)) if vcap is None else int(vcap)
+    fcap = 2 * vcap if fcap is None else int(fcap)
+    while True:
+        out = {"verts": torch.empty(vcap, 3, dtype=torch.float32, device=dev), "normals": torch.empty(vcap, 3, dtype=torch.float32, device=dev),
+               "rgba": torch.empty(vcap, 4, dtype=torch.uint8, device=dev), "faces": torch.empty(fcap, 3, dtype=torch.int32, device=dev),
+               "counts": torch.empty(2, dtype=torch.int32, device=dev)}
+        tsdf_sparse_mesh_into(vol, min_weight, out)
+        nv, nf = out["counts"].tolist()                 # the one synchronisation
+        if nv <= vcap and nf <= fcap:
+            break
+        vcap, fcap = max(nv, vcap), max(nf, fcap)
+    for k in ("verts", "normals", "rgba"):
+        out[k] = out[k][:nv]
+    out["faces"] = out["faces"][:nf]
+    return out
+
+
 def _baseline(baseline, what):
     """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
     b = float(baseline)

@@ -2,7 +2,7 @@
 
     python tools/export_map.py --datapath <.../SceneXX> --weights <checkpoint.pth> --map out.ply [--full_res] [--filter_thresh_map 0.005]
                                [--reconstruction_path DIR] [--uncertainty [--max_rel_sigma X]]
-                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight]]
+                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight] [--sparse]]
 
 --map writes the filtered point cloud of all keyframes after the global bundle adjustment (Droid.get_map: points confirmed by two
 neighbouring keyframes, pvo_map_points) as a binary little-endian PLY: x y z float, red green blue uchar, int label (the per-frame
@@ -14,7 +14,8 @@ does not refresh them) and adds `property float sigma` to the PLY; --max_rel_sig
 standard deviation sigma / disp exceeds X.  --mesh also fuses the same pixels into a TSDF volume of --voxel sized cells (truncation
 --trunc, default three voxels) and writes its surface-nets mesh (Droid.get_mesh: pvo_tsdf_integrate / pvo_tsdf_mesh) as a binary PLY
 with vertex normals, colours and triangle faces; --sigma_weight (with --uncertainty) weights every pixel by its inverse-depth
-variance instead of counting all alike.  Without --mesh the output is what it was without the option.
+variance instead of counting all alike; --sparse fuses into a brick volume over the map's full extent (pvo_tsdf_sparse_*) where the
+dense volume is clipped to what fits.  Without --mesh the output is what it was without the option, and without --sparse the mesh is.
 """
 import os
 import sys
@@ -39,6 +40,7 @@ def parse_args(argv=None):
     p.add_argument("--voxel", type=float, default=None, help="with --mesh: the TSDF volume's voxel size, in the units of the poses")
     p.add_argument("--trunc", type=float, default=None, help="with --mesh: the truncation distance (default: 3 voxels)")
     p.add_argument("--sigma_weight", action="store_true", help="with --mesh and --uncertainty: weight pixels by their variance")
+    p.add_argument("--sparse", action="store_true", help="with --mesh: a brick volume over the map's full extent")
     own, rest = p.parse_known_args(argv)
     args = test_vo.parse_args(rest)
     for k, v in vars(own).items():
@@ -49,12 +51,25 @@ def parse_args(argv=None):
         p.error("--mesh needs --voxel V with V > 0")
     if args.sigma_weight and not (args.mesh is not None and args.uncertainty):
         p.error("--sigma_weight needs --mesh and --uncertainty")
+    if args.sparse and args.mesh is None:
+        p.error("--sparse needs --mesh")
     return args
+
+
+def write_mesh(droid, args):
+    """the --mesh output of a tracked sequence; returns the line that says what was written"""
+    from pvo_amd.handoff import write_ply_mesh
+    kw = {"sparse": True} if args.sparse else {}
+    g = droid.get_mesh(voxel=args.voxel, trunc=args.trunc, thresh=args.filter_thresh_map, full_res=args.full_res,
+                       use_sigma=args.sigma_weight, max_rel_sigma=args.max_rel_sigma, **kw)
+    nv, nf = write_ply_mesh(args.mesh, g["verts"], g["faces"], g["rgba"], g["normals"])
+    what = ("%d bricks of 8^3" % g["volume"].bricks) if args.sparse else ("a %s volume" % "x".join(str(d) for d in g["tsdf"].shape))
+    return "mesh: %d vertices, %d triangles from %s of %g-sized voxels written to %s" % (nv, nf, what, args.voxel, args.mesh)
 
 
 def main(argv=None):
     from pvo_amd.droid import Droid
-    from pvo_amd.handoff import save_reconstruction, write_kitti_trajectory, write_ply, write_ply_mesh
+    from pvo_amd.handoff import save_reconstruction, write_kitti_trajectory, write_ply
     args = parse_args(argv)
     args.half_update = True
     args.store_images = True
@@ -73,11 +88,7 @@ def main(argv=None):
     n = write_ply(args.map, m["xyz"], m["rgba"], m.get("label") if args.segm_filter else None, **({"sigma": m["sigma"]} if args.uncertainty else {}))
     print("map: %d points of %d keyframes written to %s" % (n, droid.video.counter, args.map))
     if args.mesh is not None:
-        g = droid.get_mesh(voxel=args.voxel, trunc=args.trunc, thresh=args.filter_thresh_map, full_res=args.full_res,
-                           use_sigma=args.sigma_weight, max_rel_sigma=args.max_rel_sigma)
-        nv, nf = write_ply_mesh(args.mesh, g["verts"], g["faces"], g["rgba"], g["normals"])
-        print("mesh: %d vertices, %d triangles from a %s volume of %g-sized voxels written to %s"
-              % (nv, nf, "x".join(str(d) for d in g["tsdf"].shape), args.voxel, args.mesh))
+        print(write_mesh(droid, args))
     if args.reconstruction_path:
         for p in save_reconstruction(args.reconstruction_path, droid.video):
             print("wrote", p)
