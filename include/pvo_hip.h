@@ -86,7 +86,9 @@ const char* pvo_last_hip_error(void);
  * reconstruction: no existing struct changed - new structs pvo_tsdf_integrate_args / pvo_tsdf_mesh_args (their *_args_size() report the
  * sizes) and new entry points pvo_tsdf_integrate[_args_size, _workspace_bytes] / pvo_tsdf_mesh[_args_size, _workspace_bytes]; still 106,
  * sparse surface reconstruction: no existing struct changed - new structs pvo_tsdf_sparse_{allocate,integrate,mesh}_args and new entry
- * points pvo_tsdf_sparse_{allocate,integrate,mesh}[_args_size, _workspace_bytes]): a caller
+ * points pvo_tsdf_sparse_{allocate,integrate,mesh}[_args_size, _workspace_bytes]; still 106, panoptic surface reconstruction: no
+ * existing struct changed - new extension structs pvo_tsdf_panoptic_args / pvo_tsdf_mesh_labels_args (with *_args_size()) and new entry
+ * points pvo_tsdf[_sparse]_integrate_panoptic / pvo_tsdf[_sparse]_mesh_panoptic): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -903,6 +905,56 @@ typedef struct pvo_tsdf_sparse_mesh_args {
 size_t pvo_tsdf_sparse_mesh_args_size(void);
 size_t pvo_tsdf_sparse_mesh_workspace_bytes(int cap);
 int pvo_tsdf_sparse_mesh(const pvo_tsdf_sparse_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Panoptic surface reconstruction: per-voxel segment ids and a labelled mesh  */
+/* ------------------------------------------------------------------------- */
+
+/* pvo_tsdf_integrate_panoptic / pvo_tsdf_sparse_integrate_panoptic: the plain call on `a` - the same validation, workspace, launches
+ * and BYTES in tsdf / wsum / rgb - which also fuses per-frame segment ids into two more caller-owned volumes of the plain call's
+ * shape ([nz,ny,nx], or the pool's [cap,8,8,8]), zeroed when empty:
+ *     label int32   the voxel's current segment id; L <= 0 everywhere means "no segment"
+ *     lconf f32     the weight by which that id leads
+ *     labels int32 [nframes,lh,lw]  the frames' id maps, read at (vi / label_div, ui / label_div) (integer division)
+ *   Per (voxel, frame) that contributes under pvo_tsdf_integrate's sequence, with that contribution's w, sdf, ui, vi, and only if
+ *   sdf <= trunc (free space in front of a surface never votes):  L = labels[f][vi / label_div][ui / label_div];  if L > 0, a weighted
+ *   Boyer-Moore vote in fp32, one rounded operation each:
+ *     label == L: lconf += w;   else lconf < w: label = L, lconf = w - lconf;   else: lconf -= w;
+ *     then lconf = w_max where w_max > 0 and lconf > w_max.
+ *   label / lconf of a voxel are written only if the voxel was touched (a contribution, voting or not).  The vote runs in the order
+ *   of ix inside the voxel's one thread, so split calls leave the bytes of one call, and a voxel of a brick ends with the dense
+ *   call's label bytes (the same inline function, csrc/tsdf_fuse.h).
+ * No further launch, no atomics, no allocation, no host synchronisation: capturable.  workspace: the plain call's.
+ * PVO_EINVAL, before anything else is looked at: a NULL p / label / lconf / labels, label_div < 1, lh * label_div < ht or
+ * lw * label_div < wd; then the plain call's limits. */
+typedef struct pvo_tsdf_panoptic_args {
+  int32_t* label;
+  float* lconf;
+  const int32_t* labels;
+  int lh, lw, label_div;
+} pvo_tsdf_panoptic_args;
+size_t pvo_tsdf_panoptic_args_size(void);
+int pvo_tsdf_integrate_panoptic(const pvo_tsdf_integrate_args* a, const pvo_tsdf_panoptic_args* p, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int pvo_tsdf_sparse_integrate_panoptic(const pvo_tsdf_sparse_integrate_args* a, const pvo_tsdf_panoptic_args* p, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+
+/* pvo_tsdf_mesh_panoptic / pvo_tsdf_sparse_mesh_panoptic: the plain mesh call on `a` - the same bytes in verts / normals / rgba /
+ * faces / counts, the same capacity protocol and workspace - which also writes one label per vertex:
+ *     label  int32, the volume's (or the pool's) labels;   vlabel int32 [vcap]
+ *   vlabel[i] = the label of the corner with the smallest |tsdf| among the eight corners of the vertex's cell that have label > 0,
+ *   ties to the lowest corner index j = 4 dz + 2 dy + dx; 0 if no corner has one.  Comparisons only: exact.  A vertex beyond vcap is
+ *   written nowhere.
+ * PVO_EINVAL: a NULL p / label, a NULL vlabel with vcap > 0; then the plain call's limits. */
+typedef struct pvo_tsdf_mesh_labels_args {
+  const int32_t* label;
+  int32_t* vlabel;
+} pvo_tsdf_mesh_labels_args;
+size_t pvo_tsdf_mesh_labels_args_size(void);
+int pvo_tsdf_mesh_panoptic(const pvo_tsdf_mesh_args* a, const pvo_tsdf_mesh_labels_args* p, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int pvo_tsdf_sparse_mesh_panoptic(const pvo_tsdf_sparse_mesh_args* a, const pvo_tsdf_mesh_labels_args* p, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

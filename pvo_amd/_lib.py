@@ -123,6 +123,12 @@ SIGNATURES = {
     "pvo_tsdf_sparse_mesh_args_size": (_sz, []),
     "pvo_tsdf_sparse_mesh_workspace_bytes": (_sz, [_i]),
     "pvo_tsdf_sparse_mesh": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_panoptic_args_size": (_sz, []),
+    "pvo_tsdf_mesh_labels_args_size": (_sz, []),
+    "pvo_tsdf_integrate_panoptic": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pvo_tsdf_sparse_integrate_panoptic": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pvo_tsdf_mesh_panoptic": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pvo_tsdf_sparse_mesh_panoptic": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -229,6 +235,16 @@ class TsdfSparseMeshArgs(_c.Structure):
                 ("verts", _vp), ("normals", _vp), ("rgba", _vp), ("faces", _vp), ("counts", _vp)]
 
 
+class TsdfPanopticArgs(_c.Structure):
+    """pvo_tsdf_panoptic_args"""
+    _fields_ = [("label", _vp), ("lconf", _vp), ("labels", _vp), ("lh", _i), ("lw", _i), ("label_div", _i)]
+
+
+class TsdfMeshLabelsArgs(_c.Structure):
+    """pvo_tsdf_mesh_labels_args"""
+    _fields_ = [("label", _vp), ("vlabel", _vp)]
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 
@@ -267,7 +283,8 @@ def load():
     for fn, struct in ((lib.pvo_tsdf_integrate_args_size, TsdfIntegrateArgs), (lib.pvo_tsdf_mesh_args_size, TsdfMeshArgs),
                        (lib.pvo_tsdf_sparse_allocate_args_size, TsdfSparseAllocateArgs),
                        (lib.pvo_tsdf_sparse_integrate_args_size, TsdfSparseIntegrateArgs),
-                       (lib.pvo_tsdf_sparse_mesh_args_size, TsdfSparseMeshArgs)):
+                       (lib.pvo_tsdf_sparse_mesh_args_size, TsdfSparseMeshArgs),
+                       (lib.pvo_tsdf_panoptic_args_size, TsdfPanopticArgs), (lib.pvo_tsdf_mesh_labels_args_size, TsdfMeshLabelsArgs)):
         if fn() != ctypes.sizeof(struct):
             raise PvoHipError("libpvo_hip.so has a %d-byte %s; this binding is written for %d bytes - rebuild with "
                               "`python -m pvo_amd.build`" % (fn(), struct.__doc__, ctypes.sizeof(struct)))

@@ -16,6 +16,10 @@
 // No atomics anywhere: every output index is a function of the classification bits alone, and a voxel's running average is one
 // thread's sequential loop - the same operands give the same bytes.  The slot constants, the update of a voxel by one frame and the
 // vertex of a cell are the inline functions of tsdf_fuse.h, which the brick volume (tsdf_sparse.hip) calls as well.
+//
+// Panoptic (pvo_tsdf_integrate_panoptic, pvo_tsdf_mesh_panoptic): the same launches with the LAB instantiations of (b) and (c) - the
+// label vote inside the voxel's frame loop, the vertex's label beside its position.  What they need beyond the plain kernels' arguments
+// is the kernels' last argument, empty without LAB, so the plain instantiations keep their code.
 #include "tsdf_fuse.h"
 
 namespace {
@@ -38,10 +42,11 @@ __global__ __launch_bounds__(64) void tsdf_frames_kernel(const float* __restrict
   tsdf_frame_constants(poses, f, vol, o);
 }
 
-template <bool RGB>
+// LAB: with the label vote on the caller's label / lconf volumes (pvo_tsdf_integrate_panoptic)
+template <bool RGB, bool LAB>
 __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(float* __restrict__ tsdf, float* __restrict__ wsum, float* __restrict__ rgb,
                                                                const float* __restrict__ fc, const float* __restrict__ intrinsics,
-                                                               const Fuse in, int N, int nz, int ny, int nx) {
+                                                               const Fuse in, int N, int nz, int ny, int nx, const VoteVolumes<LAB> pan) {
   const long long total = static_cast<long long>(nz) * ny * nx;
   const long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
   const bool live = i < total;
@@ -50,20 +55,23 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(float* __restric
   const Intr K = load_intr(intrinsics);
   const long long HW = static_cast<long long>(in.ht) * in.wd;
   const long long plane = static_cast<long long>(in.IH) * in.IW;
-  Voxel a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, false};
+  Voxel a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, false, 0, 0.0f};
   if (live) {
     a.T = tsdf[i]; a.W = wsum[i];
     if (RGB) { a.cr = rgb[3 * i]; a.cg = rgb[3 * i + 1]; a.cb = rgb[3 * i + 2]; }
+    if constexpr (LAB) { a.L = pan.label[i]; a.lc = pan.lconf[i]; }
   }
   for (int b = 0; b < N; ++b) {
     const float* __restrict__ c = fc + static_cast<long long>(kFrameFloats) * b;      // wave-uniform
     const int f = __float_as_int(c[12]);
     if (f < 0) continue;
-    tsdf_fuse_frame<RGB>(a, c, f, xf, yf, zf, live, K, in, HW, plane);
+    if constexpr (LAB) tsdf_fuse_frame<RGB, true>(a, c, f, xf, yf, zf, live, K, in, HW, plane, pan.maps);
+    else tsdf_fuse_frame<RGB>(a, c, f, xf, yf, zf, live, K, in, HW, plane);
   }
   if (a.touched) {
     tsdf[i] = a.T; wsum[i] = a.W;
     if (RGB) { rgb[3 * i] = a.cr; rgb[3 * i + 1] = a.cg; rgb[3 * i + 2] = a.cb; }
+    if constexpr (LAB) { pan.label[i] = a.L; pan.lconf[i] = a.lc; }
   }
 }
 
@@ -166,8 +174,11 @@ __global__ __launch_bounds__(kScanThreads) void mesh_scan_kernel(const int* __re
   }
 }
 
+// LAB: the vertex's label into vlabel as well (pvo_tsdf_mesh_panoptic)
+template <bool LAB>
 __global__ __launch_bounds__(kBlock) void mesh_verts_kernel(const Grid g, long long cells, const uint8_t* __restrict__ flags,
-                                                           const int* __restrict__ vbase, int32_t* __restrict__ vidx, const MeshOut out) {
+                                                           const int* __restrict__ vbase, int32_t* __restrict__ vidx, const MeshOut out,
+                                                           const VertexLabels<LAB> lab) {
   const int tid = threadIdx.x;
   const long long k = static_cast<long long>(blockIdx.x) * kBlock + tid;
   const bool active = k < cells && (flags[k] & kActive);
@@ -190,6 +201,7 @@ __global__ __launch_bounds__(kBlock) void mesh_verts_kernel(const Grid g, long l
     s[j] = g.tsdf[at[j]];
   }
   surface_net_vertex(s, g.rgb, at, cx, cy, cz, g.ox, g.oy, g.oz, g.voxel, out, idx);
+  if constexpr (LAB) lab.vlabel[idx] = surface_net_label(s, lab.label, at);
 }
 
 __global__ __launch_bounds__(kBlock) void mesh_faces_kernel(const Grid g, long long cells, const uint8_t* __restrict__ flags,
@@ -253,6 +265,8 @@ inline bool finite_f(float v) { return v - v == 0.0f; }
 
 extern "C" size_t pvo_tsdf_integrate_args_size(void) { return sizeof(pvo_tsdf_integrate_args); }
 extern "C" size_t pvo_tsdf_mesh_args_size(void) { return sizeof(pvo_tsdf_mesh_args); }
+extern "C" size_t pvo_tsdf_panoptic_args_size(void) { return sizeof(pvo_tsdf_panoptic_args); }
+extern "C" size_t pvo_tsdf_mesh_labels_args_size(void) { return sizeof(pvo_tsdf_mesh_labels_args); }
 
 extern "C" size_t pvo_tsdf_integrate_workspace_bytes(int N) {
   return N <= 0 ? 0 : aligned(sizeof(float) * kFrameFloats * static_cast<size_t>(N));
@@ -263,8 +277,16 @@ extern "C" size_t pvo_tsdf_mesh_workspace_bytes(int nz, int ny, int nx) {
   return mesh_layout(nz, ny, nx).total;
 }
 
-extern "C" int pvo_tsdf_integrate(const pvo_tsdf_integrate_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+
+// pvo_tsdf_integrate (p == NULL) and pvo_tsdf_integrate_panoptic: one validation, one launch sequence
+int integrate_impl(const pvo_tsdf_integrate_args* a, const pvo_tsdf_panoptic_args* p, bool panoptic, void* workspace, size_t workspace_bytes,
+                   void* stream) {
   PVO_REQ(a);
+  if (panoptic) {
+    PVO_REQ(p && p->label && p->lconf && p->labels && p->label_div >= 1);
+    PVO_REQ(static_cast<long long>(p->lh) * p->label_div >= a->ht && static_cast<long long>(p->lw) * p->label_div >= a->wd);
+  }
   PVO_REQ(volume_ok(a->nz, a->ny, a->nx));
   PVO_REQ(a->N >= 0 && a->nframes >= 0 && a->ht >= 0 && a->wd >= 0 && static_cast<long long>(a->ht) * a->wd < (1ll << 31));
   PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->trunc > 0.0f && finite_f(a->trunc));
@@ -288,18 +310,42 @@ extern "C" int pvo_tsdf_integrate(const pvo_tsdf_integrate_args* a, void* worksp
   PVO_CHECK_LAUNCH();
   const Fuse in = {a->disps, a->weight, a->images, a->ht, a->wd, a->IH, a->IW, a->img_stride, a->img_offset, a->trunc, a->z_near, a->w_max};
   const dim3 grid(static_cast<unsigned>((total + kBlock - 1) / kBlock));
-  if (a->rgb)
-    hipLaunchKernelGGL(tsdf_integrate_kernel<true>, grid, dim3(kBlock), 0, s, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N,
-                       a->nz, a->ny, a->nx);
+  if (panoptic) {
+    const VoteVolumes<true> pan = {p->label, p->lconf, {p->labels, p->lh, p->lw, p->label_div}};
+    if (a->rgb)
+      hipLaunchKernelGGL((tsdf_integrate_kernel<true, true>), grid, dim3(kBlock), 0, s, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N,
+                         a->nz, a->ny, a->nx, pan);
+    else
+      hipLaunchKernelGGL((tsdf_integrate_kernel<false, true>), grid, dim3(kBlock), 0, s, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N,
+                         a->nz, a->ny, a->nx, pan);
+  } else if (a->rgb)
+    hipLaunchKernelGGL((tsdf_integrate_kernel<true, false>), grid, dim3(kBlock), 0, s, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N,
+                       a->nz, a->ny, a->nx, VoteVolumes<false>{});
   else
-    hipLaunchKernelGGL(tsdf_integrate_kernel<false>, grid, dim3(kBlock), 0, s, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N,
-                       a->nz, a->ny, a->nx);
+    hipLaunchKernelGGL((tsdf_integrate_kernel<false, false>), grid, dim3(kBlock), 0, s, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N,
+                       a->nz, a->ny, a->nx, VoteVolumes<false>{});
   PVO_CHECK_LAUNCH();
   return PVO_OK;
 }
 
-extern "C" int pvo_tsdf_mesh(const pvo_tsdf_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+}  // namespace
+
+extern "C" int pvo_tsdf_integrate(const pvo_tsdf_integrate_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  return integrate_impl(a, nullptr, false, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pvo_tsdf_integrate_panoptic(const pvo_tsdf_integrate_args* a, const pvo_tsdf_panoptic_args* p, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+  return integrate_impl(a, p, true, workspace, workspace_bytes, stream);
+}
+
+namespace {
+
+// pvo_tsdf_mesh (p == NULL) and pvo_tsdf_mesh_panoptic
+int mesh_impl(const pvo_tsdf_mesh_args* a, const pvo_tsdf_mesh_labels_args* p, bool panoptic, void* workspace, size_t workspace_bytes,
+              void* stream) {
   PVO_REQ(a);
+  if (panoptic) PVO_REQ(p && p->label && (a->vcap == 0 || p->vlabel));
   PVO_REQ(volume_ok(a->nz, a->ny, a->nx));
   PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->min_weight == a->min_weight);
   PVO_REQ(finite_f(a->origin[0]) && finite_f(a->origin[1]) && finite_f(a->origin[2]));
@@ -330,9 +376,24 @@ extern "C" int pvo_tsdf_mesh(const pvo_tsdf_mesh_args* a, void* workspace, size_
   PVO_CHECK_LAUNCH();
   hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, vcount, qcount, vbase, qbase, a->counts, static_cast<int>(L.blocks));
   PVO_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mesh_verts_kernel, grid, dim3(kBlock), 0, s, g, L.cells, flags, vbase, vidx, out);
+  if (panoptic)
+    hipLaunchKernelGGL(mesh_verts_kernel<true>, grid, dim3(kBlock), 0, s, g, L.cells, flags, vbase, vidx, out,
+                       VertexLabels<true>{p->label, p->vlabel});
+  else
+    hipLaunchKernelGGL(mesh_verts_kernel<false>, grid, dim3(kBlock), 0, s, g, L.cells, flags, vbase, vidx, out, VertexLabels<false>{});
   PVO_CHECK_LAUNCH();
   hipLaunchKernelGGL(mesh_faces_kernel, grid, dim3(kBlock), 0, s, g, L.cells, flags, qbase, vidx, out);
   PVO_CHECK_LAUNCH();
   return PVO_OK;
+}
+
+}  // namespace
+
+extern "C" int pvo_tsdf_mesh(const pvo_tsdf_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  return mesh_impl(a, nullptr, false, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pvo_tsdf_mesh_panoptic(const pvo_tsdf_mesh_args* a, const pvo_tsdf_mesh_labels_args* p, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  return mesh_impl(a, p, true, workspace, workspace_bytes, stream);
 }

@@ -35,13 +35,25 @@ struct Fuse {
   float trunc, z_near, w_max;
 };
 
-struct Voxel { float T, W, cr, cg, cb; bool touched; };
+struct Voxel { float T, W, cr, cg, cb; bool touched; int32_t L; float lc; };     // (L, lc: the label vote, LAB only)
+
+// the panoptic extension (pvo_tsdf_panoptic_args): per-frame label maps [nframes,lh,lw] read at (vi / div, ui / div)
+struct LabelMaps { const int32_t* labels; int lh, lw, div; };
+
+// what a panoptic kernel takes beyond the plain one's arguments, as its LAST argument: nothing without LAB, so that the plain
+// instantiations keep their argument layout and their code
+template <bool LAB> struct VoteVolumes {};
+template <> struct VoteVolumes<true> { int32_t* label; float* lconf; LabelMaps maps; };      // label, lconf: shaped like tsdf
+template <bool LAB> struct VertexLabels {};
+template <> struct VertexLabels<true> { const int32_t* label; int32_t* vlabel; };            // label: shaped like tsdf; vlabel [vcap]
 
 // frame f (>= 0, with the slot's constants c) applied to the voxel whose INTEGER index is (xf, yf, zf): the contract's sequence of
-// include/pvo_hip.h pvo_tsdf_integrate, one test after the other
-template <bool RGB>
+// include/pvo_hip.h pvo_tsdf_integrate, one test after the other.  LAB: the contribution also casts its pixel's label into the
+// voxel's weighted Boyer-Moore vote (pvo_tsdf_integrate_panoptic); without it `lab` is not read and the code is what it was
+template <bool RGB, bool LAB = false>
 __device__ __forceinline__ void tsdf_fuse_frame(Voxel& a, const float* __restrict__ c, int f, float xf, float yf, float zf, bool live,
-                                                const Intr K, const Fuse in, long long HW, long long plane) {
+                                                const Intr K, const Fuse in, long long HW, long long plane,
+                                                const LabelMaps lab = LabelMaps{nullptr, 0, 0, 1}) {
   const float zc = c[6] * xf + c[7] * yf + c[8] * zf + c[11];
   const float xc = c[0] * xf + c[1] * yf + c[2] * zf + c[9];
   const float yc = c[3] * xf + c[4] * yf + c[5] * zf + c[10];
@@ -66,6 +78,15 @@ __device__ __forceinline__ void tsdf_fuse_frame(Voxel& a, const float* __restric
   }
   a.W = (in.w_max > 0.0f && Wn > in.w_max) ? in.w_max : Wn;
   a.touched = true;
+  if (LAB) {
+    if (!(sdf <= in.trunc)) return;                      // free space in front of a surface never votes
+    const int32_t L = lab.labels[(static_cast<long long>(f) * lab.lh + vi / lab.div) * lab.lw + ui / lab.div];
+    if (L <= 0) return;                                  // no segment
+    if (a.L == L) a.lc = a.lc + w;
+    else if (a.lc < w) { a.L = L; a.lc = w - a.lc; }
+    else a.lc = a.lc - w;
+    if (in.w_max > 0.0f && a.lc > in.w_max) a.lc = in.w_max;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------------ surface nets
@@ -126,4 +147,18 @@ __device__ __forceinline__ void surface_net_vertex(const float (&s)[8], const fl
     }
     reinterpret_cast<uchar4*>(out.rgba)[idx] = c;
   }
+}
+
+// label of the vertex of the cell with corner values s[j]: the label of the corner with the smallest |tsdf| among the corners that
+// have one (> 0), ties to the lowest j, 0 without any; comparisons only (pvo_tsdf_mesh_panoptic)
+__device__ __forceinline__ int32_t surface_net_label(const float (&s)[8], const int32_t* __restrict__ label, const long long (&at)[8]) {
+  int32_t best = 0;
+  float dist = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int32_t L = label[at[j]];
+    const float d = fabsf(s[j]);
+    if (L > 0 && (best == 0 || d < dist)) { best = L; dist = d; }
+  }
+  return best;
 }

@@ -12,6 +12,8 @@
 //              (b) sparse_integrate_kernel   one workgroup per brick, one thread per voxel: cull per chunk of 512 slots, survivors
 //                                            compacted in slot order, then the dense kernel's per-(voxel, frame) function
 //   mesh       classify / scan / vertices / faces as in tsdf.hip, one workgroup per brick, neighbours through the grid
+//   panoptic   (pvo_tsdf_sparse_integrate_panoptic / _mesh_panoptic) the LAB instantiations of sparse_integrate_kernel and
+//              sparse_verts_kernel in the same launches, as in tsdf.hip
 //
 // No atomics anywhere: marks are same-value stores, every index is a function of flags alone, a voxel is one thread's sequential loop.
 #include "tsdf_fuse.h"
@@ -250,12 +252,13 @@ __device__ __forceinline__ bool brick_sees_frame(const float* __restrict__ c, fl
   return true;
 }
 
-template <bool RGB>
+// LAB: with the label vote on the caller's label / lconf pools (pvo_tsdf_sparse_integrate_panoptic)
+template <bool RGB, bool LAB>
 __global__ __launch_bounds__(kBrick) void sparse_integrate_kernel(float* __restrict__ tsdf, float* __restrict__ wsum, float* __restrict__ rgb,
                                                                  const int32_t* __restrict__ coord, const int32_t* __restrict__ bricks,
                                                                  int cap, const float* __restrict__ fc,
                                                                  const float* __restrict__ intrinsics, const Fuse in, int N, float voxel,
-                                                                 int32_t* __restrict__ kept) {
+                                                                 int32_t* __restrict__ kept, const VoteVolumes<LAB> pan) {
   const int slot = blockIdx.x, tid = threadIdx.x;
   if (slot >= min(bricks[0], cap)) return;              // (the whole workgroup)
   const int bz = coord[3 * slot], by = coord[3 * slot + 1], bx = coord[3 * slot + 2];
@@ -267,8 +270,9 @@ __global__ __launch_bounds__(kBrick) void sparse_integrate_kernel(float* __restr
   const long long HW = static_cast<long long>(in.ht) * in.wd;
   const long long plane = static_cast<long long>(in.IH) * in.IW;
   const long long i = static_cast<long long>(slot) * kBrick + tid;
-  Voxel a = {tsdf[i], wsum[i], 0.0f, 0.0f, 0.0f, false};
+  Voxel a = {tsdf[i], wsum[i], 0.0f, 0.0f, 0.0f, false, 0, 0.0f};
   if (RGB) { a.cr = rgb[3 * i]; a.cg = rgb[3 * i + 1]; a.cb = rgb[3 * i + 2]; }
+  if constexpr (LAB) { a.L = pan.label[i]; a.lc = pan.lconf[i]; }
   __shared__ int list[kBrick];
   __shared__ int wave_n[kBrick / 64];
   int survivors = 0;
@@ -292,7 +296,8 @@ __global__ __launch_bounds__(kBrick) void sparse_integrate_kernel(float* __restr
     for (int k = 0; k < n; ++k) {
       const int s = __builtin_amdgcn_readfirstlane(list[k]);
       const float* __restrict__ c = fc + static_cast<long long>(kFrameFloats) * s;    // wave-uniform
-      tsdf_fuse_frame<RGB>(a, c, __float_as_int(c[12]), xf, yf, zf, true, K, in, HW, plane);
+      if constexpr (LAB) tsdf_fuse_frame<RGB, true>(a, c, __float_as_int(c[12]), xf, yf, zf, true, K, in, HW, plane, pan.maps);
+      else tsdf_fuse_frame<RGB>(a, c, __float_as_int(c[12]), xf, yf, zf, true, K, in, HW, plane);
     }
     __syncthreads();                      // list and wave_n are rewritten by the next chunk
   }
@@ -300,6 +305,7 @@ __global__ __launch_bounds__(kBrick) void sparse_integrate_kernel(float* __restr
   if (a.touched) {
     tsdf[i] = a.T; wsum[i] = a.W;
     if (RGB) { rgb[3 * i] = a.cr; rgb[3 * i + 1] = a.cg; rgb[3 * i + 2] = a.cb; }
+    if constexpr (LAB) { pan.label[i] = a.L; pan.lconf[i] = a.lc; }
   }
 }
 
@@ -407,8 +413,10 @@ __global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(const int* __
   if (tid == 0) { counts[0] = nv; counts[1] = 2 * nq; }
 }
 
+// LAB: the vertex's label into vlabel as well (pvo_tsdf_sparse_mesh_panoptic)
+template <bool LAB>
 __global__ __launch_bounds__(kBrick) void sparse_verts_kernel(const Bricks g, const uint8_t* __restrict__ flags, const int* __restrict__ vbase,
-                                                             int32_t* __restrict__ vidx, const MeshOut out) {
+                                                             int32_t* __restrict__ vidx, const MeshOut out, const VertexLabels<LAB> lab) {
   const int slot = blockIdx.x, tid = threadIdx.x;
   if (slot >= min(g.bricks[0], g.cap)) return;          // (the whole workgroup)
   __shared__ int nb[27];
@@ -434,6 +442,7 @@ __global__ __launch_bounds__(kBrick) void sparse_verts_kernel(const Bricks g, co
     s[j] = g.tsdf[at[j]];
   }
   surface_net_vertex(s, g.rgb, at, kB * bx + lx, kB * by + ly, kB * bz + lz, g.ox, g.oy, g.oz, g.voxel, out, idx);
+  if constexpr (LAB) lab.vlabel[idx] = surface_net_label(s, lab.label, at);
 }
 
 __global__ __launch_bounds__(kBrick) void sparse_faces_kernel(const Bricks g, const uint8_t* __restrict__ flags, const int* __restrict__ qbase,
@@ -576,8 +585,16 @@ extern "C" int pvo_tsdf_sparse_allocate(const pvo_tsdf_sparse_allocate_args* a, 
   return PVO_OK;
 }
 
-extern "C" int pvo_tsdf_sparse_integrate(const pvo_tsdf_sparse_integrate_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+
+// pvo_tsdf_sparse_integrate (p == NULL) and pvo_tsdf_sparse_integrate_panoptic: one validation, one launch sequence
+int sparse_integrate_impl(const pvo_tsdf_sparse_integrate_args* a, const pvo_tsdf_panoptic_args* p, bool panoptic, void* workspace,
+                          size_t workspace_bytes, void* stream) {
   PVO_REQ(a);
+  if (panoptic) {
+    PVO_REQ(p && p->label && p->lconf && p->labels && p->label_div >= 1);
+    PVO_REQ(static_cast<long long>(p->lh) * p->label_div >= a->ht && static_cast<long long>(p->lw) * p->label_div >= a->wd);
+  }
   PVO_REQ(world_ok(a->gz, a->gy, a->gx, a->cap));
   PVO_REQ(a->N >= 0 && a->nframes >= 0 && a->ht >= 0 && a->wd >= 0 && static_cast<long long>(a->ht) * a->wd < (1ll << 31));
   PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->trunc > 0.0f && finite_f(a->trunc));
@@ -600,18 +617,42 @@ extern "C" int pvo_tsdf_sparse_integrate(const pvo_tsdf_sparse_integrate_args* a
                      static_cast<long long>(a->ht) * a->wd, vol);
   PVO_CHECK_LAUNCH();
   const Fuse in = {a->disps, a->weight, a->images, a->ht, a->wd, a->IH, a->IW, a->img_stride, a->img_offset, a->trunc, a->z_near, a->w_max};
-  if (a->rgb)
-    hipLaunchKernelGGL(sparse_integrate_kernel<true>, dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks, a->cap,
-                       fc, a->intrinsics, in, a->N, a->voxel, a->kept);
+  if (panoptic) {
+    const VoteVolumes<true> pan = {p->label, p->lconf, {p->labels, p->lh, p->lw, p->label_div}};
+    if (a->rgb)
+      hipLaunchKernelGGL((sparse_integrate_kernel<true, true>), dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks,
+                         a->cap, fc, a->intrinsics, in, a->N, a->voxel, a->kept, pan);
+    else
+      hipLaunchKernelGGL((sparse_integrate_kernel<false, true>), dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks,
+                         a->cap, fc, a->intrinsics, in, a->N, a->voxel, a->kept, pan);
+  } else if (a->rgb)
+    hipLaunchKernelGGL((sparse_integrate_kernel<true, false>), dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks,
+                       a->cap, fc, a->intrinsics, in, a->N, a->voxel, a->kept, VoteVolumes<false>{});
   else
-    hipLaunchKernelGGL(sparse_integrate_kernel<false>, dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks, a->cap,
-                       fc, a->intrinsics, in, a->N, a->voxel, a->kept);
+    hipLaunchKernelGGL((sparse_integrate_kernel<false, false>), dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks,
+                       a->cap, fc, a->intrinsics, in, a->N, a->voxel, a->kept, VoteVolumes<false>{});
   PVO_CHECK_LAUNCH();
   return PVO_OK;
 }
 
-extern "C" int pvo_tsdf_sparse_mesh(const pvo_tsdf_sparse_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+}  // namespace
+
+extern "C" int pvo_tsdf_sparse_integrate(const pvo_tsdf_sparse_integrate_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  return sparse_integrate_impl(a, nullptr, false, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pvo_tsdf_sparse_integrate_panoptic(const pvo_tsdf_sparse_integrate_args* a, const pvo_tsdf_panoptic_args* p, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
+  return sparse_integrate_impl(a, p, true, workspace, workspace_bytes, stream);
+}
+
+namespace {
+
+// pvo_tsdf_sparse_mesh (p == NULL) and pvo_tsdf_sparse_mesh_panoptic
+int sparse_mesh_impl(const pvo_tsdf_sparse_mesh_args* a, const pvo_tsdf_mesh_labels_args* p, bool panoptic, void* workspace,
+                     size_t workspace_bytes, void* stream) {
   PVO_REQ(a);
+  if (panoptic) PVO_REQ(p && p->label && (a->vcap == 0 || p->vlabel));
   PVO_REQ(world_ok(a->gz, a->gy, a->gx, a->cap));
   PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->min_weight == a->min_weight);
   PVO_REQ(finite_f(a->origin[0]) && finite_f(a->origin[1]) && finite_f(a->origin[2]));
@@ -643,9 +684,23 @@ extern "C" int pvo_tsdf_sparse_mesh(const pvo_tsdf_sparse_mesh_args* a, void* wo
   PVO_CHECK_LAUNCH();
   hipLaunchKernelGGL(sparse_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, vcount, qcount, vbase, qbase, a->counts, a->cap);
   PVO_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sparse_verts_kernel, grid, dim3(kBrick), 0, s, g, flags, vbase, vidx, out);
+  if (panoptic)
+    hipLaunchKernelGGL(sparse_verts_kernel<true>, grid, dim3(kBrick), 0, s, g, flags, vbase, vidx, out, VertexLabels<true>{p->label, p->vlabel});
+  else
+    hipLaunchKernelGGL(sparse_verts_kernel<false>, grid, dim3(kBrick), 0, s, g, flags, vbase, vidx, out, VertexLabels<false>{});
   PVO_CHECK_LAUNCH();
   hipLaunchKernelGGL(sparse_faces_kernel, grid, dim3(kBrick), 0, s, g, flags, qbase, vidx, out);
   PVO_CHECK_LAUNCH();
   return PVO_OK;
+}
+
+}  // namespace
+
+extern "C" int pvo_tsdf_sparse_mesh(const pvo_tsdf_sparse_mesh_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  return sparse_mesh_impl(a, nullptr, false, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pvo_tsdf_sparse_mesh_panoptic(const pvo_tsdf_sparse_mesh_args* a, const pvo_tsdf_mesh_labels_args* p, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  return sparse_mesh_impl(a, p, true, workspace, workspace_bytes, stream);
 }

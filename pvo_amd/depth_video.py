@@ -48,7 +48,7 @@ from . import droid_backends as db
 
 class DepthVideo:
     def __init__(self, image_size=(480, 640), buffer=1024, device="cuda:0", segm_filter=False, thresh=0.8,
-                 store_images=False):
+                 store_images=False, store_segment_ids=False):
         self.counter = 0
         self.ht, self.wd = ht, wd = int(image_size[0]), int(image_size[1])
         self.device = torch.device(device)
@@ -78,6 +78,8 @@ class DepthVideo:
         self.nets = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw).permute(0, 3, 1, 2)
         self.inps = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw).permute(0, 3, 1, 2)
         self.segms = torch.zeros(buffer, 1, h8, w8, dtype=torch.int, **kw)
+        # the frames' panoptic ids as given (segms relabels every frame on its own): what tsdf(panoptic=True) fuses; <= 0 = no segment
+        self.segms_raw = torch.zeros(buffer, h8, w8, dtype=torch.int32, **kw) if store_segment_ids else None
         self.full_flow = torch.ones(buffer, h8, w8, 2, dtype=torch.float, **kw)
         self.segm_filter, self.thresh = segm_filter, thresh
         self.max_segments = 1024
@@ -139,6 +141,17 @@ class DepthVideo:
             raise ValueError("frame has %d panoptic segments, more than max_segments = %d" % (n, self.max_segments))
         self._segments_seen = max(self._segments_seen, n)
         return inv.to(torch.int32).reshape(seg.shape)
+
+    def _raw_segments(self, segm, shape):
+        """a frame's (or several frames') panoptic ids unmodified, as int32 of `shape` on the device; ids outside int32 are an error"""
+        seg = torch.as_tensor(segm)
+        if seg.is_floating_point() or seg.dtype == torch.bool:
+            raise ValueError("panoptic ids must be integers, got %s" % seg.dtype)
+        if seg.numel() and seg.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8):
+            lo, hi = int(seg.min()), int(seg.max())
+            if lo < -(1 << 31) or hi > (1 << 31) - 1:
+                raise ValueError("panoptic ids in [%d, %d] do not fit int32 (store_segment_ids)" % (lo, hi))
+        return seg.to(device=self.device, dtype=torch.int32).reshape(shape)
 
     @staticmethod
     def frame_fingerprint(image):
@@ -286,6 +299,8 @@ class DepthVideo:
         self.inps[k] = inp
         if segm is not None:
             self.segms[k] = self._dense_segments(segm).reshape(self.segms[k].shape)
+            if self.segms_raw is not None:
+                self.segms_raw[k] = self._raw_segments(segm, self.segms_raw[k].shape)
         if image is not None and self.images is not None:
             self.images[k] = image
         self.counter = k + 1
@@ -315,6 +330,8 @@ class DepthVideo:
         if len(item) > 7:
             self.inps[index] = item[7]
         if self.segm_filter and len(item) > 8 and item[8] is not None:
+            if self.segms_raw is not None:
+                self.segms_raw[index] = self._raw_segments(item[8], self.segms_raw[index].shape)
             seg = torch.as_tensor(item[8], device=self.device)
             if isinstance(index, int) or seg.dim() <= 3:
                 self.segms[index] = self._dense_segments(seg).reshape(self.segms[index].shape)
@@ -536,7 +553,7 @@ class DepthVideo:
         return origin, (g[2], g[1], g[0])
 
     def tsdf(self, voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None, use_sigma=False, origin=None, dims=None,
-             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05, sparse=False, margin=2):
+             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05, sparse=False, margin=2, panoptic=False):
         """the fused surface of keyframes ix (default: all stored ones; fuse after `terminate` - poses that move later are not
         de-integrated): a TSDF volume of `voxel`-sized cells, truncation `trunc` (default 3 voxels), integrated natively
         (pvo_tsdf_integrate) from exactly the pixels map_points(ix, thresh, full_res, reject, max_rel_sigma) keeps, and its surface-nets
@@ -547,9 +564,15 @@ class DepthVideo:
         sparse=True: the same pixels and weights into a brick volume (pvo_amd.tsdf_sparse.SparseTSDF: bricks allocated within `margin`
         voxels of the samples along every kept pixel's ray, pvo_tsdf_sparse_allocate / _integrate / _mesh) - for maps a dense volume
         cannot hold.  The world defaults to tsdf_sparse_bounds of the map's points; given dims are rounded up to bricks.  Returns the
-        mesh, origin, voxel and `volume`, the SparseTSDF, in place of tsdf / wsum."""
+        mesh, origin, voxel and `volume`, the SparseTSDF, in place of tsdf / wsum.
+        panoptic=True (a video made with store_segment_ids, ValueError otherwise): the frames' raw segment ids segms_raw[:n] are fused
+        by a weighted vote per voxel (pvo_tsdf_integrate_panoptic; ids <= 0 = no segment) and every vertex gets the id of its cell's
+        nearest labelled corner: the dict gains vlabel int32 [V] and the volumes label, lconf (sparse: the SparseTSDF holds them)."""
         trunc = 3.0 * float(voxel) if trunc is None else float(trunc)
         n = self.counter
+        if panoptic and self.segms_raw is None:
+            raise ValueError("tsdf(panoptic=True) needs the raw segment ids: make the video with store_segment_ids=True")
+        labels = self.segms_raw[:n] if panoptic else None
         m = self.map_points(ix=ix, thresh=thresh, full_res=full_res, reject=reject, max_rel_sigma=max_rel_sigma)
         if full_res:
             disps, intr, stride, offset, div = self.disps_up[:n], 8.0 * self.intrinsics[0], 1, 0, 8
@@ -572,10 +595,11 @@ class DepthVideo:
                 origin, gdims = self.tsdf_sparse_bounds(m["xyz"], voxel, trunc)
             else:
                 gdims = [-(-int(v) // BRICK) for v in dims]
-            vol = SparseTSDF(origin, gdims, voxel, trunc, colours=self.images is not None, device=self.device)
+            vol = SparseTSDF(origin, gdims, voxel, trunc, colours=self.images is not None, device=self.device, labels=panoptic)
             frames = (self.poses[:n], disps.contiguous(), intr.contiguous(), ix)
             vol.allocate(*frames, weight=weight, margin=margin)
-            vol.integrate(*frames, weight=weight, images=self.images, img_stride=stride, img_offset=offset, w_max=w_max)
+            vol.integrate(*frames, weight=weight, images=self.images, img_stride=stride, img_offset=offset, w_max=w_max, labels=labels,
+                          label_div=div)
             out = vol.mesh(min_weight=min_weight)
             out.pop("counts")
             out.update(volume=vol, origin=[float(v) for v in origin], voxel=float(voxel))
@@ -586,11 +610,16 @@ class DepthVideo:
         vol = torch.zeros(nz, ny, nx, dtype=torch.float32, device=self.device)
         wsum = torch.zeros_like(vol)
         rgb = torch.zeros(nz, ny, nx, 3, dtype=torch.float32, device=self.device) if self.images is not None else None
+        label = torch.zeros(nz, ny, nx, dtype=torch.int32, device=self.device) if panoptic else None
+        lconf = torch.zeros_like(vol) if panoptic else None
         db.tsdf_integrate(vol, wsum, rgb, self.poses[:n], disps.contiguous(), intr.contiguous(), ix, origin, voxel, trunc, weight=weight,
-                          images=self.images, img_stride=stride, img_offset=offset, w_max=w_max)
-        out = db.tsdf_mesh(vol, wsum, rgb, origin, voxel, min_weight=min_weight)
+                          images=self.images, img_stride=stride, img_offset=offset, w_max=w_max, label=label, lconf=lconf, labels=labels,
+                          label_div=div)
+        out = db.tsdf_mesh(vol, wsum, rgb, origin, voxel, min_weight=min_weight, label=label)
         out.pop("counts")
         out.update(tsdf=vol, wsum=wsum, origin=[float(v) for v in origin], voxel=float(voxel))
+        if panoptic:
+            out.update(label=label, lconf=lconf)
         return out
 
     def ba(self, target, weight, eta, ii, jj, t0=1, t1=None, itrs=2, lm=1e-4, ep=0.1, motion_only=False,

@@ -25,7 +25,7 @@ def default_args(**over):
              beta=0.6, filter_thresh=1.75, warmup=12, keyframe_thresh=2.25, frontend_thresh=12.0, frontend_window=25,
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
              segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1,
-             store_images=False, uncertainty=False, opt_intr=False, opt_intr_free="all")
+             store_images=False, uncertainty=False, opt_intr=False, opt_intr_free="all", store_segment_ids=False)
     # uncertainty: after every keyframe's last frontend update, estimate the window's inverse-depth variances and pose covariance from
     # the bundle adjustment's normal equations (DepthVideo.uncertainty; get_uncertainty(), get_map(max_rel_sigma=...)).  Read only: the
     # trajectory and the depths are bit for bit those of a run without it.  A window of more than 64 poses (frontend_window above 64) is
@@ -42,6 +42,8 @@ def default_args(**over):
     # (default): `right` is IGNORED, nothing is allocated for it and every result is what a monocular run computes.
     # store_images: keep every keyframe's image on the device (DepthVideo.images, uint8 [buffer,3,H,W]) so that get_map() can colour
     # its points.  False (default): nothing is allocated, no result changes, and get_map() returns points without colours.
+    # store_segment_ids: keep every keyframe's panoptic ids AS GIVEN (DepthVideo.segms_raw, int32 [buffer,H/8,W/8]; `segms` relabels each
+    # frame on its own) so that get_mesh(panoptic=True) can fuse them across frames.  False (default): nothing is allocated or changed.
     a.update(over)
     return Namespace(**a)
 
@@ -56,7 +58,8 @@ class Droid:
             raise ValueError("args.opt_intr_free must be 'all' or 'focal', got %r" % (args.opt_intr_free,))
         self.load_weights(args.weights, args.use_aff_bri)
         self.video = DepthVideo(args.image_size, args.buffer, args.device, args.segm_filter, args.thresh,
-                                store_images=bool(getattr(args, "store_images", False)))
+                                store_images=bool(getattr(args, "store_images", False)),
+                                store_segment_ids=bool(getattr(args, "store_segment_ids", False)))
         self.filterx = MotionFilter(self.net, self.video, thresh=args.filter_thresh, device=args.device)
         self.filterx.overlap_upload = bool(getattr(args, "pipelined", False))
         self.filterx.use_depth = bool(getattr(args, "rgbd", False))
@@ -180,7 +183,8 @@ class Droid:
         """the fused surface of the keyframes: DepthVideo.tsdf(voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None,
         use_sigma=False, origin=None, dims=None, min_weight=1.0, w_max=0) - a dict of the mesh verts [V,3], normals [V,3], rgba [V,4],
         faces [F,3] and the volume tsdf, wsum [nz,ny,nx], origin, voxel.  sparse=True (with margin=2): a brick volume in place of the dense
-        one, returned as `volume` (DepthVideo.tsdf).  Call it after terminate(): poses that move later are not de-integrated."""
+        one, returned as `volume` (DepthVideo.tsdf).  panoptic=True (args.store_segment_ids): the keyframes' segment ids fused into the volume
+        as well - vlabel [V], one id per vertex, and the volumes label, lconf.  Call it after terminate(): poses that move later are not de-integrated."""
         self.flush()
         return self.video.tsdf(**kw)
 

@@ -544,13 +544,51 @@ def map_points_into(a, poses, disps, intrinsics, ix, thresh, out, min_votes=2, m
         check(lib.pvo_map_points(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "map_points")
 
 
+def _panoptic(what, dev, shape, nframes, label, lconf, labels, label_div):
+    """pvo_tsdf_panoptic_args of the label volumes label int32 / lconf f32 (both `shape`) and the frames' id maps labels int32
+    [nframes,LH,LW]; None when none of the three is given (the plain call)"""
+    if label is None and lconf is None and labels is None:
+        return None
+    if label is None or lconf is None or labels is None:
+        raise PvoHipError("%s: label, lconf and labels come together" % what)
+    for t, n in ((label, "label"), (lconf, "lconf"), (labels, "labels")):
+        _contig(t, n)
+        if t.device != dev:
+            raise PvoHipError("%s: %s must be on %s" % (what, n, dev))
+    if label.dtype != torch.int32 or lconf.dtype != torch.float32 or tuple(label.shape) != tuple(shape) or tuple(lconf.shape) != tuple(shape):
+        raise PvoHipError("%s: label int32 and lconf f32 must have the shape of tsdf" % what)
+    if labels.dtype != torch.int32 or labels.dim() < 3 or labels.shape[0] < nframes:
+        raise PvoHipError("%s: labels must be int32 [nframes,LH,LW]" % what)
+    p = _lib.TsdfPanopticArgs()
+    p.label, p.lconf, p.labels = _ptr(label), _ptr(lconf), _ptr(labels)
+    p.lh, p.lw, p.label_div = labels.shape[-2], labels.shape[-1], int(label_div)
+    return p
+
+
+def _mesh_labels(what, out, label, shape):
+    """pvo_tsdf_mesh_labels_args for the label volume `label` (None: the plain call) and out["vlabel"] int32 [vcap]"""
+    if label is None:
+        return None
+    _contig(label, "label")
+    vlabel = out["vlabel"]
+    if label.dtype != torch.int32 or tuple(label.shape) != tuple(shape) or label.device != out["verts"].device:
+        raise PvoHipError("%s: label must be int32 with the shape of tsdf, on its device" % what)
+    if vlabel.dtype != torch.int32 or vlabel.numel() < out["verts"].shape[0] or not vlabel.is_contiguous():
+        raise PvoHipError("%s: out['vlabel'] must be int32 [vcap]" % what)
+    p = _lib.TsdfMeshLabelsArgs()
+    p.label, p.vlabel = _ptr(label), _ptr(vlabel)
+    return p
+
+
 def tsdf_integrate(tsdf, wsum, rgb, poses, disps, intrinsics, ix, origin, voxel, trunc, weight=None, images=None, img_stride=8,
-                   img_offset=3, z_near=0.0, w_max=0.0):
+                   img_offset=3, z_near=0.0, w_max=0.0, label=None, lconf=None, labels=None, label_div=1):
     """Fuse keyframes ix, in that order, into the caller's volume in place (include/pvo_hip.h pvo_tsdf_integrate): tsdf / wsum f32
     [nz,ny,nx], rgb f32 [nz,ny,nx,3] or None (needs images); a zeroed volume is an empty one.  The centre of voxel (z,y,x) is
     origin + voxel * (x,y,z); poses [nframes,7] world-to-camera, disps [nframes,ht,wd] at any resolution with intrinsics [4] for it,
     weight f32 [nframes,ht,wd] or None (= 1), images uint8 [nframes,3,IH,IW] BGR sampled at [img_offset::img_stride], w_max 0 = no
-    cap.  No allocation beyond the cached workspace, no synchronisation."""
+    cap.  label int32 / lconf f32 [nz,ny,nx] with labels int32 [nframes,LH,LW] (ids read at (y // label_div, x // label_div), <= 0 =
+    no segment) also fuse the segment ids (pvo_tsdf_integrate_panoptic); tsdf / wsum / rgb get the same bytes either way.
+    No allocation beyond the cached workspace, no synchronisation."""
     for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb"), (poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"),
                  (ix, "ix"), (weight, "weight"), (images, "images")):
         if t is not None:
@@ -577,15 +615,21 @@ def tsdf_integrate(tsdf, wsum, rgb, poses, disps, intrinsics, ix, origin, voxel,
     a.voxel, a.trunc, a.z_near, a.w_max = float(voxel), float(trunc), float(z_near), float(w_max)
     a.poses, a.disps, a.intrinsics, a.ix, a.weight = _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ix), _ptr(weight)
     a.N, a.nframes, a.ht, a.wd = N, nf, ht, wd
+    p = _panoptic("tsdf_integrate", dev, tsdf.shape, nf, label, lconf, labels, label_div)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_integrate_workspace_bytes(N))
     with torch.cuda.device(dev):
-        check(lib.pvo_tsdf_integrate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_integrate")
+        if p is None:
+            check(lib.pvo_tsdf_integrate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_integrate")
+        else:
+            check(lib.pvo_tsdf_integrate_panoptic(ctypes.byref(a), ctypes.byref(p), _ptr(ws), ws.numel(), _stream(dev)),
+                  "tsdf_integrate_panoptic")
 
 
-def tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out):
+def tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out, label=None):
     """pvo_tsdf_mesh on caller-owned buffers (out: verts [vcap,3], faces [fcap,3], counts [2], optional normals / rgba).  Buffers keep
-    whatever they held beyond the elements written.  No allocation beyond the cached workspace, no synchronisation."""
+    whatever they held beyond the elements written.  label int32 [nz,ny,nx]: also one label per vertex into out["vlabel"] int32 [vcap]
+    (pvo_tsdf_mesh_panoptic).  No allocation beyond the cached workspace, no synchronisation."""
     dev = tsdf.device
     a = _lib.TsdfMeshArgs()
     a.tsdf, a.wsum, a.rgb = _ptr(tsdf), _ptr(wsum), _ptr(rgb)
@@ -595,15 +639,20 @@ def tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out):
     a.vcap, a.fcap = out["verts"].shape[0], out["faces"].shape[0]
     a.verts, a.normals, a.rgba, a.faces = _ptr(out["verts"]), _ptr(out.get("normals")), _ptr(out.get("rgba")), _ptr(out["faces"])
     a.counts = ctypes.c_void_p(out["counts"].data_ptr())
+    p = _mesh_labels("tsdf_mesh", out, label, tsdf.shape)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_mesh_workspace_bytes(a.nz, a.ny, a.nx))
     with torch.cuda.device(dev):
-        check(lib.pvo_tsdf_mesh(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_mesh")
+        if p is None:
+            check(lib.pvo_tsdf_mesh(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_mesh")
+        else:
+            check(lib.pvo_tsdf_mesh_panoptic(ctypes.byref(a), ctypes.byref(p), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_mesh_panoptic")
 
 
-def tsdf_mesh(tsdf, wsum, rgb, origin, voxel, min_weight=1.0, vcap=None, fcap=None):
+def tsdf_mesh(tsdf, wsum, rgb, origin, voxel, min_weight=1.0, vcap=None, fcap=None, label=None):
     """The surface-nets mesh of a TSDF volume (include/pvo_hip.h pvo_tsdf_mesh).  Returns a dict: verts f32 [V,3], normals f32 [V,3],
-    rgba uint8 [V,4] (rgb 0 without a colour volume), faces int32 [F,3], counts int32 [2] = (V, F).  Calls once with room for vcap
+    rgba uint8 [V,4] (rgb 0 without a colour volume), faces int32 [F,3], counts int32 [2] = (V, F), and with a label volume (int32
+    [nz,ny,nx]) vlabel int32 [V].  Calls once with room for vcap
     vertices and fcap faces (default: a guess from the volume's faces), reads counts back - the call's one host synchronisation - and
     calls again with exactly the room needed if a capacity was exceeded."""
     for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")):
@@ -621,12 +670,16 @@ def tsdf_mesh(tsdf, wsum, rgb, origin, voxel, min_weight=1.0, vcap=None, fcap=No
         out = {"verts": torch.empty(vcap, 3, dtype=torch.float32, device=dev), "normals": torch.empty(vcap, 3, dtype=torch.float32, device=dev),
                "rgba": torch.empty(vcap, 4, dtype=torch.uint8, device=dev), "faces": torch.empty(fcap, 3, dtype=torch.int32, device=dev),
                "counts": torch.empty(2, dtype=torch.int32, device=dev)}
-        tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out)
+        if label is not None:
+            out["vlabel"] = torch.empty(vcap, dtype=torch.int32, device=dev)
+        tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out, label=label)
         nv, nf = out["counts"].tolist()                 # the one synchronisation
         if nv <= vcap and nf <= fcap:
             break
         vcap, fcap = max(nv, vcap), max(nf, fcap)
-    for k in ("verts", "normals", "rgba"):
+    for k in ("verts", "normals", "rgba", "vlabel"):
+        if k not in out:
+            continue
         out[k] = out[k][:nv]
     out["faces"] = out["faces"][:nf]
     return out
@@ -691,11 +744,12 @@ def tsdf_sparse_allocate(vol, poses, disps, intrinsics, ix, trunc, weight=None, 
 
 
 def tsdf_sparse_integrate(vol, poses, disps, intrinsics, ix, trunc, weight=None, images=None, img_stride=8, img_offset=3, z_near=0.0,
-                          w_max=0.0, kept=None):
+                          w_max=0.0, kept=None, label=None, lconf=None, labels=None, label_div=1):
     """tsdf_integrate on the bricks in use of the brick volume `vol` (include/pvo_hip.h pvo_tsdf_sparse_integrate): every voxel of a
     brick gets the bytes the dense call leaves at that voxel; a frame is tested once per brick, not once per voxel.  kept: int32
-    [cap] or None, per brick in use the number of slots of ix that survived the cull.  No allocation beyond the cached workspace, no
-    synchronisation."""
+    [cap] or None, per brick in use the number of slots of ix that survived the cull.  label int32 / lconf f32 [cap,8,8,8] with
+    labels int32 [nframes,LH,LW] and label_div: the segment ids as well, as in tsdf_integrate (pvo_tsdf_sparse_integrate_panoptic).
+    No allocation beyond the cached workspace, no synchronisation."""
     a = _lib.TsdfSparseIntegrateArgs()
     dev = _sparse_world(a, vol)
     _dev(vol["grid"], poses, disps, intrinsics, ix, weight, images)
@@ -712,15 +766,20 @@ def tsdf_sparse_integrate(vol, poses, disps, intrinsics, ix, trunc, weight=None,
         if kept.dtype != torch.int32 or kept.numel() < a.cap or kept.device != dev:
             raise PvoHipError("tsdf_sparse_integrate: kept must be an int32 device tensor of at least cap elements")
         a.kept = _ptr(kept)
+    p = _panoptic("tsdf_sparse_integrate", dev, vol["tsdf"].shape, a.nframes, label, lconf, labels, label_div)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_sparse_integrate_workspace_bytes(a.N))
     with torch.cuda.device(dev):
-        check(lib.pvo_tsdf_sparse_integrate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_integrate")
+        if p is None:
+            check(lib.pvo_tsdf_sparse_integrate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_integrate")
+        else:
+            check(lib.pvo_tsdf_sparse_integrate_panoptic(ctypes.byref(a), ctypes.byref(p), _ptr(ws), ws.numel(), _stream(dev)),
+                  "tsdf_sparse_integrate_panoptic")
 
 
-def tsdf_sparse_mesh_into(vol, min_weight, out):
-    """pvo_tsdf_sparse_mesh on caller-owned buffers (out as for tsdf_mesh_into).  No allocation beyond the cached workspace, no
-    synchronisation."""
+def tsdf_sparse_mesh_into(vol, min_weight, out, label=None):
+    """pvo_tsdf_sparse_mesh on caller-owned buffers (out as for tsdf_mesh_into; label int32 [cap,8,8,8]: out["vlabel"] as well,
+    pvo_tsdf_sparse_mesh_panoptic).  No allocation beyond the cached workspace, no synchronisation."""
     a = _lib.TsdfSparseMeshArgs()
     dev = _sparse_world(a, vol)
     a.grid = _ptr(vol["grid"])
@@ -729,15 +788,20 @@ def tsdf_sparse_mesh_into(vol, min_weight, out):
     a.vcap, a.fcap = out["verts"].shape[0], out["faces"].shape[0]
     a.verts, a.normals, a.rgba, a.faces = _ptr(out["verts"]), _ptr(out.get("normals")), _ptr(out.get("rgba")), _ptr(out["faces"])
     a.counts = ctypes.c_void_p(out["counts"].data_ptr())
+    p = _mesh_labels("tsdf_sparse_mesh", out, label, vol["tsdf"].shape)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_sparse_mesh_workspace_bytes(a.cap))
     with torch.cuda.device(dev):
-        check(lib.pvo_tsdf_sparse_mesh(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_mesh")
+        if p is None:
+            check(lib.pvo_tsdf_sparse_mesh(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_mesh")
+        else:
+            check(lib.pvo_tsdf_sparse_mesh_panoptic(ctypes.byref(a), ctypes.byref(p), _ptr(ws), ws.numel(), _stream(dev)),
+                  "tsdf_sparse_mesh_panoptic")
 
 
-def tsdf_sparse_mesh(vol, min_weight=1.0, vcap=None, fcap=None):
-    """The surface-nets mesh of a brick volume (include/pvo_hip.h pvo_tsdf_sparse_mesh), the dict of tsdf_mesh; vertices in the order
-    (slot, raster order inside the brick).  One host synchronisation (the counts), a second call if a capacity was exceeded."""
+def tsdf_sparse_mesh(vol, min_weight=1.0, vcap=None, fcap=None, label=None):
+    """The surface-nets mesh of a brick volume (include/pvo_hip.h pvo_tsdf_sparse_mesh), the dict of tsdf_mesh (vlabel with a label
+    pool int32 [cap,8,8,8]); vertices in the order (slot, raster order inside the brick).  One host synchronisation (the counts), a second call if a capacity was exceeded."""
     dev = vol["tsdf"].device
     cap = vol["tsdf"].shape[0]
     vcap = min(cap * _lib.TSDF_BRICK ** 3, max(1024, 96 * cap)) if vcap is None else int(vcap)
@@ -746,12 +810,16 @@ def tsdf_sparse_mesh(vol, min_weight=1.0, vcap=None, fcap=None):
         out = {"verts": torch.empty(vcap, 3, dtype=torch.float32, device=dev), "normals": torch.empty(vcap, 3, dtype=torch.float32, device=dev),
                "rgba": torch.empty(vcap, 4, dtype=torch.uint8, device=dev), "faces": torch.empty(fcap, 3, dtype=torch.int32, device=dev),
                "counts": torch.empty(2, dtype=torch.int32, device=dev)}
-        tsdf_sparse_mesh_into(vol, min_weight, out)
+        if label is not None:
+            out["vlabel"] = torch.empty(vcap, dtype=torch.int32, device=dev)
+        tsdf_sparse_mesh_into(vol, min_weight, out, label=label)
         nv, nf = out["counts"].tolist()                 # the one synchronisation
         if nv <= vcap and nf <= fcap:
             break
         vcap, fcap = max(nv, vcap), max(nf, fcap)
-    for k in ("verts", "normals", "rgba"):
+    for k in ("verts", "normals", "rgba", "vlabel"):
+        if k not in out:
+            continue
         out[k] = out[k][:nv]
     out["faces"] = out["faces"][:nf]
     return out

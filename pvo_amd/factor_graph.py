@@ -456,9 +456,10 @@ class FactorGraph:
         right = getattr(v, "fmaps_right", None)                         # (stereo: and so does the right view's feature map)
         # (uncertainty: the variances and the pose covariance block of a keyframe are its own)
         unc = tuple(b for b in (getattr(v, n, None) for n in ("disps_var_cond", "disps_var_pose", "poses_cov")) if b is not None)
+        raw = getattr(v, "segms_raw", None)                             # (the raw panoptic ids are the keyframe's, segm_filter or not)
         for buf in (v.poses, v.disps, v.intrinsics, v.nets, v.inps, v.fmaps) + ((v.segms,) if v.segm_filter else ()) + \
                 ((up,) if self.upsample and up is not None else ()) + ((sens,) if sens is not None else ()) + \
-                ((right,) if right is not None else ()) + unc:
+                ((right,) if right is not None else ()) + unc + ((raw,) if raw is not None else ()):
             buf[ix] = buf[ix + 1].clone()
         m = [(i == ix) or (j == ix) for i, j in zip(self._ii_h, self._jj_h)]
         for t in (self.ii_inac, self.jj_inac):                       # (masked in-place updates would synchronise)

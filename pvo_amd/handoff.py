@@ -85,9 +85,10 @@ def write_ply(path, xyz, rgb=None, label=None, sigma=None):
     return n
 
 
-def write_ply_mesh(path, verts, faces, rgb=None, normals=None):
+def write_ply_mesh(path, verts, faces, rgb=None, normals=None, label=None):
     """a triangle mesh as binary little-endian PLY: per vertex x y z float, then nx ny nz float (omitted when normals is None), then
-    red green blue uchar (rgb [n,3] or [n,4], the first three columns; omitted when None); per face `property list uchar int
+    red green blue uchar (rgb [n,3] or [n,4], the first three columns; omitted when None), then an int label (the vertex's segment
+    id; omitted when None: the file is then byte for byte what it was without the argument); per face `property list uchar int
     vertex_indices`: the byte 3 and three int32 indices.  numpy only; returns (vertices, faces) written."""
     verts, faces = _host(verts), _host(faces)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
@@ -100,6 +101,10 @@ def write_ply_mesh(path, verts, faces, rgb=None, normals=None):
         rgb = _host(rgb)
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         props += ["property uchar red", "property uchar green", "property uchar blue"]
+    if label is not None:
+        label = _host(label)
+        fields.append(("label", "<i4"))
+        props.append("property int label")
     n, m = int(verts.shape[0]), int(faces.shape[0])
     rec = np.zeros(n, dtype=np.dtype(fields))
     rec["x"], rec["y"], rec["z"] = verts[:, 0], verts[:, 1], verts[:, 2]
@@ -107,6 +112,8 @@ def write_ply_mesh(path, verts, faces, rgb=None, normals=None):
         rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     if rgb is not None:
         rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    if label is not None:
+        rec["label"] = label.reshape(n)
     tri = np.zeros(m, dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
     tri["n"], tri["v"] = 3, faces.reshape(m, 3)
     header = "\n".join(["ply", "format binary_little_endian 1.0", "element vertex %d" % n] + props +
@@ -117,6 +124,50 @@ def write_ply_mesh(path, verts, faces, rgb=None, normals=None):
         f.write(rec.tobytes())
         f.write(tri.tobytes())
     return n, m
+
+
+_PLY_TYPES = {"float": "<f4", "uchar": "u1", "int": "<i4"}
+
+
+def read_ply_mesh(path):
+    """a file of write_ply_mesh back as numpy: dict verts f32 [n,3], faces int32 [m,3], and normals f32 [n,3] / rgb uint8 [n,3] /
+    label int32 [n] where the file has them"""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    n = int([l for l in lines if l.startswith("element vertex")][0].split()[2])
+    m = int([l for l in lines if l.startswith("element face")][0].split()[2])
+    fields = [(l.split()[2], _PLY_TYPES[l.split()[1]]) for l in lines if l.startswith("property") and not l.startswith("property list")]
+    dt = np.dtype(fields)
+    rec = np.frombuffer(data, dt, n, end)
+    tri = np.frombuffer(data, np.dtype([("n", "u1"), ("v", "<i4", (3,))]), m, end + n * dt.itemsize)
+    out = {"verts": np.stack([rec["x"], rec["y"], rec["z"]], 1), "faces": tri["v"].copy()}
+    names = [k for k, _ in fields]
+    if "nx" in names:
+        out["normals"] = np.stack([rec["nx"], rec["ny"], rec["nz"]], 1)
+    if "red" in names:
+        out["rgb"] = np.stack([rec["red"], rec["green"], rec["blue"]], 1)
+    if "label" in names:
+        out["label"] = rec["label"].copy()
+    return out
+
+
+def split_mesh_by_label(verts, faces, vlabel):
+    """a labelled mesh cut into one mesh per segment id: {id: (verts [n_id,3], faces [m_id,3])}.  A face goes to the label that at
+    least two of its vertices share, else to its first vertex's label; a part holds the vertices its faces use, in their old order,
+    and its faces name them by their new indices.  numpy only."""
+    verts, faces, vlabel = _host(verts), _host(faces).reshape(-1, 3), _host(vlabel).reshape(-1)
+    l = vlabel[faces] if len(faces) else np.zeros((0, 3), vlabel.dtype)
+    owner = np.where(l[:, 1] == l[:, 2], l[:, 1], l[:, 0])          # (0 == 1 or 0 == 2: the first's; 1 == 2: theirs; else the first's)
+    out = {}
+    for i in np.unique(owner):
+        f = faces[owner == i]
+        used = np.unique(f)
+        remap = np.full(len(verts), -1, np.int64)
+        remap[used] = np.arange(len(used))
+        out[int(i)] = (verts[used], remap[f].astype(np.int32))
+    return out
 
 
 def save_reconstruction(root, video):

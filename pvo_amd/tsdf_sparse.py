@@ -12,8 +12,9 @@ AXIS_LIMIT = (1 << 21) // BRICK  # bricks per axis: voxel indices stay exact in 
 
 
 class SparseTSDF:
-    def __init__(self, origin, grid_dims, voxel, trunc, colours=True, device="cuda", cap=1024):
-        """a world of grid_dims = (gz,gy,gx) bricks whose voxel (0,0,0) has its centre at origin [x,y,z]; cap: the pool's first size"""
+    def __init__(self, origin, grid_dims, voxel, trunc, colours=True, device="cuda", cap=1024, labels=False):
+        """a world of grid_dims = (gz,gy,gx) bricks whose voxel (0,0,0) has its centre at origin [x,y,z]; cap: the pool's first size;
+        labels: also own the two pools of the segment-id vote (label int32, lconf f32)"""
         gz, gy, gx = [int(v) for v in grid_dims]
         if min(gz, gy, gx) < 0 or max(gz, gy, gx) > AXIS_LIMIT or gz * gy * gx >= GRID_LIMIT:
             raise ValueError("SparseTSDF: a grid of %d x %d x %d bricks is over the limit (each axis <= %d bricks, fewer than 2^31 in all); "
@@ -23,7 +24,8 @@ class SparseTSDF:
         self.grid = torch.full((gz, gy, gx), -1, dtype=torch.int32, device=self.device)
         self.counts = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.colours = bool(colours)
-        self.tsdf = self.wsum = self.rgb = self.coord = None
+        self.labels = bool(labels)
+        self.tsdf = self.wsum = self.rgb = self.coord = self.label = self.lconf = None
         self._resize(max(int(cap), 1))
 
     @property
@@ -41,7 +43,9 @@ class SparseTSDF:
         new = {"tsdf": torch.zeros(cap, B, B, B, dtype=torch.float32, device=self.device),
                "wsum": torch.zeros(cap, B, B, B, dtype=torch.float32, device=self.device),
                "rgb": torch.zeros(cap, B, B, B, 3, dtype=torch.float32, device=self.device) if self.colours else None,
-               "coord": torch.zeros(cap, 3, dtype=torch.int32, device=self.device)}
+               "coord": torch.zeros(cap, 3, dtype=torch.int32, device=self.device),
+               "label": torch.zeros(cap, B, B, B, dtype=torch.int32, device=self.device) if self.labels else None,
+               "lconf": torch.zeros(cap, B, B, B, dtype=torch.float32, device=self.device) if self.labels else None}
         for k, t in new.items():
             old = getattr(self, k)
             if old is not None and t is not None:
@@ -68,28 +72,37 @@ class SparseTSDF:
             db.tsdf_sparse_allocate(self.volume(), *args, weight=weight, z_near=z_near, margin=margin)
         return want
 
-    def integrate(self, poses, disps, intrinsics, ix, weight=None, images=None, img_stride=8, img_offset=3, z_near=0.0, w_max=0.0, kept=None):
-        """keyframes ix, in that order, into the bricks in use (no synchronisation); kept int32 [cap] or None: survivors of the cull"""
+    def integrate(self, poses, disps, intrinsics, ix, weight=None, images=None, img_stride=8, img_offset=3, z_near=0.0, w_max=0.0, kept=None,
+                  labels=None, label_div=1):
+        """keyframes ix, in that order, into the bricks in use (no synchronisation); kept int32 [cap] or None: survivors of the cull;
+        labels int32 [nframes,LH,LW] (a volume made with labels=True): the frames' segment ids into the label pools as well"""
+        if labels is not None and not self.labels:
+            raise ValueError("SparseTSDF.integrate: labels need a volume made with labels=True")
+        pan = dict(label=self.label, lconf=self.lconf, labels=labels, label_div=label_div) if labels is not None else {}
         db.tsdf_sparse_integrate(self.volume(), poses, disps, intrinsics, ix, self.trunc, weight=weight,
                                  images=images if self.colours else None, img_stride=img_stride, img_offset=img_offset, z_near=z_near,
-                                 w_max=w_max, kept=kept)
+                                 w_max=w_max, kept=kept, **pan)
 
     def mesh(self, min_weight=1.0, vcap=None, fcap=None):
-        return db.tsdf_sparse_mesh(self.volume(), min_weight=min_weight, vcap=vcap, fcap=fcap)
+        """the mesh dict of droid_backends.tsdf_sparse_mesh; with labels=True it has vlabel"""
+        return db.tsdf_sparse_mesh(self.volume(), min_weight=min_weight, vcap=vcap, fcap=fcap, label=self.label)
 
     def nbytes(self):
         """device bytes held: the grid and the pool"""
-        return sum(t.numel() * t.element_size() for t in (self.grid, self.coord, self.counts, self.tsdf, self.wsum, self.rgb) if t is not None)
+        return sum(t.numel() * t.element_size() for t in (self.grid, self.coord, self.counts, self.tsdf, self.wsum, self.rgb, self.label, self.lconf)
+                   if t is not None)
 
     def to_dense(self):
-        """the bricks in use scattered into a dense [8gz,8gy,8gx] volume (zero elsewhere): dict tsdf, wsum, rgb (or None) and
-        allocated bool [gz,gy,gx].  For tests and small volumes."""
+        """the bricks in use scattered into a dense [8gz,8gy,8gx] volume (zero elsewhere): dict tsdf, wsum, rgb (or None), with labels=True
+        label and lconf, and allocated bool [gz,gy,gx].  For tests and small volumes."""
         B = BRICK
         gz, gy, gx = self.grid.shape
         n = self.bricks
         c = self.coord[:n].long()
         out = {"allocated": self.grid >= 0}
-        for k, t in (("tsdf", self.tsdf), ("wsum", self.wsum), ("rgb", self.rgb)):
+        for k, t in (("tsdf", self.tsdf), ("wsum", self.wsum), ("rgb", self.rgb), ("label", self.label), ("lconf", self.lconf)):
+            if t is None and k in ("label", "lconf"):
+                continue
             if t is None:
                 out[k] = None
                 continue

@@ -2,7 +2,7 @@
 
     python tools/export_map.py --datapath <.../SceneXX> --weights <checkpoint.pth> --map out.ply [--full_res] [--filter_thresh_map 0.005]
                                [--reconstruction_path DIR] [--uncertainty [--max_rel_sigma X]]
-                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight] [--sparse]]
+                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight] [--sparse] [--panoptic [--instances_dir DIR]]]
 
 --map writes the filtered point cloud of all keyframes after the global bundle adjustment (Droid.get_map: points confirmed by two
 neighbouring keyframes, pvo_map_points) as a binary little-endian PLY: x y z float, red green blue uchar, int label (the per-frame
@@ -15,7 +15,10 @@ standard deviation sigma / disp exceeds X.  --mesh also fuses the same pixels in
 --trunc, default three voxels) and writes its surface-nets mesh (Droid.get_mesh: pvo_tsdf_integrate / pvo_tsdf_mesh) as a binary PLY
 with vertex normals, colours and triangle faces; --sigma_weight (with --uncertainty) weights every pixel by its inverse-depth
 variance instead of counting all alike; --sparse fuses into a brick volume over the map's full extent (pvo_tsdf_sparse_*) where the
-dense volume is clipped to what fits.  Without --mesh the output is what it was without the option, and without --sparse the mesh is.
+dense volume is clipped to what fits; --panoptic keeps the frames' panoptic ids as given (args.store_segment_ids), fuses them into the
+volume by a weighted vote (pvo_tsdf_integrate_panoptic) and adds `property int label` to the mesh's vertices, and --instances_dir DIR
+also writes one mesh per id, DIR/segment_<id>.ply.  Without --mesh the output is what it was without the option, and without
+--sparse / --panoptic the mesh is.
 """
 import os
 import sys
@@ -41,6 +44,8 @@ def parse_args(argv=None):
     p.add_argument("--trunc", type=float, default=None, help="with --mesh: the truncation distance (default: 3 voxels)")
     p.add_argument("--sigma_weight", action="store_true", help="with --mesh and --uncertainty: weight pixels by their variance")
     p.add_argument("--sparse", action="store_true", help="with --mesh: a brick volume over the map's full extent")
+    p.add_argument("--panoptic", action="store_true", help="with --mesh: fuse the frames' panoptic ids, write a label per vertex")
+    p.add_argument("--instances_dir", default=None, help="with --panoptic: also one segment_<id>.ply per id into this folder")
     own, rest = p.parse_known_args(argv)
     args = test_vo.parse_args(rest)
     for k, v in vars(own).items():
@@ -53,18 +58,34 @@ def parse_args(argv=None):
         p.error("--sigma_weight needs --mesh and --uncertainty")
     if args.sparse and args.mesh is None:
         p.error("--sparse needs --mesh")
+    if args.panoptic and args.mesh is None:
+        p.error("--panoptic needs --mesh")
+    if args.instances_dir is not None and not args.panoptic:
+        p.error("--instances_dir needs --panoptic")
     return args
 
 
 def write_mesh(droid, args):
     """the --mesh output of a tracked sequence; returns the line that says what was written"""
-    from pvo_amd.handoff import write_ply_mesh
+    from pvo_amd.handoff import split_mesh_by_label, write_ply_mesh
     kw = {"sparse": True} if args.sparse else {}
+    if args.panoptic:
+        kw["panoptic"] = True
     g = droid.get_mesh(voxel=args.voxel, trunc=args.trunc, thresh=args.filter_thresh_map, full_res=args.full_res,
                        use_sigma=args.sigma_weight, max_rel_sigma=args.max_rel_sigma, **kw)
-    nv, nf = write_ply_mesh(args.mesh, g["verts"], g["faces"], g["rgba"], g["normals"])
+    nv, nf = write_ply_mesh(args.mesh, g["verts"], g["faces"], g["rgba"], g["normals"], **({"label": g["vlabel"]} if args.panoptic else {}))
     what = ("%d bricks of 8^3" % g["volume"].bricks) if args.sparse else ("a %s volume" % "x".join(str(d) for d in g["tsdf"].shape))
-    return "mesh: %d vertices, %d triangles from %s of %g-sized voxels written to %s" % (nv, nf, what, args.voxel, args.mesh)
+    line = "mesh: %d vertices, %d triangles from %s of %g-sized voxels written to %s" % (nv, nf, what, args.voxel, args.mesh)
+    if args.panoptic:
+        ids = sorted(set(g["vlabel"].unique().tolist()))
+        line += "; %d segments" % len(ids)
+        if args.instances_dir is not None:
+            parts = split_mesh_by_label(g["verts"], g["faces"], g["vlabel"])
+            for i in ids:                                    # (an id that owns no face: its vertices alone)
+                v, f = parts.get(i, (g["verts"][g["vlabel"] == i], g["faces"][:0]))
+                write_ply_mesh(os.path.join(args.instances_dir, "segment_%d.ply" % i), v, f)
+            line += ", one mesh each written to %s" % args.instances_dir
+    return line
 
 
 def main(argv=None):
@@ -73,14 +94,16 @@ def main(argv=None):
     args = parse_args(argv)
     args.half_update = True
     args.store_images = True
+    args.store_segment_ids = bool(args.panoptic)
     args.upsample = bool(args.full_res)
     if args.datapath.endswith("20"):
         args.thresh = 0.9
     droid = Droid(args)
-    for t, image, intr, segm in test_vo.image_stream(args.datapath, args.image_size, "val", args.segm_filter):
+    with_segm = args.segm_filter or args.panoptic                      # (--panoptic reads the ids whether or not they filter the graph)
+    for t, image, intr, segm in test_vo.image_stream(args.datapath, args.image_size, "val", with_segm):
         droid.track(t, image, intrinsics=intr, segments=segm)
     print("video frames:", droid.video.counter)
-    traj = droid.terminate(test_vo.image_stream(args.datapath, args.image_size, "val", args.segm_filter), need_inv=True)
+    traj = droid.terminate(test_vo.image_stream(args.datapath, args.image_size, "val", with_segm), need_inv=True)
     out_dir = os.path.join(args.out, os.path.basename(args.datapath.rstrip("/")), test_vo.SPLIT["val"])
     write_kitti_trajectory(os.path.join(out_dir, "pvo_traj.txt"), traj)
     kw = {"max_rel_sigma": args.max_rel_sigma if args.max_rel_sigma is not None else float("inf")} if args.uncertainty else {}
