@@ -430,7 +430,7 @@ def projmap(poses, disps, intrinsics, ii, jj):
     for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
         _contig(t, n)
     dev = _dev(poses, disps, intrinsics, ii, jj)
-    _long(ii, "ii"); _long(jj, "jj")
+    _f32(poses, "poses"); _f32(disps, "disps"); _f32(intrinsics, "intrinsics"); _long(ii, "ii"); _long(jj, "jj")
     E, ht, wd = ii.shape[0], disps.shape[1], disps.shape[2]
     coords = torch.empty(E, ht, wd, 3, dtype=torch.float32, device=dev)
     valid = torch.empty(E, ht, wd, 1, dtype=torch.float32, device=dev)
@@ -445,6 +445,7 @@ def iproj(poses, disps, intrinsics):
     for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
         _contig(t, n)
     dev = _dev(poses, disps, intrinsics)
+    _f32(poses, "poses"); _f32(disps, "disps"); _f32(intrinsics, "intrinsics")
     N, ht, wd = disps.shape
     pts = torch.empty(N, ht, wd, 3, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -458,7 +459,7 @@ def depth_filter(poses, disps, intrinsics, ix, thresh):
     for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ix, "ix"), (thresh, "thresh")):
         _contig(t, n)
     dev = _dev(poses, disps, intrinsics, ix, thresh)
-    _long(ix, "ix"); _f32(thresh, "thresh")
+    _f32(poses, "poses"); _f32(disps, "disps"); _f32(intrinsics, "intrinsics"); _long(ix, "ix"); _f32(thresh, "thresh")
     N, (nf, ht, wd) = ix.shape[0], disps.shape
     counter = torch.empty(N, ht, wd, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -842,7 +843,7 @@ def reproject(poses, disps, intrinsics, ii, jj, out=None, baseline=0.0):
     for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
         _contig(t, n)
     dev = _dev(poses, disps, intrinsics, ii, jj)
-    _long(ii, "ii"); _long(jj, "jj")
+    _f32(poses, "poses"); _f32(disps, "disps"); _f32(intrinsics, "intrinsics"); _long(ii, "ii"); _long(jj, "jj")
     E, ht, wd = ii.shape[0], disps.shape[1], disps.shape[2]
     if out is not None:
         if tuple(out.shape) != (E, ht, wd, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
@@ -1554,7 +1555,7 @@ def reproject_motion(poses, disps, intrinsics, ii, jj, target, delta_dy, raw_mas
     for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj"), (target, "target"),
                  (delta_dy, "delta_dy"), (raw_mask, "raw_mask")):
         _contig(t, n)
-    for t, n in ((target, "target"), (delta_dy, "delta_dy"), (raw_mask, "raw_mask")):
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (target, "target"), (delta_dy, "delta_dy"), (raw_mask, "raw_mask")):
         _f32(t, n)
     dev = _dev(poses, disps, intrinsics, ii, jj, target, delta_dy, raw_mask)
     _long(ii, "ii"); _long(jj, "jj")
@@ -1577,10 +1578,12 @@ def segment_hist(segm, raw_mask, heads, max_segments, dy_thresh=0.5):
     raw_mask [1,E,H,W,2] f32 (BEFORE the update), heads [E,8,H,W] channels-last -> (tot, dyn) int32 [E,max_segments]"""
     _cl(heads, "heads", 8)
     dev = _dev(segm, raw_mask, heads)
-    _contig(segm, "segm"); _contig(raw_mask, "raw_mask")
+    _contig(segm, "segm"); _contig(raw_mask, "raw_mask"); _f32(raw_mask, "raw_mask")
     E, H, W = segm.shape
     if segm.dtype != torch.int32:
         raise PvoHipError("segment_hist: segm must be int32")
+    if raw_mask.numel() != E * H * W * 2 or tuple(heads.shape) != (E, 8, H, W):
+        raise PvoHipError("segment_hist: raw_mask must hold [E,H,W,2] and heads [E,8,H,W] for segm [E,H,W]")
     tot = torch.empty(E, max_segments, dtype=torch.int32, device=dev)
     dyn = torch.empty(E, max_segments, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -1597,7 +1600,13 @@ def graph_post(coords1, heads, raw_mask, target_ba, weight_ba, dy_thresh=0.5, vo
     _cl(heads, "heads", 8)
     _contig(coords1, "coords1"); _contig(raw_mask, "raw_mask"); _contig(target_ba, "target_ba"); _contig(weight_ba, "weight_ba")
     dev = _dev(coords1, heads, raw_mask, target_ba, weight_ba)
+    for t, n in ((coords1, "coords1"), (raw_mask, "raw_mask"), (target_ba, "target_ba"), (weight_ba, "weight_ba")):
+        _f32(t, n)
     _, E, H, W, _ = coords1.shape
+    if tuple(target_ba.shape) != (E, 2, H, W) or tuple(weight_ba.shape) != (E, 2, H, W):
+        raise PvoHipError("graph_post: target_ba and weight_ba must be [E,2,H,W] = [%d,2,%d,%d]" % (E, H, W))
+    if tuple(raw_mask.shape) != tuple(coords1.shape) or tuple(heads.shape) != (E, 8, H, W):
+        raise PvoHipError("graph_post: raw_mask must have coords1's shape [1,E,H,W,2] and heads must be [E,8,H,W]")
     new = lambda: torch.empty(1, E, H, W, 2, dtype=torch.float32, device=dev)
     target, delta_dy, weight, full_flow = new(), new(), new(), new()
     segm = tot = dyn = None
