@@ -88,7 +88,8 @@ const char* pvo_last_hip_error(void);
  * sparse surface reconstruction: no existing struct changed - new structs pvo_tsdf_sparse_{allocate,integrate,mesh}_args and new entry
  * points pvo_tsdf_sparse_{allocate,integrate,mesh}[_args_size, _workspace_bytes]; still 106, panoptic surface reconstruction: no
  * existing struct changed - new extension structs pvo_tsdf_panoptic_args / pvo_tsdf_mesh_labels_args (with *_args_size()) and new entry
- * points pvo_tsdf[_sparse]_integrate_panoptic / pvo_tsdf[_sparse]_mesh_panoptic): a caller
+ * points pvo_tsdf[_sparse]_integrate_panoptic / pvo_tsdf[_sparse]_mesh_panoptic; still 106, keyframe boundary: no struct changed -
+ * new entry points pvo_update_operator_rows / pvo_graph_update_rows / pvo_corr_build_tiled_rows / pvo_edge_rows_init): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -188,6 +189,12 @@ int pvo_corr_build(const void* fmap1, const void* fmap2, void* const* levels_hos
  * anything else returns PVO_EUNSUPPORTED (use the row-major entry points). */
 int pvo_corr_build_tiled(const void* fmap1, const void* fmap2, void* const* levels_host,
                          int N, int C, int H, int W, int dtype, const int* out_slots, void* stream);
+/* pvo_corr_build_tiled straight from per-frame feature buffers: fmaps1 / fmaps2 are [F,H,W,C] and edge n correlates frame rows1[n] of
+ * the first with frame rows2[n] of the second (rows1, rows2: device int32 [N], both required; PVO_EINVAL if either is NULL with
+ * N > 0) - what the caller's two gathers fmaps[ii], fmaps[jj] fed the call above, without the gathers.  Same kernel, same values.
+ * Like out_slots the tables are not range-checked: rows inside the buffers are the caller's business. */
+int pvo_corr_build_tiled_rows(const void* fmaps1, const void* fmaps2, const int* rows1, const int* rows2,
+                              void* const* levels_host, int N, int C, int H, int W, int dtype, const int* out_slots, void* stream);
 int pvo_corr_pyramid_lookup_tiled(const void* const* volumes_host, const float* coords, void* out,
                                   int N, int h1, int w1, int h2, int w2, int num_levels, int dtype,
                                   int out_channels_last, const int* slots, int num_slots, void* stream);
@@ -212,8 +219,9 @@ int pvo_corr_lookup_encode_tiled(const void* const* volumes_host, const float* c
  *
  * ConvGRU (modules/gru.py:19-32), as issued here:
  *   static-input split   conv(W,[net|inp|corr|flow]) = conv(W[:,dyn],[net|corr|flow]) + conv(W[:,inp], inp); `inp` is
- *                        constant over an edge's life, so P_zr [rows,256] / P_q [rows,128] = conv(W[:,inp], inp) are
- *                        computed once per edge (pvo_conv3x3) and added inside the gate epilogues
+ *                        a keyframe's own and written once, so P_zr [rows,256] / P_q [rows,128] = conv(W[:,inp], inp) are
+ *                        computed once per KEYFRAME (pvo_conv3x3), kept in per-frame pools, and added inside the gate
+ *                        epilogues, which read the row of the edge's source frame (pvo_update_operator_rows)
  *   pvo_gru_glo_fused    per-chunk partial means of sigmoid(w(net) + b) * net  (gru.py:22-24, 1x1 conv inside)
  *   pvo_gate_context     g[E,384] = [convz_glo | convr_glo | convq_glo](glo) + their biases + the z/r/q conv biases
  *   pvo_gru_conv_gates / pvo_gru_conv_candidate   the two wide 3x3 convolutions with the gate arithmetic as epilogue */
@@ -249,9 +257,9 @@ int pvo_conv3x3(const void* x, const void* w_taps, const float* bias, void* y,
  *   pvo_gru_conv_candidate: net_out = (1 - Z) * net + Z * tanh(conv3x3([RN|cf], w) + g[e, 256:384] + P_q)
  * w_taps [9][256 or 128][128 + cf_channels], g f32 [E,384], P_zr [E,H,W,256], P_q / net / Z / RN / net_out [E,H,W,128];
  * net_out may alias net.
- * p_slots (int32 [E] or NULL): the static terms live in a slot pool, P_zr [slots,H,W,256] / P_q [slots,H,W,128], and edge e
- * reads image p_slots[e] - the factor graph keeps them in the slots of its volume pool, so they are written once when an edge
- * is created and never gathered or concatenated when the edge set changes. */
+ * p_slots (int32 [E] or NULL): the static terms live in a pool, P_zr [rows,H,W,256] / P_q [rows,H,W,128], and edge e reads image
+ * p_slots[e] - the factor graph keeps them per keyframe and passes the edges' source frames (before: per edge, in the slots of its
+ * volume pool), so they are never gathered or concatenated when the edge set changes.  The table is not range-checked. */
 int pvo_gru_conv_gates(const void* net, const void* cf, int cf_channels, const void* w_taps, const float* g,
                        const void* P_zr, const int* p_slots, void* Z, void* RN, int E, int H, int W, int dtype, void* stream);
 int pvo_gru_conv_candidate(const void* RN, const void* cf, int cf_channels, const void* w_taps, const float* g,
@@ -442,6 +450,12 @@ typedef struct pvo_operator_args {
 size_t pvo_operator_workspace_bytes(int E, int K, int H, int W);
 int pvo_update_operator(const pvo_update_weights* weights, const pvo_operator_args* args,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* Static terms per KEYFRAME: conv(W[:, inp], inp) is a function of the source frame alone, so a caller keeps one row per frame
+ * instead of one per edge.  static_rows (device int32 [E]) != NULL: args->P_zr / P_q (both required, else PVO_EINVAL) are pools
+ * [frames,H,W,256] / [frames,H,W,128] and edge e reads image static_rows[e] - whatever args->static_by_slot says.  The table is not
+ * range-checked (as `slots`: rows inside the pools are the caller's business).  NULL IS pvo_update_operator, which forwards here. */
+int pvo_update_operator_rows(const pvo_update_weights* weights, const pvo_operator_args* args, const int* static_rows,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* One call of FactorGraph.update (factor_graph.py:227-307) on a resident tiled volume pool. */
 typedef struct pvo_graph_update_args {
@@ -516,9 +530,24 @@ int pvo_graph_update(const pvo_update_weights* weights, const pvo_graph_update_a
  * (i, i) edges stay identity edges.  Negative, NaN or infinite: PVO_EINVAL. */
 int pvo_graph_update_rig(const pvo_update_weights* weights, const pvo_graph_update_args* args,
                          void* workspace, size_t workspace_bytes, float stereo_baseline, void* stream);
+/* pvo_graph_update_rig with the static terms read per keyframe (see pvo_update_operator_rows): static_rows (device int32 [op.E],
+ * normally an int32 copy of ii) != NULL makes op.P_zr / op.P_q frame pools indexed by static_rows[e].  NULL IS
+ * pvo_graph_update_rig, which forwards here.  The struct is pinned, hence an argument of an entry point of its own. */
+int pvo_graph_update_rows(const pvo_update_weights* weights, const pvo_graph_update_args* args,
+                          void* workspace, size_t workspace_bytes, float stereo_baseline, const int* static_rows, void* stream);
+/* The per-edge state rows of n new edges (FactorGraph.add_factors, factor_graph.py:137-161) in ONE launch, for edge e < n:
+ *   net[e]      = nets[ii[e]]                      ([H,W,128] 16-bit rows: a copy, so either 16-bit type)
+ *   target[e]   = pvo_reproject_rig(ii[e], jj[e])  coordinates only, the same device function: bit-identical, `baseline` included
+ *   weight[e] = raw_mask[e] = delta_dy[e] = 0      ([H,W,2] f32 each)
+ * nets [frames,H,W,128]; the five outputs point at the FIRST NEW ROW of the caller's buffers.  It replaces an index_select, a
+ * reprojection and three fills.  ii / jj int64 [n] as for pvo_reproject; 16-byte aligned nets / net, 8-byte aligned f32 rows;
+ * n <= 65535.  n == 0 is a no-op; n < 0, or a NULL pointer with n > 0: PVO_EINVAL. */
+int pvo_edge_rows_init(const void* nets, const float* poses, const float* disps, const float* intrinsics,
+                       const int64_t* ii, const int64_t* jj, void* net, float* target, float* weight, float* raw_mask,
+                       float* delta_dy, int n, int ht, int wd, float baseline, void* stream);
 
 /* ------------------------------------------------------------------------- */
-/* Convex 8x upsampling                                                       */
+/* Convex 8x upsampling                                                     */
 /* ------------------------------------------------------------------------- */
 
 /* cvx_upsample (VO_Module/droid_slam/droid_net.py:23-37; upsample_dim_1 / upsample_dim_x :40-54; DepthVideo.upsample, depth_video.py:139-143):

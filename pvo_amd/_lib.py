@@ -42,6 +42,7 @@ SIGNATURES = {
     "pvo_eta_head": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
     "pvo_conv1x1_c128": (_i, [_vp, _vp, _vp, _vp, _c.c_longlong, _i, _i, _i, _vp]),
     "pvo_corr_build_tiled": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pvo_corr_build_tiled_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pvo_corr_lookup_encode_tiled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "pvo_corr_pyramid_lookup_tiled": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "pvo_heads_out": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -69,6 +70,9 @@ SIGNATURES = {
     "pvo_graph_update_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "pvo_graph_update": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pvo_graph_update_rig": (_i, [_vp, _vp, _vp, _sz, _f, _vp]),
+    "pvo_update_operator_rows": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "pvo_graph_update_rows": (_i, [_vp, _vp, _vp, _sz, _f, _vp, _vp]),
+    "pvo_edge_rows_init": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "pvo_se3_unary": (_i, [_i, _vp, _vp, _c.c_longlong, _i, _vp]),
     "pvo_se3_binary": (_i, [_i, _vp, _c.c_longlong, _vp, _c.c_longlong, _vp, _c.c_longlong, _i, _vp]),
     "pvo_se3_unary_vjp": (_i, [_i, _vp, _vp, _vp, _c.c_longlong, _i, _vp]),

@@ -34,9 +34,12 @@ class DroidBackend:
 
     def _volumes_fit(self, n_edges):
         """resident correlation volumes + per-edge operator state for n_edges, against the free HBM (288 GB on MI355X): the 4-level
-        pyramid is 2.66 HW^2 bytes per edge (24 MB at 30x101), state + workspace ~5 KB per pixel"""
+        pyramid is 2.66 HW^2 bytes per edge (24 MB at 30x101), state + workspace ~4.4 KB per pixel; the static GRU terms are per
+        KEYFRAME (768 bytes per pixel and frame of the video's buffer, allocated once: counted while the video has no pool yet)"""
         hw = (self.video.ht // 8) * (self.video.wd // 8)
-        need = n_edges * (2.7 * hw * hw + 5200.0 * hw)
+        need = n_edges * (2.7 * hw * hw + 4432.0 * hw)
+        if getattr(self.video, "_static", None) is None:
+            need += 768.0 * hw * self.video.disps.shape[0]
         if torch.device(self.device).type != "cuda":
             return False
         free, _total = torch.cuda.mem_get_info(torch.device(self.device))

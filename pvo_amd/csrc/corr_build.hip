@@ -34,6 +34,7 @@ struct BuildArgs {
   int N, C, H, W, nlev;
   const int* out_slots;             // optional: edge n is written to slot out_slots[n] of the level tensors
   int tiled;                        // level l stored [N, HW, ceil(Hl/8), ceil(Wl/8), 8, 8] (see corr_lookup.hip)
+  const int* rows1; const int* rows2;   // optional, both or neither: f1 / f2 are frame buffers [F,H,W,C] and edge n reads frames rows1[n] / rows2[n]
 };
 
 // pooled = round16(((a + b) + c) + d) / 4), ATen avg_pool2d window order (kh, kw)
@@ -58,7 +59,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
   const int m0 = blockIdx.x * kTileM + wave * 32;
 
   // ---- stage the fmap2 patch: 256 pixel rows of C halves
-  const uint16_t* f2 = reinterpret_cast<const uint16_t*>(a.f2) + static_cast<long long>(n) * HW * C;
+  const int n1 = a.rows1 ? a.rows1[n] : n, n2 = a.rows2 ? a.rows2[n] : n;       // images of the two feature maps (workgroup-uniform)
+  const uint16_t* f2 = reinterpret_cast<const uint16_t*>(a.f2) + static_cast<long long>(n2) * HW * C;
   // C is a power of two here (16..128): cpr = C/8 chunks of 16 B per pixel row.  All loads of a
   // thread are issued before the first LDS store (16 independent 16-byte loads in flight);
   // a load -> store -> load loop serialises 16 memory round trips per workgroup.
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
   // ---- this lane's fmap1 fragments (row i = lane&31 of the wave's 32 source pixels)
   const int kg = lane >> 5;
   const int p1_frag = m0 + (lane & 31);
-  const uint16_t* f1row = reinterpret_cast<const uint16_t*>(a.f1) + (static_cast<long long>(n) * HW + min(p1_frag, HW - 1)) * C;
+  const uint16_t* f1row = reinterpret_cast<const uint16_t*>(a.f1) + (static_cast<long long>(n1) * HW + min(p1_frag, HW - 1)) * C;
   u32x4 afrag[kMaxC / 16];
   const int ksteps = C >> 4;
 #pragma unroll
@@ -400,12 +402,9 @@ int build_mfma(const BuildArgs& a, hipStream_t st) {
   return PVO_OK;
 }
 
-}  // namespace
-
-extern "C" int pvo_corr_build_tiled(const void* fmap1, const void* fmap2, void* const* levels_host,
-                                    int N, int C, int H, int W, int dtype, const int* out_slots, void* stream) {
-  if (N < 0 || C <= 0 || H < 0 || W < 0 || !levels_host) return PVO_EINVAL;
-  if (N == 0 || H == 0 || W == 0) return PVO_OK;
+// edge n: frame rows1[n] of fmap1 x frame rows2[n] of fmap2 (both tables nullptr: image n of each) -> slot out_slots[n]
+int build_tiled(const void* fmap1, const void* fmap2, const int* rows1, const int* rows2, void* const* levels_host,
+                int N, int C, int H, int W, int dtype, const int* out_slots, void* stream) {
   if (!fmap1 || !fmap2 || N > 65535) return PVO_EINVAL;
   for (int l = 0; l < 4; ++l)
     if (!levels_host[l]) return PVO_EINVAL;
@@ -415,9 +414,28 @@ extern "C" int pvo_corr_build_tiled(const void* fmap1, const void* fmap2, void* 
     return PVO_EUNSUPPORTED;
   BuildArgs a{};
   a.f1 = fmap1; a.f2 = fmap2; a.N = N; a.C = C; a.H = H; a.W = W; a.nlev = 4; a.out_slots = out_slots; a.tiled = 1;
+  a.rows1 = rows1; a.rows2 = rows2;
   for (int l = 0; l < 4; ++l) a.lv[l] = levels_host[l];
   hipStream_t st = pvo_stream(stream);
   return pvo_dispatch16(dtype, [&](auto tag) -> int { return build_mfma<decltype(tag)>(a, st); });
+}
+
+}  // namespace
+
+extern "C" int pvo_corr_build_tiled_rows(const void* fmaps1, const void* fmaps2, const int* rows1, const int* rows2,
+                                         void* const* levels_host, int N, int C, int H, int W, int dtype, const int* out_slots,
+                                         void* stream) {
+  if (N < 0 || C <= 0 || H < 0 || W < 0 || !levels_host) return PVO_EINVAL;
+  if (N == 0 || H == 0 || W == 0) return PVO_OK;
+  if (!rows1 || !rows2) return PVO_EINVAL;
+  return build_tiled(fmaps1, fmaps2, rows1, rows2, levels_host, N, C, H, W, dtype, out_slots, stream);
+}
+
+extern "C" int pvo_corr_build_tiled(const void* fmap1, const void* fmap2, void* const* levels_host,
+                                    int N, int C, int H, int W, int dtype, const int* out_slots, void* stream) {
+  if (N < 0 || C <= 0 || H < 0 || W < 0 || !levels_host) return PVO_EINVAL;
+  if (N == 0 || H == 0 || W == 0) return PVO_OK;
+  return build_tiled(fmap1, fmap2, nullptr, nullptr, levels_host, N, C, H, W, dtype, out_slots, stream);
 }
 
 extern "C" int pvo_corr_build(const void* fmap1, const void* fmap2, void* const* levels_host,

@@ -150,15 +150,11 @@ __device__ __forceinline__ Pose edge_pose(const float* __restrict__ poses, int i
   return rel_pose(load_pose(poses + 7 * static_cast<long long>(ix)), load_pose(poses + 7 * static_cast<long long>(jx)));
 }
 
-// projective_ops.py:102-130 with jacobian=False; per-frame intrinsics [nframes,4]
-__global__ __launch_bounds__(256) void reproject_kernel(
-    const float* __restrict__ poses, const float* __restrict__ disps, const float* __restrict__ intrinsics,
-    const int64_t* __restrict__ ii, const int64_t* __restrict__ jj,
-    float* __restrict__ coords, float* __restrict__ valid, int HW, int wd, float baseline) {
-  const int e = blockIdx.y;
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= HW) return;
-  const int ix = static_cast<int>(ii[e]), jx = static_cast<int>(jj[e]);
+// projective_ops.py:102-130 with jacobian=False; per-frame intrinsics [nframes,4]: pixel k of edge (ix, jx)
+struct Reprojected { float2 c; float valid; };
+__device__ __forceinline__ Reprojected reproject_pixel(const float* __restrict__ poses, const float* __restrict__ disps,
+                                                       const float* __restrict__ intrinsics, int ix, int jx, int k, int HW, int wd,
+                                                       float baseline) {
   const Intr Ki = load_intr(intrinsics + 4 * static_cast<long long>(ix));
   const Intr Kj = load_intr(intrinsics + 4 * static_cast<long long>(jx));
   const Pose G = edge_pose(poses, ix, jx, baseline);
@@ -170,11 +166,47 @@ __global__ __launch_bounds__(256) void reproject_kernel(
   float Z = X1[2];
   Z = (Z < 0.5f * kMinDepthPy) ? 1.0f : Z;   // projective_ops.py:48
   const float d = 1.0f / Z;
-  float2 c;
-  c.x = Kj.fx * (X1[0] * d) + Kj.cx;
-  c.y = Kj.fy * (X1[1] * d) + Kj.cy;
-  *reinterpret_cast<float2*>(coords + (static_cast<long long>(e) * HW + k) * 2) = c;
-  valid[static_cast<long long>(e) * HW + k] = (X1[2] > kMinDepthPy && X0[2] > kMinDepthPy) ? 1.0f : 0.0f;
+  Reprojected r;
+  r.c.x = Kj.fx * (X1[0] * d) + Kj.cx;
+  r.c.y = Kj.fy * (X1[1] * d) + Kj.cy;
+  r.valid = (X1[2] > kMinDepthPy && X0[2] > kMinDepthPy) ? 1.0f : 0.0f;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void reproject_kernel(
+    const float* __restrict__ poses, const float* __restrict__ disps, const float* __restrict__ intrinsics,
+    const int64_t* __restrict__ ii, const int64_t* __restrict__ jj,
+    float* __restrict__ coords, float* __restrict__ valid, int HW, int wd, float baseline) {
+  const int e = blockIdx.y;
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= HW) return;
+  const Reprojected r = reproject_pixel(poses, disps, intrinsics, static_cast<int>(ii[e]), static_cast<int>(jj[e]), k, HW, wd, baseline);
+  *reinterpret_cast<float2*>(coords + (static_cast<long long>(e) * HW + k) * 2) = r.c;
+  valid[static_cast<long long>(e) * HW + k] = r.valid;
+}
+
+// FactorGraph.add_factors' state rows of n new edges in one launch: net rows = the source frames' hidden state (a row copy of
+// 256 bytes per pixel), target rows = the edges' reprojection (reproject_pixel: the bits pvo_reproject_rig writes), zero weight /
+// raw_mask / delta_dy rows.  A workgroup owns 256 pixels of one edge: their net rows are 64 KB contiguous in both tensors.
+__global__ __launch_bounds__(256) void edge_rows_init_kernel(
+    const uint4* __restrict__ nets, const float* __restrict__ poses, const float* __restrict__ disps,
+    const float* __restrict__ intrinsics, const int64_t* __restrict__ ii, const int64_t* __restrict__ jj,
+    uint4* __restrict__ net, float2* __restrict__ target, float2* __restrict__ weight, float2* __restrict__ raw_mask,
+    float2* __restrict__ delta_dy, int HW, int wd, float baseline) {
+  const int e = blockIdx.y;
+  const int k0 = blockIdx.x * 256, k = k0 + threadIdx.x;
+  const int ix = static_cast<int>(ii[e]), jx = static_cast<int>(jj[e]);
+  // 16 chunks of 16 bytes per pixel ([H,W,128] 16-bit rows)
+  const int chunks = min(256, HW - k0) * 16;
+  const uint4* src = nets + (static_cast<long long>(ix) * HW + k0) * 16;
+  uint4* dst = net + (static_cast<long long>(e) * HW + k0) * 16;
+#pragma unroll 4
+  for (int c = threadIdx.x; c < chunks; c += 256) dst[c] = src[c];
+  if (k >= HW) return;
+  const long long idx = static_cast<long long>(e) * HW + k;
+  target[idx] = reproject_pixel(poses, disps, intrinsics, ix, jx, k, HW, wd, baseline).c;
+  const float2 z = {0.0f, 0.0f};
+  weight[idx] = z; raw_mask[idx] = z; delta_dy[idx] = z;
 }
 
 }  // namespace
@@ -329,6 +361,24 @@ extern "C" int pvo_reproject(const float* poses, const float* disps, const float
                              const int64_t* ii, const int64_t* jj, float* coords, float* valid,
                              int E, int ht, int wd, void* stream) {
   return pvo_reproject_rig(poses, disps, intrinsics, ii, jj, coords, valid, E, ht, wd, 0.0f, stream);
+}
+
+// (here and not in graph_glue.hip: this file is the one compiled without multiply-add contraction, which is what makes the target
+// rows the bits of pvo_reproject_rig)
+extern "C" int pvo_edge_rows_init(const void* nets, const float* poses, const float* disps, const float* intrinsics,
+                                  const int64_t* ii, const int64_t* jj, void* net, float* target, float* weight, float* raw_mask,
+                                  float* delta_dy, int n, int ht, int wd, float baseline, void* stream) {
+  PVO_REQ(n >= 0 && ht >= 0 && wd >= 0 && baseline >= 0.0f);
+  if (n == 0 || ht * wd == 0) return PVO_OK;
+  PVO_REQ(nets && poses && disps && intrinsics && ii && jj && net && target && weight && raw_mask && delta_dy && n <= 65535);
+  PVO_REQ(!pvo_misaligned16(nets, net) && !((reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(weight) |
+           reinterpret_cast<uintptr_t>(raw_mask) | reinterpret_cast<uintptr_t>(delta_dy)) & 7));
+  auto f2 = [](float* p) { return reinterpret_cast<float2*>(p); };
+  hipLaunchKernelGGL(edge_rows_init_kernel, dim3((ht * wd + 255) / 256, n), dim3(256), 0, pvo_stream(stream),
+                     static_cast<const uint4*>(nets), poses, disps, intrinsics, ii, jj, static_cast<uint4*>(net), f2(target), f2(weight),
+                     f2(raw_mask), f2(delta_dy), ht * wd, wd, baseline);
+  PVO_CHECK_LAUNCH();
+  return PVO_OK;
 }
 
 // RGB-D ingest: the sensor depth's 1/8 lattice as inverse depth, 0 where there is no measurement

@@ -152,8 +152,9 @@ struct MotionJob {           // pvo_graph_update's motion features: only the flo
   const float *target, *coords, *delta_dy, *raw_mask; void* motion;
 };
 
+// static_rows (int32 [E] or nullptr): a->P_zr / a->P_q are per-keyframe pools and edge e reads image static_rows[e] (its source frame)
 int run_trunk(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, const void** P_zr, const void** P_q,
-              const MotionJob* mj, bool context_ready = false) {
+              const MotionJob* mj, bool context_ready = false, const int* static_rows = nullptr) {
   const int E = a->E, H = a->H, W = a->W, dt = w->dtype;
   const long long rows = static_cast<long long>(E) * H * W;
   hipStream_t st = pvo_stream(stream);
@@ -206,8 +207,11 @@ int run_trunk(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, 
   }
   if (sc && hipStreamWaitEvent(st, sc->join, 0) != hipSuccess) return PVO_ELAUNCH;
   probe_mark(PVO_STAGE_GATES, 0, stream);
-  const int* ps = (a->static_by_slot && a->P_zr && a->P_q) ? a->slots : nullptr;
-  if (a->static_by_slot && !a->slots) return PVO_EINVAL;
+  // the image of each edge's static term: its source frame's row of a per-keyframe pool (static_rows), its volume's slot, or e
+  const bool cached = a->P_zr && a->P_q;
+  if (static_rows && !cached) return PVO_EINVAL;
+  const int* ps = static_rows ? static_rows : (a->static_by_slot && cached) ? a->slots : nullptr;
+  if (!static_rows && a->static_by_slot && !a->slots) return PVO_EINVAL;
   RUN(pvo_gru_conv_gates(a->net, b.CF, 192, w->zr_w, b.g, *P_zr, ps, b.Z, b.RN, E, H, W, dt, stream));
   probe_mark(PVO_STAGE_GATES, 1, stream);
   probe_mark(PVO_STAGE_CANDIDATE, 0, stream);
@@ -266,9 +270,9 @@ int check_op(const pvo_update_weights* w, const pvo_operator_args* a) {
 // aggregation branch, which occupy a fraction of the chip, also overlap the mask / weight glue).
 int run_operator(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, SideCtx** pending,
                  const MotionJob* mj = nullptr, bool upmask_on_side = true, bool context_ready = false,
-                 const GraphPostArgs* post = nullptr, int* post_fused = nullptr) {
+                 const GraphPostArgs* post = nullptr, int* post_fused = nullptr, const int* static_rows = nullptr) {
   const void *P_zr, *P_q;
-  RUN(run_trunk(w, a, b, stream, &P_zr, &P_q, mj, context_ready));
+  RUN(run_trunk(w, a, b, stream, &P_zr, &P_q, mj, context_ready, static_rows));
   hipStream_t st = pvo_stream(stream);
   SideCtx* sc = (a->K > 0 && !(w->flags & PVO_OP_SINGLE_STREAM)) ? side_ctx() : nullptr;
   if (sc) {
@@ -303,8 +307,8 @@ extern "C" size_t pvo_operator_workspace_bytes(int E, int K, int H, int W) {
   return carve_op(nullptr, E, K, H, W, pvo_gru_glo_chunks(H * W)).bytes + 256;
 }
 
-extern "C" int pvo_update_operator(const pvo_update_weights* w, const pvo_operator_args* a,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int pvo_update_operator_rows(const pvo_update_weights* w, const pvo_operator_args* a, const int* static_rows,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
   RUN(check_op(w, a));
   if (a->E == 0) return PVO_OK;
   if (!workspace || workspace_bytes < pvo_operator_workspace_bytes(a->E, a->K, a->H, a->W)) return PVO_EWORKSPACE;
@@ -312,8 +316,13 @@ extern "C" int pvo_update_operator(const pvo_update_weights* w, const pvo_operat
   OpWs b = carve_op(ws_base(workspace), a->E, a->K, a->H, a->W, pvo_gru_glo_chunks(a->H * a->W));
   if (ContextAhead* ca = ctx_ahead_slot()) ca->valid = false;
   SideCtx* pending = nullptr;
-  RUN(run_operator(w, a, b, stream, &pending));
+  RUN(run_operator(w, a, b, stream, &pending, nullptr, true, false, nullptr, nullptr, static_rows));
   return join(pending, stream);
+}
+
+extern "C" int pvo_update_operator(const pvo_update_weights* w, const pvo_operator_args* a,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  return pvo_update_operator_rows(w, a, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t pvo_graph_update_workspace_bytes(int E, int K, int R, int H, int W, int max_segments) {
@@ -321,8 +330,9 @@ extern "C" size_t pvo_graph_update_workspace_bytes(int E, int K, int R, int H, i
   return carve_up(nullptr, E, K, R, H, W, max_segments, pvo_operator_workspace_bytes(E, K, H, W)).bytes + 256;
 }
 
-extern "C" int pvo_graph_update_rig(const pvo_update_weights* w, const pvo_graph_update_args* u,
-                                    void* workspace, size_t workspace_bytes, float stereo_baseline, void* stream) {
+extern "C" int pvo_graph_update_rows(const pvo_update_weights* w, const pvo_graph_update_args* u,
+                                     void* workspace, size_t workspace_bytes, float stereo_baseline, const int* static_rows,
+                                     void* stream) {
   if (!w || !u) return PVO_EINVAL;
   if (!(stereo_baseline >= 0.0f) || !(stereo_baseline < __builtin_inff())) return PVO_EINVAL;      // (NaN fails the first comparison)
   pvo_operator_args a = u->op;
@@ -373,7 +383,7 @@ extern "C" int pvo_graph_update_rig(const pvo_update_weights* w, const pvo_graph
                              reinterpret_cast<float2*>(u->full_flow), u->dy_thresh};
   const bool post_in_gather = !u->segm && pvo_knob(PVO_KNOB_POST_SEPARATE) == 0;
   int post_fused = 0;
-  RUN(run_operator(w, &a, b, stream, &pending, nullptr, false, ctx_ready, post_in_gather ? &gpa : nullptr, &post_fused));
+  RUN(run_operator(w, &a, b, stream, &pending, nullptr, false, ctx_ready, post_in_gather ? &gpa : nullptr, &post_fused, static_rows));
   if (u->segm)
     RUN(pvo_segment_hist_ws(u->segm, u->raw_mask, s.heads, s.vote_tot, s.vote_dyn, E, HW, S, u->dy_thresh, dt, stream));
   if (!post_fused)
@@ -451,9 +461,14 @@ extern "C" int pvo_graph_update_rig(const pvo_update_weights* w, const pvo_graph
   return PVO_OK;
 }
 
+extern "C" int pvo_graph_update_rig(const pvo_update_weights* w, const pvo_graph_update_args* u,
+                                    void* workspace, size_t workspace_bytes, float stereo_baseline, void* stream) {
+  return pvo_graph_update_rows(w, u, workspace, workspace_bytes, stereo_baseline, nullptr, stream);
+}
+
 extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_update_args* u,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  return pvo_graph_update_rig(w, u, workspace, workspace_bytes, 0.0f, stream);
+  return pvo_graph_update_rows(w, u, workspace, workspace_bytes, 0.0f, nullptr, stream);
 }
 
 extern "C" int pvo_side_stream(void** stream_out) {

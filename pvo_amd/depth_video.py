@@ -46,6 +46,76 @@ import torch
 from . import droid_backends as db
 
 
+class StaticTermPool:
+    """The ConvGRU's static-input terms conv(W[:, inp], inp), one row per KEYFRAME: P_zr [buffer,256,h,w], P_q [buffer,128,h,w],
+    channels-last ([buffer,h,w,C] in memory), in the update operator's 16-bit type.
+
+    The terms are a function of a keyframe's context features `inps[f]` and the packed weights only, so every factor graph on a video
+    shares one pool (`DepthVideo.static_pool`) and an edge reads the row of its source frame (pvo_graph_update_rows' static_rows).
+    A row is valid while the stamp it was computed at is still the frame's `DepthVideo` stamp: `ensure(frames)` computes the rows
+    that are not, contiguous runs of frames in one pvo_conv3x3 call per term, written straight into the pool.  `computed` counts
+    the frames convolved so far."""
+
+    def __init__(self, video, weights, dtype):
+        n, h8, w8 = video.inps.shape[0], video.ht // 8, video.wd // 8
+        self.video, self.weights, self.serial, self.dtype = video, weights, weights.serial, dtype
+        self.P_zr = torch.empty(n, h8, w8, 256, dtype=dtype, device=video.device).permute(0, 3, 1, 2)
+        self.P_q = torch.empty(n, h8, w8, 128, dtype=dtype, device=video.device).permute(0, 3, 1, 2)
+        self.row_stamp = [-1] * n        # the frame's stamp its row was computed at (-1: never)
+        self.epoch = video._inps_epoch
+        self.computed = 0
+        self.ready, self.ready_serial = None, 0      # event behind the latest computation / copy, and how many there have been
+
+    def valid(self, f):
+        v = self.video
+        v._inps_foreign_check()
+        return self.epoch == v._inps_epoch and self.row_stamp[f] == v._inp_stamp[f]
+
+    def _mark(self):
+        if self.video.device.type == "cuda":
+            self.ready = torch.cuda.Event()
+            self.ready.record(torch.cuda.current_stream(self.video.device))
+        self.ready_serial += 1
+
+    def _compute(self, a, b):
+        """rows [a, b) from the frames' slab of `inps` (contiguous channels-last images), one call per term"""
+        x = self.video.inps[a:b]
+        if x.dtype != self.dtype:
+            x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
+        db.conv3x3(x, self.weights.tensors["zr_inp_w"], out=self.P_zr[a:b])
+        db.conv3x3(x, self.weights.tensors["q_inp_w"], out=self.P_q[a:b])
+
+    def ensure(self, frames):
+        """rows of `frames` (host ints) valid on the current stream; returns the number of frames computed"""
+        v = self.video
+        v._inps_foreign_check()
+        if self.epoch != v._inps_epoch:
+            self.row_stamp = [-1] * len(self.row_stamp)
+            self.epoch = v._inps_epoch
+        need = sorted({int(f) for f in frames if self.row_stamp[int(f)] != v._inp_stamp[int(f)]})
+        k = 0
+        while k < len(need):
+            a = b = need[k]
+            while k + 1 < len(need) and need[k + 1] == b + 1:
+                k += 1; b += 1
+            k += 1
+            self._compute(a, b + 1)
+            for f in range(a, b + 1):
+                self.row_stamp[f] = v._inp_stamp[f]
+        if need:
+            self.computed += len(need)
+            self._mark()
+        return len(need)
+
+    def shift(self, ix, stamp):
+        """rm_keyframe: row ix + 1 moves to ix with its validity (`stamp`: frame ix's new stamp)"""
+        self.P_zr[ix] = self.P_zr[ix + 1].clone()
+        self.P_q[ix] = self.P_q[ix + 1].clone()
+        ok = self.epoch == self.video._inps_epoch and self.row_stamp[ix + 1] == self.video._inp_stamp[ix + 1]
+        self.row_stamp[ix] = stamp if ok else -1
+        self._mark()
+
+
 class DepthVideo:
     def __init__(self, image_size=(480, 640), buffer=1024, device="cuda:0", segm_filter=False, thresh=0.8,
                  store_images=False, store_segment_ids=False):
@@ -77,6 +147,14 @@ class DepthVideo:
         # layout the update operator reads (factor_graph.py add_factors)
         self.nets = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw).permute(0, 3, 1, 2)
         self.inps = torch.zeros(buffer, h8, w8, 128, dtype=torch.half, **kw).permute(0, 3, 1, 2)
+        # who wrote `inps` last, for the per-keyframe static GRU terms (StaticTermPool): a stamp per frame, bumped where THIS class
+        # writes the frame; `inps._version` as of our last write - if it moved otherwise somebody wrote the buffer directly, and
+        # every frame's terms are invalid (a new epoch)
+        self._inp_stamp = [0] * buffer
+        self._inp_clock = 0
+        self._inps_epoch = 0
+        self._inps_seen = self.inps._version
+        self._static = None
         self.segms = torch.zeros(buffer, 1, h8, w8, dtype=torch.int, **kw)
         # the frames' panoptic ids as given (segms relabels every frame on its own): what tsdf(panoptic=True) fuses; <= 0 = no segment
         self.segms_raw = torch.zeros(buffer, h8, w8, dtype=torch.int32, **kw) if store_segment_ids else None
@@ -98,6 +176,37 @@ class DepthVideo:
         self._frame_fmaps_bytes = 0
 
     # ------------------------------------------------------------------ bookkeeping
+    def _inps_foreign_check(self):
+        """a write to `inps` that did not go through this class (torch's version counter moved): every frame's static terms are invalid"""
+        if self.inps._version != self._inps_seen:
+            self._inps_epoch += 1
+            self._inps_seen = self.inps._version
+
+    def _write_inps(self, index, value):
+        """inps[index] = value, stamped: the frames written get a new stamp (an index that is not an int: all of them)"""
+        self._inps_foreign_check()
+        self.inps[index] = value
+        self._inps_seen = self.inps._version
+        self._inp_clock += 1
+        if isinstance(index, int):
+            self._inp_stamp[index] = self._inp_clock
+        else:
+            self._inp_stamp = [self._inp_clock] * len(self._inp_stamp)
+
+    def shift_inps(self, ix):
+        """rm_keyframe's frame shift of `inps` (row ix + 1 to ix), and of the static-term pool's rows with it"""
+        self._write_inps(ix, self.inps[ix + 1].clone())
+        if self._static is not None:
+            self._static.shift(ix, self._inp_stamp[ix])
+
+    def static_pool(self, weights, dtype):
+        """the per-keyframe static GRU terms of this video for the packed weights `weights` (a PackedWeights) in `dtype`, allocated on
+        first use: 768 bytes per pixel and frame.  Other weights or another dtype start a new pool (every row invalid)."""
+        st = self._static
+        if st is None or st.serial != weights.serial or st.dtype != dtype:
+            st = self._static = StaticTermPool(self, weights, dtype)
+        return st
+
     def _fmap_cl(self, f, channels_last):
         """feature map -> the stored channels-last layout.  The layout is taken from the shape wherever that is
         unambiguous ([..,128,h,w] vs [..,h,w,128] with h,w of THIS video); for maps that are 128 wide or high pass
@@ -296,7 +405,7 @@ class DepthVideo:
         self.intrinsics[k] = self._kept_intrinsics(intrinsics)
         self.fmaps[k] = self._fmap_cl(fmap, channels_last)
         self.nets[k] = net
-        self.inps[k] = inp
+        self._write_inps(k, inp)
         if segm is not None:
             self.segms[k] = self._dense_segments(segm).reshape(self.segms[k].shape)
             if self.segms_raw is not None:
@@ -328,7 +437,7 @@ class DepthVideo:
         if len(item) > 6:
             self.nets[index] = item[6]
         if len(item) > 7:
-            self.inps[index] = item[7]
+            self._write_inps(index, item[7])
         if self.segm_filter and len(item) > 8 and item[8] is not None:
             if self.segms_raw is not None:
                 self.segms_raw[index] = self._raw_segments(item[8], self.segms_raw[index].shape)

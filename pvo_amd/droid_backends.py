@@ -263,6 +263,29 @@ def corr_build_tiled(fmap1, fmap2, out, out_slots):
     return out
 
 
+def corr_build_tiled_rows(fmaps1, fmaps2, rows1, rows2, out, out_slots):
+    """pvo_corr_build_tiled_rows: corr_build_tiled straight from frame buffers - edge n correlates frame rows1[n] of fmaps1 with
+    frame rows2[n] of fmaps2 ([F,H,W,C] channels-last 16-bit; rows1 / rows2 / out_slots device int32 [N]).  The values of the
+    tables are not checked: rows inside the buffers are the caller's business."""
+    _contig(fmaps1, "fmaps1"); _contig(fmaps2, "fmaps2")
+    dev = _dev(fmaps1, fmaps2, rows1, rows2, out_slots, *out)
+    _, H, W, C = fmaps1.shape
+    N = rows1.numel()
+    if fmaps1.shape[1:] != fmaps2.shape[1:] or fmaps1.dtype != fmaps2.dtype or len(out) != 4:
+        raise PvoHipError("corr_build_tiled_rows: fmap mismatch or not 4 levels")
+    for l, lv in enumerate(out):
+        if tuple(lv.shape[1:]) != (H, W) + tiled_level_shape(H, W, l) or lv.dtype != fmaps1.dtype or not lv.is_contiguous():
+            raise PvoHipError("corr_build_tiled_rows: level %d has shape %s" % (l, tuple(lv.shape)))
+    for t, name in ((rows1, "rows1"), (rows2, "rows2"), (out_slots, "out_slots")):
+        if t.dtype != torch.int32 or t.numel() != N or not t.is_contiguous():
+            raise PvoHipError("corr_build_tiled_rows: %s must be device int32, one per edge" % name)
+    ptrs = (ctypes.c_void_p * 4)(*[lv.data_ptr() for lv in out])
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_corr_build_tiled_rows(_ptr(fmaps1), _ptr(fmaps2), _ptr(rows1), _ptr(rows2), ptrs, N, C, H, W,
+                                                    _dtype_code(fmaps1, "fmap"), _ptr(out_slots), _stream(dev)), "corr_build_tiled_rows")
+    return out
+
+
 def corr_pyramid_lookup_tiled(pyramid, coords, channels_last=False, slots=None):
     """radius-3 lookup of all levels of an 8x8-tiled pyramid (see corr_build_tiled); same result as
     corr_pyramid_lookup on the row-major pyramid."""
@@ -860,6 +883,28 @@ def reproject(poses, disps, intrinsics, ii, jj, out=None, baseline=0.0):
             check(_lib.load().pvo_reproject_rig(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj),
                                                 _ptr(coords), _ptr(valid), E, ht, wd, baseline, _stream(dev)), "reproject (stereo)")
     return coords, valid
+
+
+def edge_rows_init(nets, poses, disps, intrinsics, ii, jj, net, target, weight, raw_mask, delta_dy, baseline=0.0):
+    """pvo_edge_rows_init: the state rows of n new edges in one launch - net[e] = nets[ii[e]], target[e] = the reprojection of
+    edge e (reproject's coordinates, bit for bit), zero weight / raw_mask / delta_dy.  nets [F,ht,wd,128] 16-bit frame rows,
+    net [n,ht,wd,128] in the same dtype, the four f32 tensors [n,ht,wd,2]: contiguous (the new rows of the caller's buffers)."""
+    baseline = _baseline(baseline, "edge_rows_init")
+    dev = _dev(nets, poses, disps, intrinsics, ii, jj, net, target, weight, raw_mask, delta_dy)
+    _f32(poses, "poses"); _f32(disps, "disps"); _f32(intrinsics, "intrinsics"); _long(ii, "ii"); _long(jj, "jj")
+    n, ht, wd = ii.shape[0], disps.shape[1], disps.shape[2]
+    for t, name in ((nets, "nets"), (poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj"), (net, "net")):
+        _contig(t, name)
+    if nets.dtype not in (torch.float16, torch.bfloat16) or net.dtype != nets.dtype or tuple(nets.shape[1:]) != (ht, wd, 128) or \
+            tuple(net.shape) != (n, ht, wd, 128) or jj.shape[0] != n or nets.shape[0] != disps.shape[0]:
+        raise PvoHipError("edge_rows_init: nets [F,ht,wd,128] and net [n,ht,wd,128] must be 16-bit tensors of one dtype")
+    for t, name in ((target, "target"), (weight, "weight"), (raw_mask, "raw_mask"), (delta_dy, "delta_dy")):
+        if tuple(t.shape) != (n, ht, wd, 2) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise PvoHipError("edge_rows_init: %s must be a contiguous float32 [n,ht,wd,2] tensor" % name)
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_edge_rows_init(_ptr(nets), _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj), _ptr(net),
+                                             _ptr(target), _ptr(weight), _ptr(raw_mask), _ptr(delta_dy), n, ht, wd, baseline,
+                                             _stream(dev)), "edge_rows_init")
 
 
 # --------------------------------------------------------------------------- bundle adjustment
@@ -1710,13 +1755,15 @@ def _op_workspace(key, dev, nbytes):
 
 
 def update_operator(weights, net, motion, inp=None, P=None, pool=None, coords=None, corr=None, agg=None,
-                    eta_rows=None, want_eta=True, want_upmask=True, net_out=None):
+                    eta_rows=None, want_eta=True, want_upmask=True, net_out=None, static_rows=None):
     """DynamicUpdateModule.forward (droid_net.py:256-314) on the 16-bit inference path as ONE call into libpvo_hip.
 
     weights: PackedWeights.  net, inp [E,128,H,W], motion [E,8,H,W], corr [E,196,H,W]: channels-last 16-bit.
     Correlation features come either from `pool` = (tiled level tensors, slots int32 [E], num_slots) + coords [E,H,W,2]
     f32 (the lookup runs fused with the first encoder layer) or from the sampled tensor `corr`.
     P = (P_zr, P_q): cached static-input terms; None -> computed from `inp` for this call.
+    static_rows (int32 [E], pvo_update_operator_rows): P holds per-keyframe pools [F,256,H,W] / [F,128,H,W] and edge e reads image
+    static_rows[e] (its source frame); the values are not checked.
     agg = (seg_ptr, seg_idx, K) runs GraphAgg; eta_rows = (frame, pos, damping, EP) selects pvo_eta_head's bookkeeping form.
     Returns (net_out, heads [E,8,H,W], eta f32 or None, upmask [K,576,H,W] or None)."""
     _cl(net, "net", 128); _cl(motion, "motion", 8)
@@ -1743,6 +1790,11 @@ def update_operator(weights, net, motion, inp=None, P=None, pool=None, coords=No
     if P is not None:
         P_zr, P_q = P
         _cl(P_zr, "P_zr", 256); _cl(P_q, "P_q", 128)
+        if static_rows is not None and (static_rows.dtype != torch.int32 or static_rows.numel() != E or not static_rows.is_contiguous()
+                                        or static_rows.device != dev):
+            raise PvoHipError("update_operator: static_rows must be a contiguous device int32 [E] tensor")
+    elif static_rows is not None:
+        raise PvoHipError("update_operator: static_rows index the pools P = (P_zr, P_q)")
     elif inp is None:
         raise PvoHipError("update_operator: pass inp or P")
     else:
@@ -1772,8 +1824,12 @@ def update_operator(weights, net, motion, inp=None, P=None, pool=None, coords=No
     else:
         ws = _op_workspace(("op", dev.index), dev, nbytes)
     with torch.cuda.device(dev):
-        check(lib.pvo_update_operator(ctypes.byref(weights.struct), ctypes.byref(a), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                      _stream(dev)), "update_operator")
+        if static_rows is None:
+            check(lib.pvo_update_operator(ctypes.byref(weights.struct), ctypes.byref(a), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                          _stream(dev)), "update_operator")
+        else:
+            check(lib.pvo_update_operator_rows(ctypes.byref(weights.struct), ctypes.byref(a), _ptr(static_rows),
+                                               ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "update_operator (frame rows)")
     return net_out, heads, eta, upmask
 
 
@@ -1944,14 +2000,21 @@ def graph_update_workspace(E, K, R, H, W, max_segments, device):
     return _op_workspace(("up", torch.device(device).index), torch.device(device), n)
 
 
-def graph_update(weights, args, workspace, stereo_baseline=0.0):
+def graph_update(weights, args, workspace, stereo_baseline=0.0, static_rows=None):
     """FactorGraph.update (factor_graph.py:227-307) as ONE call: `args` is a filled _lib.GraphUpdateArgs (the caller -
     pvo_amd.factor_graph - keeps every tensor it points to alive); see include/pvo_hip.h pvo_graph_update.
-    stereo_baseline > 0 (pvo_graph_update_rig): edges (i, i) are stereo edges of a rectified rig with that baseline."""
+    stereo_baseline > 0 (pvo_graph_update_rig): edges (i, i) are stereo edges of a rectified rig with that baseline.
+    static_rows (device int32 [E], pvo_graph_update_rows): args.op.P_zr / P_q are per-keyframe pools read at static_rows[e]."""
     dev = workspace.device
     stereo_baseline = _baseline(stereo_baseline, "graph_update")
     with torch.cuda.device(dev):
-        if stereo_baseline == 0.0:
+        if static_rows is not None:
+            if static_rows.dtype != torch.int32 or static_rows.numel() != args.op.E or static_rows.device != dev:
+                raise PvoHipError("graph_update: static_rows must be a device int32 [E] tensor")
+            check(_lib.load().pvo_graph_update_rows(ctypes.byref(weights.struct), ctypes.byref(args), ctypes.c_void_p(workspace.data_ptr()),
+                                                    workspace.numel(), stereo_baseline, _ptr(static_rows), _stream(dev)),
+                  "graph_update (frame rows)")
+        elif stereo_baseline == 0.0:
             check(_lib.load().pvo_graph_update(ctypes.byref(weights.struct), ctypes.byref(args), ctypes.c_void_p(workspace.data_ptr()),
                                                workspace.numel(), _stream(dev)), "graph_update")
         else:

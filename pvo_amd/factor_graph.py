@@ -79,6 +79,13 @@ class _EdgeRows:
 
     def append(self, rows, n, fill):
         """rows followed by n new rows; fill(dst) writes them (dst = the [n, ...] tail of the live buffer)"""
+        both, dst = self.reserve(rows, n)
+        fill(dst)
+        return both
+
+    def reserve(self, rows, n):
+        """(rows followed by n new rows, the n new rows): the new rows are NOT written - the caller fills them (one kernel for the
+        new rows of several buffers, pvo_edge_rows_init)"""
         E = rows.shape[0]
         if not self.owns(rows) or E + n > self.buf[self.cur].shape[0]:
             other = self.cur ^ 1
@@ -90,8 +97,7 @@ class _EdgeRows:
                 dst[:E].copy_(rows)
             self.cur = other
         b = self.buf[self.cur]
-        fill(b[E:E + n])
-        return b[:E + n]
+        return b[:E + n], b[E:E + n]
 
 
 _CACHE_SERIAL = itertools.count(1)
@@ -133,8 +139,11 @@ class FactorGraph:
         self.fused_glue = True      # run update() as ONE call into libpvo_hip when the operator and the pool support it
         self._cache = {}            # device index tensors derived from the host edge lists; cleared on any edge change
         self._version = 0           # bumped on every edge change
-        self.P_zr = self.P_q = None  # per-edge static-input terms of the ConvGRU (computed once when an edge is added)
-        self._static_by_slot = False  # ... stored [E, ...] in edge order, or by slot in the volume pool ([capacity, ...])
+        # static-input terms of the ConvGRU, one row per KEYFRAME: the video's pools [buffer,C,h,w] (DepthVideo.static_pool), shared by
+        # every graph on the video; an edge reads the row of its source frame
+        self.P_zr = self.P_q = None
+        self._static = None          # the StaticTermPool behind them, and the last of its computations this graph has ordered itself behind
+        self._static_seen = 0
         self.want_upmask = True     # compute GraphAgg's upsampling mask although update() discards it, as the reference does
         try:
             self._autocast = next(update_op.parameters()).dtype == torch.float32
@@ -229,49 +238,54 @@ class FactorGraph:
         if pool_path and self.corr is None:        # resident slot pool: edge changes never move a volume
             base = self.max_factors if 0 < self.max_factors <= 4096 else 96          # (the backend's budget is 'unlimited')
             self.corr = CorrVolumePool(max(base + 32, n + 32), self.ht, self.wd, self.device, self.video.fmaps.dtype)
+        rows_t = None
         if pool_path and isinstance(self.corr, CorrVolumePool):
-            # the new edges' endpoints and the slots their volumes will own: one staged upload
+            # the new edges' endpoints (int64 as the kernels read ii / jj, int32 as the frame tables of the indexed volume build) and
+            # the slots their volumes will own: one staged upload
             from .droid_backends import to_device_packed
             if n > len(self.corr.free):
                 # reserve() is about to grow the pool: its copies run on THIS stream and drop the old tensors, which a pending
                 # side-stream build (two add_factors calls without an update between them) may still be writing
                 self._corr_sync()
-            ii, jj, new_slots = to_device_packed([(ii_l, torch.long), (jj_l, torch.long), (self.corr.reserve(n), torch.int32)],
-                                                 self.device)
+            ii, jj, new_slots, r1, r2 = to_device_packed([(ii_l, torch.long), (jj_l, torch.long), (self.corr.reserve(n), torch.int32),
+                                                          (ii_l, torch.int32), (jj_l, torch.int32)], self.device)
+            rows_t = (r1, r2)
         else:
             both = self._idx(ii_l + jj_l)
             ii, jj, new_slots = both[:n], both[n:], None
-        by_slot = isinstance(self.corr, CorrVolumePool) and self._static_ok()
-        # The new edges' volumes and static GRU terms are first read by the next update's lookup / gates: with everything
-        # by slot (nothing of them is concatenated onto the live state) they are built on a second stream, beside the row
-        # appends, the frame distances and the index uploads of this keyframe; update() waits for them (_corr_sync).
-        side = self._build_stream() if by_slot and self.build_on_side_stream else None
+        by_frame = isinstance(self.corr, CorrVolumePool) and self._static_ok()
+        # The static GRU terms live per keyframe in pools on the video (allocated here, on this stream, on first use); a row is
+        # computed when an edge first needs its frame - in tracking one frame per keyframe, for re-added edges none.
+        static = self.video.static_pool(self.update_op.packed_weights(self._op_dtype()), self._op_dtype()) if by_frame else None
+        # The new edges' volumes and missing static rows are first read by the next update's lookup / gates: nothing of them is
+        # concatenated onto the live state, so they are built on a second stream, beside the row kernel, the frame distances and the
+        # index uploads of this keyframe; update() waits for them (_corr_sync).
+        side = self._build_stream() if by_frame and self.build_on_side_stream else None
         if side is not None:
             side.wait_stream(torch.cuda.current_stream(self.device))
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             if self.corr_impl == "volume":
-                if pool_path:
+                if static is not None:
+                    if static is not self._static:
+                        self._static, self._static_seen = static, 0
+                    self._static_sync()            # (rows another graph of this video computed: normally nothing to wait for)
+                    if static.ensure(ii_l):        # ... our own are ordered by this stream and the event below
+                        self._static_seen = static.ready_serial
+                    self.P_zr, self.P_q = static.P_zr, static.P_q
+                right = self._rig_baseline() != 0.0 and any(i == j for i, j in zip(ii_l, jj_l))
+                if pool_path and rows_t is not None and self.corr.tiled and not right and self.video.fmaps.is_contiguous():
+                    # edge k correlates frames ii[k] and jj[k] of the video's own buffer: no gathered copies
+                    self.corr.add(self.video.fmaps, self.video.fmaps, new_slots, rows=rows_t)
+                elif pool_path:     # (a stereo video's right-view edges substitute fmaps_right: the gathered call)
                     self.corr.add(self.video.fmaps[ii], self._fmap2(ii_l, jj_l, jj), new_slots)
                 else:
                     corr = CorrBlock(self.video.fmaps[ii][None], self._fmap2(ii_l, jj_l, jj)[None], channels_last=True)
                     self.corr = corr if self.corr is None else self.corr.cat(corr)
-                inp = self._frame_rows(self.video.inps, ii)[None]
-                if not by_slot:
-                    self.inp = self._cat_cl(self.inp, inp)   # stored channels-last once, so no update re-lays it out
-                if self._static_ok():
-                    # conv(W[:, inp], inp) of the ConvGRU's gate / candidate convolutions, once per edge (inp never changes)
-                    pz, pq = self.update_op.static_terms(self._cl5(inp)[0], self._op_dtype())
-                    if by_slot:
-                        # ... kept in the slot the edge's volume owns: like the volume, never moved when edges come and go
-                        # (as [E, ...] tensors they were 85 of the 141 MB gathered and concatenated per keyframe; `inp`
-                        # itself is video.inps[ii], materialised only if the PyTorch formulation of the operator asks)
-                        self.P_zr, self.P_q = self.corr.put("P_zr", pz), self.corr.put("P_q", pq)
-                        self._static_by_slot = True
-                    else:
-                        self.P_zr = self._cat_cl(self.P_zr, pz[None])
-                        self.P_q = self._cat_cl(self.P_q, pq[None])
+                if not by_frame:
+                    # (`inp` itself is video.inps[ii]: kept per edge only where the PyTorch formulation of the operator reads it)
+                    self.inp = self._cat_cl(self.inp, self._frame_rows(self.video.inps, ii)[None])   # stored channels-last once, so no update re-lays it out
         if side is not None:
-            for t in (ii, jj, new_slots):
+            for t in (ii, jj, new_slots) + (rows_t or ()):
                 t.record_stream(side)
             self._corr_ready = torch.cuda.Event()
             self._corr_ready.record(side)
@@ -283,13 +297,13 @@ class FactorGraph:
         if self.net is None:
             self.net = self._net_view(torch.empty((0,) + ((self.ht, self.wd, 128) if cl else (128, self.ht, self.wd)),
                                                   dtype=nets.dtype, device=self.device))
-        if cl and nets.permute(0, 2, 3, 1).is_contiguous() and self.net.dtype == nets.dtype:
+        nets_cl = cl and nets.permute(0, 2, 3, 1).is_contiguous() and self.net.dtype == nets.dtype
+        if nets_cl:
             fill_net = lambda dst: torch.index_select(nets.permute(0, 2, 3, 1), 0, ii, out=dst)      # no temporary
         elif cl:
             fill_net = lambda dst: dst.copy_(nets[ii].permute(0, 2, 3, 1))
         else:
             fill_net = lambda dst: dst.copy_(nets[ii])
-        self.net = self._net_view(self._edge_rows("net").append(self._net_rows(), n, fill_net))
 
         def fill_target(dst):
             if hasattr(self.video, "reproject_into"):
@@ -298,10 +312,24 @@ class FactorGraph:
                 target, _ = self.video.reproject(ii, jj)
                 dst.copy_(target[0])
         zero = lambda dst: dst.zero_()
-        self.target_cam = self._edge_rows("target_cam").append(self.target_cam[0], n, fill_target)[None]
-        self.weight = self._edge_rows("weight").append(self.weight[0], n, zero)[None]
-        self.raw_mask = self._edge_rows("raw_mask").append(self.raw_mask[0], n, zero)[None]
-        self.delta_dy = self._edge_rows("delta_dy").append(self.delta_dy[0], n, zero)[None]
+        fills = (("net", fill_net), ("target_cam", fill_target), ("weight", zero), ("raw_mask", zero), ("delta_dy", zero))
+        new = {}
+        for name, _ in fills:
+            rows = self._net_rows() if name == "net" else getattr(self, name)[0]
+            both, new[name] = self._edge_rows(name).reserve(rows, n)
+            setattr(self, name, self._net_view(both) if name == "net" else both[None])
+        v = self.video
+        f32x2 = all(new[k].dtype == torch.float32 and tuple(new[k].shape[1:]) == (self.ht, self.wd, 2)
+                    for k in ("target_cam", "weight", "raw_mask", "delta_dy"))
+        if nets_cl and f32x2 and nets.dtype in (torch.float16, torch.bfloat16) and hasattr(v, "reproject_into") and \
+                all(t.dtype == torch.float32 and t.is_contiguous() for t in (v.poses, v.disps, v.intrinsics)) and n <= 65535:
+            # the five buffers' new rows in ONE launch: the hidden-state rows of the source frames, the edges' reprojection, three zero fills
+            from . import droid_backends as db
+            db.edge_rows_init(nets.permute(0, 2, 3, 1), v.poses, v.disps, v.intrinsics, ii, jj, new["net"], new["target_cam"],
+                              new["weight"], new["raw_mask"], new["delta_dy"], baseline=self._rig_baseline())
+        else:               # (another dtype or layout, or a video of another class: one fill per tensor)
+            for name, fill in fills:
+                fill(new[name])
         if getattr(self.video, "segm_filter", True):     # (without the panoptic filter nothing reads them: `segm` gathers on demand)
             segms = self.video.segms
             if self._segm is None:
@@ -318,6 +346,14 @@ class FactorGraph:
         with its two update streams serialised (lookup 66 -> 139 us)"""
         from .droid_backends import side_stream
         return side_stream(self.device)
+
+    def _static_sync(self):
+        """order the current stream behind the latest computation in the video's static-term pool that this graph did not make itself
+        (a second graph on the same video; no host wait, and nothing at all while this graph is the only one computing)"""
+        st = self._static
+        if st is not None and st.ready is not None and self._static_seen != st.ready_serial:
+            torch.cuda.current_stream(self.device).wait_event(st.ready)
+            self._static_seen = st.ready_serial
 
     def _corr_sync(self):
         """order the current stream behind the side-stream build of the newest edges (no host wait)"""
@@ -430,8 +466,6 @@ class FactorGraph:
             self.net = self._net_view(self._edge_rows("net").keep(self._net_rows(), keep_l, keep_t))
         if self._inp is not None:
             self._inp = self._take_cl(self._inp, keep_t())
-        if self.P_zr is not None and not self._static_by_slot:
-            self.P_zr, self.P_q = self._take_cl(self.P_zr, keep_t()), self._take_cl(self.P_q, keep_t())
         if self._segm is not None:
             self._segm = self._edge_rows("segm").keep(self._segm[0], keep_l, keep_t)[None]
         for name in ("target_cam", "weight", "raw_mask", "delta_dy"):
@@ -444,8 +478,7 @@ class FactorGraph:
 
     def clear_edges(self):
         self.rm_factors([True] * len(self._ii_h))
-        self.net = self.inp = self.P_zr = self.P_q = None
-        self._static_by_slot = False
+        self.net = self.inp = self.P_zr = self.P_q = None      # (the static-term pools stay with the video)
 
     def rm_keyframe(self, ix):
         """drop keyframe ix and every edge touching it (factor_graph.py:202-225)"""
@@ -457,7 +490,13 @@ class FactorGraph:
         # (uncertainty: the variances and the pose covariance block of a keyframe are its own)
         unc = tuple(b for b in (getattr(v, n, None) for n in ("disps_var_cond", "disps_var_pose", "poses_cov")) if b is not None)
         raw = getattr(v, "segms_raw", None)                             # (the raw panoptic ids are the keyframe's, segm_filter or not)
-        for buf in (v.poses, v.disps, v.intrinsics, v.nets, v.inps, v.fmaps) + ((v.segms,) if v.segm_filter else ()) + \
+        if hasattr(v, "shift_inps"):                                    # (stamped: the static-term pool's rows move with the frame)
+            v.shift_inps(ix)
+            if self._static is not None and self._static is getattr(v, "_static", None):
+                self._static_seen = self._static.ready_serial           # (this stream made the copy)
+        else:
+            v.inps[ix] = v.inps[ix + 1].clone()
+        for buf in (v.poses, v.disps, v.intrinsics, v.nets, v.fmaps) + ((v.segms,) if v.segm_filter else ()) + \
                 ((up,) if self.upsample and up is not None else ()) + ((sens,) if sens is not None else ()) + \
                 ((right,) if right is not None else ()) + unc + ((raw,) if raw is not None else ()):
             buf[ix] = buf[ix + 1].clone()
@@ -800,6 +839,8 @@ class FactorGraph:
                      (seg_idx, torch.int32), (self.corr.slots, torch.int32), ([k for k, f in enumerate(m_l) if f], torch.long)]
             if self._index_dirty:
                 parts += [(self._ii_h, torch.long), (self._jj_h, torch.long), (self._age_h, torch.long)]
+            static_at = len(parts)
+            parts.append((self._ii_h, torch.int32))                # the row of each edge's static terms in the frame pools: its source frame
             if self.upsample:
                 parts.append((src, torch.long))                    # the frame of each aggregation row: rows of disps / disps_up
             up = to_device_packed(parts, self.device)
@@ -825,7 +866,7 @@ class FactorGraph:
             st = self._cache["fused"] = dict(
                 key=key, n_in=n_in, target_ba=target_ba, weight_ba=weight_ba, ii_ba=ba["ii"], jj_ba=ba["jj"], frames=frames_t,
                 pos=pos_t, seg=seg, ba=ba, R=len(rows), S=S, ii=self.ii.contiguous(), jj=self.jj.contiguous(),
-                slots=self.corr.slots_tensor(),
+                slots=self.corr.slots_tensor(), static_rows=up[static_at],
                 # (labels of another integer type - add_factors keeps a caller's dtype - are converted: the kernel reads int32)
                 segm=self.segm[0, :, 0].to(torch.int32).contiguous() if vote else None,
                 full_flow=torch.empty(1, E, ht, wd, 2, device=self.device),
@@ -866,7 +907,7 @@ class FactorGraph:
             self.net = net[None]
         a.op.net = a.op.net_out = net.data_ptr()
         a.op.P_zr, a.op.P_q = self.P_zr.data_ptr(), self.P_q.data_ptr()
-        a.op.static_by_slot = 1 if self._static_by_slot else 0
+        a.op.static_by_slot = 0                 # (frame pools: read through the table handed to pvo_graph_update_rows)
         a.op.EP = float(EP)
         a.target, a.delta_dy, a.raw_mask = self.target_cam.data_ptr(), self.delta_dy.data_ptr(), self.raw_mask.data_ptr()
         if tuple(self.weight.shape) != (1, E, ht, wd, 2):           # (a caller's own weights of another shape are only an input)
@@ -884,7 +925,7 @@ class FactorGraph:
         a.context_ahead = 1
         a.context_ready = 1 if getattr(self, "_ctx_token", None) == token else 0
         # (stereo: the baseline goes to the in-update reprojection and the BA plan - pvo_graph_update_rig; any other video makes today's call)
-        db.graph_update(weights, a, st["ws"], **({"stereo_baseline": rig} if rig != 0.0 else {}))
+        db.graph_update(weights, a, st["ws"], static_rows=st["static_rows"], **({"stereo_baseline": rig} if rig != 0.0 else {}))
         self._ctx_token = token
         if sharded is not None:
             # edge sharding: assembly + Schur on this rank's edges, ONE integer all-reduce of the reduced pose system per
@@ -899,9 +940,9 @@ class FactorGraph:
 
     @property
     def inp(self):
-        """per-edge context features (factor_graph.py:33).  With the static terms kept by slot nothing on the native path
-        reads them after an edge is created: they are video.inps[ii], gathered on demand for the PyTorch formulation."""
-        if self._inp is None and self._static_by_slot and self._ii_h:
+        """per-edge context features (factor_graph.py:33).  With the static terms kept per keyframe nothing on the native path
+        reads them: they are video.inps[ii], gathered on demand for the PyTorch formulation."""
+        if self._inp is None and self.P_zr is not None and self._ii_h:
             return self._cached("inp", lambda: self._cl5(self.video.inps[self.ii][None]))
         return self._inp
 

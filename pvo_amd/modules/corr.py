@@ -171,8 +171,6 @@ class CorrVolumePool:
         self.slots = []                       # slot of each active edge, in edge order
         self._slots_t = None
         self.device = device
-        self.extra = {}                       # other per-edge data that never changes over an edge's life, by slot (`put`)
-        self._last = None                     # slots handed out by the most recent add(), as a device tensor
         self._reserved = None
 
     def __len__(self):
@@ -185,10 +183,12 @@ class CorrVolumePool:
         self._reserved = [self.free.pop() for _ in range(n)]
         return self._reserved
 
-    def add(self, fmap1, fmap2, slots_t=None):
+    def add(self, fmap1, fmap2, slots_t=None, rows=None):
         """fmap1, fmap2: [n,H,W,C] channels-last features of the new edges (appended in order).  slots_t: device copy of
-        the slots reserve(n) returned (a caller that uploads other index tables anyway packs them into the same copy)"""
-        n = fmap1.shape[0]
+        the slots reserve(n) returned (a caller that uploads other index tables anyway packs them into the same copy).
+        rows = (rows1, rows2), device int32 [n] (tiled pools): fmap1 / fmap2 are whole FRAME buffers [F,H,W,C] and new edge k
+        correlates frame rows1[k] of the first with frame rows2[k] of the second - no gathered copies of the features"""
+        n = fmap1.shape[0] if rows is None else rows[0].numel()
         if slots_t is None:
             new = self.reserve(n)
             st = db.to_device_async(new, torch.int32, self.device)
@@ -197,24 +197,16 @@ class CorrVolumePool:
             if len(new) != n or st.numel() != n or st.dtype != torch.int32:
                 raise ValueError("CorrVolumePool.add: slots_t does not match the slots of the last reserve()")
         self._reserved = None
-        if self.tiled:
+        if rows is not None:
+            if not self.tiled:
+                raise ValueError("CorrVolumePool.add: frame rows need a tiled pool")
+            db.corr_build_tiled_rows(fmap1, fmap2, rows[0], rows[1], self.levels, st)
+        elif self.tiled:
             db.corr_build_tiled(fmap1.contiguous(), fmap2.contiguous(), self.levels, st)
         else:
             db.corr_build(fmap1.contiguous(), fmap2.contiguous(), self.num_levels, channels_last=True, out=self.levels, out_slots=st)
         self.slots += new
         self._slots_t = None
-        self._last = st
-
-    def put(self, name, rows):
-        """store `rows` [n, ...] (one row per edge of the most recent add(), same order) in the slots those edges own.
-        The factor graph keeps the ConvGRU's static-input terms here: written once per edge, read by slot
-        (pvo_gru_conv_gates' p_slots), never gathered or concatenated when the edge set changes."""
-        t = self.extra.get(name)
-        if t is None:
-            t = self.extra[name] = torch.empty((self.capacity,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device,
-                                               memory_format=torch.channels_last if rows.dim() == 4 and rows.is_contiguous(memory_format=torch.channels_last) else torch.contiguous_format)
-        t.index_copy_(0, self._last.long(), rows)
-        return t
 
     def _grow(self, need):
         """more edges than slots (the reference's pyramid simply grows, e.g. a long --warmup initialisation): move to
@@ -226,12 +218,6 @@ class CorrVolumePool:
             new[:self.capacity].copy_(lv)
             levels.append(new)
         self.levels = levels
-        for name, t in list(self.extra.items()):
-            cl = t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
-            new = torch.empty((cap,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device,
-                              memory_format=torch.channels_last if cl else torch.contiguous_format)
-            new[:self.capacity].copy_(t)
-            self.extra[name] = new
         self.free = list(range(cap - 1, self.capacity - 1, -1)) + self.free
         self.capacity = cap
 

@@ -249,7 +249,8 @@ class DynamicUpdateModule(nn.Module):
 
     def static_terms(self, inp, dt=None):
         """the part of the ConvGRU's gate / candidate convolutions that only sees `inp` (constant over an edge's life):
-        (P_zr [E,256,H,W], P_q [E,128,H,W]) channels-last; a factor graph computes them once per edge"""
+        (P_zr [E,256,H,W], P_q [E,128,H,W]) channels-last.  A factor graph keeps them once per KEYFRAME, in the video's pools
+        (DepthVideo.static_pool: the same two convolutions written straight into the pool rows)"""
         from .. import droid_backends as db
         dt = dt or inp.dtype
         pw = self.packed_weights(dt)
