@@ -105,7 +105,8 @@ enum {
   PVO_KNOB_HEADS_GATHER_FLAT = 1, /* 1: pvo_heads_gather without its LDS-tiled form */
   PVO_KNOB_NO_RIDERS = 2,         /* 1: pvo_graph_update computes the upsampling mask and the next gate context as launches of their own */
   PVO_KNOB_POST_SEPARATE = 3,     /* 1: pvo_graph_update runs pvo_graph_post as a launch of its own instead of as the epilogue of the heads' gather */
-  PVO_KNOB_COUNT = 4
+  PVO_KNOB_EDGE_BLOCKS = 4,       /* the update operator's gates -> candidate -> heads per block of edges on two streams (bit-identical to the whole launches; E >= 3 and not PVO_OP_SINGLE_STREAM): 0 shipped choice (value 6 where the gate launch has more workgroups than two per compute unit, off below) | 1 off | 2 + s + 2 p + 4 g: leading block = E/2 (s = 0) or E/3 (s = 1) edges on the launch stream, the trailing block on a stream of the library's of the same (p = 0) or the lowest (p = 1) priority, GraphAgg.conv1 whole (g = 0) or per block (g = 1) */
+  PVO_KNOB_COUNT = 5
 };
 int pvo_debug_config(int knob, int value);
 int pvo_knob(int knob); /* current value (0 for an unknown knob) */

@@ -13,6 +13,7 @@
 #include "operand16.h"
 #include <type_traits>
 #include "glo_tile.h"
+#include "conv_range.h"
 #include <stdlib.h>
 
 namespace {
@@ -871,10 +872,13 @@ extern "C" int pvo_conv3x3_c128(const void* x, const void* w_taps, const float* 
   });
 }
 
+// Edges [e0, e1) of an E-edge call: every per-edge operand is moved to edge e0 and grid.z = e1 - e0, so a workgroup computes what
+// workgroup (.., .., e0 + blockIdx.z) of the whole launch computes, from the same operands in the same order (update_exec.hip
+// launches the three stages of the update per block of edges).  The static term's pool base stays: only its table moves.
 static int launch_big(const void* x, const void* w_taps, const float* bias, void* y,
                       int E, int H, int W, int Cin, int Cout, int relu, int ystride, int yoff, int dtype, void* stream,
-                      const BigEpi& ep) {
-  if (E < 0 || H < 0 || W < 0) return PVO_EINVAL;
+                      const BigEpi& ep_all, int e0, int e1) {
+  if (E < 0 || H < 0 || W < 0 || e0 < 0 || e1 < e0 || e1 > E) return PVO_EINVAL;
   if (Cin <= 0 || (Cin & 31) || Cout <= 0 || (Cout & 127)) return PVO_EUNSUPPORTED;
   if (ystride == 0) ystride = Cout;
   if (ystride < yoff + Cout || yoff < 0 || (ystride & 7) || (yoff & 7)) return PVO_EINVAL;
@@ -882,13 +886,27 @@ static int launch_big(const void* x, const void* w_taps, const float* bias, void
   if (!x || !w_taps || !y || E > 65535) return PVO_EINVAL;
   if (pvo_misaligned16(x, w_taps, y)) return PVO_EINVAL;
   if (static_cast<long long>(H) * W * Cin > 0x7fffffffLL) return PVO_EUNSUPPORTED;
+  if (e1 == e0) return PVO_OK;
   hipStream_t st = pvo_stream(stream);
   const int ntx = (W + kBT - 1) / kBT;
   const size_t lds = kBLds;
-  dim3 grid(ntx * (Cout / 128), (H + kBT - 1) / kBT, E);
-  const uint16_t* xp = static_cast<const uint16_t*>(x);
+  dim3 grid(ntx * (Cout / 128), (H + kBT - 1) / kBT, e1 - e0);
+  const size_t px0 = static_cast<size_t>(e0) * H * W;      // pixels in front of edge e0
+  BigEpi ep = ep_all;
+  if (ep.g) ep.g += static_cast<size_t>(e0) * 384;
+  if (ep.p_slots) ep.p_slots += e0;
+  else if (ep.P) ep.P += px0 * (ep.mode == 1 ? 256 : 128);
+  if (ep.net) ep.net += px0 * 128;
+  if (ep.Z) ep.Z += px0 * 128;
+  if (ep.y2) ep.y2 += px0 * 128;
+  for (int i = 0; i < ep.nseg; ++i) ep.seg_p[i] += px0 * ep.seg_stride[i];
+  if (ep.z) ep.z += px0 * (Cout >> 7) * 18;
+  const uint16_t* xp = static_cast<const uint16_t*>(x) + (ep.nseg > 0 ? 0 : px0 * Cin);      // (segmented input: x is not read)
   const uint16_t* wp = static_cast<const uint16_t*>(w_taps);
-  uint16_t* yp = static_cast<uint16_t*>(y);
+  // (the GRU epilogues write [rows,128] tensors - Z and y2 = r * net from the 256 gate channels - whatever ystride says; mode 3
+  // writes ep.z and not y)
+  const size_t ypitch = (ep.mode == 1 || ep.mode == 2) ? 128 : ep.mode == 3 ? 0 : static_cast<size_t>(ystride);
+  uint16_t* yp = static_cast<uint16_t*>(y) + px0 * ypitch;
   return pvo_dispatch16(dtype, [&](auto tag) -> int {
     using T = decltype(tag);
     if (ep.mode == 3) {                                     // the output heads' fused second stage
@@ -905,15 +923,25 @@ static int launch_big(const void* x, const void* w_taps, const float* bias, void
 
 extern "C" int pvo_conv3x3(const void* x, const void* w_taps, const float* bias, void* y,
                            int E, int H, int W, int Cin, int Cout, int relu, int ystride, int yoff, int dtype, void* stream) {
-  return launch_big(x, w_taps, bias, y, E, H, W, Cin, Cout, relu, ystride, yoff, dtype, stream, BigEpi{});
+  return launch_big(x, w_taps, bias, y, E, H, W, Cin, Cout, relu, ystride, yoff, dtype, stream, BigEpi{}, 0, E);
+}
+
+int pvo_internal_conv3x3_range(const void* x, const void* w_taps, const float* bias, void* y, int E, int e0, int e1, int H, int W,
+                               int Cin, int Cout, int relu, int ystride, int yoff, int dtype, void* stream) {
+  return launch_big(x, w_taps, bias, y, E, H, W, Cin, Cout, relu, ystride, yoff, dtype, stream, BigEpi{}, e0, e1);
+}
+
+int pvo_internal_conv3x3_heads_range(const void* x, const void* w1_taps, const float* bias1, const void* w2_frags, float* z,
+                                     int E, int e0, int e1, int H, int W, int dtype, void* stream) {
+  if (!bias1 || !w2_frags || !z || pvo_misaligned16(w2_frags)) return PVO_EINVAL;
+  BigEpi ep{};
+  ep.mode = 3; ep.w2f = static_cast<const uint16_t*>(w2_frags); ep.z = z;
+  return launch_big(x, w1_taps, bias1, z, E, H, W, 128, 512, 1, 0, 0, dtype, stream, ep, e0, e1);      // (y is not written in this mode)
 }
 
 extern "C" int pvo_conv3x3_heads(const void* x, const void* w1_taps, const float* bias1, const void* w2_frags, float* z,
                                  int E, int H, int W, int dtype, void* stream) {
-  if (!bias1 || !w2_frags || !z || pvo_misaligned16(w2_frags)) return PVO_EINVAL;
-  BigEpi ep{};
-  ep.mode = 3; ep.w2f = static_cast<const uint16_t*>(w2_frags); ep.z = z;
-  return launch_big(x, w1_taps, bias1, z, E, H, W, 128, 512, 1, 0, 0, dtype, stream, ep);      // (y is not written in this mode)
+  return pvo_internal_conv3x3_heads_range(x, w1_taps, bias1, w2_frags, z, E, 0, E, H, W, dtype, stream);
 }
 
 // the ConvGRU input [first(128) | cf(cf_channels)] as two segments: `first` = net (gates) or r*net (candidate), `cf` = the
@@ -928,8 +956,9 @@ static int seg_setup(BigEpi& ep, const void* first, const void* cf, int cf_chann
   return PVO_OK;
 }
 
-extern "C" int pvo_gru_conv_gates(const void* net, const void* cf, int cf_channels, const void* w_taps, const float* g,
-                                  const void* P_zr, const int* p_slots, void* Z, void* RN, int E, int H, int W, int dtype, void* stream) {
+int pvo_internal_gru_conv_gates_range(const void* net, const void* cf, int cf_channels, const void* w_taps, const float* g,
+                                      const void* P_zr, const int* p_slots, void* Z, void* RN, int E, int e0, int e1, int H, int W,
+                                      int dtype, void* stream) {
   if (!g || !P_zr || !RN) return PVO_EINVAL;
   if (pvo_misaligned16(P_zr, RN)) return PVO_EINVAL;
   BigEpi ep{};
@@ -937,12 +966,17 @@ extern "C" int pvo_gru_conv_gates(const void* net, const void* cf, int cf_channe
   if (rc != PVO_OK) return rc;
   ep.mode = 1; ep.g = g; ep.P = static_cast<const uint16_t*>(P_zr); ep.p_slots = p_slots; ep.net = static_cast<const uint16_t*>(net);
   ep.y2 = static_cast<uint16_t*>(RN);
-  return launch_big(net, w_taps, nullptr, Z, E, H, W, 128 + cf_channels, 256, 0, 0, 0, dtype, stream, ep);
+  return launch_big(net, w_taps, nullptr, Z, E, H, W, 128 + cf_channels, 256, 0, 0, 0, dtype, stream, ep, e0, e1);
 }
 
-extern "C" int pvo_gru_conv_candidate(const void* RN, const void* cf, int cf_channels, const void* w_taps, const float* g,
-                                      const void* P_q, const int* p_slots, const void* Z, const void* net, void* net_out,
-                                      int E, int H, int W, int dtype, void* stream) {
+extern "C" int pvo_gru_conv_gates(const void* net, const void* cf, int cf_channels, const void* w_taps, const float* g,
+                                  const void* P_zr, const int* p_slots, void* Z, void* RN, int E, int H, int W, int dtype, void* stream) {
+  return pvo_internal_gru_conv_gates_range(net, cf, cf_channels, w_taps, g, P_zr, p_slots, Z, RN, E, 0, E, H, W, dtype, stream);
+}
+
+int pvo_internal_gru_conv_candidate_range(const void* RN, const void* cf, int cf_channels, const void* w_taps, const float* g,
+                                          const void* P_q, const int* p_slots, const void* Z, const void* net, void* net_out,
+                                          int E, int e0, int e1, int H, int W, int dtype, void* stream) {
   if (!g || !P_q || !net || !Z) return PVO_EINVAL;
   if (pvo_misaligned16(P_q, net, Z)) return PVO_EINVAL;
   BigEpi ep{};
@@ -950,5 +984,11 @@ extern "C" int pvo_gru_conv_candidate(const void* RN, const void* cf, int cf_cha
   if (rc != PVO_OK) return rc;
   ep.mode = 2; ep.g = g; ep.P = static_cast<const uint16_t*>(P_q); ep.p_slots = p_slots; ep.net = static_cast<const uint16_t*>(net);
   ep.Z = static_cast<const uint16_t*>(Z);
-  return launch_big(RN, w_taps, nullptr, net_out, E, H, W, 128 + cf_channels, 128, 0, 0, 0, dtype, stream, ep);
+  return launch_big(RN, w_taps, nullptr, net_out, E, H, W, 128 + cf_channels, 128, 0, 0, 0, dtype, stream, ep, e0, e1);
+}
+
+extern "C" int pvo_gru_conv_candidate(const void* RN, const void* cf, int cf_channels, const void* w_taps, const float* g,
+                                      const void* P_q, const int* p_slots, const void* Z, const void* net, void* net_out,
+                                      int E, int H, int W, int dtype, void* stream) {
+  return pvo_internal_gru_conv_candidate_range(RN, cf, cf_channels, w_taps, g, P_q, p_slots, Z, net, net_out, E, 0, E, H, W, dtype, stream);
 }

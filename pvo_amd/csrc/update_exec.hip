@@ -13,6 +13,7 @@
 //                         (panoptic vote) -> mask / weight glue -> eta / damping -> dense BA x itrs -> depth clamp
 #include "common.h"
 #include "graph_post.h"
+#include "conv_range.h"
 #include <stdlib.h>
 
 // operator_small.hip: pvo_segment_hist for two tables carved from one workspace (one fill for both; not part of the C ABI)
@@ -52,6 +53,58 @@ SideCtx* side_ctx() {
     c.ok = true;
   }
   return &c;
+}
+
+// The edge-blocked schedule's additional stream (run_operator): the trailing block of edges runs its gates -> candidate -> heads
+// on it beside the leading block's on the launch stream.  Two are kept per device and created on first use - one of the launch
+// stream's default priority, one of the LOWEST (the knob then makes the leading block's stream the higher-priority one) - and
+// every fork / join of the schedule has an event of its own.  (Round 21 also measured the leading block on a stream of the
+// HIGHEST priority with the trailing one on the launch stream, so that the join in front of the gather is already satisfied
+// when the launch stream reaches it: no better than the shipped choice, not kept - DESIGN.md section 5.)
+struct WaveCtx { hipStream_t s[2]; bool has[2]; hipEvent_t fork, cand0, cand1, join; bool events; };
+WaveCtx g_wave_ctx[64] = {};
+WaveCtx* wave_ctx(bool low) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+  WaveCtx& c = g_wave_ctx[dev];
+  if (!c.events) {
+    for (hipEvent_t* e : {&c.fork, &c.cand0, &c.cand1, &c.join})
+      if (hipEventCreateWithFlags(e, g_event_flags) != hipSuccess) return nullptr;
+    c.events = true;
+  }
+  if (!c.has[low]) {
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return nullptr;
+    if (hipStreamCreateWithPriority(&c.s[low], hipStreamNonBlocking, low ? least : 0) != hipSuccess) return nullptr;
+    c.has[low] = true;
+  }
+  return &c;
+}
+
+// PVO_KNOB_EDGE_BLOCKS decoded: lead = edges of the leading block (0: the schedule is off)
+struct EdgeBlocks { int lead; bool low, agg; };
+// What knob value 0 means: equal halves, GraphAgg.conv1 per block, where the gate launch has more
+// workgroups than the device holds at once (two per compute unit) - the schedule recovers the partly filled rounds of launches
+// that take several, and a launch that fits one round has none to recover, only four events more to pay for.
+constexpr int kEdgeBlocksShipped = 2 + 4;
+constexpr int kMinBlockedEdges = 3;        // below it a 1/3 block is empty
+int resident_conv_workgroups() {
+  static int slots[64] = {};
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (!slots[dev] && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) slots[dev] = 2 * cus;
+  return slots[dev];
+}
+EdgeBlocks edge_blocks(int E, int H, int W, unsigned flags) {
+  int v = pvo_knob(PVO_KNOB_EDGE_BLOCKS);
+  if (v == 0) {
+    const long long gate_workgroups = 2LL * ((W + 15) / 16) * ((H + 15) / 16) * E;
+    const int slots = resident_conv_workgroups();
+    v = (slots > 0 && gate_workgroups > slots) ? kEdgeBlocksShipped : 1;
+  }
+  if (v < 2 || v > 9 || E < kMinBlockedEdges || (flags & PVO_OP_SINGLE_STREAM)) return {0, false, false};
+  v -= 2;
+  return {(v & 1) ? E / 3 : E / 2, (v & 2) != 0, (v & 4) != 0};
 }
 
 size_t al(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
@@ -153,8 +206,9 @@ struct MotionJob {           // pvo_graph_update's motion features: only the flo
 };
 
 // static_rows (int32 [E] or nullptr): a->P_zr / a->P_q are per-keyframe pools and edge e reads image static_rows[e] (its source frame)
+// *ps: the table that names each edge's image of the static term (nullptr: edge e reads image e)
 int run_trunk(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, const void** P_zr, const void** P_q,
-              const MotionJob* mj, bool context_ready = false, const int* static_rows = nullptr) {
+              const int** ps, const MotionJob* mj, bool context_ready = false, const int* static_rows = nullptr) {
   const int E = a->E, H = a->H, W = a->W, dt = w->dtype;
   const long long rows = static_cast<long long>(E) * H * W;
   hipStream_t st = pvo_stream(stream);
@@ -206,19 +260,29 @@ int run_trunk(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, 
     *P_zr = b.P_zr; *P_q = b.P_q;
   }
   if (sc && hipStreamWaitEvent(st, sc->join, 0) != hipSuccess) return PVO_ELAUNCH;
-  probe_mark(PVO_STAGE_GATES, 0, stream);
   // the image of each edge's static term: its source frame's row of a per-keyframe pool (static_rows), its volume's slot, or e
   const bool cached = a->P_zr && a->P_q;
   if (static_rows && !cached) return PVO_EINVAL;
-  const int* ps = static_rows ? static_rows : (a->static_by_slot && cached) ? a->slots : nullptr;
+  *ps = static_rows ? static_rows : (a->static_by_slot && cached) ? a->slots : nullptr;
   if (!static_rows && a->static_by_slot && !a->slots) return PVO_EINVAL;
-  RUN(pvo_gru_conv_gates(a->net, b.CF, 192, w->zr_w, b.g, *P_zr, ps, b.Z, b.RN, E, H, W, dt, stream));
-  probe_mark(PVO_STAGE_GATES, 1, stream);
-  probe_mark(PVO_STAGE_CANDIDATE, 0, stream);
-  RUN(pvo_gru_conv_candidate(b.RN, b.CF, 192, w->q_w, b.g, *P_q, ps, b.Z, a->net, a->net_out, E, H, W, dt, stream));
-  probe_mark(PVO_STAGE_CANDIDATE, 1, stream);
   return PVO_OK;
 }
+
+// the ConvGRU's two convolutions for edges [e0, e1): gates -> candidate, the new hidden state in a->net_out.  The probe marks
+// (marks = true) go on `stream` around what is launched HERE: with the edge-blocked schedule on, the leading block only.
+int run_gru(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, const void* P_zr, const void* P_q,
+            const int* ps, int e0, int e1, bool marks) {
+  const int E = a->E, H = a->H, W = a->W, dt = w->dtype;
+  if (marks) probe_mark(PVO_STAGE_GATES, 0, stream);
+  RUN(pvo_internal_gru_conv_gates_range(a->net, b.CF, 192, w->zr_w, b.g, P_zr, ps, b.Z, b.RN, E, e0, e1, H, W, dt, stream));
+  if (marks) probe_mark(PVO_STAGE_GATES, 1, stream);
+  if (marks) probe_mark(PVO_STAGE_CANDIDATE, 0, stream);
+  RUN(pvo_internal_gru_conv_candidate_range(b.RN, b.CF, 192, w->q_w, b.g, P_q, ps, b.Z, a->net, a->net_out, E, e0, e1, H, W, dt, stream));
+  if (marks) probe_mark(PVO_STAGE_CANDIDATE, 1, stream);
+  return PVO_OK;
+}
+
+int run_heads_gather(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, const GraphPostArgs* post, int* post_fused);
 
 // post != nullptr: the graph update's mask / target / weight arithmetic (pvo_graph_post without the panoptic vote) runs as the
 // gather's epilogue where the gather's tiled form applies; *post_fused says whether it did
@@ -227,6 +291,11 @@ int run_heads(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, 
   const int E = a->E, H = a->H, W = a->W, dt = w->dtype;
   // (b.h1 holds z [E,H,W,4,18] f32: the hidden tensor itself stays in the first launch's LDS)
   RUN(pvo_conv3x3_heads(a->net_out, w->heads1_w, w->heads1_b, w->heads2_w, reinterpret_cast<float*>(b.h1), E, H, W, dt, stream));
+  return run_heads_gather(w, a, b, stream, post, post_fused);
+}
+
+int run_heads_gather(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, const GraphPostArgs* post, int* post_fused) {
+  const int E = a->E, H = a->H, W = a->W, dt = w->dtype;
   RUN(pvo_internal_heads_gather_post(reinterpret_cast<const float*>(b.h1), w->heads2_b, a->heads, post, post_fused, E, H, W, dt, stream));
   return PVO_OK;
 }
@@ -236,10 +305,20 @@ int run_upmask(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b,
   return pvo_conv1x1_c128(b.a2, w->up_w, w->up_b, a->upmask, static_cast<long long>(a->K) * a->H * a->W, 576, 0, w->dtype, stream);
 }
 
-int run_agg(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, SideCtx* mark = nullptr, bool with_upmask = true) {
+// blocks != nullptr (the edge-blocked schedule): conv1 waits for the two blocks' candidates - each in front of its own block's
+// launch where conv1 is blocked too (the wide form only), both in front of the whole launch otherwise
+struct AggBlocks { int lead; bool split; hipEvent_t cand0, cand1; };
+int run_agg(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, SideCtx* mark = nullptr, bool with_upmask = true,
+            const AggBlocks* blocks = nullptr) {
   const int E = a->E, H = a->H, W = a->W, K = a->K, dt = w->dtype;
   if (K <= 0) return PVO_OK;
-  if (w->flags & PVO_OP_CONV128_WIDE)
+  const bool split = blocks && blocks->split && (w->flags & PVO_OP_CONV128_WIDE);
+  if (blocks && hipStreamWaitEvent(pvo_stream(stream), blocks->cand0, 0) != hipSuccess) return PVO_ELAUNCH;
+  if (split) RUN(pvo_internal_conv3x3_range(a->net_out, w->agg1_w, nullptr, b.a1, E, 0, blocks->lead, H, W, 128, 128, 0, 0, 0, dt, stream));
+  if (blocks && hipStreamWaitEvent(pvo_stream(stream), blocks->cand1, 0) != hipSuccess) return PVO_ELAUNCH;
+  if (split)
+    RUN(pvo_internal_conv3x3_range(a->net_out, w->agg1_w, nullptr, b.a1, E, blocks->lead, E, H, W, 128, 128, 0, 0, 0, dt, stream));
+  else if (w->flags & PVO_OP_CONV128_WIDE)
     RUN(pvo_conv3x3(a->net_out, w->agg1_w, nullptr, b.a1, E, H, W, 128, 128, 0, 0, 0, dt, stream));
   else
     RUN(pvo_conv3x3_c128(a->net_out, w->agg1_w, nullptr, b.a1, E, H, W, 128, 0, 0, 0, dt, stream));
@@ -272,9 +351,43 @@ int run_operator(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& 
                  const MotionJob* mj = nullptr, bool upmask_on_side = true, bool context_ready = false,
                  const GraphPostArgs* post = nullptr, int* post_fused = nullptr, const int* static_rows = nullptr) {
   const void *P_zr, *P_q;
-  RUN(run_trunk(w, a, b, stream, &P_zr, &P_q, mj, context_ready, static_rows));
+  const int* ps = nullptr;
+  RUN(run_trunk(w, a, b, stream, &P_zr, &P_q, &ps, mj, context_ready, static_rows));
   hipStream_t st = pvo_stream(stream);
   SideCtx* sc = (a->K > 0 && !(w->flags & PVO_OP_SINGLE_STREAM)) ? side_ctx() : nullptr;
+  const EdgeBlocks eb = edge_blocks(a->E, a->H, a->W, w->flags);
+  if (eb.lead > 0) {
+    // The edge-blocked wavefront.  The edges are independent images: block b's candidate needs
+    // block b's gates only, its heads its candidate only.  The leading block [0, lead) runs the three stages on the launch
+    // stream, the trailing block beside it on a stream of the library's own, so that stage k + 1 of the leading block is ready
+    // to be dispatched when stage k of the trailing block runs out of workgroups.  The same workgroups on the same operands:
+    // bit-identical to the whole launches.  The gather behind the join, the glue and the BA run alone on the device as before.
+    const int E = a->E, H = a->H, W = a->W, dt = w->dtype, lead = eb.lead;
+    WaveCtx* wc = wave_ctx(eb.low);
+    if (!wc) return PVO_ELAUNCH;
+    hipStream_t ws = wc->s[eb.low];
+    if (hipEventRecord(wc->fork, st) != hipSuccess) return PVO_ELAUNCH;
+    if (hipStreamWaitEvent(ws, wc->fork, 0) != hipSuccess) return PVO_ELAUNCH;
+    RUN(run_gru(w, a, b, stream, P_zr, P_q, ps, 0, lead, true));
+    RUN(run_gru(w, a, b, ws, P_zr, P_q, ps, lead, E, false));
+    if (sc) {
+      if (hipEventRecord(wc->cand0, st) != hipSuccess) return PVO_ELAUNCH;
+      if (hipEventRecord(wc->cand1, ws) != hipSuccess) return PVO_ELAUNCH;
+      const AggBlocks ab = {lead, eb.agg, wc->cand0, wc->cand1};
+      RUN(run_agg(w, a, b, sc->side, sc, upmask_on_side, &ab));
+      if (hipEventRecord(sc->join, sc->side) != hipSuccess) return PVO_ELAUNCH;
+    }
+    float* const z = reinterpret_cast<float*>(b.h1);
+    RUN(pvo_internal_conv3x3_heads_range(a->net_out, w->heads1_w, w->heads1_b, w->heads2_w, z, E, 0, lead, H, W, dt, stream));
+    RUN(pvo_internal_conv3x3_heads_range(a->net_out, w->heads1_w, w->heads1_b, w->heads2_w, z, E, lead, E, H, W, dt, ws));
+    if (hipEventRecord(wc->join, ws) != hipSuccess) return PVO_ELAUNCH;
+    if (hipStreamWaitEvent(st, wc->join, 0) != hipSuccess) return PVO_ELAUNCH;
+    RUN(run_heads_gather(w, a, b, stream, post, post_fused));
+    if (!sc) RUN(run_agg(w, a, b, stream, nullptr, upmask_on_side));
+    *pending = sc;
+    return PVO_OK;
+  }
+  RUN(run_gru(w, a, b, stream, P_zr, P_q, ps, 0, a->E, true));
   if (sc) {
     if (hipEventRecord(sc->fork, st) != hipSuccess) return PVO_ELAUNCH;
     if (hipStreamWaitEvent(sc->side, sc->fork, 0) != hipSuccess) return PVO_ELAUNCH;

@@ -7,6 +7,8 @@ cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/ut
 # (second argument: an experiment build of the library, tools/variant.py build <variant> ...)
 if [ -n "$2" ]; then BENCH="$GRAFT_REPO_ROOT/tools/variant.py bench $2"; else BENCH="$GRAFT_REPO_ROOT/bench.py"; fi
+# (third argument: debug knobs for the run, tools/with_knob.py - `bash tools/update_timeline.sh r21_third_low "" edge_blocks=third+low`)
+if [ -n "$3" ]; then BENCH="$(dirname "$OUT")/../tools/with_knob.py $3 bench.py"; fi
 rocprofv3 --kernel-trace -f csv -d /tmp/ut -- python $BENCH --steps 10 --warmup 3 --steps-only > /tmp/ut_bench.log 2>&1
 python - > $OUT <<PY
 import csv, glob
