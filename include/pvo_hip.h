@@ -89,7 +89,9 @@ const char* pvo_last_hip_error(void);
  * points pvo_tsdf_sparse_{allocate,integrate,mesh}[_args_size, _workspace_bytes]; still 106, panoptic surface reconstruction: no
  * existing struct changed - new extension structs pvo_tsdf_panoptic_args / pvo_tsdf_mesh_labels_args (with *_args_size()) and new entry
  * points pvo_tsdf[_sparse]_integrate_panoptic / pvo_tsdf[_sparse]_mesh_panoptic; still 106, keyframe boundary: no struct changed -
- * new entry points pvo_update_operator_rows / pvo_graph_update_rows / pvo_corr_build_tiled_rows / pvo_edge_rows_init): a caller
+ * new entry points pvo_update_operator_rows / pvo_graph_update_rows / pvo_corr_build_tiled_rows / pvo_edge_rows_init; still 106,
+ * volume rendering: no existing struct changed - new structs pvo_tsdf_render_args / pvo_tsdf_sparse_render_args (with *_args_size())
+ * and new entry points pvo_tsdf_render[_workspace_bytes] / pvo_tsdf_sparse_render[_workspace_bytes]): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -985,6 +987,115 @@ int pvo_tsdf_mesh_panoptic(const pvo_tsdf_mesh_args* a, const pvo_tsdf_mesh_labe
                            void* stream);
 int pvo_tsdf_sparse_mesh_panoptic(const pvo_tsdf_sparse_mesh_args* a, const pvo_tsdf_mesh_labels_args* p, void* workspace,
                                   size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Rendering a TSDF volume: depth, normal, colour and segment id per view      */
+/* ------------------------------------------------------------------------- */
+
+/* pvo_tsdf_render: the volume of pvo_tsdf_integrate[_panoptic] seen from cameras - per view and pixel the first zero crossing of the
+ * trilinear TSDF along the pixel's ray, sampled at fixed depth steps (no counterpart in the reference).  Device pointers, dense.
+ *
+ *   Volume (read only): tsdf, wsum f32 [nz,ny,nx]; rgb f32 [nz,ny,nx,3] or NULL; label int32 [nz,ny,nx] or NULL; origin, voxel as in
+ *   pvo_tsdf_integrate; min_weight as in pvo_tsdf_mesh.
+ *   Views: poses [nviews,7] world-to-camera, intrinsics [4] for ht x wd, ix [N] int64; z_near >= 0, z_far > z_near, dz > 0: the
+ *   depth range and step ALONG THE OPTICAL AXIS (the convention of disps and of the volume's sdf).
+ *   Outputs, written for EVERY pixel of every slot (a caller never clears them):
+ *     depth     f32 [N,ht,wd]            depth along the optical axis; 0 = no surface
+ *     normal    f32 [N,ht,wd,3] or NULL  world frame, unit, toward increasing tsdf (outward, as pvo_tsdf_mesh)
+ *     rgba      uint8 [N,ht,wd,4] or NULL, 4-byte aligned
+ *     out_label int32 [N,ht,wd] or NULL  (needs the label volume)
+ *     visited   int32 [N,ht,wd,2] or NULL: a diagnostic - the samples the pixel's walk examined, and the samples of its clipped
+ *                                         range (tools/tsdf_render_bench.py reports the share the brick jump removes)
+ *   A MISS is depth 0, normal (0,0,0), rgba (0,0,0,0), label 0.  A slot whose id is outside [0, nviews) is all miss and its pose is
+ *   never dereferenced.
+ *
+ * Per view (first launch), with R the matrix of the quaternion as stored (pvo_tsdf_integrate's expressions) and t the translation,
+ * every multiply-add below one fused operation, every other operation rounded to fp32:
+ *   M_ij = R_ji / voxel;   c_i = -fma(R_2i, t_z, fma(R_1i, t_y, R_0i * t_x));   p0_i = (c_i - origin_i) / voxel.
+ * Per pixel (vi, ui):  rx = (ui - cx) / fx, ry = (vi - cy) / fy;  g_i = fma(M_i0, rx, fma(M_i1, ry, M_i2)).  In voxel coordinates
+ * (axis 0 = x) the ray is p_i(z) = fma(z, g_i, p0_i).
+ *   Samples lie on a GLOBAL lattice: z_k = float(k) * dz for k = ceil(z_near / dz) .. floor(z_far / dz) (both quotients in fp32) - not
+ *   relative to where the ray enters the volume, and never an accumulated sum.
+ *   Sample k is VALID iff 0 <= p_i(z_k) <= n_i - 1 on every axis (n = (nx, ny, nz)) and all eight corners of its cell
+ *   c_i = min(floor(p_i), n_i - 2) have wsum >= min_weight.  Its value S_k is the trilinear interpolant of tsdf at the fraction
+ *   f_i = p_i - c_i, with lerp(a, b, t) = fma(t, b - a, a): along x on the four edges, then y, then z.
+ *   The ray ENDS at the first valid sample with S_k < 0 (the mesh's INSIDE rule).  It is a HIT iff sample k-1 exists, is valid and has
+ *   S_{k-1} >= 0; then t = S_{k-1} / (S_{k-1} - S_k) and depth = (float(k-1) + t) * dz.  Otherwise - the ray started inside or behind
+ *   a surface - and for a ray that never ends, the pixel is a miss.
+ *   At a hit the attributes blend the two bracketing samples:
+ *     normal = normalise(lerp(grad_{k-1}, grad_k, t)), grad the analytic gradient of the trilinear interpolant in the sample's cell
+ *              (each component the bilinear lerp of four corner differences; the length sqrt(fma(x, x, fma(y, y, z * z)))); a zero
+ *              vector gives (0,0,0)
+ *     rgba   = floor(lerp(C_{k-1}, C_k, t) + 0.5) clamped to [0,255] per channel, C the trilinear interpolant of rgb; a = 255;
+ *              (0,0,0,255) without an rgb volume
+ *     label  = pvo_tsdf_mesh_panoptic's vertex rule on the eight corners of sample k's cell: comparisons only, exact.
+ *   An implementation MAY skip a sample it can prove invalid; a skipped sample counts as invalid for "sample k-1 is valid".  This one
+ *   clips the lattice against the volume's box (slab test, opened by two samples at each end), reads corner 0's weight before the
+ *   other fifteen values, and in the brick volume jumps over bricks that do not exist.
+ *
+ * Two launches (per-view constants; one thread per pixel, a wave on an 8 x 8 tile), no atomics, no allocation, no host
+ * synchronisation: capturable; the same operands give the same bytes.  workspace: pvo_tsdf_render_workspace_bytes(N) bytes
+ * (PVO_EWORKSPACE otherwise), 16-byte aligned.
+ * Limits (PVO_EINVAL): nz*ny*nx < 2^31, voxel > 0 and finite, min_weight not NaN, ht*wd < 2^31, dz > 0, z_far > z_near >= 0, all
+ * finite, (z_far - z_near) / dz <= 65536 (every pixel's loop has a hard bound), z_far / dz < 2^22, rgba not 4-byte aligned, out_label
+ * without label; then, unless N == 0 or ht*wd == 0 (PVO_OK, nothing written): a NULL depth; then, unless a dimension is < 2 (no cell:
+ * every output all miss, PVO_OK): a NULL poses / intrinsics / ix / tsdf / wsum. */
+typedef struct pvo_tsdf_render_args {
+  const float* tsdf;
+  const float* wsum;
+  const float* rgb;
+  const int32_t* label;
+  int nz, ny, nx;
+  float origin[3];
+  float voxel, min_weight;
+  const float* poses;
+  const float* intrinsics;
+  const int64_t* ix;
+  int N, nviews, ht, wd;
+  float z_near, z_far, dz;
+  float* depth;
+  float* normal;
+  uint8_t* rgba;
+  int32_t* out_label;
+  int32_t* visited;
+} pvo_tsdf_render_args;
+size_t pvo_tsdf_render_args_size(void);
+size_t pvo_tsdf_render_workspace_bytes(int N);
+int pvo_tsdf_render(const pvo_tsdf_render_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pvo_tsdf_sparse_render: pvo_tsdf_render on the GLOBAL lattice [8gz,8gy,8gx] of a brick volume (tsdf, wsum, rgb, label: the pools
+ * [cap,8,8,8(,3)]; grid as in pvo_tsdf_sparse_mesh, a slot >= cap is no brick).  A sample is valid only if all eight corners of its
+ * cell lie in bricks that exist, whatever min_weight is.  Position, cell, value, hit and attributes come from the same inline
+ * functions (csrc/tsdf_ray.h) called with the global integer cell index: the BYTES of pvo_tsdf_render over the [8gz,8gy,8gx] volume
+ * that holds the bricks and zeros elsewhere, for min_weight > 0.
+ *   When the brick that holds a sample's corner 0 does not exist, that sample and every later one with corner 0 in the same brick are
+ *   invalid: k jumps to the first sample that can have left the brick, computed to land early (by two samples) and never less than
+ *   k + 1.  The last (brick -> slot) lookup stays in registers; only cells that straddle a brick face go back to grid.
+ * Launches, workspace (pvo_tsdf_sparse_render_workspace_bytes(N)) and limits as pvo_tsdf_render with the grid limits of the brick
+ * volume; cap == 0 or an empty grid: every output all miss, PVO_OK; otherwise a NULL grid is PVO_EINVAL as well. */
+typedef struct pvo_tsdf_sparse_render_args {
+  const int32_t* grid;
+  const float* tsdf;
+  const float* wsum;
+  const float* rgb;
+  const int32_t* label;
+  int gz, gy, gx, cap;
+  float origin[3];
+  float voxel, min_weight;
+  const float* poses;
+  const float* intrinsics;
+  const int64_t* ix;
+  int N, nviews, ht, wd;
+  float z_near, z_far, dz;
+  float* depth;
+  float* normal;
+  uint8_t* rgba;
+  int32_t* out_label;
+  int32_t* visited;
+} pvo_tsdf_sparse_render_args;
+size_t pvo_tsdf_sparse_render_args_size(void);
+size_t pvo_tsdf_sparse_render_workspace_bytes(int N);
+int pvo_tsdf_sparse_render(const pvo_tsdf_sparse_render_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

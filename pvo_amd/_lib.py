@@ -133,6 +133,12 @@ SIGNATURES = {
     "pvo_tsdf_sparse_integrate_panoptic": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pvo_tsdf_mesh_panoptic": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pvo_tsdf_sparse_mesh_panoptic": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pvo_tsdf_render_args_size": (_sz, []),
+    "pvo_tsdf_render_workspace_bytes": (_sz, [_i]),
+    "pvo_tsdf_render": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_sparse_render_args_size": (_sz, []),
+    "pvo_tsdf_sparse_render_workspace_bytes": (_sz, [_i]),
+    "pvo_tsdf_sparse_render": (_i, [_vp, _vp, _sz, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -249,6 +255,23 @@ class TsdfMeshLabelsArgs(_c.Structure):
     _fields_ = [("label", _vp), ("vlabel", _vp)]
 
 
+_RENDER_TAIL = [("origin", _f * 3), ("voxel", _f), ("min_weight", _f),
+                ("poses", _vp), ("intrinsics", _vp), ("ix", _vp), ("N", _i), ("nviews", _i), ("ht", _i), ("wd", _i),
+                ("z_near", _f), ("z_far", _f), ("dz", _f),
+                ("depth", _vp), ("normal", _vp), ("rgba", _vp), ("out_label", _vp), ("visited", _vp)]
+
+
+class TsdfRenderArgs(_c.Structure):
+    """pvo_tsdf_render_args"""
+    _fields_ = [("tsdf", _vp), ("wsum", _vp), ("rgb", _vp), ("label", _vp), ("nz", _i), ("ny", _i), ("nx", _i)] + _RENDER_TAIL
+
+
+class TsdfSparseRenderArgs(_c.Structure):
+    """pvo_tsdf_sparse_render_args"""
+    _fields_ = [("grid", _vp), ("tsdf", _vp), ("wsum", _vp), ("rgb", _vp), ("label", _vp),
+                ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i)] + _RENDER_TAIL
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 PVO_KNOB_EDGE_BLOCKS = 4
@@ -289,7 +312,8 @@ def load():
                        (lib.pvo_tsdf_sparse_allocate_args_size, TsdfSparseAllocateArgs),
                        (lib.pvo_tsdf_sparse_integrate_args_size, TsdfSparseIntegrateArgs),
                        (lib.pvo_tsdf_sparse_mesh_args_size, TsdfSparseMeshArgs),
-                       (lib.pvo_tsdf_panoptic_args_size, TsdfPanopticArgs), (lib.pvo_tsdf_mesh_labels_args_size, TsdfMeshLabelsArgs)):
+                       (lib.pvo_tsdf_panoptic_args_size, TsdfPanopticArgs), (lib.pvo_tsdf_mesh_labels_args_size, TsdfMeshLabelsArgs),
+                       (lib.pvo_tsdf_render_args_size, TsdfRenderArgs), (lib.pvo_tsdf_sparse_render_args_size, TsdfSparseRenderArgs)):
         if fn() != ctypes.sizeof(struct):
             raise PvoHipError("libpvo_hip.so has a %d-byte %s; this binding is written for %d bytes - rebuild with "
                               "`python -m pvo_amd.build`" % (fn(), struct.__doc__, ctypes.sizeof(struct)))

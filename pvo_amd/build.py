@@ -25,6 +25,7 @@ HIP_SOURCES = [
     "map_points.hip",
     "tsdf.hip",
     "tsdf_sparse.hip",
+    "tsdf_render.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",

@@ -662,7 +662,7 @@ class DepthVideo:
         return origin, (g[2], g[1], g[0])
 
     def tsdf(self, voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None, use_sigma=False, origin=None, dims=None,
-             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05, sparse=False, margin=2, panoptic=False):
+             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05, sparse=False, margin=2, panoptic=False, keep_rgb=False):
         """the fused surface of keyframes ix (default: all stored ones; fuse after `terminate` - poses that move later are not
         de-integrated): a TSDF volume of `voxel`-sized cells, truncation `trunc` (default 3 voxels), integrated natively
         (pvo_tsdf_integrate) from exactly the pixels map_points(ix, thresh, full_res, reject, max_rel_sigma) keeps, and its surface-nets
@@ -676,7 +676,9 @@ class DepthVideo:
         mesh, origin, voxel and `volume`, the SparseTSDF, in place of tsdf / wsum.
         panoptic=True (a video made with store_segment_ids, ValueError otherwise): the frames' raw segment ids segms_raw[:n] are fused
         by a weighted vote per voxel (pvo_tsdf_integrate_panoptic; ids <= 0 = no segment) and every vertex gets the id of its cell's
-        nearest labelled corner: the dict gains vlabel int32 [V] and the volumes label, lconf (sparse: the SparseTSDF holds them)."""
+        nearest labelled corner: the dict gains vlabel int32 [V] and the volumes label, lconf (sparse: the SparseTSDF holds them).
+        keep_rgb=True (dense, a video with images): the dict also keeps the colour volume rgb [nz,ny,nx,3], so that tsdf_render
+        can colour its images (the SparseTSDF holds its own)."""
         trunc = 3.0 * float(voxel) if trunc is None else float(trunc)
         n = self.counter
         if panoptic and self.segms_raw is None:
@@ -727,9 +729,63 @@ class DepthVideo:
         out = db.tsdf_mesh(vol, wsum, rgb, origin, voxel, min_weight=min_weight, label=label)
         out.pop("counts")
         out.update(tsdf=vol, wsum=wsum, origin=[float(v) for v in origin], voxel=float(voxel))
+        if keep_rgb and rgb is not None:
+            out.update(rgb=rgb)
         if panoptic:
             out.update(label=label, lconf=lconf)
         return out
+
+    def tsdf_render(self, volume, ix=None, poses=None, full_res=False, **kw):
+        """the fused volume seen from cameras (pvo_tsdf_render / pvo_tsdf_sparse_render): `volume` is the dict `tsdf` returns - dense
+        (tsdf, wsum, origin, voxel, with images rgb, with panoptic=True label) or with volume = the SparseTSDF.  Views: the stored
+        keyframes ix (default: all) with the video's intrinsics at 1/8 resolution, or with full_res at image resolution (8 * intrinsics);
+        or explicit poses [n,7] (world-to-camera), all of them rendered.  Returns a dict: depth [n,ht,wd], normal [n,ht,wd,3], rgba
+        [n,ht,wd,4] and, for a panoptic volume, label [n,ht,wd].  kw: dz, z_near, z_far, min_weight, normals, out of
+        droid_backends.tsdf_render."""
+        if poses is None:
+            n = self.counter
+            ix = torch.arange(n, device=self.device) if ix is None else torch.as_tensor(ix, dtype=torch.long, device=self.device).reshape(-1)
+            poses, ix = self.poses[:n], ix.contiguous()
+        else:
+            if ix is not None:
+                raise ValueError("tsdf_render: explicit poses are all rendered, in their order: no ix")
+            poses = torch.as_tensor(poses, dtype=torch.float32, device=self.device).reshape(-1, 7).contiguous()
+            ix = torch.arange(poses.shape[0], device=self.device)
+        scale = 8 if full_res else 1
+        intr = (float(scale) * self.intrinsics[0]).contiguous()
+        ht, wd = scale * (self.ht // 8), scale * (self.wd // 8)
+        if "volume" in volume:
+            return volume["volume"].render(poses, intr, ix, ht, wd, **kw)
+        return db.tsdf_render(volume["tsdf"], volume["wsum"], volume.get("rgb"), volume["origin"], volume["voxel"], poses, intr, ix, ht, wd,
+                              label=volume.get("label"), **kw)
+
+    @staticmethod
+    def depth_residual(disps, depth):
+        """per frame of disps / depth [n,ht,wd] (a keyframe's own inverse depths and the model's rendered depth, 0 = no surface): the
+        median and the 90th percentile of |1/disps - depth| / depth over the pixels where both exist (disps finite and > 0, depth > 0),
+        and the share of pixels that do; NaN for a frame without such a pixel.  Returns three [n] float64 tensors.  Works on CPU tensors."""
+        n = disps.shape[0]
+        med, p90, share = [torch.full((n,), float("nan"), dtype=torch.float64, device=disps.device) for _ in range(3)]
+        for k in range(n):
+            d, z = disps[k].reshape(-1).double(), depth[k].reshape(-1).double()
+            both = torch.isfinite(d) & (d > 0) & (z > 0)
+            share[k] = both.double().mean() if both.numel() else 0.0
+            if both.any():
+                rel = (1.0 / d[both] - z[both]).abs() / z[both]
+                q = torch.quantile(rel, torch.tensor([0.5, 0.9], dtype=torch.float64, device=rel.device))
+                med[k], p90[k] = q[0], q[1]
+        return med, p90, share
+
+    def model_residual(self, volume, ix=None, full_res=False):
+        """how well each keyframe's own depth agrees with the fused surface: the volume rendered at the keyframes ix (tsdf_render) against
+        1/disps (disps_up with full_res) - a dict of ix and, per keyframe, median, p90 (of |1/disps - depth| / depth where both exist)
+        and share (of pixels where both exist)"""
+        r = self.tsdf_render(volume, ix=ix, full_res=full_res, normals=False)
+        n = self.counter
+        ix = torch.arange(n, device=self.device) if ix is None else torch.as_tensor(ix, dtype=torch.long, device=self.device).reshape(-1)
+        own = (self.disps_up if full_res else self.disps)[ix.clamp(0, max(n - 1, 0))]
+        med, p90, share = self.depth_residual(own, r["depth"])
+        return {"ix": ix, "median": med, "p90": p90, "share": share}
 
     def ba(self, target, weight, eta, ii, jj, t0=1, t1=None, itrs=2, lm=1e-4, ep=0.1, motion_only=False,
            t1_hint=None):

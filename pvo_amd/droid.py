@@ -188,6 +188,13 @@ class Droid:
         self.flush()
         return self.video.tsdf(**kw)
 
+    def get_renders(self, volume, **kw):
+        """the fused volume seen from the keyframes (or from explicit poses): DepthVideo.tsdf_render(volume, ix=None, poses=None,
+        full_res=False, dz=None, z_near=0.0, z_far=None, min_weight=1.0, normals=True) on the dict get_mesh returned - a dict of depth
+        [n,ht,wd], normal [n,ht,wd,3], rgba [n,ht,wd,4] and, for a panoptic volume, label [n,ht,wd]"""
+        self.flush()
+        return self.video.tsdf_render(volume, **kw)
+
     def get_flow(self):
         self.flush()
         return upsample_inter(self.video.full_flow[:self.video.counter][None] * 8)

@@ -849,6 +849,134 @@ def tsdf_sparse_mesh(vol, min_weight=1.0, vcap=None, fcap=None, label=None):
     return out
 
 
+RENDER_MAX_SAMPLES = 65536                 # (z_far - z_near) / dz of pvo_tsdf_render
+
+
+def _render_range(what, dims, origin, voxel, poses, ix, dz, z_near, z_far):
+    """(dz, z_near, z_far) with the defaults dz = voxel / 2 and z_far = the largest depth of a corner of the volume's box over the
+    views ix (one small reduction read back: a synchronisation; none when z_far is given); raises where the range has more than
+    RENDER_MAX_SAMPLES samples"""
+    dz = 0.5 * float(voxel) if dz is None else float(dz)
+    if z_far is None:
+        nz, ny, nx = dims
+        o = torch.tensor([float(v) for v in origin], dtype=torch.float64)
+        ext = float(voxel) * torch.tensor([max(nx - 1, 0), max(ny - 1, 0), max(nz - 1, 0)], dtype=torch.float64)
+        corners = torch.stack([o + ext * torch.tensor([(j >> 0) & 1, (j >> 1) & 1, (j >> 2) & 1], dtype=torch.float64) for j in range(8)])
+        sel = ix[(ix >= 0) & (ix < poses.shape[0])]
+        z_far = 0.0
+        if sel.numel():
+            p = poses[sel].double().cpu()
+            x, y, z, w = p[:, 3], p[:, 4], p[:, 5], p[:, 6]
+            row = torch.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1)         # the third row of R(q)
+            z_far = float((row @ corners.T + p[:, 2:3]).max())
+        z_far = max(z_far, float(z_near)) + dz
+    z_near, z_far = float(z_near), float(z_far)
+    if dz > 0 and (z_far - z_near) / dz > RENDER_MAX_SAMPLES:
+        raise PvoHipError("%s: %g .. %g in steps of %g is more than %d samples per ray - raise dz (or bring z_near / z_far closer)"
+                          % (what, z_near, z_far, dz, RENDER_MAX_SAMPLES))
+    return dz, z_near, z_far
+
+
+def _render_views(a, what, dev, poses, intrinsics, ix, ht, wd, label, normals, out):
+    """the view and output fields both render calls share; returns the dict of outputs (caller-owned with out=)"""
+    for t, n in ((poses, "poses"), (intrinsics, "intrinsics"), (ix, "ix")):
+        _contig(t, n)
+        if t.device != dev:
+            raise PvoHipError("%s: %s must be on %s" % (what, n, dev))
+    _long(ix, "ix")
+    _f32(poses, "poses")
+    _f32(intrinsics, "intrinsics")
+    N, ht, wd = ix.shape[0], int(ht), int(wd)
+    if poses.dim() != 2 or poses.shape[1] != 7 or intrinsics.numel() < 4:
+        raise PvoHipError("%s: poses must be [nviews,7] and intrinsics [4]" % what)
+    want = {"depth": ((N, ht, wd), torch.float32)}
+    if normals:
+        want["normal"] = ((N, ht, wd, 3), torch.float32)
+    want["rgba"] = ((N, ht, wd, 4), torch.uint8)
+    if label is not None:
+        want["label"] = ((N, ht, wd), torch.int32)
+    if out is None:
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in want.items()}
+    else:
+        for k, t in out.items():
+            known = dict(want, normal=((N, ht, wd, 3), torch.float32), visited=((N, ht, wd, 2), torch.int32))
+            if k not in known or (k == "label" and label is None):
+                raise PvoHipError("%s: out has no use for %r" % (what, k))
+            shape, dt = known[k]
+            if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                raise PvoHipError("%s: out[%r] must be a contiguous %s %s on %s" % (what, k, dt, list(shape), dev))
+        if "depth" not in out:
+            raise PvoHipError("%s: out needs 'depth'" % what)
+    a.poses, a.intrinsics, a.ix = _ptr(poses), _ptr(intrinsics), _ptr(ix)
+    a.N, a.nviews, a.ht, a.wd = N, poses.shape[0], ht, wd
+    a.depth, a.normal, a.rgba = _ptr(out["depth"]), _ptr(out.get("normal")), _ptr(out.get("rgba"))
+    a.out_label, a.visited = _ptr(out.get("label")), _ptr(out.get("visited"))
+    return out
+
+
+def tsdf_render(tsdf, wsum, rgb, origin, voxel, poses, intrinsics, ix, ht, wd, dz=None, z_near=0.0, z_far=None, min_weight=1.0, label=None,
+                normals=True, out=None):
+    """The volume seen from cameras (include/pvo_hip.h pvo_tsdf_render): per view ix[b] of poses [nviews,7] (world-to-camera) with
+    intrinsics [4] for ht x wd pixels, the first zero crossing of the trilinear TSDF along every pixel's ray.  Returns a dict: depth f32
+    [N,ht,wd] along the optical axis (0 = no surface), normal f32 [N,ht,wd,3] (world frame, outward; not with normals=False), rgba uint8
+    [N,ht,wd,4] ((0,0,0,255) on hits without an rgb volume, 0 on misses) and, only with a label volume (int32 [nz,ny,nx]), label int32
+    [N,ht,wd].  Rays are sampled at the depths k * dz between z_near and z_far.  Defaults: dz = 0.5 * voxel; z_far = the farthest
+    corner of the volume's box over the views (plus one step), which reads the poses back once - pass z_far to stay asynchronous.  A
+    range of more than 65536 samples raises: use a larger dz.  out=: caller-owned buffers (depth, and any of normal / rgba / label,
+    visited int32 [N,ht,wd,2]) - with z_far given: no allocation beyond the cached workspace, no synchronisation, capturable."""
+    for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb"), (label, "label")):
+        if t is not None:
+            _contig(t, n)
+    dev = _dev(tsdf, wsum, rgb, label, poses, intrinsics, ix)
+    for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")):
+        if t is not None:
+            _f32(t, n)
+    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
+        raise PvoHipError("tsdf_render: tsdf and wsum must be [nz,ny,nx], rgb [nz,ny,nx,3]")
+    if label is not None and (label.dtype != torch.int32 or label.shape != tsdf.shape):
+        raise PvoHipError("tsdf_render: label must be int32 with the shape of tsdf")
+    a = _lib.TsdfRenderArgs()
+    out = _render_views(a, "tsdf_render", dev, poses, intrinsics, ix, ht, wd, label, normals, out)
+    a.dz, a.z_near, a.z_far = _render_range("tsdf_render", tsdf.shape, origin, voxel, poses, ix, dz, z_near, z_far)
+    a.tsdf, a.wsum, a.rgb, a.label = _ptr(tsdf), _ptr(wsum), _ptr(rgb), _ptr(label)
+    a.nz, a.ny, a.nx = tsdf.shape
+    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
+    a.voxel, a.min_weight = float(voxel), float(min_weight)
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_render_workspace_bytes(a.N))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_render(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_render")
+    return out
+
+
+def tsdf_sparse_render(vol, poses, intrinsics, ix, ht, wd, dz=None, z_near=0.0, z_far=None, min_weight=1.0, label=None, normals=True,
+                       out=None):
+    """tsdf_render of the brick volume `vol` (a dict, see _sparse_world; include/pvo_hip.h pvo_tsdf_sparse_render): the bytes of the dense
+    render over the [8gz,8gy,8gx] volume that holds the bricks, with rays jumping over bricks that do not exist.  label: the label pool
+    int32 [cap,8,8,8].  Defaults (dz = 0.5 * voxel, z_far from the world's box), out= and the sample limit as in tsdf_render."""
+    a = _lib.TsdfSparseRenderArgs()
+    c = _lib.TsdfSparseMeshArgs()                          # (the checks and the world's fields: _sparse_world fills coord / bricks too)
+    dev = _sparse_world(c, vol)
+    _dev(vol["grid"], poses, intrinsics, ix, label)
+    if label is not None:
+        _contig(label, "label")
+        if label.dtype != torch.int32 or label.shape != vol["tsdf"].shape:
+            raise PvoHipError("tsdf_sparse_render: label must be int32 with the shape of the pool")
+    a.gz, a.gy, a.gx, a.cap = c.gz, c.gy, c.gx, c.cap
+    a.origin[0], a.origin[1], a.origin[2] = c.origin[0], c.origin[1], c.origin[2]
+    a.voxel, a.min_weight = c.voxel, float(min_weight)
+    out = _render_views(a, "tsdf_sparse_render", dev, poses, intrinsics, ix, ht, wd, label, normals, out)
+    B = _lib.TSDF_BRICK
+    a.dz, a.z_near, a.z_far = _render_range("tsdf_sparse_render", (B * a.gz, B * a.gy, B * a.gx), vol["origin"], vol["voxel"], poses, ix,
+                                            dz, z_near, z_far)
+    a.grid, a.tsdf, a.wsum, a.rgb, a.label = _ptr(vol["grid"]), _ptr(vol["tsdf"]), _ptr(vol["wsum"]), _ptr(vol.get("rgb")), _ptr(label)
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_sparse_render_workspace_bytes(a.N))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_sparse_render(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_render")
+    return out
+
+
 def _baseline(baseline, what):
     """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
     b = float(baseline)

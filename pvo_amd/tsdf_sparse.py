@@ -87,6 +87,12 @@ class SparseTSDF:
         """the mesh dict of droid_backends.tsdf_sparse_mesh; with labels=True it has vlabel"""
         return db.tsdf_sparse_mesh(self.volume(), min_weight=min_weight, vcap=vcap, fcap=fcap, label=self.label)
 
+    def render(self, poses, intrinsics, ix, ht, wd, dz=None, z_near=0.0, z_far=None, min_weight=1.0, normals=True, out=None):
+        """the volume seen from the views ix of poses: the dict of droid_backends.tsdf_sparse_render (depth, normal, rgba; with
+        labels=True label as well)"""
+        return db.tsdf_sparse_render(self.volume(), poses, intrinsics, ix, ht, wd, dz=dz, z_near=z_near, z_far=z_far,
+                                     min_weight=min_weight, label=self.label, normals=normals, out=out)
+
     def nbytes(self):
         """device bytes held: the grid and the pool"""
         return sum(t.numel() * t.element_size() for t in (self.grid, self.coord, self.counts, self.tsdf, self.wsum, self.rgb, self.label, self.lconf)

@@ -2,7 +2,8 @@
 
     python tools/export_map.py --datapath <.../SceneXX> --weights <checkpoint.pth> --map out.ply [--full_res] [--filter_thresh_map 0.005]
                                [--reconstruction_path DIR] [--uncertainty [--max_rel_sigma X]]
-                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight] [--sparse] [--panoptic [--instances_dir DIR]]]
+                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight] [--sparse] [--panoptic [--instances_dir DIR]]
+                                [--render_dir DIR]]
 
 --map writes the filtered point cloud of all keyframes after the global bundle adjustment (Droid.get_map: points confirmed by two
 neighbouring keyframes, pvo_map_points) as a binary little-endian PLY: x y z float, red green blue uchar, int label (the per-frame
@@ -17,8 +18,12 @@ with vertex normals, colours and triangle faces; --sigma_weight (with --uncertai
 variance instead of counting all alike; --sparse fuses into a brick volume over the map's full extent (pvo_tsdf_sparse_*) where the
 dense volume is clipped to what fits; --panoptic keeps the frames' panoptic ids as given (args.store_segment_ids), fuses them into the
 volume by a weighted vote (pvo_tsdf_integrate_panoptic) and adds `property int label` to the mesh's vertices, and --instances_dir DIR
-also writes one mesh per id, DIR/segment_<id>.ply.  Without --mesh the output is what it was without the option, and without
---sparse / --panoptic the mesh is.
+also writes one mesh per id, DIR/segment_<id>.ply.  --render_dir DIR (with --mesh) also looks at the fused volume from every keyframe
+(Droid.get_renders: pvo_tsdf_render / pvo_tsdf_sparse_render, at the resolution the volume was fused from) and writes per keyframe k
+DIR/depth_%06d.npy (f32 [ht,wd], 0 = no surface), normal_%06d.npy (f32 [ht,wd,3]), rgba_%06d.npy (uint8 [ht,wd,4]) and, with
+--panoptic, label_%06d.npy (int32 [ht,wd]: ids that are consistent across keyframes); it prints how each keyframe's own depth
+agrees with the fused surface (DepthVideo.model_residual).  Without --mesh the output is what it was without the option, and without
+--sparse / --panoptic / --render_dir the mesh is.
 """
 import os
 import sys
@@ -46,6 +51,7 @@ def parse_args(argv=None):
     p.add_argument("--sparse", action="store_true", help="with --mesh: a brick volume over the map's full extent")
     p.add_argument("--panoptic", action="store_true", help="with --mesh: fuse the frames' panoptic ids, write a label per vertex")
     p.add_argument("--instances_dir", default=None, help="with --panoptic: also one segment_<id>.ply per id into this folder")
+    p.add_argument("--render_dir", default=None, help="with --mesh: also depth / normal / rgba (/ label) images of the fused volume per keyframe")
     own, rest = p.parse_known_args(argv)
     args = test_vo.parse_args(rest)
     for k, v in vars(own).items():
@@ -62,6 +68,8 @@ def parse_args(argv=None):
         p.error("--panoptic needs --mesh")
     if args.instances_dir is not None and not args.panoptic:
         p.error("--instances_dir needs --panoptic")
+    if args.render_dir is not None and args.mesh is None:
+        p.error("--render_dir needs --mesh")
     return args
 
 
@@ -71,6 +79,9 @@ def write_mesh(droid, args):
     kw = {"sparse": True} if args.sparse else {}
     if args.panoptic:
         kw["panoptic"] = True
+    render_dir = getattr(args, "render_dir", None)
+    if render_dir is not None and not args.sparse:
+        kw["keep_rgb"] = True                                # (the dense colour volume, for the renders; the mesh is the same)
     g = droid.get_mesh(voxel=args.voxel, trunc=args.trunc, thresh=args.filter_thresh_map, full_res=args.full_res,
                        use_sigma=args.sigma_weight, max_rel_sigma=args.max_rel_sigma, **kw)
     nv, nf = write_ply_mesh(args.mesh, g["verts"], g["faces"], g["rgba"], g["normals"], **({"label": g["vlabel"]} if args.panoptic else {}))
@@ -85,7 +96,30 @@ def write_mesh(droid, args):
                 v, f = parts.get(i, (g["verts"][g["vlabel"] == i], g["faces"][:0]))
                 write_ply_mesh(os.path.join(args.instances_dir, "segment_%d.ply" % i), v, f)
             line += ", one mesh each written to %s" % args.instances_dir
+    if render_dir is not None:
+        line += "\n" + write_renders(droid, args, g)
     return line
+
+
+def write_renders(droid, args, volume):
+    """the --render_dir output: the volume of write_mesh seen from every keyframe; returns the line that says what was written"""
+    import numpy as np
+    os.makedirs(args.render_dir, exist_ok=True)
+    r = droid.get_renders(volume, full_res=args.full_res)
+    names = ["depth", "normal", "rgba"] + (["label"] if args.panoptic else [])
+    host = {k: r[k].cpu().numpy() for k in names}
+    n = host["depth"].shape[0]
+    for k in range(n):
+        for name in names:
+            np.save(os.path.join(args.render_dir, "%s_%06d.npy" % (name, k)), host[name][k])
+    res = droid.video.model_residual(volume, full_res=args.full_res)
+    med, p90, share = [res[k].cpu().numpy() for k in ("median", "p90", "share")]
+    seen = np.isfinite(med)
+    worst = (float(np.median(med[seen])), float(med[seen].max()), float(np.median(p90[seen])), float(p90[seen].max())) if seen.any() else (float("nan"),) * 4
+    return ("renders: %s of %d keyframes at %d x %d written to %s; model residual |1/disp - depth| / depth per keyframe: median %.4f "
+            "(worst keyframe %.4f), 90th percentile %.4f (worst %.4f), over %.1f %% of the pixels"
+            % (" / ".join(names), n, host["depth"].shape[1], host["depth"].shape[2], args.render_dir, worst[0], worst[1], worst[2], worst[3],
+               100.0 * float(share.mean()) if n else 0.0))
 
 
 def main(argv=None):
