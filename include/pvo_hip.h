@@ -91,7 +91,8 @@ const char* pvo_last_hip_error(void);
  * points pvo_tsdf[_sparse]_integrate_panoptic / pvo_tsdf[_sparse]_mesh_panoptic; still 106, keyframe boundary: no struct changed -
  * new entry points pvo_update_operator_rows / pvo_graph_update_rows / pvo_corr_build_tiled_rows / pvo_edge_rows_init; still 106,
  * volume rendering: no existing struct changed - new structs pvo_tsdf_render_args / pvo_tsdf_sparse_render_args (with *_args_size())
- * and new entry points pvo_tsdf_render[_workspace_bytes] / pvo_tsdf_sparse_render[_workspace_bytes]): a caller
+ * and new entry points pvo_tsdf_render[_workspace_bytes] / pvo_tsdf_sparse_render[_workspace_bytes]; still 106, shard invariance:
+ * no struct changed - new entry points pvo_ba_finish_graph / pvo_ba_solve_kind): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -1192,8 +1193,20 @@ int pvo_ba(float* poses, float* disps, const float* intrinsics,
  *                  identical dx), retract poses, back-substitute this rank's dz.
  * `sys` holds 64-bit FIXED-POINT numbers (int64, units of 2^-28): integer sums commute, so the
  * system - and with it every pose and depth - is bitwise reproducible from run to run and
- * identical for any partition of the edges over ranks (the reference's host-side sum of fp32
+ * identical for any partition of the edges BY SOURCE FRAME over ranks (the reference's host-side sum of fp32
  * block sums has no such guarantee either way; fp64 atomics, used in round 1, did not).
+ * What makes the words of `sys` partition-invariant: every fp32 partial sum behind a fixed-point addend is formed from one source
+ * frame's edges, and the launch rules that fix those sums read only what every rank shares - the pixel chunk and the dense-window
+ * form from (P, nframes, HW); whether a depth frame's chunk sums are added in fp64 and rounded once ("staged") from the frame's
+ * IDENTITY: in a dense window (P <= 29 whose 256-pixel grid exceeds 192 workgroups) the window's frames and the 8 frames right in
+ * front of t0 have a staging slot, any other source frame rounds chunk by chunk.  Nothing reads K_eta, this call's edge count, the
+ * number of depth frames of this call or the eta layout (one broadcast row or full rows of the same values: the same words).
+ * The solve form of pvo_ba_finish is chosen on the host from P and an EDGE COUNT: this call's E, which is the whole graph's on one
+ * GPU.  A rank that finishes a densely all-reduced system with a shard's ii / jj calls pvo_ba_finish_graph and states the whole
+ * graph's count, so that every rank factorises the same words with the same algorithm; a packed message (pvo_ba_finish_packed)
+ * never takes the edge-count form.  The whole graph on one GPU and its shards then choose alike, too.  pvo_ba_solve_kind(P,
+ * graph_edges, packed) returns the choice without touching a GPU: 0 status words only, 1 dense, 2 envelope (partitioned where it
+ * can be), 3 one chain, 4 dense in 48 x 48 blocks.
  * pvo_ba_finish converts to fp64, solves in fp64 (as SparseBlock::solve, droid_kernels.cu:1160-1198)
  * and leaves `sys` ZEROED; bit 1 of pvo_ba_local's motion_only argument says that `sys` is
  * already zero (local -> finish -> local chains), otherwise pvo_ba_local clears it first.
@@ -1278,6 +1291,15 @@ int pvo_ba_finish(float* poses, float* disps, void* sys,
                   float lm, float ep, int motion_only, int clamp_frames, float disp_min,
                   float* dx_out, float* dz_out, int dz_rows, int* status_out,
                   void* workspace, size_t workspace_bytes, void* stream);
+/* pvo_ba_finish on a rank of an edge-sharded step whose `sys` was all-reduced as the dense image: graph_edges >= E is the edge count of
+ * the WHOLE graph (see above).  No riders. */
+int pvo_ba_finish_graph(float* poses, float* disps, void* sys,
+                        const int64_t* ii, const int64_t* jj,
+                        int E, int nframes, int ht, int wd, int t0, int t1,
+                        float lm, float ep, int motion_only, int clamp_frames, float disp_min,
+                        float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                        void* workspace, size_t workspace_bytes, int graph_edges, void* stream);
+int pvo_ba_solve_kind(int P, int graph_edges, int packed);      /* host only; -1 for a negative argument */
 /* Depth and pose uncertainty from the normal equations of ONE depth-BA Gauss-Newton step (no reference counterpart).  With the
  * notation of that step - P = t1 - t0, kx = unique([t0, t1) U ii), C the summed depth blocks, add = eta (alpha on pixels the
  * sensor-depth prior measures), Q = 1 / (C + add), the rows of depth frame k = its own pose row Ei[kx[k] - t0] and Eij[e] at pose

@@ -148,6 +148,9 @@ SIGNATURES = {
                           _i, _vp, _vp, _sz, _vp]),
     "pvo_ba_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _f,
                            _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "pvo_ba_finish_graph": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _f,
+                                 _vp, _vp, _i, _vp, _vp, _sz, _i, _vp]),
+    "pvo_ba_solve_kind": (_i, [_i, _i, _i]),
     "pvo_ba_finish_riders": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _f,
                                   _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
     "pvo_ba_finish_conv1x1": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _f,

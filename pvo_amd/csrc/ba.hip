@@ -105,14 +105,24 @@ struct Ws {
   double* xvec;          // ... and its solution [6P]
   float* Mrg;            // [E][6][HW]: the summed Eij rows of edges that share source AND target frame (Schur kernel), at the first one's index
   // dense windows (P <= kDenseMaxPoses), two-stage Schur sums: per (depth frame, 256-pixel chunk) the tile-pair sums of the chunk,
-  // the frame's row -> system-entry table and its tile count (0 = this frame went the atomic way)
+  // the frame's row -> system-entry table and its tile count (0 = this frame went the atomic way).  All three are indexed by the
+  // frame's staging SLOT (schur_stage_slot: by frame identity), not by its row in the call's plan
   float* spart;          // [kSchurStageFrames(P)][ceil(HW/256)][kSchurStagePairs][256]
   short* srow;           // [kSchurStageFrames(P)][128]
   int* sT;               // [kSchurStageFrames(P)]
   size_t bytes;
 };
 constexpr int kSchurStagePairs = 36;     // tile pairs of up to 8 row tiles
-__host__ __device__ __forceinline__ int schur_stage_frames(int P) { return (P > 0 && P <= 29) ? P + 8 : 0; }
+constexpr int kSchurStageFront = 8;      // source frames right in front of the window that have a staging slot beside the window's own
+__host__ __device__ __forceinline__ int schur_stage_frames(int P) { return (P > 0 && P <= 29) ? P + kSchurStageFront : 0; }
+// The staging slot of a depth frame, by the frame's IDENTITY: the window's frames [t0, t1) and the kSchurStageFront frames in front
+// of them, slot = frame - (t0 - kSchurStageFront); -1 = no slot, the frame's chunks go to the system one by one.  Whether a frame's
+// chunk sums are rounded to fixed point once or chunk by chunk changes the words of `sys`, so the choice must not read anything a
+// rank of an edge-sharded run sees differently (the row of the frame in this call's plan, the number of depth frames, the eta layout).
+__host__ __device__ __forceinline__ int schur_stage_slot(int frame, int t0, int P) {
+  const int slot = frame - t0 + kSchurStageFront;
+  return (slot >= 0 && slot < schur_stage_frames(P)) ? slot : -1;
+}
 
 __host__ size_t align_up(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
@@ -1049,10 +1059,11 @@ __device__ __forceinline__ void ba_schur_body(
   }
   BA_WG_PROBE(1, 4);                     // depth rows (and merged rows) stored
   const bool lds_path = lds_floats > 0 && T > kFastTiles && static_cast<long long>(nrows) * (PIX + kLdsRowPad) + PIX <= lds_floats;
-  const bool staged = lds_path && spart != nullptr && T * (T + 1) / 2 <= kSchurStagePairs;
-  if (sT != nullptr && blockIdx.x == 0 && zi == 0) {          // what ba_schur_reduce_kernel needs to know about this frame
-    if (tid == 0) sT[k] = staged ? T : 0;
-    if (staged && tid < 16 * T) srow[k * 128 + tid] = rowout[tid];
+  const int slot = schur_stage_slot(pl.kx[k], t0, P);        // (by frame identity: the same on every rank, whatever row k the frame has here)
+  const bool staged = lds_path && spart != nullptr && slot >= 0 && T * (T + 1) / 2 <= kSchurStagePairs;
+  if (sT != nullptr && slot >= 0 && blockIdx.x == 0 && zi == 0) {          // what ba_schur_reduce_kernel needs to know about this frame
+    if (tid == 0) sT[slot] = staged ? T : 0;
+    if (staged && tid < 16 * T) srow[slot * 128 + tid] = rowout[tid];
   }
   if (nrows == 0) return;
 
@@ -1107,7 +1118,7 @@ __device__ __forceinline__ void ba_schur_body(
     }
     __syncthreads();
     BA_WG_PROBE(1, 5);                   // (LDS form: rows staged)
-    float* part_out = staged ? spart + (static_cast<size_t>(k) * gridDim.x + blockIdx.x) * kSchurStagePairs * 256 : nullptr;
+    float* part_out = staged ? spart + (static_cast<size_t>(slot) * gridDim.x + blockIdx.x) * kSchurStagePairs * 256 : nullptr;
     for (int ti = 0; ti < T; ++ti) {
       if (ti == 1) BA_WG_PROBE(1, 6);    // (LDS form: first row pass - the longest: T tile pairs - done)
       const int ph = ti % (2 * Z);
@@ -1168,21 +1179,24 @@ __global__ __launch_bounds__(256) void ba_schur_mfma_kernel(
 
 // second stage of the dense-window Schur sums: tile pair p of depth frame k = the sum over the frame's chunks (fixed order, fp64: the
 // addends are fp32) -> one fixed-point atomic per entry.  Integer sums across frames as before: bitwise reproducible, and an
-// edge-sharded run gets the whole graph's bits (a frame's edges, hence its chunks, live on one rank).
+// edge-sharded run gets the whole graph's bits (a frame's edges, hence its chunks, live on one rank, and whether a frame is staged
+// is decided by its identity: schur_stage_slot).
 __global__ __launch_bounds__(256) void ba_schur_reduce_kernel(Plan pl, const float* __restrict__ spart, const short* __restrict__ srow,
-                                                              const int* __restrict__ sT, long long* __restrict__ sys, int gx, int n6) {
+                                                              const int* __restrict__ sT, long long* __restrict__ sys, int gx, int n6, int t0) {
   const int k = blockIdx.y, p = blockIdx.x, tid = threadIdx.x;
   if (k >= pl.meta[0]) return;
-  const int T = sT[k];
+  const int slot = schur_stage_slot(pl.kx[k], t0, n6 / 6);
+  if (slot < 0) return;
+  const int T = sT[slot];
   if (T == 0 || p >= T * (T + 1) / 2) return;
   __shared__ short rowout[128];
-  if (tid < 128) rowout[tid] = tid < 16 * T ? srow[k * 128 + tid] : static_cast<short>(-1);
+  if (tid < 128) rowout[tid] = tid < 16 * T ? srow[slot * 128 + tid] : static_cast<short>(-1);
   __syncthreads();
   int ti = 0, base = 0;
   while (base + (T - ti) <= p) { base += T - ti; ++ti; }
   const int tj = ti + (p - base);
   double v = 0.0;
-  const float* sp = spart + (static_cast<size_t>(k) * gx * kSchurStagePairs + p) * 256 + tid;
+  const float* sp = spart + (static_cast<size_t>(slot) * gx * kSchurStagePairs + p) * 256 + tid;
   const size_t step = static_cast<size_t>(kSchurStagePairs) * 256;
   for (int x0 = 0; x0 < gx; x0 += 8) {                     // (eight chunks' loads in flight; the additions keep the chunk order)
     float a[8];
@@ -3999,7 +4013,11 @@ extern "C" int pvo_ba_local(const float* poses, const float* disps, const float*
       hipLaunchKernelGGL(ba_depth_kernel, dim3((HW + 255) / 256, Kgrid), dim3(256), 0, st, w.plan, eta, K_eta, w.Eii, w.Cii, w.bz, w.Ei, w.Q, w.w, HW, t0, P, disps);
       PVO_CHECK_LAUNCH();
     }
-    const bool stage2 = dense_window && Kgrid <= schur_stage_frames(P);       // (the workspace holds the chunk sums of that many frames)
+    // two-stage Schur sums: on for every dense window; WHICH frames are staged is the kernel's choice by frame identity
+    // (schur_stage_slot: the window's frames and the kSchurStageFront in front of them - the slots the workspace holds).  Until this
+    // rule it was `Kgrid <= P + 8`, a count of THIS call's depth frames: a whole graph with more than 8 source frames in front of
+    // the window ran unstaged while its shards (fewer local depth rows) ran staged, and a broadcast eta (Kgrid = Kmax) flipped it too.
+    const bool stage2 = dense_window;
 #define PVO_SCHUR_LAUNCH(V, PX) hipLaunchKernelGGL((ba_schur_mfma_kernel<V, PX>), sgrid, dim3(256), (PX == 256 ? sdyn : 0), st, w.plan, jj, eta, K_eta, w.Eii, w.Cii, w.bz, w.Ei, \
                                                    w.Eij, w.Q, w.w, sys, HW, t0, P, two_stage ? w.part : nullptr, ii, E, chunksA, deal_rows, w.Mrg, depth_done, (PX == 256 ? lds_floats : 0), \
                                                    (stage2 && PX == 256) ? w.spart : nullptr, w.srow, stage2 ? w.sT : nullptr, disps)
@@ -4008,7 +4026,7 @@ extern "C" int pvo_ba_local(const float* poses, const float* disps, const float*
 #undef PVO_SCHUR_LAUNCH
     PVO_CHECK_LAUNCH();
     if (stage2) {
-      hipLaunchKernelGGL(ba_schur_reduce_kernel, dim3(kSchurStagePairs, Kgrid), dim3(256), 0, st, w.plan, w.spart, w.srow, w.sT, sys, gx, 6 * P);
+      hipLaunchKernelGGL(ba_schur_reduce_kernel, dim3(kSchurStagePairs, Kgrid), dim3(256), 0, st, w.plan, w.spart, w.srow, w.sT, sys, gx, 6 * P, t0);
       PVO_CHECK_LAUNCH();
     }
   }
@@ -4045,7 +4063,7 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
                           float lm, float ep, int motion_only, int clamp_frames, float disp_min,
                           float* dx_out, float* dz_out, int dz_rows, int* status_out,
                           void* workspace, size_t workspace_bytes,
-                          const pvo_ba_riders* jobs, void* stream);
+                          const pvo_ba_riders* jobs, int graph_edges, void* stream);
 
 extern "C" int pvo_ba_finish_riders(float* poses, float* disps, void* sys_,
                                     const int64_t* ii, const int64_t* jj,
@@ -4056,7 +4074,18 @@ extern "C" int pvo_ba_finish_riders(float* poses, float* disps, void* sys_,
                                     const pvo_ba_riders* jobs, void* stream) {
   if (!sys_) return PVO_EINVAL;
   return ba_finish_impl(poses, disps, sys_, nullptr, nullptr, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
-                        dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, jobs, stream);
+                        dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, jobs, -1, stream);
+}
+
+extern "C" int pvo_ba_finish_graph(float* poses, float* disps, void* sys_,
+                                   const int64_t* ii, const int64_t* jj,
+                                   int E, int nframes, int ht, int wd, int t0, int t1,
+                                   float lm, float ep, int motion_only, int clamp_frames, float disp_min,
+                                   float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                                   void* workspace, size_t workspace_bytes, int graph_edges, void* stream) {
+  if (!sys_ || graph_edges < E) return PVO_EINVAL;
+  return ba_finish_impl(poses, disps, sys_, nullptr, nullptr, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
+                        dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, graph_edges, stream);
 }
 
 extern "C" size_t pvo_ba_packed_elems(const int* first_host, int P) {
@@ -4088,11 +4117,15 @@ extern "C" int pvo_ba_finish_packed(float* poses, float* disps, const void* msg,
                                     void* workspace, size_t workspace_bytes, void* stream) {
   if (!msg || !first_s) return PVO_EINVAL;
   return ba_finish_impl(poses, disps, nullptr, static_cast<const long long*>(msg), first_s, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only,
-                        clamp_frames, disp_min, dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, stream);
+                        clamp_frames, disp_min, dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, -1, stream);
 }
 
-// The form that factorises the reduced pose system, from the free poses P, this call's edge count E, whether the system arrives as a
-// packed message (an edge-sharded step, whose ranks must all choose alike) and the debug knob PVO_KNOB_BA_SOLVER.  Shipped (knob 0):
+// The form that factorises the reduced pose system, from the free poses P, the edge count E OF THE WHOLE GRAPH, whether the system
+// arrives as a packed message and the debug knob PVO_KNOB_BA_SOLVER.  Every rank of an edge-sharded step factorises the same summed
+// system and must choose alike, so nothing here may be rank-local: a call on a shard whose system was all-reduced densely says how
+// many edges the whole graph has (pvo_ba_finish_graph); every other entry point's E is the graph's own count - the single-GPU
+// choice.  (Until this rule E was this call's count: of two unequal shards of a 438-edge, 39-pose graph, one with more than 8 P
+// edges took the 48 x 48 blocks and the other the envelope solve.)  pvo_ba_solve_kind states the rule to the host.  Shipped (knob 0):
 //   P = 0                     status words only (a packed message: nothing at all);
 //   P <= kDenseMaxPoses       dense on the fp64 matrix cores, ba_solve_dense_kernel: a window, one launch;
 //   E > 8 P, dense image      dense in 48 x 48 blocks over many workgroups: a global graph connected by proximity rather than a
@@ -4112,13 +4145,20 @@ static SolveForm solve_form(int P, int E, bool packed, int knob) {
   return {kSolveEnvelope, 2};
 }
 
+// host only, no GPU: the kind solve_form picks (0 status words only, 1 dense, 2 envelope, 3 one chain, 4 48 x 48 blocks) from what it
+// reads - the free poses, the whole graph's edge count, whether the system is a packed message - under the current debug knob
+extern "C" int pvo_ba_solve_kind(int P, int graph_edges, int packed) {
+  if (P < 0 || graph_edges < 0) return -1;
+  return static_cast<int>(solve_form(P, graph_edges, packed != 0, pvo_knob(PVO_KNOB_BA_SOLVER)).kind);
+}
+
 static int ba_finish_impl(float* poses, float* disps, void* sys_, const long long* msg, const int* first_s,
                           const int64_t* ii, const int64_t* jj,
                           int E, int nframes, int ht, int wd, int t0, int t1,
                           float lm, float ep, int motion_only, int clamp_frames, float disp_min,
                           float* dx_out, float* dz_out, int dz_rows, int* status_out,
                           void* workspace, size_t workspace_bytes,
-                          const pvo_ba_riders* jobs, void* stream) {
+                          const pvo_ba_riders* jobs, int graph_edges, void* stream) {
   Riders rider{};
   size_t rider_lds = 0;
   if (jobs && jobs->cy && jobs->crows > 0) {
@@ -4159,7 +4199,7 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
   Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   hipStream_t st = pvo_stream(stream);
   const int n6 = 6 * P;
-  const SolveForm form = solve_form(P, E, msg != nullptr, pvo_knob(PVO_KNOB_BA_SOLVER));
+  const SolveForm form = solve_form(P, graph_edges >= 0 ? graph_edges : E, msg != nullptr, pvo_knob(PVO_KNOB_BA_SOLVER));
   if (msg && form.kind == kSolveStatus) return PVO_OK;
   constexpr size_t kSolveLdsMax = 142000;      // dynamic LDS of a one-workgroup solve: the CU's 163840 B minus the envelope solve's 20528 B of static tables
   if (form.kind == kSolveDense) {

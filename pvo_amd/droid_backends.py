@@ -1350,14 +1350,28 @@ def ba_pack(sys, first_dev, msg):
     return msg
 
 
+BA_SOLVE_KINDS = ("status", "dense", "envelope", "chain", "blocks")
+
+
+def ba_solve_kind(P, graph_edges, packed=False):
+    """the form ba_finish factorises the reduced pose system with (pvo_ba_solve_kind: the host-side rule, no GPU), a name of
+    BA_SOLVE_KINDS, from what the rule reads: the free poses, the WHOLE graph's edge count, whether the system is a packed message"""
+    k = int(_lib.load().pvo_ba_solve_kind(int(P), int(graph_edges), 1 if packed else 0))
+    if k < 0:
+        raise PvoHipError("ba_solve_kind: P and graph_edges must not be negative")
+    return BA_SOLVE_KINDS[k]
+
+
 def ba_finish(poses, disps, sys, ii, jj, t0, t1, lm, ep, motion_only, workspace, dz_rows=0, status=None, outputs=True,
-              clamp_frames=0, disp_min=0.001, rider=None, packed=None):
+              clamp_frames=0, disp_min=0.001, rider=None, packed=None, graph_edges=None):
     """damp + solve the (all-reduced) system (left zeroed afterwards), retract poses, back-substitute this rank's depths -> [dx, dz]
     (outputs=False: poses / disps are updated in place and no dx / dz tensors are produced -> [None, None]).
     clamp_frames > 0: disps[:clamp_frames].clamp_(min=disp_min) in the same launch.
     rider = (x, w, bias): an independent 1x1 convolution of x [N,128,H,W] (conv1x1_c128 without ReLU) computed by additional
     workgroups of the pose solve's dispatch (pvo_ba_finish_conv1x1); its result is appended to the returned list.
-    packed = (msg, first_dev): the all-reduced envelope message of ba_pack instead of the dense `sys` (which is not read)."""
+    packed = (msg, first_dev): the all-reduced envelope message of ba_pack instead of the dense `sys` (which is not read).
+    graph_edges: the edge count of the WHOLE graph where ii / jj are a shard of it and `sys` was all-reduced densely
+    (pvo_ba_finish_graph) - the solve form is chosen from it, so every rank chooses alike; None: ii / jj are the whole graph."""
     dev = _dev(poses, disps, sys, ii, jj, workspace)
     rx = rw = rb = ry = None
     rrows = rC = rdt = 0
@@ -1388,6 +1402,17 @@ def ba_finish(poses, disps, sys, ii, jj, t0, t1, lm, ep, motion_only, workspace,
                 int(clamp_frames), float(disp_min), _ptr(dx), _ptr(dz), int(dz_rows),
                 _ptr(status) if status is not None else ctypes.c_void_p(0),
                 ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream(dev)), "ba_finish_packed")
+        return [dx, dz]
+    if graph_edges is not None:
+        if rider is not None:
+            raise PvoHipError("ba_finish: a rider and graph_edges together are not supported")
+        with torch.cuda.device(dev):
+            check(_lib.load().pvo_ba_finish_graph(
+                _ptr(poses), _ptr(disps), _ptr(sys), _ptr(ii), _ptr(jj), ii.shape[0], F, ht, wd,
+                int(t0), int(t1), float(lm), float(ep), 1 if motion_only else 0,
+                int(clamp_frames), float(disp_min), _ptr(dx), _ptr(dz), int(dz_rows),
+                _ptr(status) if status is not None else ctypes.c_void_p(0),
+                ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), int(graph_edges), _stream(dev)), "ba_finish_graph")
         return [dx, dz]
     with torch.cuda.device(dev):
         check(_lib.load().pvo_ba_finish_conv1x1(

@@ -143,6 +143,7 @@ class ShardedBA:
             self.db.ba_plan(ii_local, jj_local, F, ht * wd, K_eta, t0, t1, ws)
             self._plan_key, self._plan_edges = key, (ii_local, jj_local)
             self._env_idx = None
+            self._graph_edges = None                    # (the whole graph's edge count belongs to the edge set too)
             self._prior_key = None                      # (a fresh plan carries no prior)
             self._rig_key = 0.0                         # (... and no stereo baseline)
         prior_key = None if disps_sens is None or motion_only else (disps_sens.data_ptr(), float(alpha))
@@ -164,10 +165,24 @@ class ShardedBA:
                                  torch.empty(self.db.ba_packed_elems(first), dtype=torch.int64, device=disps.device))
             else:
                 self._env_idx = envelope_index(first, disps.device)
+        # the dense message: every rank factorises the same summed system and must pick the same solve form, which the library
+        # chooses by the edge count of the WHOLE graph - from `structure` where the caller gave it, else summed over the ranks once
+        # per plan (this rank's own count is what the library would read otherwise: two unequal shards, two forms)
+        fixed = hasattr(self.db, "BA_SYS_DTYPE")       # the HIP library: finish leaves the buffer zeroed
+        dense_msg = not (structure is not None and self._env_idx is not None and native)
+        if fixed and dense_msg and getattr(self, "_graph_edges", None) is None:
+            if structure is not None:
+                self._graph_edges = len(structure[0])
+            elif multi:
+                n = torch.tensor([E], dtype=torch.int64, device=disps.device)
+                self._allreduce(n)
+                self._graph_edges = int(n.item())
+            else:
+                self._graph_edges = E
         sys_buf = self._sys
         dx = None
         ii_local, jj_local = self._plan_edges          # the tensors the plan was built from
-        fixed = hasattr(self.db, "BA_SYS_DTYPE")       # the HIP library: finish leaves the buffer zeroed
+        fkw = {"graph_edges": self._graph_edges} if fixed and dense_msg and self._graph_edges != E else {}
         for it in range(itrs):
             kw = {"sys_is_zero": True} if fixed and self._sys_clean else {}
             self._sys_clean = False                     # (until this step's finish has run)
@@ -191,7 +206,7 @@ class ShardedBA:
             elif multi:
                 self._allreduce(sys_buf)                                           # the one collective per step
                 self.last_message_bytes = sys_buf.numel() * sys_buf.element_size()
-            dx, _ = self.db.ba_finish(poses, disps, sys_buf, ii_local, jj_local, t0, t1, lm, ep, motion_only, ws)
+            dx, _ = self.db.ba_finish(poses, disps, sys_buf, ii_local, jj_local, t0, t1, lm, ep, motion_only, ws, **fkw)
             self._sys_clean = fixed
         return dx
 

@@ -8,7 +8,9 @@ the comparison with a bound derived from the case's own sensitivity (`sensitivit
     reduced_system     (S, rhs): the undamped A - E Q E^T and its right-hand side in fp64 - the first half of rgbd_reference.gn_step
     reduced_abs        the same sums with every addend replaced by its magnitude: T, what a summation error is relative to
     decode_sys         the device's 64-bit fixed-point system -> fp64
-    sys_bound          (n_add + 16) 2^-24 T + n_fix 2^-29 per entry, n_add and n_fix read off pvo_amd/csrc/ba.hip (see n_add)
+    sys_bound          (n_add + 16) 2^-24 T + n_fix 2^-29 per entry, n_add and n_fix read off pvo_amd/csrc/ba.hip (see n_add) for the form
+                       of pvo_ba_local's launch rule that the window reaches
+    launch_form        that form, as a predicate over the graph (frame_rows, frame_paths): every GPU test asserts the one it claims
     case / admission   a (graph, regime, damping) triple with its fp64 step, s_case and the conditions it must meet to be used on the GPU
 
 ADMISSION (tests/test_ba_fp64_host.py asserts it for every name in ADMITTED, tests/test_ba_fp64_gpu.py runs exactly those):
@@ -82,7 +84,36 @@ GRAPHS = {
     "dense29_s8": dict(F=30, ht=8, wd=10, radius=2, seed=8),
     "twin39_s27": dict(F=40, ht=8, wd=10, radius=2, seed=27),
     "tiny_s9": dict(F=6, ht=9, wd=12, radius=2, seed=9),        # `behind`, two chained steps: the seed (of 1..24) whose chain meets the cap
+    # The windows that reach every form of pvo_ba_local's launch rule (launch_form below; LAUNCH_FORMS names the form each claims), the
+    # smallest that do.  What decides a frame's branch is its ROW count - 6 per distinct free neighbour and its own pose, + 1 - so a
+    # radius-2 graph (31 rows, two row tiles) reaches schur_pass only, at any chunk size: staging starts at 65 rows, radius 5.
+    # Maps of ~1600 pixels under one fixed frame miss the cap whatever the seed (F=30, t0=1, radius 5, 32 x 49 and 33 x 47: 4 s_case(dx)
+    # = 5.2e-3 .. 7.4e-3 over seeds 1..8; seed moves it by a third, the number of fixed frames by a factor of four), so the dense
+    # windows keep frames in front of the window fixed: t0 = 2 (win29 1.52e-3 at seed 7, 1.48e-3 at seed 4; win29_odd 1.62e-3, 1.52e-3),
+    # t0 = 3 for the wide window (mixed26: 2.9e-3 at t0 = 1, 2.5e-3 at 2, 1.35e-3 at 3).  `behind` on win29: 4 s_case(dx) = 0.15 .. 1.2
+    # over seeds 1..8 - no seed comes near the cap; it stays with the windows listed above.
+    "win29": dict(F=31, ht=32, wd=49, radius=5, t0=2),          # 7 chunks x 30 = 210 workgroups, P = 29: 19 frames of 67 rows staged, 12 on schur_pass
+    "win29_odd": dict(F=31, ht=33, wd=47, radius=5, t0=2),      # HW = 1551, HW & 3 != 0: the non-vector loads of the same form
+    # 20 free poses behind 10 fixed frames, 10 chunks x 21; frame 0 - ten frames in front of t0, beyond the 8 staging slots - sees 11
+    # free poses (67 rows): it fits the LDS but has no slot, schur_rowpass_lds straight into the system, beside 10 staged frames
+    "front10": dict(F=30, ht=48, wd=49, radius=5, t0=10, closures=([0] * 11, list(range(10, 21)))),
+    # 8 chunks x 26; radius 9: 9 middle frames hold 109 - 115 rows, too many for the LDS segment (107), and stream; 14 are staged
+    "mixed26": dict(F=28, ht=36, wd=50, radius=9, t0=3),
+    # 7 chunks x 31 = 217 workgroups, P = 30: 512-pixel chunks, 1568 = 3 x 512 + 32 leaves a partial last chunk; radius 5: 20 frames of
+    # five row tiles on schur_rowpass over the four z-slices, 11 on schur_pass.  Seed 7 meets the cap (1.86e-3)
+    "c512": dict(F=31, ht=32, wd=49, radius=5),
+    "c512_odd": dict(F=31, ht=33, wd=47, radius=5, seed=4),     # the non-vector variant; seed 4 (1.73e-3; seed 7: 1.91e-3, 1, 2, 3, 5: 2.05e-3 .. 2.7e-3)
+    # 17 chunks x 64 = 1088 workgroups: 1024-pixel chunks (4160 = 4 x 1024 + 64).  63 free poses on maps of 4160 pixels are ~50 times
+    # stiffer than gmem63's against the same ep, and the chain's far end floats: 4 s_case(dx) = 6.5e-3 (local) / 6.6e-2 (global) at
+    # weight 1, whatever the seed (1..8), t0 (2, 3, 5: 5.5e-3 .. 6.1e-3), radius (1: 7.9e-3, 3: 8.3e-3) or closures (7.5e-3 .. 1.1e-2).
+    # Weights and eta x 2^-8 put the entries where gmem63's are (1.81e-3; 2^-7: 2.7e-3, 2^-6: 3.7e-3), and gmem63's closures bring frame 1
+    # to 13 row blocks - five row tiles: schur_rowpass at 1024 pixels beside schur_pass - at 1.53e-3
+    "c1024": dict(F=64, ht=64, wd=65, radius=2, closures=_closures(range(52, 62)), scale=2.0 ** -8),
 }
+# graph -> the form of the launch rule its tests claim (asserted against launch_form before anything runs on the GPU)
+LAUNCH_FORMS = {"tiny": "fused256", "hw264": "fused256", "hw273": "fused256", "sb": "fused256", "blocked39": "fused256",
+                "win29": "window_staged", "win29_odd": "window_staged", "front10": "window_direct", "mixed26": "window_mixed",
+                "c512": "chunk512", "c512_odd": "chunk512", "c1024": "chunk1024"}
 
 
 def regime_window(name, seed=7, F=6, ht=9, wd=12, radius=2, t0=1, closures=None, scale=None):
@@ -259,11 +290,15 @@ def block_support(s):
 
 def fix_addends(s):
     """n_fix per block (S [P,P]) and per pose (rhs [P]): the fixed-point addends behind an entry - one per edge that reaches it (the
-    assembly's chunk sums are added in fp64 and quantised once per edge, ba.hip:891-893) and one per (depth frame, 256-pixel chunk)
-    whose rows hold both poses (scatter_tile, ba.hip:678-681)"""
+    assembly's chunk sums are added in fp64 and quantised once per edge, the deal rows of ba_schur_body: `val += part[...]` in double,
+    then __double2ll_rn) and, per depth frame whose rows hold both poses, what frame_paths counts for the frame's path: one per pixel
+    chunk of the launch's size (256, 512 or 1024: every chunk's tile-pair sum goes through scatter_tile's fix_add, in schur_pass,
+    schur_rowpass and schur_rowpass_lds without part_out alike), or ONE for a staged frame - its chunks' fp32 sums are added in fp64
+    by ba_schur_reduce_kernel (`v += static_cast<double>(a[u])`: exact to 2^-53, nothing at the 2^-24 scale of the bound) and that
+    sum is quantised once"""
     ii, jj, t0, t1 = s["ii"].numpy(), s["jj"].numpy(), s["t0"], s["t1"]
-    P, HW = t1 - t0, s["disps"].shape[1] * s["disps"].shape[2]
-    chunks = (HW + SCHUR_CHUNK - 1) // SCHUR_CHUNK
+    P = t1 - t0
+    paths = frame_paths(s)
     nS, nr = np.zeros((P, P)), np.zeros(P)
     by_frame = {}
     for i, j in zip(ii, jj):
@@ -274,8 +309,10 @@ def fix_addends(s):
         if 0 <= pi < P and 0 <= pj < P:
             nS[max(pi, pj), min(pi, pj)] += 1
         by_frame.setdefault(int(i), {pi}).add(pj)
-    for ps in by_frame.values():
+    for fr, ps in by_frame.items():
         ps = [p for p in ps if 0 <= p < P]
+        chunks = paths[fr][2]
+        assert chunks > 0 or not ps
         for a in ps:
             nr[a] += chunks
             for b in ps:
@@ -284,23 +321,122 @@ def fix_addends(s):
     return nS, nr
 
 
+# ------------------------------------------------------------------------------------------------ the launch rule
+# pvo_ba_local's size rules (ba.hip, "pixels per workgroup" down to the Schur launch) and ba_schur_body's per-frame branches, restated
+# as predicates over the GRAPH: every GPU test asserts the form it claims before it runs, so a rule change fails the test instead of
+# moving it onto another kernel.  The constants, where they are in ba.hip:
+FAST_TILES = 4            # kFastTiles: up to 4 row tiles (64 rows) take schur_pass, all tile pairs in one pass
+STAGE_PAIRS = 36          # kSchurStagePairs: tile pairs a staged frame may have (8 row tiles)
+STAGE_FRONT = 8           # kSchurStageFront: the frames in front of t0 that have a staging slot (schur_stage_slot)
+ROWS_LDS_FLOATS = 110 * 1024 // 4      # kSchurRowsLds: the dynamic LDS of the dense-window form
+LDS_ROW_PAD = 4           # kLdsRowPad
+DENSE_MAX_POSES = 29      # kDenseMaxPoses
+FORM_NAMES = ("fused256", "window_staged", "window_mixed", "window_direct", "chunk512", "chunk1024")
+
+
+def frame_rows(s):
+    """depth frame -> rows of its M in ba_schur_body's row table: 6 for its own pose if that is free, 6 per DISTINCT free target pose
+    of its out-edges (edges that share a target are merged into one row block), and the w row if there is any row at all"""
+    ii, jj, t0, t1 = s["ii"].numpy(), s["jj"].numpy(), s["t0"], s["t1"]
+    out = {}
+    for fr in np.unique(np.concatenate([np.arange(t0, t1), ii])):
+        tg = {int(j) for i, j in zip(ii, jj) if int(i) == int(fr) and t0 <= int(j) < t1}
+        r = 6 * (len(tg) + (1 if t0 <= int(fr) < t1 else 0))
+        out[int(fr)] = r + 1 if r else 0
+    return out
+
+
+def frame_paths(s):
+    """depth frame -> (path, chunk, n_fix): which branch of ba_schur_body sums the frame's tile pairs, the pixels per workgroup, and the
+    fixed-point addends the frame puts behind one entry.  Paths:
+      "none"    no rows (a source frame in front of the window whose targets are all fixed);
+      "pass"    T = ceil(rows / 16) <= kFastTiles: schur_pass, one addend per chunk;
+      "staged"  dense window, T > kFastTiles, the frame's rows fit the dynamic LDS (rows (256 + kLdsRowPad) + 256 <= kSchurRowsLds / 4,
+                that is rows <= 107; T (T + 1) / 2 <= kSchurStagePairs then holds by itself: T <= 7) and the frame has a staging slot
+                (t0 - kSchurStageFront <= frame < t1): schur_rowpass_lds -> spart -> ba_schur_reduce_kernel, ONE addend per frame;
+      "lds"     the same without a slot: schur_rowpass_lds straight into the system, one addend per chunk;
+      "stream"  T > kFastTiles otherwise: schur_rowpass from global memory (in a dense window: rows > 107), one addend per chunk"""
+    F, ht, wd = s["disps"].shape
+    t0, t1 = s["t0"], s["t1"]
+    P, HW = t1 - t0, ht * wd
+    wg = ((HW + 255) // 256) * min(F, P + 1)
+    dense = P <= DENSE_MAX_POSES and wg > 192
+    pix = 256 if (wg <= 192 or dense) else (512 if wg <= 1024 else 1024)
+    chunks = (HW + pix - 1) // pix
+    out = {}
+    for fr, rows in frame_rows(s).items():
+        T = (rows + 15) // 16
+        if rows == 0:
+            out[fr] = ("none", pix, 0)
+        elif T <= FAST_TILES:
+            out[fr] = ("pass", pix, chunks)
+        elif dense and rows * (256 + LDS_ROW_PAD) + 256 <= ROWS_LDS_FLOATS:
+            assert T * (T + 1) // 2 <= STAGE_PAIRS
+            slot = t0 - STAGE_FRONT <= fr < t1
+            out[fr] = ("staged", pix, 1) if slot else ("lds", pix, chunks)
+        else:
+            out[fr] = ("stream", pix, chunks)
+    return out
+
+
+def launch_form(s):
+    """the form of pvo_ba_local's Schur launch the window reaches, one of FORM_NAMES.  With chunks = ceil(HW / 256), frames = min(F, P + 1),
+    wg = chunks * frames (the rule reads the map size and the pose window only):
+      fused256        wg <= 192: 256-pixel chunks, the depth phase fused into the Schur kernel, four z-slices;
+      a dense window  wg > 192 and P <= 29: 256-pixel chunks, ONE slice, ba_depth_kernel in front, the dynamic LDS segment, and per frame
+                      (frame_paths) staged | lds | stream | pass.  Named by what its frames of more than kFastTiles row tiles do:
+        window_staged   all of them are staged (and there is one);
+        window_mixed    some are staged and some too wide for the LDS stream their rows: both in one launch;
+        window_direct   some are staged and some - more than kSchurStageFront frames in front of t0 - go from LDS straight to the system;
+      chunk512        P > 29, 192 < wg <= 1024: 512-pixel chunks, depth kernel in front, four z-slices;
+      chunk1024       P > 29, wg > 1024."""
+    F, ht, wd = s["disps"].shape
+    P, HW = s["t1"] - s["t0"], ht * wd
+    wg = ((HW + 255) // 256) * min(F, P + 1)
+    if wg <= 192:
+        return "fused256"
+    if P > DENSE_MAX_POSES:
+        return "chunk512" if wg <= 1024 else "chunk1024"
+    kinds = {p for p, _, _ in frame_paths(s).values()}
+    if "staged" not in kinds:
+        return "window_unstaged"      # (no test claims it: a dense window none of whose frames has more than four row tiles)
+    if "lds" in kinds:
+        return "window_direct"
+    return "window_mixed" if "stream" in kinds else "window_staged"
+
+
 def max_out_degree(s):
     return int(np.bincount(s["ii"].numpy()).max())
 
 
 # fp32 additions behind one fixed-point addend, read off pvo_amd/csrc/ba.hip:
 ASSEMBLE_CHUNK = 512      # kChunkA = 256 kPPT, kPPT = 2 pixels per thread (ba.hip:61-62)
-SCHUR_CHUNK = 256         # kSchurPix (ba.hip:622); pvo_ba_local keeps 256-pixel chunks while (HW / 256) (P + 1) <= 192 (ba.hip:3974-3983)
+SCHUR_CHUNK = 256         # kSchurPix (ba.hip:622); pvo_ba_local keeps 256-pixel chunks while (HW / 256) (P + 1) <= 192, and in a dense window
 
 
-def n_add(deg):
-    """the longest chain of fp32 additions behind one fixed-point addend, for a window whose frames have at most `deg` out-edges:
+def schur_chunk(s):
+    """pixels per workgroup of the window's Schur launch (pvo_ba_local's `pix`): 256, 512 or 1024"""
+    return next(iter(frame_paths(s).values()))[1]
+
+
+def n_add(deg, pix=SCHUR_CHUNK):
+    """the longest chain of fp32 additions behind one fixed-point addend, for a window whose frames have at most `deg` out-edges and
+    whose Schur launch takes `pix` pixels per workgroup (the line numbers are those of the 256-pixel form's first derivation; the
+    other forms are read off the same functions):
       pose part   2 kPPT = 4 per thread (two pixels, rows u and v: pixel_terms, ba.hip:287,312) + 6 steps of the wave's reduce-scatter
                   (ba.hip:499-526) + 2 across the four waves (ba.hip:538) = 12; the chunks of an edge are then added in fp64 (ba.hip:891);
       Schur part  64 per wave - a quarter of a 256-pixel chunk, 16 MFMAs of K = 4 (schur_pass, ba.hip:700-717) - + 2 across the waves
                   (ba.hip:733-734) = 66, on operands that are sums over the frame's out-edges themselves: Ei on either side, or w
-                  (deg - 1 each, depth_pixel ba.hip:582-589), C + eta (deg, ba.hip:584,603), the division and the product E Q (2)."""
-    return max(12, 66 + 2 * (deg - 1) + deg + 2)
+                  (deg - 1 each, depth_pixel ba.hip:582-589), C + eta (deg, ba.hip:584,603), the division and the product E Q (2).
+      512 / 1024  schur_pass<T, VEC4, PIX> and schur_rowpass<CNT, VEC4, PIX> are templates over the chunk: a wave owns PIX / 4 pixels
+                  (pix_base = blockIdx.x PIX + wave PIX / 4) and walks them in PIX / 64 steps of four MFMAs of K = 4 - one product per pixel
+                  added to the accumulator, a chain of PIX / 4 = 128 / 256 - then the same (w0 + w1) + (w2 + w3) across the waves:
+                  PIX / 4 + 2.  The z-slices of the 512 / 1024 grids deal whole ROW TILES over workgroups (ti by the snake in
+                  ba_schur_body); every tile pair is still one workgroup's chain, so they add nothing.  The operands are those of the
+                  256-pixel form: ba_depth_kernel runs depth_pixel itself.
+      dense window   schur_rowpass_lds<CNT, 256>: the same chain from LDS, 64 + 2 per chunk; a staged frame's chunk sums then meet in
+                  fp64 (ba_schur_reduce_kernel), which lengthens no fp32 chain - see fix_addends for what it does to n_fix."""
+    return max(12, pix // 4 + 2 + 2 * (deg - 1) + deg + 2)
 
 
 def sys_bound(s, T):
@@ -308,7 +444,7 @@ def sys_bound(s, T):
     perturbation s_case is defined with; 2^-29 is half a unit of the 2^-28 fixed-point grid (fix_add, ba.hip:52-58)."""
     TS, Tr = T
     nS, nr = fix_addends(s)
-    k = (n_add(max_out_degree(s)) + 16) * 2.0 ** -24
+    k = (n_add(max_out_degree(s), schur_chunk(s)) + 16) * 2.0 ** -24
     return k * TS + np.kron(nS, np.ones((6, 6))) * 2.0 ** -29, k * Tr + np.repeat(nr, 6) * 2.0 ** -29
 
 
@@ -458,5 +594,7 @@ FORMS = [("dense5", "control", "global"), ("dense5", "behind", "local"),
          ("gmem63", "control", "global"),
          ("blocked39", "control", "local"),
          ("sb", "control", "global")]
-ADMITTED = TINY + SHAPES + FORMS
+# ... and under every form of the launch rule (LAUNCH_FORMS): cut A and cut C
+LAUNCHES = [(g, "control", "local") for g in ("win29", "win29_odd", "front10", "mixed26", "c512", "c512_odd", "c1024")]
+ADMITTED = TINY + SHAPES + FORMS + LAUNCHES
 TWO_STEPS = [("tiny", "control", "local"), ("tiny_s9", "behind", "local")]

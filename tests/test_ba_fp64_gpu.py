@@ -10,7 +10,9 @@ tests/calib_reference.py, qualified and admitted case by case in tests/test_ba_f
   the failure contract    include/pvo_hip.h under pvo_ba: a poisoned operand is a status and a zero pose update, never a wrong one.
 
 Nothing here compares the device with itself, except the two repeatability assertions (a second ba_local, a call after a rejected
-one).  Every test prints the device's share of its bound (profiles/r15_ba_fp64.txt)."""
+one).  Every test prints the device's share of its bound (profiles/r15_ba_fp64.txt;
+profiles/r23_ba_launch_forms.txt for the windows of ba_reference.LAUNCHES, one per form of pvo_ba_local's launch rule - each of them
+asserts the form it claims before it runs)."""
 import ctypes
 
 import numpy as np
@@ -68,7 +70,7 @@ n64 = lambda t: t.detach().cpu().numpy().astype(np.float64)
 
 
 # ------------------------------------------------------------------------------------------------ A: the reduced system
-_CUT_A = sorted({(g, r) for g, r, _ in B.TINY + B.SHAPES})
+_CUT_A = sorted({(g, r) for g, r, _ in B.TINY + B.SHAPES}) + [(g, r) for g, r, _ in B.LAUNCHES]      # the 256-pixel fused form, then every other
 
 
 @pytest.mark.parametrize("graph,regime", _CUT_A, ids=["-".join(k) for k in _CUT_A])
@@ -77,7 +79,8 @@ def test_reduced_system_matches_fp64_within_the_summation_bound(cuda, graph, reg
     s, f = B.window_of(graph, regime)
     F, ht, wd = s["disps"].shape
     P, HW = s["t1"] - s["t0"], ht * wd
-    assert ((HW + 255) // 256) * (P + 1) <= 192                                  # the 256-pixel Schur chunks n_add counts (ba_reference.SCHUR_CHUNK)
+    form = B.launch_form(s)
+    assert form == B.LAUNCH_FORMS[graph]                                       # the form n_add and fix_addends count for (ba_reference.frame_paths)
     S, rhs = B.reduced_system(f, s)
     bS, br = B.sys_bound(s, B.reduced_abs(f, s))
     o = _operands(s, cuda)
@@ -99,7 +102,7 @@ def test_reduced_system_matches_fp64_within_the_summation_bound(cuda, graph, reg
     eS, er = np.abs(Sd - S), np.abs(rd - rhs)
     sel = low & sup
     sh_S, sh_r = float((eS[sel] / bS[sel]).max()), float((er / br).max())
-    print("%s-%s: reduced system, device's share of the bound S %.3f rhs %.3f (largest entry %.2e)" % (graph, regime, sh_S, sh_r, np.abs(S).max()))
+    print("%s-%s [%s]: reduced system, device's share of the bound S %.3f rhs %.3f (largest entry %.2e)" % (graph, regime, form, sh_S, sh_r, np.abs(S).max()))
     assert np.all(eS[sel] <= bS[sel]) and np.all(er <= br)
     assert raw[sel].any() and np.abs(Sd).max() > 0.5 * np.abs(S).max()
 
@@ -209,10 +212,12 @@ def _assert_step(name, c, dx, dz, st):
     assert ok_x and ok_z
 
 
-@pytest.mark.parametrize("key", B.TINY + B.FORMS, ids=_id)
+@pytest.mark.parametrize("key", B.TINY + B.FORMS + B.LAUNCHES, ids=_id)
 def test_one_step_matches_the_fp64_step_within_its_own_sensitivity(cuda, key):
     c = B.case(*key)
     s, base = c["s"], c["base"]
+    if key in B.LAUNCHES:
+        assert B.launch_form(s) == B.LAUNCH_FORMS[key[0]]
     o = _operands(s, cuda)
     dx, dz, st = _ba(o, s, 1, c["lm"], c["ep"])
     _assert_step(_id(key), c, dx, dz, st)
