@@ -108,11 +108,18 @@ enum {
   PVO_KNOB_HEADS_GATHER_FLAT = 1, /* 1: pvo_heads_gather without its LDS-tiled form */
   PVO_KNOB_NO_RIDERS = 2,         /* 1: pvo_graph_update computes the upsampling mask and the next gate context as launches of their own */
   PVO_KNOB_POST_SEPARATE = 3,     /* 1: pvo_graph_update runs pvo_graph_post as a launch of its own instead of as the epilogue of the heads' gather */
-  PVO_KNOB_EDGE_BLOCKS = 4,       /* the update operator's gates -> candidate -> heads per block of edges on two streams (bit-identical to the whole launches; E >= 3 and not PVO_OP_SINGLE_STREAM): 0 shipped choice (value 6 where the gate launch has more workgroups than two per compute unit, off below) | 1 off | 2 + s + 2 p + 4 g: leading block = E/2 (s = 0) or E/3 (s = 1) edges on the launch stream, the trailing block on a stream of the library's of the same (p = 0) or the lowest (p = 1) priority, GraphAgg.conv1 whole (g = 0) or per block (g = 1) */
+  PVO_KNOB_EDGE_BLOCKS = 4,       /* the update operator's gates -> candidate -> heads per block of edges on two streams (bit-identical to the whole launches; E >= 3 and not PVO_OP_SINGLE_STREAM; values 2 ... 17): 0 shipped choice (value 14 where the gate launch has more workgroups than two per compute unit, off below) | 1 off | 2 + s + 2 p + 4 g + 8 t: leading block = E/2 (s = 0) or E/3 (s = 1) edges on the launch stream, the trailing block on a stream of the library's of the same (p = 0) or the lowest (p = 1) priority, GraphAgg.conv1 whole (g = 0) or per block (g = 1) ; t = 1: the trunk per block as well - each block's lookup -> corr_encoder[2] and 7x7 -> flow_encoder[2] in front of its own gates, the trailing block's beside the leading block's gates; the leading block then goes on on the library's stream and the trailing one on the launch stream (with PVO_OP_ENC_SIDE_STREAM and cached static terms; the whole trunk otherwise) */
   PVO_KNOB_COUNT = 5
 };
 int pvo_debug_config(int knob, int value);
 int pvo_knob(int knob); /* current value (0 for an unknown knob) */
+/* Test hook: edges [e0, e1) of one launch of the update's trunk, as the edge-blocked trunk (PVO_KNOB_EDGE_BLOCKS, t = 1) issues it - the
+ * whole launch's workgroups (.., e0 + z) on the whole launch's operands, so the rows of those edges get the whole launch's bits and no
+ * other row is written.  which = 0 pvo_corr_lookup_encode_tiled (levels, x = coords, slots, num_slots) | 1 pvo_corr_encode (x = corr
+ * [E*H*W,196]) | 2 pvo_conv7x7_c8 | 3 pvo_conv3x3_c128 (Cout, relu, ystride, yoff); arguments a launch does not take are ignored. */
+int pvo_debug_trunk_range(int which, const void* const* levels, const void* x, const void* w, const float* bias, void* y,
+                          int E, int e0, int e1, int H, int W, int Cout, int relu, int ystride, int yoff,
+                          const int* slots, int num_slots, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Correlation lookup                                                         */

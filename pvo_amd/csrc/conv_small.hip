@@ -786,21 +786,29 @@ extern "C" int pvo_debug_conv_probe(void* buf) {
 }
 #endif
 
-extern "C" int pvo_conv7x7_c8(const void* x, const void* w_taps, const float* bias, void* y,
-                              int E, int H, int W, int dtype, void* stream) {
-  if (E < 0 || H < 0 || W < 0) return PVO_EINVAL;
+// (edges [e0, e1): x and y moved to edge e0, grid.z = e1 - e0 - the contract in front of launch_big below)
+int pvo_internal_conv7x7_c8_range(const void* x, const void* w_taps, const float* bias, void* y, int E, int e0, int e1, int H, int W,
+                                  int dtype, void* stream) {
+  if (E < 0 || H < 0 || W < 0 || e0 < 0 || e1 < e0 || e1 > E) return PVO_EINVAL;
   if (E == 0 || H == 0 || W == 0) return PVO_OK;
   if (!x || !w_taps || !bias || !y || E > 65535) return PVO_EINVAL;
   if (pvo_misaligned16(x, w_taps, y)) return PVO_EINVAL;
+  if (e1 == e0) return PVO_OK;
   hipStream_t st = pvo_stream(stream);
-  dim3 grid((W + kTW - 1) / kTW, (H + kTH7 - 1) / kTH7, E);
+  dim3 grid((W + kTW - 1) / kTW, (H + kTH7 - 1) / kTH7, e1 - e0);
+  const size_t px0 = static_cast<size_t>(e0) * H * W;      // pixels in front of edge e0
   return pvo_dispatch16(dtype, [&](auto tag) -> int {
     using T = decltype(tag);
-    hipLaunchKernelGGL(conv7x7_c8_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x),
-                       static_cast<const uint16_t*>(w_taps), bias, static_cast<uint16_t*>(y), H, W);
+    hipLaunchKernelGGL(conv7x7_c8_kernel<T>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x) + px0 * 8,
+                       static_cast<const uint16_t*>(w_taps), bias, static_cast<uint16_t*>(y) + px0 * 128, H, W);
     PVO_CHECK_LAUNCH();
     return PVO_OK;
   });
+}
+
+extern "C" int pvo_conv7x7_c8(const void* x, const void* w_taps, const float* bias, void* y,
+                              int E, int H, int W, int dtype, void* stream) {
+  return pvo_internal_conv7x7_c8_range(x, w_taps, bias, y, E, 0, E, H, W, dtype, stream);
 }
 
 extern "C" int pvo_flow_encoder(const void* x, const void* w7_taps, const float* bias7, const void* w3_taps, const float* bias3,
@@ -843,33 +851,41 @@ extern "C" int pvo_gru_glo_fused(const void* net, const void* w_weight, const fl
   });
 }
 
-extern "C" int pvo_conv3x3_c128(const void* x, const void* w_taps, const float* bias, void* y,
-                                int E, int H, int W, int Cout, int relu, int ystride, int yoff, int dtype, void* stream) {
-  if (E < 0 || H < 0 || W < 0) return PVO_EINVAL;
+int pvo_internal_conv3x3_c128_range(const void* x, const void* w_taps, const float* bias, void* y, int E, int e0, int e1, int H, int W,
+                                    int Cout, int relu, int ystride, int yoff, int dtype, void* stream) {
+  if (E < 0 || H < 0 || W < 0 || e0 < 0 || e1 < e0 || e1 > E) return PVO_EINVAL;
   if (Cout != 64 && (Cout <= 0 || (Cout & 127))) return PVO_EUNSUPPORTED;
   if (ystride == 0) ystride = Cout;
   if (ystride < yoff + Cout || yoff < 0 || (ystride & 7) || (yoff & 7)) return PVO_EINVAL;
   if (E == 0 || H == 0 || W == 0) return PVO_OK;
   if (!x || !w_taps || !y || E > 65535) return PVO_EINVAL;
   if (pvo_misaligned16(x, w_taps, y)) return PVO_EINVAL;
+  if (e1 == e0) return PVO_OK;
   hipStream_t st = pvo_stream(stream);
   const int ntx = (W + kTW - 1) / kTW;
   const size_t lds = static_cast<size_t>(kC3Halo) * kC3Stride;      // 48960 B >= the output slab (128 px x 272 B)
-  const uint16_t* xp = static_cast<const uint16_t*>(x);
+  const size_t px0 = static_cast<size_t>(e0) * H * W;               // pixels in front of edge e0: x and y move there, grid.z = e1 - e0
+  const int En = e1 - e0;
+  const uint16_t* xp = static_cast<const uint16_t*>(x) + px0 * 128;
   const uint16_t* wp = static_cast<const uint16_t*>(w_taps);
-  uint16_t* yp = static_cast<uint16_t*>(y);
+  uint16_t* yp = static_cast<uint16_t*>(y) + px0 * ystride;
   return pvo_dispatch16(dtype, [&](auto tag) -> int {
     using T = decltype(tag);
     if (Cout == 64) {
-      dim3 grid(ntx, (H + kTH - 1) / kTH, E);
+      dim3 grid(ntx, (H + kTH - 1) / kTH, En);
       hipLaunchKernelGGL((conv3x3_c128_kernel<T, 1>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cout, relu, ystride, yoff);
     } else {
-      dim3 grid(ntx * (Cout / 128), (H + kTH - 1) / kTH, E);
+      dim3 grid(ntx * (Cout / 128), (H + kTH - 1) / kTH, En);
       hipLaunchKernelGGL((conv3x3_c128_kernel<T, 2>), grid, dim3(256), lds, st, xp, wp, bias, yp, H, W, Cout, relu, ystride, yoff);
     }
     PVO_CHECK_LAUNCH();
     return PVO_OK;
   });
+}
+
+extern "C" int pvo_conv3x3_c128(const void* x, const void* w_taps, const float* bias, void* y,
+                                int E, int H, int W, int Cout, int relu, int ystride, int yoff, int dtype, void* stream) {
+  return pvo_internal_conv3x3_c128_range(x, w_taps, bias, y, E, 0, E, H, W, Cout, relu, ystride, yoff, dtype, stream);
 }
 
 // Edges [e0, e1) of an E-edge call: every per-edge operand is moved to edge e0 and grid.z = e1 - e0, so a workgroup computes what

@@ -26,6 +26,7 @@
 #pragma clang fp contract(off)
 
 #include "operand16.h"
+#include "conv_range.h"
 
 namespace {
 
@@ -715,11 +716,13 @@ extern "C" int pvo_corr_pyramid_lookup_tiled(const void* const* volumes_host, co
   return dispatch_lookup(a, 3, dtype, pvo_stream(stream));
 }
 
-extern "C" int pvo_corr_lookup_encode_tiled(const void* const* volumes_host, const float* coords,
-                                            const void* enc_weight, const float* enc_bias, void* out,
-                                            int N, int h1, int w1, int dtype,
-                                            const int* slots, int num_slots, void* stream) {
-  if (N < 0 || h1 < 0 || w1 < 0 || !volumes_host) return PVO_EINVAL;
+// Edges [e0, e1) of an N-edge call (conv_range.h): the grid's edge dimension is e1 - e0 and every per-edge operand is moved to edge e0 -
+// coords, out, and the slot table; the pool base and num_slots stay.  Without a slot table edge n reads volume n, so each level's
+// base moves by e0 volumes instead.
+int pvo_internal_corr_lookup_encode_tiled_range(const void* const* volumes_host, const float* coords, const void* enc_weight,
+                                                const float* enc_bias, void* out, int N, int e0, int e1, int h1, int w1, int dtype,
+                                                const int* slots, int num_slots, void* stream) {
+  if (N < 0 || h1 < 0 || w1 < 0 || !volumes_host || e0 < 0 || e1 < e0 || e1 > N) return PVO_EINVAL;
   if (dtype != PVO_F16 && dtype != PVO_BF16) return PVO_EUNSUPPORTED;
   if (N == 0 || h1 == 0 || w1 == 0) return PVO_OK;
   if (!coords || !out || !enc_weight || !enc_bias) return PVO_EINVAL;
@@ -736,11 +739,26 @@ extern "C" int pvo_corr_lookup_encode_tiled(const void* const* volumes_host, con
     a.lv[l] = LookupLevel{volumes_host[l], static_cast<long long>(slots ? num_slots : N) * h1 * w1 * pe, hl, wl,
                           1.0f / static_cast<float>(1 << l), tw, pe};
   }
-  a.coords = coords; a.out = out; a.nlev = kMaxLevels; a.coords_interleaved = 1; a.HW = h1 * w1; a.N = N;
+  const long long px0 = static_cast<long long>(e0) * h1 * w1;      // pixels (= volume planes) in front of edge e0
+  if (!slots)
+    for (int l = 0; l < kMaxLevels; ++l) {
+      a.lv[l].vol = static_cast<const uint16_t*>(a.lv[l].vol) + px0 * a.lv[l].plane_elems;
+      a.lv[l].total -= px0 * a.lv[l].plane_elems;
+    }
+  a.coords = coords + px0 * 2; a.out = static_cast<uint16_t*>(out) + px0 * 128; a.nlev = kMaxLevels; a.coords_interleaved = 1;
+  a.HW = h1 * w1; a.N = e1 - e0;
   a.out_channels_last = 1;
-  a.slots = slots;
+  a.slots = slots ? slots + e0 : nullptr;
   a.enc_w = enc_weight; a.enc_b = enc_bias;
   return dispatch_lookup(a, 3, dtype, pvo_stream(stream));
+}
+
+extern "C" int pvo_corr_lookup_encode_tiled(const void* const* volumes_host, const float* coords,
+                                            const void* enc_weight, const float* enc_bias, void* out,
+                                            int N, int h1, int w1, int dtype,
+                                            const int* slots, int num_slots, void* stream) {
+  return pvo_internal_corr_lookup_encode_tiled_range(volumes_host, coords, enc_weight, enc_bias, out, N, 0, N, h1, w1, dtype, slots,
+                                                     num_slots, stream);
 }
 
 extern "C" int pvo_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad,

@@ -14,6 +14,7 @@
 #include "operand16.h"
 #include "conv1x1_tile.h"
 #include "glo_tile.h"
+#include "conv_range.h"
 
 namespace {
 
@@ -245,6 +246,17 @@ extern "C" int pvo_conv1x1_c128(const void* x, const void* w, const float* bias,
     PVO_CHECK_LAUNCH();
     return PVO_OK;
   });
+}
+
+// rows [e0 * HW, e1 * HW) of an E-edge call (conv_range.h): corr and y moved to the first of them
+int pvo_internal_corr_encode_range(const void* corr, const void* enc_weight, const float* enc_bias, void* y, int E, int e0, int e1,
+                                   int HW, int dtype, void* stream) {
+  if (E < 0 || HW < 0 || e0 < 0 || e1 < e0 || e1 > E) return PVO_EINVAL;
+  if (static_cast<long long>(E) * HW > (1LL << 31) - 64) return PVO_EINVAL;
+  if (!corr || !y) return (E == 0 || HW == 0) ? PVO_OK : PVO_EINVAL;
+  const size_t r0 = static_cast<size_t>(e0) * HW;
+  return pvo_corr_encode(static_cast<const uint16_t*>(corr) + r0 * 196, enc_weight, enc_bias, static_cast<uint16_t*>(y) + r0 * 128,
+                         static_cast<long long>(e1 - e0) * HW, dtype, stream);
 }
 
 extern "C" int pvo_corr_encode(const void* corr, const void* enc_weight, const float* enc_bias, void* y, long long rows,

@@ -61,14 +61,16 @@ SideCtx* side_ctx() {
 // every fork / join of the schedule has an event of its own.  (Round 21 also measured the leading block on a stream of the
 // HIGHEST priority with the trailing one on the launch stream, so that the join in front of the gather is already satisfied
 // when the launch stream reaches it: no better than the shipped choice, not kept - DESIGN.md section 5.)
-struct WaveCtx { hipStream_t s[2]; bool has[2]; hipEvent_t fork, cand0, cand1, join; bool events; };
+// (enc, lk, flow0, flow1, ctx: the blocked trunk's fork of the side stream, the leading block's lookup - where this stream forks
+// from the launch stream -, the two blocks' flow features, and the gate context where this call computes it: run_trunk_blocked)
+struct WaveCtx { hipStream_t s[2]; bool has[2]; hipEvent_t fork, cand0, cand1, join, enc, lk, flow0, flow1, ctx; bool events; };
 WaveCtx g_wave_ctx[64] = {};
 WaveCtx* wave_ctx(bool low) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
   WaveCtx& c = g_wave_ctx[dev];
   if (!c.events) {
-    for (hipEvent_t* e : {&c.fork, &c.cand0, &c.cand1, &c.join})
+    for (hipEvent_t* e : {&c.fork, &c.cand0, &c.cand1, &c.join, &c.enc, &c.lk, &c.flow0, &c.flow1, &c.ctx})
       if (hipEventCreateWithFlags(e, g_event_flags) != hipSuccess) return nullptr;
     c.events = true;
   }
@@ -82,11 +84,11 @@ WaveCtx* wave_ctx(bool low) {
 }
 
 // PVO_KNOB_EDGE_BLOCKS decoded: lead = edges of the leading block (0: the schedule is off)
-struct EdgeBlocks { int lead; bool low, agg; };
-// What knob value 0 means: equal halves, GraphAgg.conv1 per block, where the gate launch has more
-// workgroups than the device holds at once (two per compute unit) - the schedule recovers the partly filled rounds of launches
-// that take several, and a launch that fits one round has none to recover, only four events more to pay for.
-constexpr int kEdgeBlocksShipped = 2 + 4;
+struct EdgeBlocks { int lead; bool low, agg, trunk; };
+// What knob value 0 means (rounds 21 and 24): equal halves, GraphAgg.conv1 and the trunk per block, where the
+// gate launch has more workgroups than the device holds at once (two per compute unit) - the schedule recovers the partly filled
+// rounds of launches that take several, and a launch that fits one round has none to recover, only the events more to pay for.
+constexpr int kEdgeBlocksShipped = 2 + 4 + 8;
 constexpr int kMinBlockedEdges = 3;        // below it a 1/3 block is empty
 int resident_conv_workgroups() {
   static int slots[64] = {};
@@ -102,9 +104,9 @@ EdgeBlocks edge_blocks(int E, int H, int W, unsigned flags) {
     const int slots = resident_conv_workgroups();
     v = (slots > 0 && gate_workgroups > slots) ? kEdgeBlocksShipped : 1;
   }
-  if (v < 2 || v > 9 || E < kMinBlockedEdges || (flags & PVO_OP_SINGLE_STREAM)) return {0, false, false};
+  if (v < 2 || v > 17 || E < kMinBlockedEdges || (flags & PVO_OP_SINGLE_STREAM)) return {0, false, false, false};
   v -= 2;
-  return {(v & 1) ? E / 3 : E / 2, (v & 2) != 0, (v & 4) != 0};
+  return {(v & 1) ? E / 3 : E / 2, (v & 2) != 0, (v & 4) != 0, (v & 8) != 0};
 }
 
 size_t al(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
@@ -268,8 +270,77 @@ int run_trunk(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, 
   return PVO_OK;
 }
 
+// The trunk per block of edges (PVO_KNOB_EDGE_BLOCKS' trunk bit), up to the point where each block's
+// gates can be launched.  The edges are independent images up to the gather: block b's gates read block b's rows of CF only, and
+// those come from b's lookup -> corr_encoder[2] and b's 7x7 -> flow_encoder[2].  With A = [0, lead) and B = [lead, E):
+//   launch stream  fork -> lookup(A) -> `lk` -> lookup(B) -> corr_encoder[2](B) -> (wait ctx) -> wait flow1          [-> gates(B) ...]
+//   wave stream    (wait fork -> context pair -> `ctx`) -> wait lk -> corr_encoder[2](A) -> wait flow0               [-> gates(A) ...]
+//   side stream    wait fork -> 7x7(A) -> flow_encoder[2](A) -> `flow0` -> 7x7(B) -> flow_encoder[2](B) -> `flow1`   [-> GraphAgg]
+// so that A's gates start when A's front is done and B's front - memory-side work - runs beside them on an otherwise idle matrix
+// pipe.  The two lookups are back to back on the launch stream (side by side they share the request rate they saturate and finish
+// together), and the wave stream forks from the LAUNCH stream through `lk`: it inherits whatever the launch stream had in front of
+// the lookup (the keyframe boundary's volume build among it).  The range launches run the whole launches' workgroups on the same
+// operands: bit-identical.  (Round 24 also measured lookup(B) -> B's chain on the wave stream with A staying on the launch stream:
+// B's flow_encoder[2], last on the side stream, then crawls beside A's gates and B's gates start 60 us late - 4 % SLOWER than the
+// whole trunk, profiles/r24_bench_alternating_exploration.jsonl; not kept.)
+// The context pair, where this call computes it (the first update of a step), stays whole and runs on the wave stream, which has
+// nothing else to do until `lk`: on the launch stream behind corr_encoder[2](B) both blocks' gates waited 27 us for it (the update
+// 665 us against 623, +0.65 % of the step - round 24).  Both blocks' gates are ordered behind it: A's by stream order, B's by `ctx`.
+// Only for cached static terms and no motion job (the caller checks); everything else is run_trunk.
+int run_trunk_blocked(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, WaveCtx* wc, void* wave, int lead,
+                      const int** ps, bool context_ready, const int* static_rows) {
+  const int E = a->E, H = a->H, W = a->W, dt = w->dtype;
+  hipStream_t st = pvo_stream(stream), ws = pvo_stream(wave);
+  SideCtx* sc = side_ctx();
+  if (!sc) return PVO_ELAUNCH;
+  if (!a->levels[0] && !a->corr) return PVO_EINVAL;
+  *ps = static_rows ? static_rows : a->static_by_slot ? a->slots : nullptr;
+  if (!static_rows && a->static_by_slot && !a->slots) return PVO_EINVAL;
+  auto lookup = [&](int e0, int e1) -> int {
+    if (a->levels[0])
+      return pvo_internal_corr_lookup_encode_tiled_range(a->levels, a->coords, w->enc0_w, w->enc0_b, b.c1, E, e0, e1, H, W, dt, a->slots,
+                                                         a->num_slots, stream);
+    return pvo_internal_corr_encode_range(a->corr, w->enc0_w, w->enc0_b, b.c1, E, e0, e1, H * W, dt, stream);
+  };
+  auto cenc2 = [&](int e0, int e1, void* s) -> int {
+    if (w->flags & PVO_OP_CONV128_WIDE)
+      return pvo_internal_conv3x3_range(b.c1, w->cenc2_w, w->cenc2_b, b.CF, E, e0, e1, H, W, 128, 128, 1, 192, 0, dt, s);
+    return pvo_internal_conv3x3_c128_range(b.c1, w->cenc2_w, w->cenc2_b, b.CF, E, e0, e1, H, W, 128, 1, 192, 0, dt, s);
+  };
+  if (hipEventRecord(wc->enc, st) != hipSuccess) return PVO_ELAUNCH;
+  if (hipStreamWaitEvent(sc->side, wc->enc, 0) != hipSuccess) return PVO_ELAUNCH;
+  if (!context_ready) {
+    if (hipStreamWaitEvent(ws, wc->enc, 0) != hipSuccess) return PVO_ELAUNCH;
+    RUN(pvo_gru_glo_fused(a->net, w->glo_w, w->glo_b, b.part, E, H * W, dt, wave));
+    RUN(pvo_gate_context(b.part, w->gate_wt, w->gate_b, b.g, E, pvo_gru_glo_chunks(H * W), wave));
+    if (hipEventRecord(wc->ctx, ws) != hipSuccess) return PVO_ELAUNCH;
+  }
+  if (a->levels[0]) {
+    probe_mark(PVO_STAGE_EMPTY, 0, stream);      // (calibration, as in run_trunk)
+    probe_mark(PVO_STAGE_EMPTY, 1, stream);
+    probe_mark(PVO_STAGE_LOOKUP, 0, stream);     // the pair spans BOTH lookups: the time all E edges took
+  }
+  RUN(lookup(0, lead));
+  if (hipEventRecord(wc->lk, st) != hipSuccess) return PVO_ELAUNCH;
+  if (hipStreamWaitEvent(ws, wc->lk, 0) != hipSuccess) return PVO_ELAUNCH;
+  RUN(lookup(lead, E));
+  if (a->levels[0]) probe_mark(PVO_STAGE_LOOKUP, 1, stream);
+  const struct { int e0, e1; hipEvent_t done; } blk[2] = {{0, lead, wc->flow0}, {lead, E, wc->flow1}};
+  for (const auto& k : blk) {
+    RUN(pvo_internal_conv7x7_c8_range(a->motion, w->fenc0_w, w->fenc0_b, b.f1, E, k.e0, k.e1, H, W, dt, sc->side));
+    RUN(pvo_internal_conv3x3_c128_range(b.f1, w->fenc2_w, w->fenc2_b, b.CF, E, k.e0, k.e1, H, W, 64, 1, 192, 128, dt, sc->side));
+    if (hipEventRecord(k.done, sc->side) != hipSuccess) return PVO_ELAUNCH;
+  }
+  RUN(cenc2(0, lead, wave));
+  RUN(cenc2(lead, E, stream));
+  if (!context_ready && hipStreamWaitEvent(st, wc->ctx, 0) != hipSuccess) return PVO_ELAUNCH;
+  if (hipStreamWaitEvent(ws, wc->flow0, 0) != hipSuccess) return PVO_ELAUNCH;
+  if (hipStreamWaitEvent(st, wc->flow1, 0) != hipSuccess) return PVO_ELAUNCH;
+  return PVO_OK;
+}
+
 // the ConvGRU's two convolutions for edges [e0, e1): gates -> candidate, the new hidden state in a->net_out.  The probe marks
-// (marks = true) go on `stream` around what is launched HERE: with the edge-blocked schedule on, the leading block only.
+// (marks = true) go on `stream` around what is launched HERE: with the edge-blocked schedule on, the launch stream's block only.
 int run_gru(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& b, void* stream, const void* P_zr, const void* P_q,
             const int* ps, int e0, int e1, bool marks) {
   const int E = a->E, H = a->H, W = a->W, dt = w->dtype;
@@ -352,34 +423,49 @@ int run_operator(const pvo_update_weights* w, const pvo_operator_args* a, OpWs& 
                  const GraphPostArgs* post = nullptr, int* post_fused = nullptr, const int* static_rows = nullptr) {
   const void *P_zr, *P_q;
   const int* ps = nullptr;
-  RUN(run_trunk(w, a, b, stream, &P_zr, &P_q, &ps, mj, context_ready, static_rows));
+  const EdgeBlocks eb = edge_blocks(a->E, a->H, a->W, w->flags);
+  // the trunk per block too: with the encoder side stream and cached static terms only (a motion job or the static terms' own
+  // convolutions belong to the whole trunk)
+  const bool trunk_blocked = eb.lead > 0 && eb.trunk && (w->flags & PVO_OP_ENC_SIDE_STREAM) && !mj && a->P_zr && a->P_q;
+  WaveCtx* wc = eb.lead > 0 ? wave_ctx(eb.low) : nullptr;
+  if (eb.lead > 0 && !wc) return PVO_ELAUNCH;
+  if (trunk_blocked) {
+    RUN(run_trunk_blocked(w, a, b, stream, wc, wc->s[eb.low], eb.lead, &ps, context_ready, static_rows));
+    P_zr = a->P_zr; P_q = a->P_q;
+  } else {
+    RUN(run_trunk(w, a, b, stream, &P_zr, &P_q, &ps, mj, context_ready, static_rows));
+  }
   hipStream_t st = pvo_stream(stream);
   SideCtx* sc = (a->K > 0 && !(w->flags & PVO_OP_SINGLE_STREAM)) ? side_ctx() : nullptr;
-  const EdgeBlocks eb = edge_blocks(a->E, a->H, a->W, w->flags);
   if (eb.lead > 0) {
     // The edge-blocked wavefront.  The edges are independent images: block b's candidate needs
     // block b's gates only, its heads its candidate only.  The leading block [0, lead) runs the three stages on the launch
     // stream, the trailing block beside it on a stream of the library's own, so that stage k + 1 of the leading block is ready
     // to be dispatched when stage k of the trailing block runs out of workgroups.  The same workgroups on the same operands:
     // bit-identical to the whole launches.  The gather behind the join, the glue and the BA run alone on the device as before.
+    // With the trunk blocked as well (run_trunk_blocked) the second stream has forked already, each block's gates follow its own
+    // front, and the blocks change places: the leading block, whose front is done first, goes on on the library's stream and the
+    // trailing block on the launch stream, behind its lookup.
     const int E = a->E, H = a->H, W = a->W, dt = w->dtype, lead = eb.lead;
-    WaveCtx* wc = wave_ctx(eb.low);
-    if (!wc) return PVO_ELAUNCH;
     hipStream_t ws = wc->s[eb.low];
-    if (hipEventRecord(wc->fork, st) != hipSuccess) return PVO_ELAUNCH;
-    if (hipStreamWaitEvent(ws, wc->fork, 0) != hipSuccess) return PVO_ELAUNCH;
-    RUN(run_gru(w, a, b, stream, P_zr, P_q, ps, 0, lead, true));
-    RUN(run_gru(w, a, b, ws, P_zr, P_q, ps, lead, E, false));
+    if (!trunk_blocked) {
+      if (hipEventRecord(wc->fork, st) != hipSuccess) return PVO_ELAUNCH;
+      if (hipStreamWaitEvent(ws, wc->fork, 0) != hipSuccess) return PVO_ELAUNCH;
+    }
+    void* const sA = trunk_blocked ? static_cast<void*>(ws) : stream;      // the leading block's stream
+    void* const sB = trunk_blocked ? stream : static_cast<void*>(ws);      // the trailing block's
+    RUN(run_gru(w, a, b, sA, P_zr, P_q, ps, 0, lead, !trunk_blocked));     // (the probe marks: the launch stream's block)
+    RUN(run_gru(w, a, b, sB, P_zr, P_q, ps, lead, E, trunk_blocked));
     if (sc) {
-      if (hipEventRecord(wc->cand0, st) != hipSuccess) return PVO_ELAUNCH;
-      if (hipEventRecord(wc->cand1, ws) != hipSuccess) return PVO_ELAUNCH;
+      if (hipEventRecord(wc->cand0, pvo_stream(sA)) != hipSuccess) return PVO_ELAUNCH;
+      if (hipEventRecord(wc->cand1, pvo_stream(sB)) != hipSuccess) return PVO_ELAUNCH;
       const AggBlocks ab = {lead, eb.agg, wc->cand0, wc->cand1};
       RUN(run_agg(w, a, b, sc->side, sc, upmask_on_side, &ab));
       if (hipEventRecord(sc->join, sc->side) != hipSuccess) return PVO_ELAUNCH;
     }
     float* const z = reinterpret_cast<float*>(b.h1);
-    RUN(pvo_internal_conv3x3_heads_range(a->net_out, w->heads1_w, w->heads1_b, w->heads2_w, z, E, 0, lead, H, W, dt, stream));
-    RUN(pvo_internal_conv3x3_heads_range(a->net_out, w->heads1_w, w->heads1_b, w->heads2_w, z, E, lead, E, H, W, dt, ws));
+    RUN(pvo_internal_conv3x3_heads_range(a->net_out, w->heads1_w, w->heads1_b, w->heads2_w, z, E, 0, lead, H, W, dt, sA));
+    RUN(pvo_internal_conv3x3_heads_range(a->net_out, w->heads1_w, w->heads1_b, w->heads2_w, z, E, lead, E, H, W, dt, sB));
     if (hipEventRecord(wc->join, ws) != hipSuccess) return PVO_ELAUNCH;
     if (hipStreamWaitEvent(st, wc->join, 0) != hipSuccess) return PVO_ELAUNCH;
     RUN(run_heads_gather(w, a, b, stream, post, post_fused));
@@ -582,6 +668,20 @@ extern "C" int pvo_graph_update_rig(const pvo_update_weights* w, const pvo_graph
 extern "C" int pvo_graph_update(const pvo_update_weights* w, const pvo_graph_update_args* u,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   return pvo_graph_update_rows(w, u, workspace, workspace_bytes, 0.0f, nullptr, stream);
+}
+
+// test hook: one of the blocked trunk's range launches by itself (conv_range.h; tests compare it with the whole launch bit for bit)
+extern "C" int pvo_debug_trunk_range(int which, const void* const* levels, const void* x, const void* w, const float* bias, void* y,
+                                     int E, int e0, int e1, int H, int W, int Cout, int relu, int ystride, int yoff,
+                                     const int* slots, int num_slots, int dtype, void* stream) {
+  switch (which) {
+    case 0: return pvo_internal_corr_lookup_encode_tiled_range(levels, static_cast<const float*>(x), w, bias, y, E, e0, e1, H, W, dtype,
+                                                               slots, num_slots, stream);
+    case 1: return pvo_internal_corr_encode_range(x, w, bias, y, E, e0, e1, H * W, dtype, stream);
+    case 2: return pvo_internal_conv7x7_c8_range(x, w, bias, y, E, e0, e1, H, W, dtype, stream);
+    case 3: return pvo_internal_conv3x3_c128_range(x, w, bias, y, E, e0, e1, H, W, Cout, relu, ystride, yoff, dtype, stream);
+    default: return PVO_EINVAL;
+  }
 }
 
 extern "C" int pvo_side_stream(void** stream_out) {

@@ -2140,7 +2140,7 @@ def frame_normalise(image, mean, std, dtype=torch.float16):
 def debug_config(knob, value):
     """the library's test hook (include/pvo_hip.h pvo_debug_config): "ba_solver" = None | "blocked" | "wave" | "pipe" | "twin" | "dense" | "blocks",
     "heads_gather_flat" = bool, "no_riders" = bool, "post_separate" = bool,
-    "edge_blocks" = None | "off" | "half" | "third", with "+low" / "+agg" (or the header's number).  Process-wide; tests that compare bit-identical forms call it in a process of
+    "edge_blocks" = None | "off" | "half" | "third", with "+low" / "+agg" / "+trunk" (or the header's number).  Process-wide; tests that compare bit-identical forms call it in a process of
     their own.  (These were environment variables read inside the library until round 5.)"""
     knobs = {"ba_solver": _lib.PVO_KNOB_BA_SOLVER, "heads_gather_flat": _lib.PVO_KNOB_HEADS_GATHER_FLAT, "no_riders": _lib.PVO_KNOB_NO_RIDERS,
              "post_separate": _lib.PVO_KNOB_POST_SEPARATE, "edge_blocks": _lib.PVO_KNOB_EDGE_BLOCKS}
@@ -2148,14 +2148,15 @@ def debug_config(knob, value):
         value = 0
     if knob == "edge_blocks" and isinstance(value, str) and not value.isdigit():
         # "off", or "half" | "third" (the leading block's share of the edges) with "+low" (the trailing block's stream of the lowest
-        # priority) and "+agg" (GraphAgg.conv1 per block too) in any order: "third+low+agg"
+        # priority), "+agg" (GraphAgg.conv1 per block too) and "+trunk" (the trunk per block too: each block's lookup and encoders in
+        # front of its own gates) in any order: "third+low+agg+trunk"
         parts = value.split("+")
         if parts[0] == "off" and len(parts) == 1:
             value = 1
         else:
-            if parts[0] not in ("half", "third") or any(p not in ("low", "agg") for p in parts[1:]):
+            if parts[0] not in ("half", "third") or any(p not in ("low", "agg", "trunk") for p in parts[1:]):
                 raise ValueError("edge_blocks: " + value)
-            value = 2 + (parts[0] == "third") + 2 * ("low" in parts[1:]) + 4 * ("agg" in parts[1:])
+            value = 2 + (parts[0] == "third") + 2 * ("low" in parts[1:]) + 4 * ("agg" in parts[1:]) + 8 * ("trunk" in parts[1:])
     if knob == "ba_solver":
         value = {None: 0, "": 0, "blocked": 1, "wave": 2, "pipe": 3, "twin": 4, "dense": 5, "blocks": 6}[value]
     check(_lib.load().pvo_debug_config(knobs[knob], int(value)), "pvo_debug_config")

@@ -2,6 +2,7 @@
 variable, so a measurement of a knob needs the knob set inside the measuring process):
     python tools/with_knob.py edge_blocks=third+low [knob=value ...] bench.py [bench.py arguments]
     python tools/with_knob.py edge_blocks=half tools/update_poison_check.py
+    python tools/with_knob.py edge_blocks=half+agg+trunk bench.py          (the trunk per block of edges as well)
 The script runs as __main__ in this process, with the product library (or, lib=<tag>, a tools/variant.py build)."""
 import os, runpy, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
