@@ -33,1201 +33,22 @@
 // scaled by 1e-3, poses below t0 fixed, fp64 solve with `diag += ep + lm*diag`, zero
 // update when the factorisation fails, EvT6x1's skip of window pose 0 in the depth
 // back-substitution (:1084).  Deviation: expSE3 uses xi[5], not xi[45] (:154).
+//
+// One translation unit.  The first three stages are headers, included in their order of definition:
+//   ba_workspace.h     fix_add, chunk constants, Plan / Ws / carve, staging slots, the prior / stereo / plan kernels
+//   ba_assemble.h      EdgeGeom, pixel_terms, ba_assemble_kernel
+//   ba_schur.h         row passes, ba_schur_mfma_kernel, ba_schur_reduce_kernel, ba_depth_kernel
+// The rest follows here: the pose-solve forms, back-substitution, uncertainty, calibration, the host entry points.
 #include "se3.h"
 #include "conv1x1_tile.h"
 #include "glo_tile.h"
 #include <stdlib.h>
 #include <type_traits>
+#include "ba_workspace.h"
+#include "ba_assemble.h"
+#include "ba_schur.h"
 
 namespace {
-
-constexpr float kMinDepth = 0.25f;
-
-// The reduced pose system is accumulated in 64-bit FIXED POINT (units of 2^-28): integer atomics commute, so the sums - and
-// with them poses and depths - are bitwise reproducible from run to run, and identical whether the edges sit on one GPU or
-// are sharded over several (fp64 atomics, used before, made the last bits order dependent).  Every addend is an fp32
-// partial sum (|v| <~ 1e8 at most: w J^2 over a chunk of pixels), so 2^-28 = 3.7e-9 absolute resolution is far below its
-// own rounding error, and |sum| < 2^35 leaves 7 bits of headroom.  Non-finite or out-of-range addends raise meta[4]; the
-// solve then takes the reference's failure path (zero update, droid_kernels.cu:1186-1189).
-constexpr double kFix = 268435456.0, kInvFix = 1.0 / 268435456.0;
-__device__ __forceinline__ void fix_add(long long* sys, long long idx, double v, int* meta) {
-  if (!(fabs(v) < 3.0e10)) { meta[4] = 1; return; }
-#ifdef PVO_BA_NO_ATOMICS                 // (timing experiment only - tools/ba_kernel_timeline.py PROBE_DEFS: the sums are lost)
-  if (idx >= 0) return;
-#endif
-  atomicAdd(reinterpret_cast<unsigned long long*>(sys + idx), static_cast<unsigned long long>(__double2ll_rn(v * kFix)));
-}
-constexpr int kDealEdges = 2;           // edges (consecutive in the plan's by-source order) per chunk-sum workgroup of the Schur kernel
-constexpr int kPPT = 2;                 // pixels per thread in assemble (1: 432 workgroups, measured slower - profiles/r03_ba_ablation.txt)
-constexpr int kChunkA = 256 * kPPT;     // pixels per assemble workgroup
-constexpr int kMaxSep = 12;                                      // separator poses of the partitioned solve (beyond: not partitioned)
-constexpr int kXchgDoubles = 2 + 36 * kMaxSep * kMaxSep + 12 * kMaxSep;
-
-
-// tools/ba_kernel_timeline.py builds this file with -DPVO_BA_PROBE=3: every workgroup of the assembly / Schur / back-substitution
-// kernels stamps the constant-rate clock (10 ns) at its phases: g_ba_wg_probe[(kernel * 4096 + workgroup) * 8 + slot]
-#if defined(PVO_BA_PROBE) && PVO_BA_PROBE == 3
-__device__ unsigned long long* g_ba_wg_probe = nullptr;
-#define BA_WG_PROBE(kern, slot)                                                                                         \
-  do {                                                                                                                  \
-    if (g_ba_wg_probe && threadIdx.x == 0 && blockIdx.z == 0) {                                                         \
-      const unsigned wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                                         \
-      if (wg_ < 4096u) g_ba_wg_probe[((kern) * 4096u + wg_) * 8u + (slot)] = wall_clock64();                            \
-    }                                                                                                                   \
-  } while (0)
-#else
-#define BA_WG_PROBE(kern, slot)
-#endif
-
-struct Plan {            // int region of the workspace
-  int* kidx;             // [F]   frame -> depth index, -1 if none
-  int* kx;               // [F]   depth index -> frame
-  int* eptr;             // [F+1] CSR over depth index -> edges (ascending edge id)
-  int* eidx;             // [E]
-  int* meta;             // [16]  0:K 1:status(non-SPD) 2:eta mismatch 3:row table overflow 4:non-finite / out-of-range system entry
-                         //       5,6: the sensor-depth prior's map (low / high word of a const float*, 0 = none) 7: its alpha (float bits)
-                         //       8: the stereo baseline (float bits, 0 = none: an edge (i, i) is an identity edge)
-  int* env;              // [P]   numeric envelope of a system for the envelope solve (ba_env_kernel; INT_MAX between solves)
-};
-
-struct Ws {
-  Plan plan;
-  float *Eii, *Eij;      // [E][6][HW]
-  float *Cii, *bz;       // [E][HW]
-  float *Ei;             // [P][6][HW]
-  float *Q, *w;          // [F'][HW]   (F' = min(F, P+E) rows)
-  float *dx;             // [P][6]
-  float *part;           // [E][assembly chunks][90]: per-chunk sums of an edge's pose blocks and gradients (depth BA)
-  long long* sys;        // [(6P)^2 + 6P] fixed point
-  double* chol;          // [(6P)^2 + 6P] scratch for the global-memory factorisation
-  double* xchg;          // partitioned pose solve: [2 doubles = 4 ints: flags, split | separator terms | separator solution] (kXchgDoubles)
-  double* ldiag;         // blocked multi-workgroup solve (big dense-ish systems): factored diagonal blocks [n / 48 + 1][48 x 48 + 48]
-  double* xvec;          // ... and its solution [6P]
-  float* Mrg;            // [E][6][HW]: the summed Eij rows of edges that share source AND target frame (Schur kernel), at the first one's index
-  // dense windows (P <= kDenseMaxPoses), two-stage Schur sums: per (depth frame, 256-pixel chunk) the tile-pair sums of the chunk,
-  // the frame's row -> system-entry table and its tile count (0 = this frame went the atomic way).  All three are indexed by the
-  // frame's staging SLOT (schur_stage_slot: by frame identity), not by its row in the call's plan
-  float* spart;          // [kSchurStageFrames(P)][ceil(HW/256)][kSchurStagePairs][256]
-  short* srow;           // [kSchurStageFrames(P)][128]
-  int* sT;               // [kSchurStageFrames(P)]
-  size_t bytes;
-};
-constexpr int kSchurStagePairs = 36;     // tile pairs of up to 8 row tiles
-constexpr int kSchurStageFront = 8;      // source frames right in front of the window that have a staging slot beside the window's own
-__host__ __device__ __forceinline__ int schur_stage_frames(int P) { return (P > 0 && P <= 29) ? P + kSchurStageFront : 0; }
-// The staging slot of a depth frame, by the frame's IDENTITY: the window's frames [t0, t1) and the kSchurStageFront frames in front
-// of them, slot = frame - (t0 - kSchurStageFront); -1 = no slot, the frame's chunks go to the system one by one.  Whether a frame's
-// chunk sums are rounded to fixed point once or chunk by chunk changes the words of `sys`, so the choice must not read anything a
-// rank of an edge-sharded run sees differently (the row of the frame in this call's plan, the number of depth frames, the eta layout).
-__host__ __device__ __forceinline__ int schur_stage_slot(int frame, int t0, int P) {
-  const int slot = frame - t0 + kSchurStageFront;
-  return (slot >= 0 && slot < schur_stage_frames(P)) ? slot : -1;
-}
-
-__host__ size_t align_up(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
-
-__host__ Ws carve(void* base, int E, int P, int F, int HW) {
-  Ws w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-  const int Kmax = (F < P + E) ? F : (P + E);
-  const size_t n6 = static_cast<size_t>(6) * (P > 0 ? P : 0);
-  w.plan.kidx = reinterpret_cast<int*>(take(sizeof(int) * (F + 1)));
-  w.plan.kx = reinterpret_cast<int*>(take(sizeof(int) * (F + 1)));
-  w.plan.eptr = reinterpret_cast<int*>(take(sizeof(int) * (F + 2)));
-  w.plan.eidx = reinterpret_cast<int*>(take(sizeof(int) * (E + 1)));
-  w.plan.meta = reinterpret_cast<int*>(take(sizeof(int) * 16));
-  w.plan.env = reinterpret_cast<int*>(take(sizeof(int) * ((P > 0 ? P : 0) + 1)));
-  w.Eii = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(E) * 6 * HW));
-  w.Eij = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(E) * 6 * HW));
-  w.Cii = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(E) * HW));
-  w.bz = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(E) * HW));
-  w.Ei = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(P > 0 ? P : 0) * 6 * HW));
-  w.Q = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(Kmax) * HW));
-  w.w = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(Kmax) * HW));
-  w.dx = reinterpret_cast<float*>(take(sizeof(float) * (n6 + 8)));
-  w.part = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(E) * ((HW + kChunkA - 1) / kChunkA) * 90 + 16));
-  w.sys = reinterpret_cast<long long*>(take(sizeof(double) * (n6 * n6 + n6 + 8)));
-  // (both at every size: a packed envelope message - pvo_ba_finish_packed - is factorised from the compact image whatever P is)
-  w.chol = reinterpret_cast<double*>(take(sizeof(double) * (n6 * n6 + n6 + 27 * (n6 / 6) + 32)));
-  w.xchg = reinterpret_cast<double*>(take(sizeof(double) * kXchgDoubles));
-  w.ldiag = reinterpret_cast<double*>(take(sizeof(double) * (n6 / 48 + 2) * (48 * 48 + 48)));
-  w.xvec = reinterpret_cast<double*>(take(sizeof(double) * (n6 + 8)));
-  w.Mrg = reinterpret_cast<float*>(take(sizeof(float) * static_cast<size_t>(E) * 6 * HW));
-  {
-    const size_t ks = static_cast<size_t>(schur_stage_frames(P));
-    w.spart = reinterpret_cast<float*>(take(sizeof(float) * ks * ((HW + 255) / 256) * kSchurStagePairs * 256));
-    w.srow = reinterpret_cast<short*>(take(sizeof(short) * ks * 128));
-    w.sT = reinterpret_cast<int*>(take(sizeof(int) * (ks + 1)));
-  }
-  w.bytes = off;
-  return w;
-}
-
-// ---------------------------------------------------------------------------
-// the sensor-depth prior (pvo_ba_depth_prior): part of the plan's device-side state, read once per workgroup by the depth phase
-// ---------------------------------------------------------------------------
-struct DepthPrior { const float* sens; float alpha; };     // sens: [F][HW] measured inverse depth, 0 = no measurement; nullptr = none
-
-__device__ __forceinline__ void store_prior(int* meta, const float* sens, float alpha) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(sens);
-  meta[5] = static_cast<int>(a & 0xffffffffull);
-  meta[6] = static_cast<int>(a >> 32);
-  meta[7] = sens ? __float_as_int(alpha) : 0;
-}
-__device__ __forceinline__ DepthPrior load_prior(const int* meta) {
-  const unsigned long long a = (static_cast<unsigned long long>(static_cast<unsigned>(meta[6])) << 32) | static_cast<unsigned>(meta[5]);
-  DepthPrior pr;
-  pr.sens = reinterpret_cast<const float*>(a);
-  pr.alpha = __int_as_float(meta[7]);
-  return pr;
-}
-__global__ void ba_prior_kernel(int* meta, const float* sens, float alpha) { store_prior(meta, sens, alpha); }
-
-// the stereo baseline (pvo_ba_stereo): with b > 0 an edge (i, i) is the fixed left -> right transform of the rig.  Read once per
-// workgroup by the assembly.
-__global__ void ba_stereo_kernel(int* meta, float baseline) { meta[8] = __float_as_int(baseline); }
-
-// ---------------------------------------------------------------------------
-// plan
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ba_plan_kernel(
-    const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, Plan pl,
-    int E, int F, int t0, int t1, int K_eta, int motion_only, const float* sens, float alpha, float baseline) {
-  __shared__ int seg[257];
-  const int tid = threadIdx.x;
-  for (int b = tid; b < t1 - t0; b += 256) pl.env[b] = 0x7fffffff;
-  // presence bitmap
-  for (int f = tid; f < F; f += 256) pl.kidx[f] = (f >= t0 && f < t1) ? 1 : 0;
-  __syncthreads();
-  for (int e = tid; e < E; e += 256) {
-    const long long f = ii[e];
-    if (f >= 0 && f < F) pl.kidx[f] = 1;   // benign race: everyone writes 1
-  }
-  __syncthreads();
-  // exclusive scan of the bitmap, one contiguous segment per thread
-  const int per = (F + 255) / 256;
-  const int lo = min(tid * per, F), hi = min(lo + per, F);
-  int cnt = 0;
-  for (int f = lo; f < hi; ++f) cnt += pl.kidx[f];
-  seg[tid + 1] = cnt;
-  if (tid == 0) seg[0] = 0;
-  __syncthreads();
-  if (tid == 0) for (int i = 1; i <= 256; ++i) seg[i] += seg[i - 1];
-  __syncthreads();
-  int run = seg[tid];
-  for (int f = lo; f < hi; ++f) {
-    if (pl.kidx[f]) { pl.kx[run] = f; pl.kidx[f] = run; ++run; } else pl.kidx[f] = -1;
-  }
-  const int K = seg[256];
-  __syncthreads();
-  // CSR of edges by depth index (= source frame), ascending edge id inside a row
-  for (int k = tid; k < K; k += 256) {
-    const int f = pl.kx[k];
-    int c = 0;
-    for (int e = 0; e < E; ++e) c += (ii[e] == f) ? 1 : 0;
-    pl.eptr[k + 1] = c;
-  }
-  if (tid == 0) pl.eptr[0] = 0;
-  __syncthreads();
-  if (tid == 0) for (int k = 1; k <= K; ++k) pl.eptr[k] += pl.eptr[k - 1];
-  __syncthreads();
-  for (int k = tid; k < K; k += 256) {
-    const int f = pl.kx[k];
-    int o = pl.eptr[k];
-    for (int e = 0; e < E; ++e) if (ii[e] == f) pl.eidx[o++] = e;
-  }
-  if (tid == 0) {
-    pl.meta[0] = K;
-    pl.meta[1] = 0;
-    pl.meta[3] = 0;
-    pl.meta[4] = 0;
-    // eta must have one row per depth frame (or one row, broadcast).  Anything else is a caller error the host cannot see
-    // without a synchronisation (K is found here): flagged, and the step becomes a NO-OP - the Schur grid is sized by the caller's
-    // row count, so depth frames beyond it would keep stale Q / w; the solve reports failure (dx = 0, poses untouched) and the
-    // back-substitution leaves every depth map alone (status_out[0] = 1, [2] = 1).
-    pl.meta[2] = (!motion_only && K_eta != K && K_eta != 1) ? 1 : 0;
-    store_prior(pl.meta, sens, alpha);      // (pvo_ba_plan: none - a fresh plan runs the arithmetic without the term)
-    pl.meta[8] = __float_as_int(baseline);  // (pvo_ba_plan: 0 - no stereo edges)
-  }
-}
-
-// ---------------------------------------------------------------------------
-// assemble
-// ---------------------------------------------------------------------------
-struct EdgeGeom { Pose G; float fx, fy, cx, cy; };
-
-// one pixel of projective_transform_kernel (droid_kernels.cu:266-357): accumulates the
-// upper triangle h[78] of [Ji Jj]^T W [Ji Jj], the gradients vi/vj, and returns the
-// depth-coupling terms.
-__device__ __forceinline__ void pixel_terms(const EdgeGeom& g, float u, float v, float disp,
-                                            float tu, float tv, float wgu, float wgv,
-                                            float (&h)[78], float (&vi)[6], float (&vj)[6],
-                                            float (&eii)[6], float (&eij)[6], float& cii, float& bzz) {
-  float Xi[4] = {(u - g.cx) / g.fx, (v - g.cy) / g.fy, 1.0f, disp};
-  float Xj[4];
-  act4(g.G, Xi, Xj);
-  const float x = Xj[0], y = Xj[1], hh = Xj[3];
-  const bool ok = !(Xj[2] < kMinDepth);
-  const float d = ok ? 1.0f / Xj[2] : 0.0f;
-  const float d2 = d * d;
-  // droid_kernels.cu:290-291 write `.001 * weight`: a DOUBLE literal, so the product is formed in double and rounded to
-  // float once - not the same number as 0.001f * w (0.001f != 0.001).  Followed literally; `1.0 / Xj[2]` (:287) equals the
-  // correctly rounded float division (double rounding of a quotient is innocuous at 53 >= 2 * 24 + 2 bits).
-  const float wu = ok ? static_cast<float>(0.001 * static_cast<double>(wgu)) : 0.0f;
-  const float wv = ok ? static_cast<float>(0.001 * static_cast<double>(wgv)) : 0.0f;
-  const float ru = tu - (g.fx * d * x + g.cx);
-  const float rv = tv - (g.fy * d * y + g.cy);
-  float J[12];   // [Ji | Jj]
-  float Jz;
-  // ---- x residual
-  J[6] = g.fx * (hh * d); J[7] = 0.0f; J[8] = g.fx * (-x * hh * d2);
-  J[9] = g.fx * (-x * y * d2); J[10] = g.fx * (1.0f + x * x * d2); J[11] = g.fx * (-y * d);
-  Jz = g.fx * (g.G.t.x * d - g.G.t.z * (x * d2));
-  adjT(g.G, &J[6], &J[0]);
-#pragma unroll
-  for (int n = 0; n < 6; ++n) J[n] = -J[n];
-  {
-    int l = 0;
-#pragma unroll
-    for (int n = 0; n < 12; ++n) {
-      const float wj = wu * J[n];
-#pragma unroll
-      for (int m = 0; m <= n; ++m) { h[l] += wj * J[m]; ++l; }
-    }
-  }
-#pragma unroll
-  for (int n = 0; n < 6; ++n) {
-    vi[n] += wu * ru * J[n];
-    vj[n] += wu * ru * J[6 + n];
-    eii[n] = wu * Jz * J[n];
-    eij[n] = wu * Jz * J[6 + n];
-  }
-  cii = wu * Jz * Jz;
-  bzz = wu * ru * Jz;
-  // ---- y residual
-  J[6] = 0.0f; J[7] = g.fy * (hh * d); J[8] = g.fy * (-y * hh * d2);
-  J[9] = g.fy * (-1.0f - y * y * d2); J[10] = g.fy * (x * y * d2); J[11] = g.fy * (x * d);
-  Jz = g.fy * (g.G.t.y * d - g.G.t.z * (y * d2));
-  adjT(g.G, &J[6], &J[0]);
-#pragma unroll
-  for (int n = 0; n < 6; ++n) J[n] = -J[n];
-  {
-    int l = 0;
-#pragma unroll
-    for (int n = 0; n < 12; ++n) {
-      const float wj = wv * J[n];
-#pragma unroll
-      for (int m = 0; m <= n; ++m) { h[l] += wj * J[m]; ++l; }
-    }
-  }
-#pragma unroll
-  for (int n = 0; n < 6; ++n) {
-    vi[n] += wv * rv * J[n];
-    vj[n] += wv * rv * J[6 + n];
-    eii[n] += wv * Jz * J[n];
-    eij[n] += wv * Jz * J[6 + n];
-  }
-  cii += wv * Jz * Jz;
-  bzz += wv * rv * Jz;
-}
-
-// one pixel of a STEREO edge (i, i): g.G is the rig's fixed transform, so the residual depends on no pose - only the depth terms
-// remain.  The projection, the Z test, the weights and Jz are pixel_terms' own expressions in its own order.
-__device__ __forceinline__ void stereo_pixel_terms(const EdgeGeom& g, float u, float v, float disp,
-                                                   float tu, float tv, float wgu, float wgv, float& cii, float& bzz) {
-  float Xi[4] = {(u - g.cx) / g.fx, (v - g.cy) / g.fy, 1.0f, disp};
-  float Xj[4];
-  act4(g.G, Xi, Xj);
-  const float x = Xj[0], y = Xj[1];
-  const bool ok = !(Xj[2] < kMinDepth);
-  const float d = ok ? 1.0f / Xj[2] : 0.0f;
-  const float d2 = d * d;
-  const float wu = ok ? static_cast<float>(0.001 * static_cast<double>(wgu)) : 0.0f;
-  const float wv = ok ? static_cast<float>(0.001 * static_cast<double>(wgv)) : 0.0f;
-  const float ru = tu - (g.fx * d * x + g.cx);
-  const float rv = tv - (g.fy * d * y + g.cy);
-  float Jz = g.fx * (g.G.t.x * d - g.G.t.z * (x * d2));
-  cii = wu * Jz * Jz;
-  bzz = wu * ru * Jz;
-  Jz = g.fy * (g.G.t.y * d - g.G.t.z * (y * d2));
-  cii += wv * Jz * Jz;
-  bzz += wv * rv * Jz;
-}
-
-// Entry t of an edge's 90 sums - upper triangle of [Ji Jj]^T W [Ji Jj] (78, droid_kernels.cu:309-315 ordering), vi (6), vj (6) -
-// added to the pose system in fixed point.
-__device__ __forceinline__ void pose_block_scatter(int t, double val, int pi, int pj, int P, long long* __restrict__ sys, int* __restrict__ meta) {
-  const bool iok = pi >= 0 && pi < P, jok = pj >= 0 && pj < P;
-  const int n6 = 6 * P;
-  if (t < 78) {
-    // invert l -> (n, m), m <= n
-    int n = 0, base = 0;
-    while (base + n + 1 <= t) { base += n + 1; ++n; }
-    const int m = t - base;
-    if (n < 6) {                                  // (ii,ii), symmetric
-      if (iok) {
-        fix_add(sys, static_cast<long long>(6 * pi + n) * n6 + 6 * pi + m, val, meta);
-        if (n != m) fix_add(sys, static_cast<long long>(6 * pi + m) * n6 + 6 * pi + n, val, meta);
-      }
-    } else if (m < 6) {                           // (ii,jj)[m][n-6] and (jj,ii)[n-6][m]
-      // only the LOWER block triangle of the system is ever read (the solve factorises it; an edge-sharded run all-reduces
-      // exactly those blocks): of the two mirrored off-diagonal blocks the one above the diagonal is not written.  Nothing at
-      // window size; a global bundle adjustment's Schur kernel is bound by these atomics (round 4)
-      if (iok && jok) {
-        if (pi > pj) fix_add(sys, static_cast<long long>(6 * pi + m) * n6 + 6 * pj + (n - 6), val, meta);
-        else fix_add(sys, static_cast<long long>(6 * pj + (n - 6)) * n6 + 6 * pi + m, val, meta);
-      }
-    } else {                                      // (jj,jj), symmetric
-      if (jok) {
-        fix_add(sys, static_cast<long long>(6 * pj + n - 6) * n6 + 6 * pj + m - 6, val, meta);
-        if (n != m) fix_add(sys, static_cast<long long>(6 * pj + m - 6) * n6 + 6 * pj + n - 6, val, meta);
-      }
-    }
-  } else if (t < 84) {
-    if (iok) fix_add(sys, static_cast<long long>(n6) * n6 + 6 * pi + (t - 78), val, meta);
-  } else {
-    if (jok) fix_add(sys, static_cast<long long>(n6) * n6 + 6 * pj + (t - 84), val, meta);
-  }
-}
-
-// The (at most two) entries of the pose system pose_block_scatter adds entry t of edge (pi -> pj) to; -1 = none.  Same case
-// analysis, kept beside it.
-__device__ __forceinline__ void pose_block_targets(int t, int pi, int pj, int P, long long idx[2]) {
-  const bool iok = pi >= 0 && pi < P, jok = pj >= 0 && pj < P;
-  const long long n6 = 6 * P;
-  idx[0] = idx[1] = -1;
-  if (t < 78) {
-    int n = 0, base = 0;
-    while (base + n + 1 <= t) { base += n + 1; ++n; }
-    const int m = t - base;
-    if (n < 6) {
-      if (iok) { idx[0] = (6 * pi + n) * n6 + 6 * pi + m; if (n != m) idx[1] = (6 * pi + m) * n6 + 6 * pi + n; }
-    } else if (m < 6) {
-      if (iok && jok) idx[0] = (pi > pj) ? (6 * pi + m) * n6 + 6 * pj + (n - 6) : (6 * pj + (n - 6)) * n6 + 6 * pi + m;
-    } else {
-      if (jok) { idx[0] = (6 * pj + n - 6) * n6 + 6 * pj + m - 6; if (n != m) idx[1] = (6 * pj + m - 6) * n6 + 6 * pj + n - 6; }
-    }
-  } else if (t < 84) {
-    if (iok) idx[0] = n6 * n6 + 6 * pi + (t - 78);
-  } else {
-    if (jok) idx[0] = n6 * n6 + 6 * pj + (t - 84);
-  }
-}
-
-__global__ __launch_bounds__(256) void ba_assemble_kernel(
-    const float* __restrict__ poses, const float* __restrict__ disps, const float* __restrict__ intr,
-    const float* __restrict__ targets, const float* __restrict__ weights,
-    const int64_t* __restrict__ ii, const int64_t* __restrict__ jj,
-    float* __restrict__ Eii, float* __restrict__ Eij, float* __restrict__ Cii, float* __restrict__ bz,
-    long long* __restrict__ sys, int* __restrict__ meta, int HW, int wd, int t0, int P, int motion_only, float* __restrict__ part) {
-  // Every (edge, pixel chunk) workgroup ends with 90 sums.  Added to `sys` right here they are 216 x 90 memory-side atomics on
-  // ~1800 addresses at S-B - each address serialises the ~30 workgroups that hit it, 5 of this kernel's 14 us (ablation build).
-  // In a depth BA (`part`) the chunk sums are stored instead and the Schur kernel, which follows anyway, adds them up per edge:
-  // a sixth of the atomics, issued while its own work starts.
-  __shared__ float red[4][90];
-  BA_WG_PROBE(0, 0);
-  const int e = blockIdx.y;
-  const int ix = static_cast<int>(ii[e]), jx = static_cast<int>(jj[e]);
-  EdgeGeom g;
-  g.fx = intr[0]; g.fy = intr[1]; g.cx = intr[2]; g.cy = intr[3];
-  const float baseline = __int_as_float(meta[8]);
-  if (baseline != 0.0f && ix == jx) {
-    // A stereo edge (uniform over the workgroup: e is blockIdx.y).  The rig is rigid: no pose sums, so none of the reduce-scatter
-    // below; the depth terms go out with ZERO coupling rows, which the depth phase, the Schur kernel and the back-substitution read
-    // like any edge's.  Motion-only: it adds nothing at all.
-    if (motion_only) return;
-    g.G = rig_pose(baseline);
-#pragma unroll
-    for (int s = 0; s < kPPT; ++s) {
-      const int k = blockIdx.x * kChunkA + s * 256 + threadIdx.x;
-      if (k < HW) {
-        const int i = k / wd, j = k - i * wd;
-        const float* __restrict__ tg = targets + static_cast<long long>(e) * 2 * HW;
-        const float* __restrict__ wg = weights + static_cast<long long>(e) * 2 * HW;
-        float cii, bzz;
-        stereo_pixel_terms(g, static_cast<float>(j), static_cast<float>(i), disps[static_cast<long long>(ix) * HW + k], tg[k], tg[HW + k],
-                           wg[k], wg[HW + k], cii, bzz);
-        const long long eb = static_cast<long long>(e) * 6 * HW + k;
-#pragma unroll
-        for (int n = 0; n < 6; ++n) { Eii[eb + static_cast<long long>(n) * HW] = 0.0f; Eij[eb + static_cast<long long>(n) * HW] = 0.0f; }
-        Cii[static_cast<long long>(e) * HW + k] = cii;
-        bz[static_cast<long long>(e) * HW + k] = bzz;
-      }
-    }
-    // (the Schur kernel adds every edge's chunk sums into the pose system: this edge's are zero)
-    if (part && threadIdx.x < 90) part[(static_cast<long long>(e) * gridDim.x + blockIdx.x) * 90 + threadIdx.x] = 0.0f;
-    return;
-  }
-  g.G = rel_pose(load_pose(poses + 7 * static_cast<long long>(ix)), load_pose(poses + 7 * static_cast<long long>(jx)));
-
-  float h[78], vi[6], vj[6];
-#pragma unroll
-  for (int l = 0; l < 78; ++l) h[l] = 0.0f;
-#pragma unroll
-  for (int n = 0; n < 6; ++n) { vi[n] = 0.0f; vj[n] = 0.0f; }
-
-  const float* __restrict__ d_i = disps + static_cast<long long>(ix) * HW;
-  const float* __restrict__ tg = targets + static_cast<long long>(e) * 2 * HW;
-  const float* __restrict__ wg = weights + static_cast<long long>(e) * 2 * HW;
-#pragma unroll
-  for (int s = 0; s < kPPT; ++s) {
-    const int k = blockIdx.x * kChunkA + s * 256 + threadIdx.x;
-    if (k < HW) {
-      const int i = k / wd, j = k - i * wd;
-      float eii[6], eij[6], cii, bzz;
-      pixel_terms(g, static_cast<float>(j), static_cast<float>(i), d_i[k], tg[k], tg[HW + k], wg[k], wg[HW + k],
-                  h, vi, vj, eii, eij, cii, bzz);
-      if (!motion_only) {
-        const long long eb = static_cast<long long>(e) * 6 * HW + k;
-#pragma unroll
-        for (int n = 0; n < 6; ++n) { Eii[eb + static_cast<long long>(n) * HW] = eii[n]; Eij[eb + static_cast<long long>(n) * HW] = eij[n]; }
-        Cii[static_cast<long long>(e) * HW + k] = cii;
-        bz[static_cast<long long>(e) * HW + k] = bzz;
-      }
-    }
-  }
-  BA_WG_PROBE(0, 1);                     // pixel terms done (stores issued)
-  // 90 sums per wave.  Ninety separate wave reductions (6 DPP steps each) were 5.2 of this kernel's 9.5 us at S-B
-  // (profiles/r04_ba_kernel_timeline.txt); a reduce-SCATTER does the same work in a third of the instructions: the values sit in
-  // 96 registers, and at every step a lane and its partner each keep one half of the array and add the other's copy of it -
-  // 48, 24, 12, 6, 3 additions, then one plain exchange.  Partners: lane ^ 32 and lane ^ 16 by v_permlane32_swap /
-  // v_permlane16_swap (gfx950: the two halves change places in one instruction, no select), then the DPP mirrors inside a row
-  // (i <-> 15 - i, i <-> 7 - i, i <-> 3 - i) and quad_perm [1,0,3,2]; which half a lane keeps is its bit 5, 4, 3, 2, 1 in turn,
-  // so lane L ends with the sums of entries [48 b5 + 24 b4 + 12 b3 + 6 b2 + 3 b1, + 3).  A fixed order of additions, as before.
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  {
-    float c[96];
-#pragma unroll
-    for (int l = 0; l < 78; ++l) c[l] = h[l];
-#pragma unroll
-    for (int n = 0; n < 6; ++n) { c[78 + n] = vi[n]; c[84 + n] = vj[n]; c[90 + n] = 0.0f; }
-    auto fbits = [](float x) { return __builtin_bit_cast(unsigned, x); };
-    auto bitsf = [](unsigned x) { return __builtin_bit_cast(float, x); };
-#pragma unroll
-    for (int q = 0; q < 48; ++q) {
-      const auto r = __builtin_amdgcn_permlane32_swap(fbits(c[q]), fbits(c[q + 48]), false, false);
-      c[q] = bitsf(r[0]) + bitsf(r[1]);
-    }
-#pragma unroll
-    for (int q = 0; q < 24; ++q) {
-      const auto r = __builtin_amdgcn_permlane16_swap(fbits(c[q]), fbits(c[q + 24]), false, false);
-      c[q] = bitsf(r[0]) + bitsf(r[1]);
-    }
-    const bool b3 = lane & 8, b2 = lane & 4, b1 = lane & 2;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) {
-      const float keep = b3 ? c[q + 12] : c[q], send = b3 ? c[q] : c[q + 12];
-      c[q] = keep + pvo_dpp_move<0x140>(send);      // row_mirror
-    }
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      const float keep = b2 ? c[q + 6] : c[q], send = b2 ? c[q] : c[q + 6];
-      c[q] = keep + pvo_dpp_move<0x141>(send);      // row_half_mirror
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const float keep = b1 ? c[q + 3] : c[q], send = b1 ? c[q] : c[q + 3];
-      c[q] = keep + pvo_dpp_move<0x1b>(send);       // quad_perm [3,2,1,0]
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-      c[q] = pvo_dpp_step<0xb1>(c[q]);             // quad_perm [1,0,3,2]
-    const int start = ((lane >> 5) & 1) * 48 + ((lane >> 4) & 1) * 24 + ((lane >> 3) & 1) * 12 + ((lane >> 2) & 1) * 6 + ((lane >> 1) & 1) * 3;
-    if (!(lane & 1)) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        if (start + q < 90) red[wave][start + q] = c[q];
-    }
-  }
-  __syncthreads();
-  BA_WG_PROBE(0, 2);                     // wave reductions done
-  const int t = threadIdx.x;
-  if (t < 90) {
-    const float sum = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-    if (part) part[(static_cast<long long>(e) * gridDim.x + blockIdx.x) * 90 + t] = sum;      // summed per edge by the Schur kernel
-    else pose_block_scatter(t, static_cast<double>(sum), ix - t0, jx - t0, P, sys, meta);
-  }
-  BA_WG_PROBE(0, 3);
-}
-
-// ---------------------------------------------------------------------------
-// schur: depth elimination for one (pixel chunk, depth frame)
-// ---------------------------------------------------------------------------
-// Row r of depth frame k: r == -1 is the window-pose row (Ei[k], pose kx[k]-t0),
-// r >= 0 is outgoing edge eidx[eptr[k]+r] (Eij, pose jj-t0).
-struct RowRef { const float* base; int pose; };
-
-__device__ __forceinline__ RowRef row_of(int r, int k, const Plan& pl, const float* Ei, const float* Eij,
-                                         const int64_t* jj, int HW, int t0, int P) {
-  RowRef R;
-  if (r < 0) {
-    const int p = pl.kx[k] - t0;
-    R.pose = (p >= 0 && p < P) ? p : -1;
-    R.base = Ei + static_cast<long long>(p >= 0 && p < P ? p : 0) * 6 * HW;
-  } else {
-    const int e = pl.eidx[pl.eptr[k] + r];
-    const int p = static_cast<int>(jj[e]) - t0;
-    R.pose = (p >= 0 && p < P) ? p : -1;
-    R.base = Eij + static_cast<long long>(e) * 6 * HW;
-  }
-  return R;
-}
-
-// ---- depth: C, w, Q and the window-pose rows Ei for one (pixel, depth frame) ----------
-// (accum_cuda x3 + the Q expression of ba_cuda, droid_kernels.cu:1374-1378).  Runs as the first phase of the Schur
-// kernel: every workgroup prepares Q, w and Ei for exactly the pixels it is about to reduce.
-__device__ __forceinline__ void depth_pixel(const Plan& pl, int k, int x, const float* __restrict__ eta, int K_eta,
-                                            const float* __restrict__ Eii, const float* __restrict__ Cii, const float* __restrict__ bz,
-                                            float* __restrict__ Ei, float* __restrict__ Q, float* __restrict__ w, int HW, int t0, int P,
-                                            const int* __restrict__ edges, int deg, int pself,
-                                            const DepthPrior& pr, const float* __restrict__ disps) {
-  // `edges` = this depth frame's out-edges in LDS (round 4): read from the plan in global memory inside this loop, every
-  // iteration was two dependent round trips (eidx[o], then the rows of edge e) - 6 x 2 of them in front of the first product
-  const bool self_in = pself >= 0 && pself < P;
-  float C = 0.0f, ww = 0.0f, ei[6] = {0, 0, 0, 0, 0, 0};
-  // (six edges' 48 loads in flight: a frame of a real window has ~18 out-edges and this loop was a third of the kernel at unroll 2)
-#pragma unroll 6
-  for (int o = 0; o < deg; ++o) {
-    const int e = edges[o];
-    C += Cii[static_cast<long long>(e) * HW + x];
-    ww += bz[static_cast<long long>(e) * HW + x];
-    if (self_in) {
-#pragma unroll
-      for (int n = 0; n < 6; ++n) ei[n] += Eii[(static_cast<long long>(e) * 6 + n) * HW + x];
-    }
-  }
-  // K_eta == 1 broadcasts; a row-count mismatch is flagged in meta[2] and clamped here
-  const float et = eta[static_cast<long long>(k < K_eta ? k : K_eta - 1) * HW + x];
-  // The sensor-depth prior (upstream DROID-SLAM's RGB-D term): where the frame has a measurement s > 0, alpha takes eta's place in C
-  // and alpha (d - s) leaves w.  SELECTS, not blends: no map, or no measurement at this pixel, is C + et and ww - 0.0f - the bits
-  // of the arithmetic without the term.  Only for a frame with out-edges in THIS call (deg > 0): an edge-sharded rank plans every
-  // window frame, and one it does not own has C = w = 0 here and must keep dz = 0, or the ranks would each apply the term.
-  float cp = et, wp = 0.0f;
-  if (pr.sens != nullptr && deg > 0) {
-    const long long fx = static_cast<long long>(pself + t0) * HW + x;      // (pself + t0 = the frame, kx[k])
-    const float s = pr.sens[fx];
-    if (s > 0.0f) { cp = pr.alpha; wp = pr.alpha * (disps[fx] - s); }
-  }
-  Q[static_cast<long long>(k) * HW + x] = 1.0f / (C + cp);           // droid_kernels.cu:1376
-  w[static_cast<long long>(k) * HW + x] = ww - wp;
-  if (self_in) {
-#pragma unroll
-    for (int n = 0; n < 6; ++n) Ei[(static_cast<long long>(pself) * 6 + n) * HW + x] = ei[n];
-  }
-}
-
-// For depth frame k, M stacks the 6-row blocks that couple it to window poses: Ei[k] (its own
-// pose) and Eij[e] for every outgoing edge whose target pose is free, plus one extra row w_k,
-// so that the rhs correction M (Q w) falls out of the same product.  One workgroup owns
-// (512 pixels, k); each wave reduces its 128 pixels with v_mfma_f32_16x16x4_f32 — exact fp32
-// FMA chains, K = pixels — one 16x16 tile pair at a time (row tiles re-read from L2, which
-// keeps any graph degree in one code path).  Wave partials meet in LDS and leave as fp64
-// atomics on the dense pose system: S is SUBTRACTED (A - S, v - E Q w; :1382).  Up to 4 row
-// tiles (10 free neighbours) all tile pairs accumulate in one pass; beyond that one pair at a time.
-// The reference enumerates (a,b,k) triples on the host and launches one 256-thread block per
-// triple with 36 LDS tree reductions each (schur_block :1201-1290, EEt6x6 :980-1035).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kSchurPix = 256;           // pixels per workgroup (a quarter per wave); 512: 48 workgroups at S-B, 19.9 us; 256: 96, 18.1 us
-constexpr int kMaxRows = 1024;           // rows of M the LDS row table can describe
-constexpr int kFastTiles = 4;            // up to 4 row tiles (63 rows + w) accumulate in one pass
-
-// Row pointers pass through an LDS table: typed as GLOBAL-address-space pointers, so that what is loaded through them is a
-// global_load (a plain `const float*` read back from LDS is a generic pointer and every access a flat_load: 112 of them in
-// this kernel, each counting against both vmcnt and lgkmcnt)
-typedef const float __attribute__((address_space(1))) gfloat;
-
-// The LDS row table says, per row of M, where the row lives - a source array and a row index in it, packed into one int - and which
-// entry of the pose system its sums go to (a short).  6 KB for kMaxRows rows instead of the 12 KB that pointers + ints took: with the
-// 40 KB of `red` the workgroup stays under a third of the CU's 160 KB (three workgroups per CU instead of two; a frontend window
-// with its inactive edges launches 550-700 of them).
-constexpr int kRowEij = 0, kRowMrg = 1, kRowEi = 2, kRowW = 3;
-__device__ __forceinline__ int row_code(int src, long long row) { return (src << 28) | static_cast<int>(row); }
-struct RowTab {
-  const int* code;           // LDS: (source << 28) | row index, -1 = padding
-  const short* out;          // LDS: 6 * pose + comp for an M row, -2 for the w row, -1 padding
-  const float* base[4];      // Eij, Mrg, Ei, w
-  int HW;
-  __device__ __forceinline__ gfloat* ptr(int r) const {
-    const int c = code[r];
-    if (c < 0) return nullptr;
-    const int src = c >> 28;
-    const float* b = src == kRowEij ? base[0] : (src == kRowMrg ? base[1] : (src == kRowEi ? base[2] : base[3]));
-    return (gfloat*)(b + static_cast<long long>(c & 0x0fffffff) * HW);
-  }
-};
-
-template <bool VEC4>
-__device__ __forceinline__ f32x4 load4(gfloat* __restrict__ row, int p, int HW) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (row == nullptr) return v;
-  if (VEC4) {
-    if (p + 3 < HW) return *reinterpret_cast<const f32x4 __attribute__((address_space(1)))*>(row + p);
-  }
-  if (p < HW) v.x = row[p];
-  if (p + 1 < HW) v.y = row[p + 1];
-  if (p + 2 < HW) v.z = row[p + 2];
-  if (p + 3 < HW) v.w = row[p + 3];
-  return v;
-}
-
-// scatter one reduced 16x16 tile (ti,tj) of -S into the pose system
-template <typename V>
-__device__ __forceinline__ void scatter_tile(V v, int reg, int l, int ti, int tj, const short* rowout,
-                                             long long* __restrict__ sys, int n6, int* meta) {
-  // D[i][j]: i = 4*(lane>>4)+reg (row in tile ti), j = lane&15 (row in tile tj)
-  const int oi = rowout[ti * 16 + 4 * (l >> 4) + reg];
-  const int oj = rowout[tj * 16 + (l & 15)];
-  if (oi < 0) return;
-  const double val = -static_cast<double>(v);
-  if (oj >= 0) {
-    // lower block triangle only (see pose_block_scatter): entry (oi, oj) if its block row is not above its block column, and
-    // the mirrored entry of an off-diagonal tile pair under the same rule - inside a diagonal 6 x 6 block both are kept
-    const int bi = oi / 6, bj = oj / 6;
-    if (bi >= bj) fix_add(sys, static_cast<long long>(oi) * n6 + oj, val, meta);
-    if (ti != tj && bj >= bi) fix_add(sys, static_cast<long long>(oj) * n6 + oi, val, meta);   // mirrored tile
-  } else if (oj == -2) {
-    fix_add(sys, static_cast<long long>(n6) * n6 + oi, val, meta);                 // rhs: - E (Q w)
-  }
-}
-
-// all T(T+1)/2 tile pairs in ONE pass over the pixels (rows read once, accumulators static)
-template <int T, bool VEC4, int PIX>
-__device__ __forceinline__ void schur_pass(const RowTab& rt,
-                                           gfloat* __restrict__ qrow, float* red /*[4][NT*4][64]*/,
-                                           long long* __restrict__ sys, int HW, int n6, int pix_base, int* meta) {
-  constexpr int NT = T * (T + 1) / 2;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int idx = lane & 15, kq = lane >> 4;
-  gfloat* rows[T];
-#pragma unroll
-  for (int t = 0; t < T; ++t) rows[t] = rt.ptr(t * 16 + idx);
-  f32x4 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-  for (int s = 0; s < PIX / 64; ++s) {
-    const int p = pix_base + s * 16 + 4 * kq;
-    const f32x4 q = load4<VEC4>(qrow, p, HW);
-    f32x4 b[T], a[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) { b[t] = load4<VEC4>(rows[t], p, HW); a[t] = b[t] * q; }
-    int n = 0;
-#pragma unroll
-    for (int ti = 0; ti < T; ++ti)
-#pragma unroll
-      for (int tj = ti; tj < T; ++tj) {
-        // K index of step c = pixel p + c of lane group kq (the same pixel for A and B)
-        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ti].x, b[tj].x, acc[n], 0, 0, 0);
-        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ti].y, b[tj].y, acc[n], 0, 0, 0);
-        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ti].z, b[tj].z, acc[n], 0, 0, 0);
-        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ti].w, b[tj].w, acc[n], 0, 0, 0);
-        ++n;
-      }
-  }
-  BA_WG_PROBE(1, 5);                     // products done (wave 0)
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    float* r = red + (static_cast<size_t>(wave) * NT + t) * 256;
-    r[lane] = acc[t].x; r[64 + lane] = acc[t].y; r[128 + lane] = acc[t].z; r[192 + lane] = acc[t].w;
-  }
-  __syncthreads();
-  BA_WG_PROBE(1, 6);                     // all four waves' products in LDS
-  int n = 0;
-#pragma unroll
-  for (int ti = 0; ti < T; ++ti)
-#pragma unroll
-    for (int tj = ti; tj < T; ++tj) {
-      const float* r0 = red + static_cast<size_t>(n) * 256 + tid;
-      const float v = (r0[0] + r0[static_cast<size_t>(NT) * 256]) +
-                      (r0[static_cast<size_t>(2 * NT) * 256] + r0[static_cast<size_t>(3 * NT) * 256]);
-      scatter_tile(v, tid >> 6, tid & 63, ti, tj, rt.out, sys, n6, meta);
-      ++n;
-    }
-}
-
-// Row tile ti against the CNT row tiles tj0 .. tj0 + CNT - 1 (tj0 >= ti) in one pass over the pixels: what a depth frame with more
-// than kFastTiles row tiles (> 9 free neighbours: a frontend window with its inactive edges, found by the full-sequence run of
-// bench.py - the replayed S-B / S-A windows have no inactive edges and never came here) used to do one tile PAIR at a time, two
-// workgroup barriers per pair: 15 to 36 rounds, 118 us per launch.  Per pair the SAME chain of MFMAs in the same order and the
-// same (w0 + w1) + (w2 + w3) reduction as every other path: bit-identical sums.
-template <int CNT, bool VEC4, int PIX>
-__device__ __forceinline__ void schur_rowpass(const RowTab& rt, gfloat* __restrict__ qrow, float* red,
-                                              long long* __restrict__ sys, int HW, int n6, int pix_base, int* meta, int ti, int tj0) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int idx = lane & 15, kq = lane >> 4;
-  gfloat* __restrict__ ra = rt.ptr(ti * 16 + idx);
-  gfloat* rb[CNT];
-#pragma unroll
-  for (int t = 0; t < CNT; ++t) rb[t] = rt.ptr((tj0 + t) * 16 + idx);
-  f32x4 acc[CNT];
-#pragma unroll
-  for (int t = 0; t < CNT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-  for (int s = 0; s < PIX / 64; ++s) {
-    const int p = pix_base + s * 16 + 4 * kq;
-    const f32x4 q = load4<VEC4>(qrow, p, HW);
-    const f32x4 a0 = load4<VEC4>(ra, p, HW);
-    const f32x4 a = a0 * q;
-    f32x4 b[CNT];
-#pragma unroll
-    for (int t = 0; t < CNT; ++t) b[t] = load4<VEC4>(rb[t], p, HW);
-#pragma unroll
-    for (int t = 0; t < CNT; ++t) {
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[t].x, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[t].y, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[t].z, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[t].w, acc[t], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < CNT; ++t) {
-    float* r = red + (static_cast<size_t>(wave) * CNT + t) * 256;
-    r[lane] = acc[t].x; r[64 + lane] = acc[t].y; r[128 + lane] = acc[t].z; r[192 + lane] = acc[t].w;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < CNT; ++t) {
-    const float* r0 = red + static_cast<size_t>(t) * 256 + tid;
-    const float v = (r0[0] + r0[static_cast<size_t>(CNT) * 256]) + (r0[static_cast<size_t>(2 * CNT) * 256] + r0[static_cast<size_t>(3 * CNT) * 256]);
-    scatter_tile(v, tid >> 6, tid & 63, ti, tj0 + t, rt.out, sys, n6, meta);
-  }
-  __syncthreads();                        // `red` is rewritten by the next pass
-}
-
-// schur_rowpass with the depth frame's rows STAGED IN LDS (round 6: dense frontend windows).  Streaming from global memory, every row
-// tile is read once per row pass it takes part in: 26 frames x 6 chunks with 7 row tiles re-read 1.1 MB of a (frame, chunk)'s 211 KB
-// of rows - 170 MB per launch, the whole of its 75 us (tools/ba_kernel_timeline.py at NF=26 RAD=8 HT=30 WD=101: tile pairs 38-52 us
-// per workgroup against ~3 us of MFMA).  Staged once per (frame, 256-pixel chunk) the pairs read LDS.  Same operands, same chain of
-// MFMAs in the same order, same (w0 + w1) + (w2 + w3) reduction: bit-identical to the streaming form at the same chunk size.
-constexpr int kLdsRowPad = 4;            // floats between rows: 16-byte alignment of every row, rows 8 apart share a bank group (2-way)
-template <int CNT, int PIX>
-__device__ __forceinline__ void schur_rowpass_lds(const float* L, const float* Lq, int nrows, const short* rowout, float* red,
-                                                  long long* __restrict__ sys, int n6, int* meta, int ti, int tj0,
-                                                  float* __restrict__ part_out, int pair0) {
-  constexpr int pitch = PIX + kLdsRowPad;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int idx = lane & 15, kq = lane >> 4;
-  const int ra_row = ti * 16 + idx;
-  const float* ra = L + static_cast<size_t>(ra_row < nrows ? ra_row : 0) * pitch;
-  const bool oka = ra_row < nrows;
-  const float* rb[CNT];
-  bool okb[CNT];
-#pragma unroll
-  for (int t = 0; t < CNT; ++t) {
-    const int r = (tj0 + t) * 16 + idx;
-    okb[t] = r < nrows;
-    rb[t] = L + static_cast<size_t>(okb[t] ? r : 0) * pitch;
-  }
-  f32x4 acc[CNT];
-#pragma unroll
-  for (int t = 0; t < CNT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-  for (int s = 0; s < PIX / 64; ++s) {
-    const int p = wave * (PIX / 4) + s * 16 + 4 * kq;                    // (inside the chunk)
-    const f32x4 q = *reinterpret_cast<const f32x4*>(Lq + p);
-    const f32x4 a0 = oka ? *reinterpret_cast<const f32x4*>(ra + p) : zero;
-    const f32x4 a = a0 * q;
-    f32x4 b[CNT];
-#pragma unroll
-    for (int t = 0; t < CNT; ++t) b[t] = okb[t] ? *reinterpret_cast<const f32x4*>(rb[t] + p) : zero;
-#pragma unroll
-    for (int t = 0; t < CNT; ++t) {
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[t].x, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[t].y, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[t].z, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[t].w, acc[t], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < CNT; ++t) {
-    float* r = red + (static_cast<size_t>(wave) * CNT + t) * 256;
-    r[lane] = acc[t].x; r[64 + lane] = acc[t].y; r[128 + lane] = acc[t].z; r[192 + lane] = acc[t].w;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < CNT; ++t) {
-    const float* r0 = red + static_cast<size_t>(t) * 256 + tid;
-    const float v = (r0[0] + r0[static_cast<size_t>(CNT) * 256]) + (r0[static_cast<size_t>(2 * CNT) * 256] + r0[static_cast<size_t>(3 * CNT) * 256]);
-    // two-stage sums (dense windows): the chunk's tile-pair sum goes to the workspace, ba_schur_reduce_kernel adds a frame's chunks and
-    // issues ONE fixed-point atomic per entry and frame - with one per chunk the 3.3 M memory-side atomics of a window's launch were
-    // half of its 93 us (tools/ba_kernel_timeline.py with PROBE_DEFS=-DPVO_BA_NO_ATOMICS)
-    if (part_out) part_out[static_cast<size_t>(pair0 + t) * 256 + tid] = v;
-    else scatter_tile(v, tid >> 6, tid & 63, ti, tj0 + t, rowout, sys, n6, meta);
-  }
-  __syncthreads();                        // `red` is rewritten by the next pass
-}
-
-template <bool VEC4, int PIX>
-__device__ __forceinline__ void ba_schur_body(
-    const Plan& pl, const int64_t* __restrict__ jj, const float* __restrict__ eta, int K_eta,
-    const float* __restrict__ Eii, const float* __restrict__ Cii, const float* __restrict__ bz,
-    float* __restrict__ Ei, const float* __restrict__ Eij,
-    float* __restrict__ Q, float* __restrict__ w, long long* __restrict__ sys,
-    int HW, int t0, int P, const float* __restrict__ part, const int64_t* __restrict__ ii, int E, int chunksA, int deal_rows,
-    float* __restrict__ Mrg, int depth_done, int lds_floats, float* __restrict__ spart, short* __restrict__ srow, int* __restrict__ sT,
-    const float* __restrict__ disps) {
-  __shared__ int rowcode[kMaxRows];       // see RowTab
-  __shared__ short rowout[kMaxRows];
-  __shared__ int nrows_s;
-  __shared__ float red[4 * (kFastTiles * (kFastTiles + 1) / 2) * 256];   // 40 KB
-  // the assembly's chunk sums, per edge, are added up and scattered by workgroups of their OWN: the last `deal_rows` rows of the
-  // grid (at most two edges each).  Dealt over the depth frames' workgroups, as in round 3, the 36 of 96 that had an edge at S-B
-  // started their own work 3.5 us late - and the kernel ends with its slowest workgroup (profiles/r04_ba_kernel_timeline.txt).
-  // gridDim.z slices: the row-tile passes of a depth frame with MANY neighbours (more than kFastTiles row tiles: a frontend window
-  // with its inactive edges) are dealt over the slices, ti = z, z + gridDim.z, ...; everything else is slice 0's and the other
-  // slices leave at once.  Every slice that stays runs the depth phase itself (identical values to identical addresses - the
-  // rows a slice reads are the ones it wrote) and every tile pair is still summed by ONE workgroup in the fixed order.
-  const int zi = blockIdx.z, Z = gridDim.z;
-  if (static_cast<int>(blockIdx.y) >= static_cast<int>(gridDim.y) - deal_rows) {
-    if (zi != 0) return;
-    if (part && threadIdx.x < 90) {
-      // kDealEdges edges per workgroup, CONSECUTIVE in the plan's by-source order: an edge's (ii, ii) block and vi entries land on
-      // the same addresses as its neighbours' (same source frame), so their fixed-point addends are summed in a register and
-      // leave as one atomic when the address changes - integer sums: the system is bit for bit what one atomic per edge gave.
-      // (A real window's 342 edges were 30 780 memory-side atomics, up to ~33 deep on a diagonal entry: half of the launch's
-      // 105 us, bench.py `sequence`; two edges a workgroup apart in the edge list shared nothing.)
-      const int t = threadIdx.x;
-      const int wgi = (blockIdx.y - (gridDim.y - deal_rows)) * gridDim.x + blockIdx.x;
-      // (the plan lists only edges whose source frame lies in [0, F): eidx[eptr[K] ..) is not initialised - bound by the plan's count)
-      const int Epl = pl.eptr[pl.meta[0]];
-      const int p0 = wgi * kDealEdges, p1 = (p0 + kDealEdges < Epl) ? p0 + kDealEdges : Epl;
-      long long pend_idx[2] = {-1, -1}, pend_acc[2] = {0, 0};
-      for (int pos = p0; pos < p1; ++pos) {
-        const int e = pl.eidx[pos];
-        double val = 0.0;
-        for (int c = 0; c < chunksA; ++c) val += static_cast<double>(part[(static_cast<long long>(e) * chunksA + c) * 90 + t]);
-        if (!(fabs(val) < 3.0e10)) { pl.meta[4] = 1; continue; }       // (fix_add's range check)
-        const long long q = __double2ll_rn(val * kFix);
-        long long idx[2];
-        pose_block_targets(t, static_cast<int>(ii[e]) - t0, static_cast<int>(jj[e]) - t0, P, idx);
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-          if (idx[sl] < 0) continue;
-          if (idx[sl] == pend_idx[sl]) { pend_acc[sl] += q; continue; }
-          if (pend_idx[sl] >= 0) atomicAdd(reinterpret_cast<unsigned long long*>(sys + pend_idx[sl]), static_cast<unsigned long long>(pend_acc[sl]));
-          pend_idx[sl] = idx[sl]; pend_acc[sl] = q;
-        }
-      }
-#pragma unroll
-      for (int sl = 0; sl < 2; ++sl)
-        if (pend_idx[sl] >= 0) atomicAdd(reinterpret_cast<unsigned long long*>(sys + pend_idx[sl]), static_cast<unsigned long long>(pend_acc[sl]));
-    }
-    return;
-  }
-  const int k = blockIdx.y;
-  BA_WG_PROBE(1, 0);
-  if (k >= pl.meta[0]) return;
-  BA_WG_PROBE(1, 1);                     // chunk sums of the assembly added, meta read
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n6 = 6 * P;
-  // this depth frame's out-edges and their target poses, fetched ONCE and in parallel into LDS: eptr -> eidx -> jj is a chain
-  // of three dependent loads that the depth phase and the row table used to walk per edge (12 + 12 serial round trips at S-B)
-  __shared__ int s_edge[256], s_pose[256];
-  __shared__ int s_lead[64], s_merged[64], any_merged_s;      // (the ballot path below: at most 64 out-edges)
-  const int e0 = pl.eptr[k], deg_all = pl.eptr[k + 1] - e0;
-  const int pself = pl.kx[k] - t0;
-  const bool in_lds = deg_all <= 256;
-  if (zi > 0 && 6 * deg_all + 7 <= 16 * kFastTiles) return;      // at most kFastTiles row tiles whatever the poses: slice 0 alone
-  if (in_lds && tid < deg_all) {
-    const int e = pl.eidx[e0 + tid];
-    s_edge[tid] = e;
-    s_pose[tid] = static_cast<int>(jj[e]) - t0;
-  }
-  __syncthreads();
-  BA_WG_PROBE(1, 2);                     // edge list in LDS
-  // The depth phase needs the edge list only.  Slice 0 issues it BEFORE wave 0 builds the row table, so the table's ~1 us of LDS
-  // work hides behind the depth phase's loads (as up to round 4); ONE barrier behind both publishes table and rows together.
-  // (S-B's launch: 18.2 us with the table in front and a 64-step follower scan, 17.3 now, 16.2 with round 4's kernel -
-  // profiles/r05_schur_sweep.txt, block 6.)
-  auto depth_phase = [&]() {
-    const DepthPrior pr = load_prior(pl.meta);      // (uniform: one read per workgroup, and none when ba_depth_kernel ran in front)
-#pragma unroll
-    for (int h = 0; h < PIX / 256; ++h) {
-      const int x = blockIdx.x * PIX + h * 256 + tid;
-      if (x < HW) depth_pixel(pl, k, x, eta, K_eta, Eii, Cii, bz, Ei, Q, w, HW, t0, P, in_lds ? s_edge : pl.eidx + e0, deg_all, pself, pr, disps);
-    }
-  };
-  // (every slice that gets here may have to stay - more than kFastTiles row tiles unless targets merge or are fixed - and then needs
-  // the rows: it issues the depth phase in front of the table like slice 0 instead of behind it; a slice that leaves after all has
-  // written the same values to the same addresses as slice 0.)
-  // depth_done: ba_depth_kernel ran in front of this launch (windows on 512-pixel chunks, round 6): at a real frontend window every
-  // one of the four slices re-read the frame's 16-18 edges x 8 rows here - 164 MB per launch instead of 41, and 20 us at the head of
-  // every workgroup (tools/ba_kernel_timeline.py, NF=26 RAD=8 HT=30 WD=101)
-  if (!depth_done) depth_phase();
-  if (in_lds && deg_all <= 64) {
-    // row table by wave 0, one lane per out-edge: the position of an edge's six rows = the number of free target poses before it
-    // (ballot + popcount) - the same order as the sequential walk below, which took 1.9 us of this kernel at S-B
-    // Round 5: edges of this frame that share their TARGET pose (a frontend window keeps every aged-out edge as an inactive one,
-    // factor_graph.py:281-289: the same frame pair several times - 18 out-edges to ~7 distinct poses) contribute row blocks that
-    // only ever meet as their SUM: S gets (sum_e E_e) Q (sum_e E_e)^T for that pose.  The first edge of each target (the "leader",
-    // in edge order) stands for the group; a leader with followers reads the group's summed rows from `Mrg` (written below by
-    // this workgroup for its own pixels, in edge order), one without reads its own Eij rows as before.  Rows 6 x 18 + 7 -> 6 x 7 + 7:
-    // four row tiles, the one-pass path.  Frames without repeated targets take exactly the path they took (bit-identical).
-    if (tid < 64) {
-      const bool free_pose = tid < deg_all && s_pose[tid] >= 0 && s_pose[tid] < P;      // fixed target pose: drops out (:1125, :1227)
-      int lead = tid;
-      if (free_pose) {
-        const int p = s_pose[tid];
-        for (int u = 0; u < tid; ++u) if (s_pose[u] == p) { lead = u; break; }
-      }
-      s_lead[tid] = free_pose ? lead : -1;
-      const bool is_lead = free_pose && lead == tid;
-      const unsigned long long mask = __ballot(is_lead);
-      // followers per leader: a leader has some iff another lane names it
-      const int named = (free_pose && lead != tid) ? lead : -1;
-      unsigned long long has_f = 0ull;
-      for (int u = 1; u < deg_all; ++u) {          // (lane 0 leads itself; uniform bound: deg_all is the workgroup's)
-        const int lu = __shfl(named, u);
-        if (lu >= 0) has_f |= 1ull << lu;
-      }
-      const bool self = pself >= 0 && pself < P;
-      const int base = self ? 6 : 0;
-      const bool merged = is_lead && ((has_f >> tid) & 1ull);
-      s_merged[tid] = merged ? 1 : 0;
-      if (is_lead) {
-        const int r = base + 6 * __popcll(mask & ((1ull << tid) - 1ull));
-        const int e = s_edge[tid], p = s_pose[tid];
-        const int src = merged ? kRowMrg : kRowEij;
-#pragma unroll
-        for (int n = 0; n < 6; ++n) { rowcode[r + n] = row_code(src, static_cast<long long>(e) * 6 + n); rowout[r + n] = static_cast<short>(6 * p + n); }
-      }
-      if (tid == 0) {
-        if (self) {
-#pragma unroll
-          for (int n = 0; n < 6; ++n) { rowcode[n] = row_code(kRowEi, static_cast<long long>(pself) * 6 + n); rowout[n] = static_cast<short>(6 * pself + n); }
-        }
-        int r = base + 6 * __popcll(mask);
-        if (r > 0) { rowcode[r] = row_code(kRowW, k); rowout[r] = -2; ++r; }
-        const int padded = (r + 15) & ~15;
-        for (int q = r; q < padded; ++q) { rowcode[q] = -1; rowout[q] = -1; }
-        nrows_s = r;
-        any_merged_s = has_f != 0ull ? 1 : 0;
-      }
-    }
-  } else if (tid == 0) {                  // any degree: sequential
-    any_merged_s = 0;
-    int r = 0;
-    if (pself >= 0 && pself < P) {
-      for (int n = 0; n < 6; ++n) { rowcode[r] = row_code(kRowEi, static_cast<long long>(pself) * 6 + n); rowout[r] = static_cast<short>(6 * pself + n); ++r; }
-    }
-    for (int o = 0; o < deg_all; ++o) {
-      const int e = in_lds ? s_edge[o] : pl.eidx[e0 + o];
-      const int p = in_lds ? s_pose[o] : static_cast<int>(jj[e]) - t0;
-      if (p < 0 || p >= P) continue;      // fixed target pose: drops out (:1125, :1227)
-      if (r + 7 > kMaxRows) { pl.meta[3] = 1; break; }   // > 169 free neighbours of one frame: flagged
-      for (int n = 0; n < 6; ++n) { rowcode[r] = row_code(kRowEij, static_cast<long long>(e) * 6 + n); rowout[r] = static_cast<short>(6 * p + n); ++r; }
-    }
-    if (r > 0) { rowcode[r] = row_code(kRowW, k); rowout[r] = -2; ++r; }
-    const int padded = (r + 15) & ~15;
-    for (int q = r; q < padded; ++q) { rowcode[q] = -1; rowout[q] = -1; }
-    nrows_s = r;
-  }
-  // Slice 0 has issued its depth phase in front of the table (above); the other slices need the tile count first - most of them
-  // leave here - and run the depth phase now.
-  if (zi > 0) {
-    __syncthreads();
-    if (((nrows_s + 15) >> 4) <= kFastTiles) return;               // (uniform: nrows_s is the workgroup's)
-  }
-  BA_WG_PROBE(1, 3);                     // row table built, depth phase issued
-  __syncthreads();
-  const int nrows = nrows_s;
-  const int T = (nrows + 15) >> 4;
-  if (in_lds && deg_all <= 64 && any_merged_s) {        // the summed rows of every target group with more than one edge, this workgroup's pixels
-#pragma unroll
-    for (int h = 0; h < PIX / 256; ++h) {
-      const int x = blockIdx.x * PIX + h * 256 + tid;
-      if (x >= HW) continue;
-      for (int L = 0; L < deg_all; ++L) {
-        if (!s_merged[L]) continue;                       // (uniform over the workgroup)
-        float m[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-        for (int t = L; t < deg_all; ++t) {
-          if (s_lead[t] != L) continue;
-          const int e = s_edge[t];
-#pragma unroll
-          for (int n = 0; n < 6; ++n) m[n] += Eij[(static_cast<long long>(e) * 6 + n) * HW + x];
-        }
-        const int el = s_edge[L];
-#pragma unroll
-        for (int n = 0; n < 6; ++n) Mrg[(static_cast<long long>(el) * 6 + n) * HW + x] = m[n];
-      }
-    }
-    __syncthreads();                      // (uniform: any_merged_s is the workgroup's)
-  }
-  BA_WG_PROBE(1, 4);                     // depth rows (and merged rows) stored
-  const bool lds_path = lds_floats > 0 && T > kFastTiles && static_cast<long long>(nrows) * (PIX + kLdsRowPad) + PIX <= lds_floats;
-  const int slot = schur_stage_slot(pl.kx[k], t0, P);        // (by frame identity: the same on every rank, whatever row k the frame has here)
-  const bool staged = lds_path && spart != nullptr && slot >= 0 && T * (T + 1) / 2 <= kSchurStagePairs;
-  if (sT != nullptr && slot >= 0 && blockIdx.x == 0 && zi == 0) {          // what ba_schur_reduce_kernel needs to know about this frame
-    if (tid == 0) sT[slot] = staged ? T : 0;
-    if (staged && tid < 16 * T) srow[slot * 128 + tid] = rowout[tid];
-  }
-  if (nrows == 0) return;
-
-  gfloat* __restrict__ qrow = (gfloat*)(Q + static_cast<long long>(k) * HW);
-  const RowTab rt = {rowcode, rowout, {Eij, Mrg, Ei, w}, HW};
-  const int pix_base = blockIdx.x * PIX + wave * (PIX / 4);
-
-  switch (T) {
-    case 1: schur_pass<1, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta); BA_WG_PROBE(1, 7); return;
-    case 2: schur_pass<2, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta); BA_WG_PROBE(1, 7); return;
-    case 3: schur_pass<3, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta); BA_WG_PROBE(1, 7); return;
-    case 4: schur_pass<4, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta); BA_WG_PROBE(1, 7); return;
-    default: break;
-  }
-  // any degree: one ROW TILE against up to eight others per pass (row tiles re-read from L2 once per pass)
-  constexpr int kPassTiles = 8;           // 8 x 4 x 256 floats of `red` = 32 KB
-  if (lds_path) {
-    // (round 6) the frame's rows of this chunk + Q, once into LDS (dynamic segment; the host asks for it only on 256-pixel chunks of
-    // a dense window and launches ONE slice then); a frame whose rows do not fit streams them as before, a few lines down
-    extern __shared__ __attribute__((aligned(16))) float dyn_rows[];
-    constexpr int pitch = PIX + kLdsRowPad;
-    float* Lq = dyn_rows + static_cast<size_t>(nrows) * pitch;
-    const int x0 = blockIdx.x * PIX;
-    // (eight rows' loads in flight per wave before the first store: one row at a time the staging was 26 serial round trips to HBM
-    // per wave - 50 of the workgroup's 60 us)
-    static_assert(PIX == 256 || PIX == 512 || PIX == 1024, "chunk");
-    for (int r0 = wave; r0 < nrows; r0 += 32) {
-      f32x4 v[8][PIX / 256];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int r = r0 + 4 * u;
-        gfloat* src = rt.ptr(r < nrows ? r : r0);
-#pragma unroll
-        for (int c = 0; c < PIX / 256; ++c) v[u][c] = load4<VEC4>(src, x0 + c * 256 + lane * 4, HW);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int r = r0 + 4 * u;
-        if (r < nrows) {
-#pragma unroll
-          for (int c = 0; c < PIX / 256; ++c)
-            *reinterpret_cast<f32x4*>(dyn_rows + static_cast<size_t>(r) * pitch + c * 256 + lane * 4) = v[u][c];
-        }
-      }
-    }
-    if (wave == 0) {
-#pragma unroll
-      for (int c = 0; c < PIX / 256; ++c) {
-        const int px = c * 256 + lane * 4;
-        *reinterpret_cast<f32x4*>(Lq + px) = load4<VEC4>(qrow, x0 + px, HW);
-      }
-    }
-    __syncthreads();
-    BA_WG_PROBE(1, 5);                   // (LDS form: rows staged)
-    float* part_out = staged ? spart + (static_cast<size_t>(slot) * gridDim.x + blockIdx.x) * kSchurStagePairs * 256 : nullptr;
-    for (int ti = 0; ti < T; ++ti) {
-      if (ti == 1) BA_WG_PROBE(1, 6);    // (LDS form: first row pass - the longest: T tile pairs - done)
-      const int ph = ti % (2 * Z);
-      if ((ph < Z ? ph : 2 * Z - 1 - ph) != zi) continue;
-      for (int tj0 = ti; tj0 < T; tj0 += kPassTiles) {
-        const int cnt = (T - tj0 < kPassTiles) ? T - tj0 : kPassTiles;
-        const int pair0 = ti * T - ti * (ti - 1) / 2 + (tj0 - ti);      // index of pair (ti, tj0) among the T (T + 1) / 2
-        switch (cnt) {
-          case 1: schur_rowpass_lds<1, PIX>(dyn_rows, Lq, nrows, rowout, red, sys, n6, pl.meta, ti, tj0, part_out, pair0); break;
-          case 2: schur_rowpass_lds<2, PIX>(dyn_rows, Lq, nrows, rowout, red, sys, n6, pl.meta, ti, tj0, part_out, pair0); break;
-          case 3: schur_rowpass_lds<3, PIX>(dyn_rows, Lq, nrows, rowout, red, sys, n6, pl.meta, ti, tj0, part_out, pair0); break;
-          case 4: schur_rowpass_lds<4, PIX>(dyn_rows, Lq, nrows, rowout, red, sys, n6, pl.meta, ti, tj0, part_out, pair0); break;
-          case 5: schur_rowpass_lds<5, PIX>(dyn_rows, Lq, nrows, rowout, red, sys, n6, pl.meta, ti, tj0, part_out, pair0); break;
-          case 6: schur_rowpass_lds<6, PIX>(dyn_rows, Lq, nrows, rowout, red, sys, n6, pl.meta, ti, tj0, part_out, pair0); break;
-          case 7: schur_rowpass_lds<7, PIX>(dyn_rows, Lq, nrows, rowout, red, sys, n6, pl.meta, ti, tj0, part_out, pair0); break;
-          default: schur_rowpass_lds<8, PIX>(dyn_rows, Lq, nrows, rowout, red, sys, n6, pl.meta, ti, tj0, part_out, pair0); break;
-        }
-      }
-    }
-    BA_WG_PROBE(1, 7);
-    return;
-  }
-  // row tile ti costs T - ti tile pairs: the slices take them in a SNAKE (0 1 2 3 3 2 1 0 0 1 ...), so that every slice gets the same
-  // number of pairs (T = 7, four slices: 7 | 6 + 1 | 5 + 2 | 4 + 3; dealt ti = z, z + 4, .. slice 0 had 10 and slice 3 had 4, and the
-  // launch ends with its slowest slice).  Every pair is still one workgroup's chain in the same order: bit-identical.
-  for (int ti = 0; ti < T; ++ti) {
-    const int ph = ti % (2 * Z);
-    if ((ph < Z ? ph : 2 * Z - 1 - ph) != zi) continue;
-    for (int tj0 = ti; tj0 < T; tj0 += kPassTiles) {
-      const int cnt = (T - tj0 < kPassTiles) ? T - tj0 : kPassTiles;
-      switch (cnt) {
-        case 1: schur_rowpass<1, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta, ti, tj0); break;
-        case 2: schur_rowpass<2, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta, ti, tj0); break;
-        case 3: schur_rowpass<3, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta, ti, tj0); break;
-        case 4: schur_rowpass<4, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta, ti, tj0); break;
-        case 5: schur_rowpass<5, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta, ti, tj0); break;
-        case 6: schur_rowpass<6, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta, ti, tj0); break;
-        case 7: schur_rowpass<7, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta, ti, tj0); break;
-        default: schur_rowpass<8, VEC4, PIX>(rt, qrow, red, sys, HW, n6, pix_base, pl.meta, ti, tj0); break;
-      }
-    }
-  }
-  BA_WG_PROBE(1, 7);
-}
-
-template <bool VEC4, int PIX>
-__global__ __launch_bounds__(256) void ba_schur_mfma_kernel(
-    Plan pl, const int64_t* __restrict__ jj, const float* __restrict__ eta, int K_eta,
-    const float* __restrict__ Eii, const float* __restrict__ Cii, const float* __restrict__ bz,
-    float* __restrict__ Ei, const float* __restrict__ Eij,
-    float* __restrict__ Q, float* __restrict__ w, long long* __restrict__ sys,
-    int HW, int t0, int P, const float* __restrict__ part, const int64_t* __restrict__ ii, int E, int chunksA, int deal_rows,
-    float* __restrict__ Mrg, int depth_done, int lds_floats, float* __restrict__ spart, short* __restrict__ srow, int* __restrict__ sT,
-    const float* __restrict__ disps) {
-  ba_schur_body<VEC4, PIX>(pl, jj, eta, K_eta, Eii, Cii, bz, Ei, Eij, Q, w, sys, HW, t0, P, part, ii, E, chunksA, deal_rows, Mrg, depth_done, lds_floats,
-                           spart, srow, sT, disps);
-}
-
-// second stage of the dense-window Schur sums: tile pair p of depth frame k = the sum over the frame's chunks (fixed order, fp64: the
-// addends are fp32) -> one fixed-point atomic per entry.  Integer sums across frames as before: bitwise reproducible, and an
-// edge-sharded run gets the whole graph's bits (a frame's edges, hence its chunks, live on one rank, and whether a frame is staged
-// is decided by its identity: schur_stage_slot).
-__global__ __launch_bounds__(256) void ba_schur_reduce_kernel(Plan pl, const float* __restrict__ spart, const short* __restrict__ srow,
-                                                              const int* __restrict__ sT, long long* __restrict__ sys, int gx, int n6, int t0) {
-  const int k = blockIdx.y, p = blockIdx.x, tid = threadIdx.x;
-  if (k >= pl.meta[0]) return;
-  const int slot = schur_stage_slot(pl.kx[k], t0, n6 / 6);
-  if (slot < 0) return;
-  const int T = sT[slot];
-  if (T == 0 || p >= T * (T + 1) / 2) return;
-  __shared__ short rowout[128];
-  if (tid < 128) rowout[tid] = tid < 16 * T ? srow[slot * 128 + tid] : static_cast<short>(-1);
-  __syncthreads();
-  int ti = 0, base = 0;
-  while (base + (T - ti) <= p) { base += T - ti; ++ti; }
-  const int tj = ti + (p - base);
-  double v = 0.0;
-  const float* sp = spart + (static_cast<size_t>(slot) * gx * kSchurStagePairs + p) * 256 + tid;
-  const size_t step = static_cast<size_t>(kSchurStagePairs) * 256;
-  for (int x0 = 0; x0 < gx; x0 += 8) {                     // (eight chunks' loads in flight; the additions keep the chunk order)
-    float a[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) a[u] = sp[static_cast<size_t>(x0 + u < gx ? x0 + u : x0) * step];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) if (x0 + u < gx) v += static_cast<double>(a[u]);
-  }
-  scatter_tile(v, tid >> 6, tid & 63, ti, tj, rowout, sys, n6, pl.meta);
-}
-
-// the depth phase of the Schur kernel as a launch of its own (one thread per pixel and depth frame): C, w, Q and the frame's own pose
-// rows Ei, in exactly the order depth_pixel states - the values are bit for bit what the fused form writes.  Used in front of the
-// 512- / 1024-pixel Schur grids (windows beyond ~15 poses), where the Schur kernel's z-slices would each repeat it.
-__global__ __launch_bounds__(256) void ba_depth_kernel(
-    Plan pl, const float* __restrict__ eta, int K_eta, const float* __restrict__ Eii, const float* __restrict__ Cii,
-    const float* __restrict__ bz, float* __restrict__ Ei, float* __restrict__ Q, float* __restrict__ w, int HW, int t0, int P,
-    const float* __restrict__ disps) {
-  const int k = blockIdx.y;
-  if (k >= pl.meta[0]) return;
-  const DepthPrior pr = load_prior(pl.meta);
-  __shared__ int s_edge[256];
-  const int tid = threadIdx.x;
-  const int e0 = pl.eptr[k], deg_all = pl.eptr[k + 1] - e0;
-  const int pself = pl.kx[k] - t0;
-  const bool in_lds = deg_all <= 256;
-  if (in_lds && tid < deg_all) s_edge[tid] = pl.eidx[e0 + tid];
-  __syncthreads();
-  const int x = blockIdx.x * 256 + tid;
-  if (x < HW) depth_pixel(pl, k, x, eta, K_eta, Eii, Cii, bz, Ei, Q, w, HW, t0, P, in_lds ? s_edge : pl.eidx + e0, deg_all, pself, pr, disps);
-}
 
 // ---------------------------------------------------------------------------
 // solve: damping + fp64 Cholesky + substitution + pose retraction, one workgroup
@@ -3894,8 +2715,6 @@ extern "C" int pvo_debug_ba_wg_probe(void* buf) { return hipMemcpyToSymbol(HIP_S
 extern "C" int pvo_debug_ba_probe(void* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g_ba_probe), &buf, sizeof(buf)) == hipSuccess ? 0 : 1; }
 #endif
 
-
-
 extern "C" size_t pvo_ba_workspace_bytes(int E, int P, int nframes, int HW) {
   if (E < 0 || P < 0 || nframes < 0 || HW < 0) return 0;
   return carve(nullptr, E, P, nframes, HW).bytes + 256;
@@ -3905,18 +2724,32 @@ static inline void* ws_base(void* workspace) {
   return reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
 }
 
+// the caller's workspace carved for these sizes; false: it is shorter than pvo_ba_workspace_bytes asks (PVO_EWORKSPACE)
+static bool carve_checked(Ws* w, void* workspace, size_t workspace_bytes, int E, int P, int nframes, int HW) {
+  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return false;
+  *w = carve(ws_base(workspace), E, P, nframes, HW);
+  return true;
+}
+
+// operand checks shared by the entry points that take a sensor-depth prior / a stereo baseline
+static bool prior_ok(const float* sens, float alpha) { return !sens || alpha > 0.0f; }      // (alpha stands in C's denominator; NaN fails here too)
+static bool baseline_ok(float baseline) { return baseline >= 0.0f && baseline < __builtin_inff(); }      // (NaN fails the first comparison)
+
+static int launch_plan(const Ws& w, const int64_t* ii, const int64_t* jj, int E, int nframes, int t0, int t1, int K_eta, int motion_only,
+                       const float* sens, float alpha, float baseline, hipStream_t st) {
+  hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, st, ii, jj, w.plan, E, nframes, t0, t1, K_eta, motion_only, sens, alpha, baseline);
+  PVO_CHECK_LAUNCH();
+  return PVO_OK;
+}
+
 extern "C" int pvo_ba_plan(const int64_t* ii, const int64_t* jj, int E, int nframes, int HW,
                            int K_eta, int t0, int t1, void* workspace, size_t workspace_bytes,
                            void* stream) {
   if (E < 0 || nframes <= 0 || t0 < 0 || t1 < t0 || t1 > nframes || !workspace) return PVO_EINVAL;
   if (E > 0 && (!ii || !jj)) return PVO_EINVAL;
-  const int P = t1 - t0;
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
-  hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, pvo_stream(stream),
-                     ii, jj, w.plan, E, nframes, t0, t1, K_eta, K_eta < 0 ? 1 : 0, static_cast<const float*>(nullptr), 0.0f, 0.0f);
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, t1 - t0, nframes, HW)) return PVO_EWORKSPACE;
+  return launch_plan(w, ii, jj, E, nframes, t0, t1, K_eta, K_eta < 0 ? 1 : 0, nullptr, 0.0f, 0.0f, pvo_stream(stream));
 }
 
 // the sensor-depth prior of every later pvo_ba_local on this workspace: one single-thread launch that writes the plan's meta words
@@ -3924,9 +2757,9 @@ extern "C" int pvo_ba_plan(const int64_t* ii, const int64_t* jj, int E, int nfra
 extern "C" int pvo_ba_depth_prior(void* workspace, size_t workspace_bytes, int E, int P, int nframes, int HW,
                                   const float* disps_sens, float alpha, void* stream) {
   if (!workspace || E < 0 || P < 0 || nframes <= 0 || HW <= 0) return PVO_EINVAL;
-  if (disps_sens && !(alpha > 0.0f)) return PVO_EINVAL;      // (alpha stands in C's denominator; NaN fails here too)
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
+  if (!prior_ok(disps_sens, alpha)) return PVO_EINVAL;
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, P, nframes, HW)) return PVO_EWORKSPACE;
   hipLaunchKernelGGL(ba_prior_kernel, dim3(1), dim3(1), 0, pvo_stream(stream), w.plan.meta, disps_sens, alpha);
   PVO_CHECK_LAUNCH();
   return PVO_OK;
@@ -3936,9 +2769,9 @@ extern "C" int pvo_ba_depth_prior(void* workspace, size_t workspace_bytes, int E
 // (no host synchronisation, capturable); pvo_ba_plan resets it to 0
 extern "C" int pvo_ba_stereo(void* workspace, size_t workspace_bytes, int E, int P, int nframes, int HW, float baseline, void* stream) {
   if (!workspace || E < 0 || P < 0 || nframes <= 0 || HW <= 0) return PVO_EINVAL;
-  if (!(baseline >= 0.0f) || !(baseline < __builtin_inff())) return PVO_EINVAL;      // (NaN fails the first comparison)
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
+  if (!baseline_ok(baseline)) return PVO_EINVAL;
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, P, nframes, HW)) return PVO_EWORKSPACE;
   hipLaunchKernelGGL(ba_stereo_kernel, dim3(1), dim3(1), 0, pvo_stream(stream), w.plan.meta, baseline);
   PVO_CHECK_LAUNCH();
   return PVO_OK;
@@ -3958,8 +2791,8 @@ extern "C" int pvo_ba_local(const float* poses, const float* disps, const float*
   if (E > 0 && (!targets || !weights || !ii || !jj)) return PVO_EINVAL;
   if (!motion_only && !eta) return PVO_EINVAL;
   if (P > 5400 || nframes >= (1 << 28)) return PVO_EUNSUPPORTED;      // (the Schur kernel's row table: 6 P + 5 in a short, row indices in 28 bits)
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, P, nframes, HW)) return PVO_EWORKSPACE;
   hipStream_t st = pvo_stream(stream);
   // pvo_ba_finish leaves `sys` zeroed after reading it; callers that chain local -> finish -> local on the same buffer
   // say so with bit 1 of motion_only and save the memset
@@ -4031,93 +2864,6 @@ extern "C" int pvo_ba_local(const float* poses, const float* disps, const float*
     }
   }
   return PVO_OK;
-}
-
-extern "C" int pvo_ba_finish(float* poses, float* disps, void* sys_,
-                             const int64_t* ii, const int64_t* jj,
-                             int E, int nframes, int ht, int wd, int t0, int t1,
-                             float lm, float ep, int motion_only, int clamp_frames, float disp_min,
-                             float* dx_out, float* dz_out, int dz_rows, int* status_out,
-                             void* workspace, size_t workspace_bytes, void* stream) {
-  return pvo_ba_finish_riders(poses, disps, sys_, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
-                              dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, stream);
-}
-
-extern "C" int pvo_ba_finish_conv1x1(float* poses, float* disps, void* sys_,
-                                     const int64_t* ii, const int64_t* jj,
-                                     int E, int nframes, int ht, int wd, int t0, int t1,
-                                     float lm, float ep, int motion_only, int clamp_frames, float disp_min,
-                                     float* dx_out, float* dz_out, int dz_rows, int* status_out,
-                                     void* workspace, size_t workspace_bytes,
-                                     const void* cx, const void* cw, const float* cbias, void* cy, long long crows, int cCout, int cdtype,
-                                     void* stream) {
-  pvo_ba_riders r{};
-  r.cx = cx; r.cw = cw; r.cbias = cbias; r.cy = cy; r.crows = crows; r.cCout = cCout; r.cdtype = cdtype;
-  return pvo_ba_finish_riders(poses, disps, sys_, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
-                              dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, cy ? &r : nullptr, stream);
-}
-
-static int ba_finish_impl(float* poses, float* disps, void* sys_, const long long* msg, const int* first_s,
-                          const int64_t* ii, const int64_t* jj,
-                          int E, int nframes, int ht, int wd, int t0, int t1,
-                          float lm, float ep, int motion_only, int clamp_frames, float disp_min,
-                          float* dx_out, float* dz_out, int dz_rows, int* status_out,
-                          void* workspace, size_t workspace_bytes,
-                          const pvo_ba_riders* jobs, int graph_edges, void* stream);
-
-extern "C" int pvo_ba_finish_riders(float* poses, float* disps, void* sys_,
-                                    const int64_t* ii, const int64_t* jj,
-                                    int E, int nframes, int ht, int wd, int t0, int t1,
-                                    float lm, float ep, int motion_only, int clamp_frames, float disp_min,
-                                    float* dx_out, float* dz_out, int dz_rows, int* status_out,
-                                    void* workspace, size_t workspace_bytes,
-                                    const pvo_ba_riders* jobs, void* stream) {
-  if (!sys_) return PVO_EINVAL;
-  return ba_finish_impl(poses, disps, sys_, nullptr, nullptr, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
-                        dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, jobs, -1, stream);
-}
-
-extern "C" int pvo_ba_finish_graph(float* poses, float* disps, void* sys_,
-                                   const int64_t* ii, const int64_t* jj,
-                                   int E, int nframes, int ht, int wd, int t0, int t1,
-                                   float lm, float ep, int motion_only, int clamp_frames, float disp_min,
-                                   float* dx_out, float* dz_out, int dz_rows, int* status_out,
-                                   void* workspace, size_t workspace_bytes, int graph_edges, void* stream) {
-  if (!sys_ || graph_edges < E) return PVO_EINVAL;
-  return ba_finish_impl(poses, disps, sys_, nullptr, nullptr, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
-                        dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, graph_edges, stream);
-}
-
-extern "C" size_t pvo_ba_packed_elems(const int* first_host, int P) {
-  if (!first_host || P < 0) return 0;
-  size_t blocks = 0;
-  for (int b = 0; b < P; ++b) {
-    const int f = first_host[b] < b ? (first_host[b] < 0 ? 0 : first_host[b]) : b;
-    blocks += static_cast<size_t>(b - f + 1) * 36;
-  }
-  return blocks + static_cast<size_t>(6) * P;
-}
-
-extern "C" int pvo_ba_pack(void* sys_, const int* first_s, void* msg, int P, void* stream) {
-  if (!sys_ || !first_s || !msg || P < 0) return PVO_EINVAL;
-  if (P > kMaxEnvBlocks) return PVO_EUNSUPPORTED;
-  if (P == 0) return PVO_OK;
-  const int n6 = 6 * P;
-  hipLaunchKernelGGL(ba_pack_kernel, dim3((n6 * n6 + n6 + 2047) / 2048), dim3(256), 0, pvo_stream(stream),
-                     static_cast<long long*>(sys_), first_s, static_cast<long long*>(msg), n6);
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
-}
-
-extern "C" int pvo_ba_finish_packed(float* poses, float* disps, const void* msg, const int* first_s,
-                                    const int64_t* ii, const int64_t* jj,
-                                    int E, int nframes, int ht, int wd, int t0, int t1,
-                                    float lm, float ep, int motion_only, int clamp_frames, float disp_min,
-                                    float* dx_out, float* dz_out, int dz_rows, int* status_out,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
-  if (!msg || !first_s) return PVO_EINVAL;
-  return ba_finish_impl(poses, disps, nullptr, static_cast<const long long*>(msg), first_s, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only,
-                        clamp_frames, disp_min, dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, -1, stream);
 }
 
 // The form that factorises the reduced pose system, from the free poses P, the edge count E OF THE WHOLE GRAPH, whether the system
@@ -4195,8 +2941,8 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
   long long* sys = static_cast<long long*>(sys_);
   if (!poses || !disps || (!sys && !msg) || !workspace) return PVO_EINVAL;
   if (P > kMaxEnvBlocks) return PVO_EUNSUPPORTED;           // (a 12288^2 fp64 system: 1.2 GB)
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, P, nframes, HW)) return PVO_EWORKSPACE;
   hipStream_t st = pvo_stream(stream);
   const int n6 = 6 * P;
   const SolveForm form = solve_form(P, graph_edges >= 0 ? graph_edges : E, msg != nullptr, pvo_knob(PVO_KNOB_BA_SOLVER));
@@ -4261,6 +3007,85 @@ static int ba_finish_impl(float* poses, float* disps, void* sys_, const long lon
   return PVO_OK;
 }
 
+extern "C" int pvo_ba_finish(float* poses, float* disps, void* sys_,
+                             const int64_t* ii, const int64_t* jj,
+                             int E, int nframes, int ht, int wd, int t0, int t1,
+                             float lm, float ep, int motion_only, int clamp_frames, float disp_min,
+                             float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  return pvo_ba_finish_riders(poses, disps, sys_, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
+                              dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int pvo_ba_finish_conv1x1(float* poses, float* disps, void* sys_,
+                                     const int64_t* ii, const int64_t* jj,
+                                     int E, int nframes, int ht, int wd, int t0, int t1,
+                                     float lm, float ep, int motion_only, int clamp_frames, float disp_min,
+                                     float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                                     void* workspace, size_t workspace_bytes,
+                                     const void* cx, const void* cw, const float* cbias, void* cy, long long crows, int cCout, int cdtype,
+                                     void* stream) {
+  pvo_ba_riders r{};
+  r.cx = cx; r.cw = cw; r.cbias = cbias; r.cy = cy; r.crows = crows; r.cCout = cCout; r.cdtype = cdtype;
+  return pvo_ba_finish_riders(poses, disps, sys_, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
+                              dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, cy ? &r : nullptr, stream);
+}
+
+extern "C" int pvo_ba_finish_riders(float* poses, float* disps, void* sys_,
+                                    const int64_t* ii, const int64_t* jj,
+                                    int E, int nframes, int ht, int wd, int t0, int t1,
+                                    float lm, float ep, int motion_only, int clamp_frames, float disp_min,
+                                    float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                                    void* workspace, size_t workspace_bytes,
+                                    const pvo_ba_riders* jobs, void* stream) {
+  if (!sys_) return PVO_EINVAL;
+  return ba_finish_impl(poses, disps, sys_, nullptr, nullptr, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
+                        dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, jobs, -1, stream);
+}
+
+extern "C" int pvo_ba_finish_graph(float* poses, float* disps, void* sys_,
+                                   const int64_t* ii, const int64_t* jj,
+                                   int E, int nframes, int ht, int wd, int t0, int t1,
+                                   float lm, float ep, int motion_only, int clamp_frames, float disp_min,
+                                   float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                                   void* workspace, size_t workspace_bytes, int graph_edges, void* stream) {
+  if (!sys_ || graph_edges < E) return PVO_EINVAL;
+  return ba_finish_impl(poses, disps, sys_, nullptr, nullptr, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only, clamp_frames, disp_min,
+                        dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, graph_edges, stream);
+}
+
+extern "C" size_t pvo_ba_packed_elems(const int* first_host, int P) {
+  if (!first_host || P < 0) return 0;
+  size_t blocks = 0;
+  for (int b = 0; b < P; ++b) {
+    const int f = first_host[b] < b ? (first_host[b] < 0 ? 0 : first_host[b]) : b;
+    blocks += static_cast<size_t>(b - f + 1) * 36;
+  }
+  return blocks + static_cast<size_t>(6) * P;
+}
+
+extern "C" int pvo_ba_pack(void* sys_, const int* first_s, void* msg, int P, void* stream) {
+  if (!sys_ || !first_s || !msg || P < 0) return PVO_EINVAL;
+  if (P > kMaxEnvBlocks) return PVO_EUNSUPPORTED;
+  if (P == 0) return PVO_OK;
+  const int n6 = 6 * P;
+  hipLaunchKernelGGL(ba_pack_kernel, dim3((n6 * n6 + n6 + 2047) / 2048), dim3(256), 0, pvo_stream(stream),
+                     static_cast<long long*>(sys_), first_s, static_cast<long long*>(msg), n6);
+  PVO_CHECK_LAUNCH();
+  return PVO_OK;
+}
+
+extern "C" int pvo_ba_finish_packed(float* poses, float* disps, const void* msg, const int* first_s,
+                                    const int64_t* ii, const int64_t* jj,
+                                    int E, int nframes, int ht, int wd, int t0, int t1,
+                                    float lm, float ep, int motion_only, int clamp_frames, float disp_min,
+                                    float* dx_out, float* dz_out, int dz_rows, int* status_out,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  if (!msg || !first_s) return PVO_EINVAL;
+  return ba_finish_impl(poses, disps, nullptr, static_cast<const long long*>(msg), first_s, ii, jj, E, nframes, ht, wd, t0, t1, lm, ep, motion_only,
+                        clamp_frames, disp_min, dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, -1, stream);
+}
+
 // diagnostic (tests, tools): the partition the last pvo_ba_finish on this workspace chose - out[0] = m, out[1] = s, both 0 when the
 // pose chain was solved in one piece.  Synchronises the stream.
 extern "C" int pvo_ba_last_partition(void* workspace, size_t workspace_bytes, int E, int P, int nframes, int HW, int* out, void* stream) {
@@ -4288,16 +3113,13 @@ extern "C" int pvo_ba_rig(float* poses, float* disps, const float* intrinsics,
   int rc = check_common(E, nframes, ht, wd, t0, t1);
   if (rc != PVO_OK) return rc;
   if (iterations < 0) return PVO_EINVAL;
-  if (disps_sens && !(alpha > 0.0f)) return PVO_EINVAL;
-  if (!(baseline >= 0.0f) || !(baseline < __builtin_inff())) return PVO_EINVAL;
+  if (!prior_ok(disps_sens, alpha) || !baseline_ok(baseline)) return PVO_EINVAL;
   const int P = t1 - t0, HW = ht * wd;
   if (!workspace) return PVO_EINVAL;
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
-  hipStream_t st = pvo_stream(stream);
-  hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, st, ii, jj, w.plan, E, nframes, t0, t1,
-                     K_eta, motion_only, disps_sens, alpha, baseline);
-  PVO_CHECK_LAUNCH();
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, P, nframes, HW)) return PVO_EWORKSPACE;
+  rc = launch_plan(w, ii, jj, E, nframes, t0, t1, K_eta, motion_only, disps_sens, alpha, baseline, pvo_stream(stream));
+  if (rc != PVO_OK) return rc;
   for (int it = 0; it < iterations; ++it) {
     rc = pvo_ba_local(poses, disps, intrinsics, targets, weights, eta, ii, jj, E, nframes, ht, wd, K_eta,
                       t0, t1, (motion_only ? 1 : 0) | (it > 0 ? 2 : 0), w.sys, workspace, workspace_bytes, stream);
@@ -4332,6 +3154,17 @@ extern "C" int pvo_ba(float* poses, float* disps, const float* intrinsics,
                       motion_only, dx_out, dz_out, dz_rows, status_out, workspace, workspace_bytes, nullptr, 0.0f, stream);
 }
 
+// The inverse of the damped reduced pose system `sys` (n = 6 P > 0 unknowns) into cov [n][n], through the workspace's `chol` scratch:
+// prepare / factor / invtri / product (the sigma stage above).  status_out: where the factorisation reports, or nullptr.
+static int launch_pose_cov(const Ws& w, const long long* sys, int n, float lm, float ep, double* cov, int* status_out, hipStream_t st) {
+  hipLaunchKernelGGL(ba_sigma_prepare_kernel, dim3((n * n + 255) / 256), dim3(256), 0, st, sys, w.chol, n, lm, ep);
+  hipLaunchKernelGGL(ba_sigma_factor_kernel, dim3(1), dim3(1024), 0, st, w.chol, n, w.plan.meta, status_out);
+  hipLaunchKernelGGL(ba_sigma_invtri_kernel, dim3(n), dim3(64), 0, st, w.chol, n);
+  hipLaunchKernelGGL(ba_sigma_product_kernel, dim3((n + 63) / 64, n), dim3(64), 0, st, w.chol, cov, n);
+  PVO_CHECK_LAUNCH();
+  return PVO_OK;
+}
+
 // Depth and pose uncertainty of the step pvo_ba_local has just assembled on this planned workspace (include/pvo_hip.h).  Reads
 // `sys`, the plan and the workspace's Q / Ei / Eij; writes the workspace's `chol` scratch and the caller's outputs only.
 extern "C" int pvo_ba_sigma(const void* sys_, void* workspace, size_t workspace_bytes,
@@ -4345,15 +3178,12 @@ extern "C" int pvo_ba_sigma(const void* sys_, void* workspace, size_t workspace_
   if (!workspace || (P > 0 && (!sys_ || !pose_cov))) return PVO_EINVAL;
   if (E == 0 || !ii || !jj) return PVO_EINVAL;              // (without an edge pvo_ba_local assembles nothing: there is no Q to report)
   const int HW = ht * wd, n = 6 * P;
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, P, nframes, HW)) return PVO_EWORKSPACE;
   hipStream_t st = pvo_stream(stream);
   if (P > 0) {
-    hipLaunchKernelGGL(ba_sigma_prepare_kernel, dim3((n * n + 255) / 256), dim3(256), 0, st, static_cast<const long long*>(sys_), w.chol, n, lm, ep);
-    hipLaunchKernelGGL(ba_sigma_factor_kernel, dim3(1), dim3(1024), 0, st, w.chol, n, w.plan.meta, status_out);
-    hipLaunchKernelGGL(ba_sigma_invtri_kernel, dim3(n), dim3(64), 0, st, w.chol, n);
-    hipLaunchKernelGGL(ba_sigma_product_kernel, dim3((n + 63) / 64, n), dim3(64), 0, st, w.chol, pose_cov, n);
-    PVO_CHECK_LAUNCH();
+    rc = launch_pose_cov(w, static_cast<const long long*>(sys_), n, lm, ep, pose_cov, status_out, st);
+    if (rc != PVO_OK) return rc;
   }
   const int Kmax = (nframes < P + E) ? nframes : (P + E);      // (>= 1: E >= 1)
   if (var_cond || var_pose || (P == 0 && status_out)) {
@@ -4375,16 +3205,14 @@ extern "C" int pvo_ba_uncertainty(const float* poses, const float* disps, const 
                                   const float* disps_sens, float alpha, float baseline, void* stream) {
   int rc = check_common(E, nframes, ht, wd, t0, t1);
   if (rc != PVO_OK) return rc;
-  if (disps_sens && !(alpha > 0.0f)) return PVO_EINVAL;
-  if (!(baseline >= 0.0f) || !(baseline < __builtin_inff())) return PVO_EINVAL;
+  if (!prior_ok(disps_sens, alpha) || !baseline_ok(baseline)) return PVO_EINVAL;
   const int P = t1 - t0, HW = ht * wd;
   if (P > kSigmaMaxPoses) return PVO_EUNSUPPORTED;
   if (!workspace) return PVO_EINVAL;
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
-  hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, pvo_stream(stream), ii, jj, w.plan, E, nframes, t0, t1,
-                     K_eta, 0, disps_sens, alpha, baseline);
-  PVO_CHECK_LAUNCH();
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, P, nframes, HW)) return PVO_EWORKSPACE;
+  rc = launch_plan(w, ii, jj, E, nframes, t0, t1, K_eta, 0, disps_sens, alpha, baseline, pvo_stream(stream));
+  if (rc != PVO_OK) return rc;
   rc = pvo_ba_local(poses, disps, intrinsics, targets, weights, eta, ii, jj, E, nframes, ht, wd, K_eta, t0, t1, 0, w.sys,
                     workspace, workspace_bytes, stream);
   if (rc != PVO_OK) return rc;
@@ -4412,14 +3240,13 @@ extern "C" int pvo_ba_calib(float* poses, float* disps, float* intrinsics,
   if (P < 1 || P > kCalibMaxPoses) return PVO_EUNSUPPORTED;
   if (E < 1 || iterations < 0 || !(ep_c >= 0.0f) || free_mask < 0 || free_mask > 15) return PVO_EINVAL;
   if (!poses || !disps || !intrinsics || !targets || !weights || !eta || !ii || !jj || !workspace || !calib_workspace) return PVO_EINVAL;
-  if (workspace_bytes < pvo_ba_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
+  Ws w;
+  if (!carve_checked(&w, workspace, workspace_bytes, E, P, nframes, HW)) return PVO_EWORKSPACE;
   if (calib_bytes < pvo_ba_calib_workspace_bytes(E, P, nframes, HW)) return PVO_EWORKSPACE;
-  Ws w = carve(ws_base(workspace), E, P, nframes, HW);
   CalibWs c = carve_calib(ws_base(calib_workspace), E, P, nframes, HW);
   hipStream_t st = pvo_stream(stream);
-  hipLaunchKernelGGL(ba_plan_kernel, dim3(1), dim3(256), 0, st, ii, jj, w.plan, E, nframes, t0, t1,
-                     K_eta, 0, static_cast<const float*>(nullptr), 0.0f, 0.0f);
-  PVO_CHECK_LAUNCH();
+  rc = launch_plan(w, ii, jj, E, nframes, t0, t1, K_eta, 0, nullptr, 0.0f, 0.0f, st);
+  if (rc != PVO_OK) return rc;
   if (hipMemsetAsync(c.dc, 0, sizeof(float) * 8, st) != hipSuccess) return PVO_ELAUNCH;
   int* cflag = reinterpret_cast<int*>(c.dc) + 5;
   const int Kmax = (nframes < P + E) ? nframes : (P + E);
@@ -4434,11 +3261,8 @@ extern "C" int pvo_ba_calib(float* poses, float* disps, float* intrinsics,
     hipLaunchKernelGGL(ba_calib_schur_kernel, dim3(chunks, Kmax), dim3(256), 0, st, w.plan, jj, w.Ei, w.Eij, w.Q, w.w, c.gc, c.Gc,
                        c.fix, cflag, HW, t0, P);
     PVO_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ba_sigma_prepare_kernel, dim3((n * n + 255) / 256), dim3(256), 0, st, w.sys, w.chol, n, lm, ep);
-    hipLaunchKernelGGL(ba_sigma_factor_kernel, dim3(1), dim3(1024), 0, st, w.chol, n, w.plan.meta, static_cast<int*>(nullptr));
-    hipLaunchKernelGGL(ba_sigma_invtri_kernel, dim3(n), dim3(64), 0, st, w.chol, n);
-    hipLaunchKernelGGL(ba_sigma_product_kernel, dim3((n + 63) / 64, n), dim3(64), 0, st, w.chol, c.X, n);
-    PVO_CHECK_LAUNCH();
+    rc = launch_pose_cov(w, w.sys, n, lm, ep, c.X, nullptr, st);
+    if (rc != PVO_OK) return rc;
     hipLaunchKernelGGL(ba_calib_solve_kernel, dim3(1), dim3(1024), 0, st, w.sys, c.X, reinterpret_cast<const int*>(w.chol + static_cast<size_t>(n) * n),
                        c.fix, w.plan.meta, poses, intrinsics, w.dx, dx_out, c.dc, dc_out, status_out, P, t0, lm, ep_c, free_mask);
     hipLaunchKernelGGL(ba_calib_backsub_kernel, dim3(chunks, Kmax), dim3(256), 0, st, w.plan, jj, w.Ei, w.Eij, w.Q, w.w, w.dx, c.Gc, c.dc,

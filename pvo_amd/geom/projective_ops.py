@@ -8,7 +8,7 @@ kernels (`pvo_reproject`, `pvo_ba`).
 
 Unlike the reference, no 4x6 point Jacobian or 2x4 projection Jacobian is materialised and
 multiplied: the 2x6 product is written out in closed form (the same expressions the HIP
-assemble kernel uses, pvo_amd/csrc/ba.hip), and the poses broadcast instead of being repeated
+assemble kernel uses, pvo_amd/csrc/ba_assemble.h), and the poses broadcast instead of being repeated
 per pixel.
 """
 import torch

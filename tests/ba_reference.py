@@ -8,7 +8,7 @@ the comparison with a bound derived from the case's own sensitivity (`sensitivit
     reduced_system     (S, rhs): the undamped A - E Q E^T and its right-hand side in fp64 - the first half of rgbd_reference.gn_step
     reduced_abs        the same sums with every addend replaced by its magnitude: T, what a summation error is relative to
     decode_sys         the device's 64-bit fixed-point system -> fp64
-    sys_bound          (n_add + 16) 2^-24 T + n_fix 2^-29 per entry, n_add and n_fix read off pvo_amd/csrc/ba.hip (see n_add) for the form
+    sys_bound          (n_add + 16) 2^-24 T + n_fix 2^-29 per entry, n_add and n_fix read off pvo_amd/csrc/ba_assemble.h and ba_schur.h (see n_add) for the form
                        of pvo_ba_local's launch rule that the window reaches
     launch_form        that form, as a predicate over the graph (frame_rows, frame_paths): every GPU test asserts the one it claims
     case / admission   a (graph, regime, damping) triple with its fp64 step, s_case and the conditions it must meet to be used on the GPU
@@ -324,7 +324,7 @@ def fix_addends(s):
 # ------------------------------------------------------------------------------------------------ the launch rule
 # pvo_ba_local's size rules (ba.hip, "pixels per workgroup" down to the Schur launch) and ba_schur_body's per-frame branches, restated
 # as predicates over the GRAPH: every GPU test asserts the form it claims before it runs, so a rule change fails the test instead of
-# moving it onto another kernel.  The constants, where they are in ba.hip:
+# moving it onto another kernel.  The constants, by their names in ba_schur.h, ba_workspace.h and ba.hip:
 FAST_TILES = 4            # kFastTiles: up to 4 row tiles (64 rows) take schur_pass, all tile pairs in one pass
 STAGE_PAIRS = 36          # kSchurStagePairs: tile pairs a staged frame may have (8 row tiles)
 STAGE_FRONT = 8           # kSchurStageFront: the frames in front of t0 that have a staging slot (schur_stage_slot)
@@ -409,9 +409,9 @@ def max_out_degree(s):
     return int(np.bincount(s["ii"].numpy()).max())
 
 
-# fp32 additions behind one fixed-point addend, read off pvo_amd/csrc/ba.hip:
-ASSEMBLE_CHUNK = 512      # kChunkA = 256 kPPT, kPPT = 2 pixels per thread (ba.hip:61-62)
-SCHUR_CHUNK = 256         # kSchurPix (ba.hip:622); pvo_ba_local keeps 256-pixel chunks while (HW / 256) (P + 1) <= 192, and in a dense window
+# fp32 additions behind one fixed-point addend, read off pvo_amd/csrc/ba_workspace.h and ba_schur.h:
+ASSEMBLE_CHUNK = 512      # kChunkA = 256 kPPT, kPPT = 2 pixels per thread (ba_workspace.h)
+SCHUR_CHUNK = 256         # kSchurPix (ba_schur.h); pvo_ba_local keeps 256-pixel chunks while (HW / 256) (P + 1) <= 192, and in a dense window
 
 
 def schur_chunk(s):
@@ -421,13 +421,14 @@ def schur_chunk(s):
 
 def n_add(deg, pix=SCHUR_CHUNK):
     """the longest chain of fp32 additions behind one fixed-point addend, for a window whose frames have at most `deg` out-edges and
-    whose Schur launch takes `pix` pixels per workgroup (the line numbers are those of the 256-pixel form's first derivation; the
+    whose Schur launch takes `pix` pixels per workgroup (the functions named are those the 256-pixel form was first derived from; the
     other forms are read off the same functions):
-      pose part   2 kPPT = 4 per thread (two pixels, rows u and v: pixel_terms, ba.hip:287,312) + 6 steps of the wave's reduce-scatter
-                  (ba.hip:499-526) + 2 across the four waves (ba.hip:538) = 12; the chunks of an edge are then added in fp64 (ba.hip:891);
-      Schur part  64 per wave - a quarter of a 256-pixel chunk, 16 MFMAs of K = 4 (schur_pass, ba.hip:700-717) - + 2 across the waves
-                  (ba.hip:733-734) = 66, on operands that are sums over the frame's out-edges themselves: Ei on either side, or w
-                  (deg - 1 each, depth_pixel ba.hip:582-589), C + eta (deg, ba.hip:584,603), the division and the product E Q (2).
+      pose part   2 kPPT = 4 per thread (two pixels, rows u and v: pixel_terms, ba_assemble.h) + 6 steps of the wave's reduce-scatter
+                  + 2 across the four waves (both in ba_assemble_kernel) = 12; the chunks of an edge are then added in fp64
+                  (the deal rows of ba_schur_body, ba_schur.h);
+      Schur part  64 per wave - a quarter of a 256-pixel chunk, 16 MFMAs of K = 4 (schur_pass, ba_schur.h) - + 2 across the waves
+                  (schur_pass's end) = 66, on operands that are sums over the frame's out-edges themselves: Ei on either side, or w
+                  (deg - 1 each, depth_pixel in ba_schur.h), C + eta (deg, depth_pixel), the division and the product E Q (2).
       512 / 1024  schur_pass<T, VEC4, PIX> and schur_rowpass<CNT, VEC4, PIX> are templates over the chunk: a wave owns PIX / 4 pixels
                   (pix_base = blockIdx.x PIX + wave PIX / 4) and walks them in PIX / 64 steps of four MFMAs of K = 4 - one product per pixel
                   added to the accumulator, a chain of PIX / 4 = 128 / 256 - then the same (w0 + w1) + (w2 + w3) across the waves:
@@ -441,7 +442,7 @@ def n_add(deg, pix=SCHUR_CHUNK):
 
 def sys_bound(s, T):
     """per entry of (S, rhs): (n_add + 16) 2^-24 T + n_fix 2^-29.  16 units cover the per-pixel products - the 2^-20 relative
-    perturbation s_case is defined with; 2^-29 is half a unit of the 2^-28 fixed-point grid (fix_add, ba.hip:52-58)."""
+    perturbation s_case is defined with; 2^-29 is half a unit of the 2^-28 fixed-point grid (fix_add, ba_workspace.h)."""
     TS, Tr = T
     nS, nr = fix_addends(s)
     k = (n_add(max_out_degree(s), schur_chunk(s)) + 16) * 2.0 ** -24
@@ -451,8 +452,8 @@ def sys_bound(s, T):
 def decode_sys(sys, P):
     """the device's fixed-point system, int64 [(6P)^2 + 6P] (row-major S, then rhs; units of 2^-28) -> (S [6P,6P], rhs [6P]) in fp64.
     Only the LOWER BLOCK TRIANGLE of `sys` is ever written - confirmed in the code: pose_block_scatter adds an edge's (i, j) block at
-    (max, min) only (ba.hip:364-371) and scatter_tile keeps an entry only if its block row is not above its block column
-    (ba.hip:675-679); inside a diagonal block both triangles are written.  So S is read from the lower block triangle and mirrored;
+    (max, min) only (ba_assemble.h) and scatter_tile keeps an entry only if its block row is not above its block column
+    (ba_schur.h); inside a diagonal block both triangles are written.  So S is read from the lower block triangle and mirrored;
     the words above it are not read here: tests/test_ba_fp64_gpu.py asserts that they are 0."""
     v = np.asarray(sys.cpu().numpy() if hasattr(sys, "cpu") else sys, np.int64)
     n6 = 6 * P
@@ -563,7 +564,7 @@ def chain(graph, regime, damping, iters=2):
     return _chains[key]
 
 
-FIX_LIMIT = 3.0e10      # fix_add's range check per addend (ba.hip:54); the sums live in int64 units of 2^-28: |sum| < 2^35
+FIX_LIMIT = 3.0e10      # fix_add's range check per addend (ba_workspace.h); the sums live in int64 units of 2^-28: |sum| < 2^35
 
 
 def overflow_window():

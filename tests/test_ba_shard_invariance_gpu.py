@@ -1,6 +1,6 @@
 """Shard invariance of the dense bundle adjustment at the WORDS of `sys` (include/pvo_hip.h, pvo_ba_local: "identical for any partition
 of the edges by source frame over ranks"), under every form of the launch rule, and the two rules that used to read rank-local
-quantities (ba.hip):
+quantities (schur_stage_slot in ba_workspace.h, solve_form in ba.hip):
 
   staging      whether a dense window's frame adds its chunk sums in fp64 and rounds once was decided by the NUMBER of depth frames of
                the call (`Kgrid <= P + 8`, from K_eta).  front10 - 30 depth frames on the whole graph, 25 or fewer on a balanced shard, P + 8 = 28 -

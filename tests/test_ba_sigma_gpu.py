@@ -158,7 +158,7 @@ def test_one_call_form_equals_plan_recorders_local_sigma_and_nothing_is_modified
 
 
 def _workspace_q(ws, E, P, F, HW, K):
-    """rows [0, K) of Q in a BA workspace: the regions in front of it as the library carves them (pvo_amd/csrc/ba.hip, `carve`: the
+    """rows [0, K) of Q in a BA workspace: the regions in front of it as the library carves them (pvo_amd/csrc/ba_workspace.h, `carve`: the
     plan's int tables, Eii, Eij, Cii, bz, Ei; every region padded to 256 bytes, the base aligned to 256)"""
     from pvo_amd import droid_backends as db
     up = lambda n: (n + 255) & ~255
