@@ -92,7 +92,9 @@ const char* pvo_last_hip_error(void);
  * new entry points pvo_update_operator_rows / pvo_graph_update_rows / pvo_corr_build_tiled_rows / pvo_edge_rows_init; still 106,
  * volume rendering: no existing struct changed - new structs pvo_tsdf_render_args / pvo_tsdf_sparse_render_args (with *_args_size())
  * and new entry points pvo_tsdf_render[_workspace_bytes] / pvo_tsdf_sparse_render[_workspace_bytes]; still 106, shard invariance:
- * no struct changed - new entry points pvo_ba_finish_graph / pvo_ba_solve_kind): a caller
+ * no struct changed - new entry points pvo_ba_finish_graph / pvo_ba_solve_kind; still 106, frame-to-model tracking: no existing
+ * struct changed - new structs pvo_tsdf_track_args / pvo_tsdf_sparse_track_args (with *_args_size()) and new entry points
+ * pvo_tsdf_track[_workspace_bytes] / pvo_tsdf_sparse_track[_workspace_bytes]): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -1104,6 +1106,114 @@ typedef struct pvo_tsdf_sparse_render_args {
 size_t pvo_tsdf_sparse_render_args_size(void);
 size_t pvo_tsdf_sparse_render_workspace_bytes(int N);
 int pvo_tsdf_sparse_render(const pvo_tsdf_sparse_render_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Frame-to-model tracking: a camera pose refined against the TSDF volume     */
+/* ------------------------------------------------------------------------- */
+
+/* pvo_tsdf_track: Gauss-Newton on the fused signed distance at a frame's back-projected pixels (direct SDF tracking, Bylow et al. 2013;
+ * no counterpart in the reference): per slot, the pose G that minimises  sum_pixels w rho(S(G^-1 X_pixel)).  No rendered depth, no
+ * correspondence search: one trilinear sample per pixel and evaluation.  Device pointers, dense.  Stated per pixel and per evaluation:
+ * an implementation may order the work as it likes, as long as the sums below are formed in an order that depends on the shapes alone.
+ *
+ *   Volume (read only): tsdf, wsum, nz, ny, nx, origin, voxel, min_weight as in pvo_tsdf_render.
+ *   Frames: disps f32 [nframes,ht,wd] inverse depth with intrinsics [4] for ht x wd; weight f32 [nframes,ht,wd] or NULL (= 1);
+ *   ix int64 [N]: slot s uses frame ix[s].
+ *   Start: poses f32 [N,7] world-to-camera, ONE PER SLOT (not per frame): several slots may name one frame with different starts.
+ *   Parameters: iters in [0, PVO_TSDF_TRACK_MAX_ITERS]; band in (0, 1]; huber >= 0 (0 = off); lm >= 0, ep >= 0; min_count >= 1.
+ *   Outputs, all written for every slot (a caller never clears them):
+ *     poses_out f32 [N,7]                  may be the very array `poses` (the same pointer; no other overlap)
+ *     info      f32 [N,iters+1,4]          per evaluation (E, count, max|xi| of the step taken from it, status); the last row is the
+ *                                          evaluation AT the final pose, its step is 0.  count is exact below 2^24
+ *     system    f64 [N,27] or NULL         of the LAST evaluation: the undamped H (upper triangle, row-major, 21 values), then b: the
+ *                                          pose's information matrix
+ *     residual  f32 [N,ht,wd] or NULL      S at the final pose, NaN where the pixel does not contribute
+ *     jac       f32 [N,ht,wd,6] or NULL    the pixel's J at the final pose, 0 where it does not contribute (a diagnostic)
+ *
+ * One EVALUATION at pose G = (R, t), with M, p0 the view constants of pvo_tsdf_render made from G (R of the quaternion as stored), every
+ * multiply-add below one fused operation, every other operation rounded to fp32:
+ *   1. pixel (vi, ui) needs d finite and > 0 and w finite and > 0;  z = 1 / d.
+ *   2. rx, ry, g as in pvo_tsdf_render;  p_i = fma(z, g_i, p0_i) in voxel coordinates.
+ *   3. it is VALID under the render's sample rule: 0 <= p_i <= n_i - 1, cell c_i = min(floor(p_i), n_i - 2), all eight corners with
+ *      wsum >= min_weight (in the brick volume: in bricks that exist).
+ *   4. S = the trilinear interpolant at f = p - c, grad its analytic gradient per voxel (the render's, csrc/tsdf_ray.h).
+ *   5. the pixel CONTRIBUTES iff it is valid and |S| < band.  (Truncated free space, S = 1, has no gradient and never votes.)
+ *   6. Xc = (z rx, z ry, z);  gc_i = fma(M_0i, grad_0, fma(M_1i, grad_1, M_2i grad_2))  (= R grad / voxel);
+ *      J = -(gc, Xc x gc), the cross product's components fma(a, b, -(c d)): the derivative of S under G <- Exp(xi) G, xi = (tau, phi),
+ *      the retraction of pvo_ba and pvo_se3_unary.
+ *   7. a = |S|;  k = 1, rho = S^2 if huber == 0 or a <= huber;  otherwise k = huber / a, rho = huber fma(2, a, -huber).
+ *   8. over the frame's pixels:  H += (w k J_i) J_j,  b += (w k J_i) S,  E += w rho,  count += 1.  The terms are fp32; they are summed
+ *      in a fixed tree: 64 pixels of an 8 x 8 tile (six levels), four tiles side by side (two levels) in fp32, the rest in fp64.
+ * One STEP:  A = H + diag(lm H_ii + ep);  Cholesky in fp64;  xi = -A^-1 b, rounded to fp32.  status = 1 if count < min_count; else 2 if a
+ * pivot is not finite and > 0 or xi is not finite; else 0.  Only with status 0 the step is applied:  G <- Exp(xi) G  with csrc/se3.h's
+ * retract, the function pvo_ba's retraction calls (like it, the product of two unit quaternions is stored as it comes).  Otherwise the
+ * pose stays.  The last row's status is formed in the same way; no step follows it.
+ * A slot whose id is outside [0, nframes): its pose is copied, every row of info is (0, 0, 0, 4), system and jac are 0, residual is NaN
+ * (no pixel of it contributes); its frame is never dereferenced.
+ *
+ * 2 iters + 3 launches (view constants; per evaluation one thread per pixel - a wave on an 8 x 8 tile, one 128-byte slab of partial
+ * sums per workgroup - and one workgroup per slot that sums, solves and retracts).  No atomics, no allocation, no host
+ * synchronisation: capturable; the same operands give the same bytes; no device loop's trip count depends on data.
+ * workspace: pvo_tsdf_track_workspace_bytes(N, ht, wd) bytes (PVO_EWORKSPACE otherwise), 16-byte aligned.
+ * Limits (PVO_EINVAL): the volume limits of pvo_tsdf_render; ht*wd < 2^31, ht <= 524280; a parameter outside its range or not finite; then, unless
+ * N == 0 or ht*wd == 0 (PVO_OK, nothing written): a NULL poses / poses_out / info / disps / intrinsics / ix, N * workgroups per image
+ * >= 2^31; then the workspace; then, unless a dimension is < 2 (no cell: no pixel contributes, every status 1 - or 4 -, PVO_OK): a NULL
+ * tsdf / wsum. */
+#define PVO_TSDF_TRACK_MAX_ITERS 64
+typedef struct pvo_tsdf_track_args {
+  const float* tsdf;
+  const float* wsum;
+  int nz, ny, nx;
+  float origin[3];
+  float voxel, min_weight;
+  const float* poses;
+  const float* disps;
+  const float* intrinsics;
+  const int64_t* ix;
+  const float* weight;
+  int N, nframes, ht, wd;
+  int iters, min_count;
+  float band, huber, lm, ep;
+  float* poses_out;
+  float* info;
+  double* system;
+  float* residual;
+  float* jac;
+} pvo_tsdf_track_args;
+size_t pvo_tsdf_track_args_size(void);
+size_t pvo_tsdf_track_workspace_bytes(int N, int ht, int wd);
+int pvo_tsdf_track(const pvo_tsdf_track_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pvo_tsdf_sparse_track: pvo_tsdf_track on the GLOBAL lattice [8gz,8gy,8gx] of a brick volume (grid, tsdf, wsum, cap as in
+ * pvo_tsdf_sparse_render).  A pixel is valid only if all eight corners of its cell lie in bricks that exist.  Position, cell, value,
+ * gradient and sums come from the same inline functions called with the global integer cell index, in the same order: every output has
+ * the BYTES of pvo_tsdf_track over the [8gz,8gy,8gx] volume that holds the bricks and zeros elsewhere, for min_weight > 0.
+ * Launches, workspace (pvo_tsdf_sparse_track_workspace_bytes(N, ht, wd)) and limits as pvo_tsdf_track with the grid limits of the brick
+ * volume; cap == 0 or an empty grid: no pixel contributes, PVO_OK; otherwise a NULL grid is PVO_EINVAL as well. */
+typedef struct pvo_tsdf_sparse_track_args {
+  const int32_t* grid;
+  const float* tsdf;
+  const float* wsum;
+  int gz, gy, gx, cap;
+  float origin[3];
+  float voxel, min_weight;
+  const float* poses;
+  const float* disps;
+  const float* intrinsics;
+  const int64_t* ix;
+  const float* weight;
+  int N, nframes, ht, wd;
+  int iters, min_count;
+  float band, huber, lm, ep;
+  float* poses_out;
+  float* info;
+  double* system;
+  float* residual;
+  float* jac;
+} pvo_tsdf_sparse_track_args;
+size_t pvo_tsdf_sparse_track_args_size(void);
+size_t pvo_tsdf_sparse_track_workspace_bytes(int N, int ht, int wd);
+int pvo_tsdf_sparse_track(const pvo_tsdf_sparse_track_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

@@ -140,6 +140,12 @@ SIGNATURES = {
     "pvo_tsdf_sparse_render_args_size": (_sz, []),
     "pvo_tsdf_sparse_render_workspace_bytes": (_sz, [_i]),
     "pvo_tsdf_sparse_render": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_track_args_size": (_sz, []),
+    "pvo_tsdf_track_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pvo_tsdf_track": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_sparse_track_args_size": (_sz, []),
+    "pvo_tsdf_sparse_track_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pvo_tsdf_sparse_track": (_i, [_vp, _vp, _sz, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -276,6 +282,25 @@ class TsdfSparseRenderArgs(_c.Structure):
                 ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i)] + _RENDER_TAIL
 
 
+TSDF_TRACK_MAX_ITERS = 64                  # PVO_TSDF_TRACK_MAX_ITERS
+
+_TRACK_TAIL = [("origin", _f * 3), ("voxel", _f), ("min_weight", _f),
+               ("poses", _vp), ("disps", _vp), ("intrinsics", _vp), ("ix", _vp), ("weight", _vp),
+               ("N", _i), ("nframes", _i), ("ht", _i), ("wd", _i), ("iters", _i), ("min_count", _i),
+               ("band", _f), ("huber", _f), ("lm", _f), ("ep", _f),
+               ("poses_out", _vp), ("info", _vp), ("system", _vp), ("residual", _vp), ("jac", _vp)]
+
+
+class TsdfTrackArgs(_c.Structure):
+    """pvo_tsdf_track_args"""
+    _fields_ = [("tsdf", _vp), ("wsum", _vp), ("nz", _i), ("ny", _i), ("nx", _i)] + _TRACK_TAIL
+
+
+class TsdfSparseTrackArgs(_c.Structure):
+    """pvo_tsdf_sparse_track_args"""
+    _fields_ = [("grid", _vp), ("tsdf", _vp), ("wsum", _vp), ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i)] + _TRACK_TAIL
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 PVO_KNOB_EDGE_BLOCKS = 4        # 0 shipped | 1 off | 2 + bits (third, low, agg, trunk): 2 ... 17
@@ -317,7 +342,8 @@ def load():
                        (lib.pvo_tsdf_sparse_integrate_args_size, TsdfSparseIntegrateArgs),
                        (lib.pvo_tsdf_sparse_mesh_args_size, TsdfSparseMeshArgs),
                        (lib.pvo_tsdf_panoptic_args_size, TsdfPanopticArgs), (lib.pvo_tsdf_mesh_labels_args_size, TsdfMeshLabelsArgs),
-                       (lib.pvo_tsdf_render_args_size, TsdfRenderArgs), (lib.pvo_tsdf_sparse_render_args_size, TsdfSparseRenderArgs)):
+                       (lib.pvo_tsdf_render_args_size, TsdfRenderArgs), (lib.pvo_tsdf_sparse_render_args_size, TsdfSparseRenderArgs),
+                       (lib.pvo_tsdf_track_args_size, TsdfTrackArgs), (lib.pvo_tsdf_sparse_track_args_size, TsdfSparseTrackArgs)):
         if fn() != ctypes.sizeof(struct):
             raise PvoHipError("libpvo_hip.so has a %d-byte %s; this binding is written for %d bytes - rebuild with "
                               "`python -m pvo_amd.build`" % (fn(), struct.__doc__, ctypes.sizeof(struct)))

@@ -26,6 +26,7 @@ HIP_SOURCES = [
     "tsdf.hip",
     "tsdf_sparse.hip",
     "tsdf_render.hip",
+    "tsdf_track.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",

@@ -1,4 +1,4 @@
-// tsdf_ray.h — the arithmetic of looking at a TSDF volume from a camera (tsdf_render.hip), shared by the dense and the brick volume:
+// tsdf_ray.h — the arithmetic of looking at a TSDF volume from a camera (tsdf_render.hip, tsdf_track.hip), shared by the dense and the brick volume:
 // a view's constants, a pixel's ray, the position, cell and fraction of a lattice sample, the trilinear value and its gradient, the
 // hit's interpolation and the blend of the two bracketing samples.  Each is ONE inline function, called with the GLOBAL integer cell
 // index; a volume only supplies where the eight corners of a cell are stored.  Every multiply-add is written as an explicit fmaf, so
@@ -46,6 +46,19 @@ __device__ __forceinline__ Ray ray_of_pixel(const float* __restrict__ c, const I
 // nz), each >= 2; a NaN fails); then cell = min(floor(p), n-2) and frac = p - cell
 __device__ __forceinline__ bool ray_sample_cell(const Ray r, int k, float dz, const int (&n)[3], int (&cell)[3], float (&frac)[3]) {
   const float z = static_cast<float>(k) * dz;
+  bool in = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float p = fmaf(z, r.g[i], r.p0[i]);
+    in = in && p >= 0.0f && p <= static_cast<float>(n[i] - 1);
+    cell[i] = min(pvo_floor_to_int(p), n[i] - 2);
+    frac[i] = p - static_cast<float>(cell[i]);
+  }
+  return in;
+}
+
+// the same at an arbitrary depth z along the optical axis (tsdf_track.hip: z = 1 / d of the pixel's own inverse depth)
+__device__ __forceinline__ bool ray_point_cell(const Ray r, float z, const int (&n)[3], int (&cell)[3], float (&frac)[3]) {
   bool in = true;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {

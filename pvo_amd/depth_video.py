@@ -787,6 +787,40 @@ class DepthVideo:
         med, p90, share = self.depth_residual(own, r["depth"])
         return {"ix": ix, "median": med, "p90": p90, "share": share}
 
+    def tsdf_track(self, volume, ix=None, poses=None, disps=None, weight=None, full_res=False, **kw):
+        """frame-to-model tracking (pvo_tsdf_track / pvo_tsdf_sparse_track): camera poses refined so that the frames' own depths lie on
+        the fused surface.  `volume` is the dict `tsdf` returns (dense, or with volume = the SparseTSDF).  By default slot s tracks
+        the stored keyframe ix[s] (default: all) from its own depth (disps, or disps_up with full_res) starting at its own pose.
+        disps= [nframes,ht,wd]: any inverse-depth maps in place of the stored ones (for example disps_sens for RGB-D), at the 1/8
+        resolution or with full_res at image resolution, ix then indexing them (default: all).  poses= [N,7]: explicit starts, ONE PER
+        SLOT (several slots may track one frame from different starts).  weight like disps or None.  kw: iters, band, huber, lm, ep,
+        min_count, min_weight, system, residual, jac, out of droid_backends.tsdf_track.  Returns its dict with ix added.  The video
+        is never written."""
+        n = self.counter
+        if disps is None:
+            disps = (self.disps_up if full_res else self.disps)[:n]
+        disps = torch.as_tensor(disps, dtype=torch.float32, device=self.device).contiguous()
+        nf = disps.shape[0]
+        ix = torch.arange(nf, device=self.device) if ix is None else torch.as_tensor(ix, dtype=torch.long, device=self.device).reshape(-1)
+        ix = ix.contiguous()
+        if poses is None:
+            if nf > n:
+                raise ValueError("tsdf_track: %d depth maps but %d stored keyframes: pass poses, one start per slot" % (nf, n))
+            poses = self.poses[:n][ix.clamp(0, max(n - 1, 0))]
+        poses = torch.as_tensor(poses, dtype=torch.float32, device=self.device).reshape(-1, 7).contiguous()
+        if poses.shape[0] != ix.shape[0]:
+            raise ValueError("tsdf_track: %d starts for %d slots" % (poses.shape[0], ix.shape[0]))
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).contiguous()
+        intr = (float(8 if full_res else 1) * self.intrinsics[0]).contiguous()
+        if "volume" in volume:
+            out = volume["volume"].track(poses, disps, intr, ix, weight=weight, **kw)
+        else:
+            out = db.tsdf_track(volume["tsdf"], volume["wsum"], volume["origin"], volume["voxel"], poses, disps, intr, ix, weight=weight, **kw)
+        out = dict(out)
+        out["ix"] = ix
+        return out
+
     def ba(self, target, weight, eta, ii, jj, t0=1, t1=None, itrs=2, lm=1e-4, ep=0.1, motion_only=False,
            t1_hint=None):
         """dense bundle adjustment (depth_video.py:197-214); in place on poses / disps"""

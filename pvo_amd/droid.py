@@ -195,6 +195,49 @@ class Droid:
         self.flush()
         return self.video.tsdf_render(volume, **kw)
 
+    # refine_to_model's Huber threshold, in truncations.  A keyframe's residuals against the volume it was fused into are heavy-tailed:
+    # at the true pose of the analytic test scene their median is 0.006 while 14 % exceed 0.1 (beside a silhouette the views that see
+    # past it average free space into the surface's voxels).  The quadratic loss follows that tail to a pose where the keyframe's median
+    # model_residual is 2.4 times the other keyframes'; five times the inliers' median holds it at 1.35.
+    REFINE_HUBER = 0.03
+
+    def refine_to_model(self, volume, ix=None, apply=False, **kw):
+        """frame-to-model tracking of the keyframes ix (default: all) against the fused volume get_mesh returned:
+        DepthVideo.tsdf_track(volume, ix, **kw) from each keyframe's own depth and pose, with huber = REFINE_HUBER unless given (kw:
+        weight, full_res, iters, band, huber, lm, ep, min_count, min_weight; not disps / poses: the residuals below are the stored
+        keyframes').  apply=True writes the refined poses of the slots whose last status is 0 into video.poses (one small
+        read-back) and needs ix, without repeats: which keyframes to overwrite is the caller's decision - a keyframe that already
+        agrees with the volume gains nothing from it.  Otherwise the video is not touched.  Returns a dict: ix, poses [N,7], info
+        [N,iters+1,4] and DepthVideo.model_residual of those keyframes `before` and `after` (after: at the refined poses, whether
+        applied or not)."""
+        for k in ("disps", "poses"):
+            if k in kw:
+                raise ValueError("refine_to_model tracks the stored keyframes from their own depths and poses: no %s= (DepthVideo.tsdf_track takes it)" % k)
+        if apply:
+            if ix is None:
+                raise ValueError("refine_to_model(apply=True) needs ix: the keyframes whose poses to overwrite")
+            ids = torch.as_tensor(ix, dtype=torch.long).reshape(-1)
+            if ids.unique().numel() != ids.numel():
+                raise ValueError("refine_to_model(apply=True): ix names a keyframe twice")
+        kw.setdefault("huber", self.REFINE_HUBER)
+        self.flush()
+        v = self.video
+        n = v.counter
+        full_res = bool(kw.get("full_res", False))
+        before = v.model_residual(volume, ix=ix, full_res=full_res)
+        out = v.tsdf_track(volume, ix=ix, **kw)
+        sel = out["ix"]
+        inside = (sel >= 0) & (sel < n)
+        rows = sel.clamp(0, max(n - 1, 0))
+        good = inside & (out["info"][:, -1, 3] == 0)
+        poses = torch.where(good[:, None], out["poses"], v.poses[:n][rows])
+        depth = v.tsdf_render(volume, poses=poses, full_res=full_res, normals=False)["depth"]
+        med, p90, share = v.depth_residual((v.disps_up if full_res else v.disps)[:n][rows], depth)
+        after = {"ix": sel, "median": med, "p90": p90, "share": share}
+        if apply:
+            v.poses[rows[good]] = out["poses"][good]
+        return {"ix": sel, "poses": out["poses"], "info": out["info"], "before": before, "after": after}
+
     def get_flow(self):
         self.flush()
         return upsample_inter(self.video.full_flow[:self.video.counter][None] * 8)

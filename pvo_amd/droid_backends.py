@@ -977,6 +977,109 @@ def tsdf_sparse_render(vol, poses, intrinsics, ix, ht, wd, dz=None, z_near=0.0, 
     return out
 
 
+def _track_frames(a, what, dev, poses, disps, intrinsics, ix, weight, iters, band, huber, lm, ep, min_count, system, residual, jac, out):
+    """the frame, parameter and output fields both tracking calls share; returns the dict of outputs (caller-owned with out=)"""
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ix, "ix"), (weight, "weight")):
+        if t is None:
+            continue
+        _contig(t, n)
+        if t.device != dev:
+            raise PvoHipError("%s: %s must be on %s" % (what, n, dev))
+    _long(ix, "ix")
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (weight, "weight")):
+        if t is not None:
+            _f32(t, n)
+    iters = int(iters)
+    if not 0 <= iters <= _lib.TSDF_TRACK_MAX_ITERS:
+        raise PvoHipError("%s: iters must lie in [0, %d]" % (what, _lib.TSDF_TRACK_MAX_ITERS))
+    if disps.dim() != 3 or ix.dim() != 1 or tuple(poses.shape) != (ix.shape[0], 7) or intrinsics.numel() < 4:
+        raise PvoHipError("%s: disps must be [nframes,ht,wd], ix [N], poses [N,7] (one start per slot) and intrinsics [4]" % what)
+    if weight is not None and weight.shape != disps.shape:
+        raise PvoHipError("%s: weight must have the shape of disps" % what)
+    N, (nf, ht, wd) = ix.shape[0], disps.shape
+    want = {"poses": ((N, 7), torch.float32), "info": ((N, iters + 1, 4), torch.float32)}
+    optional = {"system": ((N, 27), torch.float64), "residual": ((N, ht, wd), torch.float32), "jac": ((N, ht, wd, 6), torch.float32)}
+    for k, on in (("system", system), ("residual", residual), ("jac", jac)):
+        if on:
+            want[k] = optional[k]
+    if out is None:
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in want.items()}
+    else:
+        known = dict(want, **optional)
+        for k, t in out.items():
+            if k not in known:
+                raise PvoHipError("%s: out has no use for %r" % (what, k))
+            shape, dt = known[k]
+            if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                raise PvoHipError("%s: out[%r] must be a contiguous %s %s on %s" % (what, k, dt, list(shape), dev))
+        missing = [k for k in want if k not in out]
+        if missing:
+            raise PvoHipError("%s: out lacks %s (poses and info always, system / residual / jac when asked for)" % (what, ", ".join(missing)))
+    a.poses, a.disps, a.intrinsics, a.ix, a.weight = _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ix), _ptr(weight)
+    a.N, a.nframes, a.ht, a.wd = N, nf, ht, wd
+    a.iters, a.min_count = iters, int(min_count)
+    a.band, a.huber, a.lm, a.ep = float(band), float(huber), float(lm), float(ep)
+    a.poses_out, a.info = _ptr(out["poses"]), _ptr(out["info"])
+    a.system, a.residual, a.jac = _ptr(out.get("system")), _ptr(out.get("residual")), _ptr(out.get("jac"))
+    return out
+
+
+def tsdf_track(tsdf, wsum, origin, voxel, poses, disps, intrinsics, ix, weight=None, iters=10, band=0.9, huber=0.0, lm=1e-4, ep=1e-6,
+               min_count=32, min_weight=1.0, system=False, residual=False, jac=False, out=None):
+    """Frame-to-model tracking (include/pvo_hip.h pvo_tsdf_track): per slot s, the start pose poses[s] ([N,7], world-to-camera, ONE
+    PER SLOT) refined by `iters` Gauss-Newton steps so that the back-projected pixels of frame ix[s] (disps [nframes,ht,wd] inverse
+    depth, intrinsics [4] for ht x wd, weight like disps or None) lie on the zero level of the volume tsdf / wsum [nz,ny,nx].  Pixels
+    with |S| < band (in truncations) vote; huber > 0 bounds a pixel's pull; lm, ep damp the 6 x 6 system; a slot with fewer than
+    min_count voting pixels keeps its pose.  Returns a dict: poses f32 [N,7], info f32 [N,iters+1,4] = (E, count, max|xi| of the step
+    taken, status) per evaluation (status 0 = stepped, 1 = too few pixels, 2 = factorisation failed, 4 = ix outside the frames), and on
+    request system f64 [N,27] (the undamped H's upper triangle and b of the last evaluation), residual f32 [N,ht,wd] (S at the final
+    pose, NaN where the pixel does not vote), jac f32 [N,ht,wd,6].
+    The defaults band = 0.9, huber = 0 and min_count = 32 rest on nothing measured on real sequences: they are the values the
+    analytic test scene was checked with.
+    out=: caller-owned buffers (poses and info, and any of system / residual / jac: a buffer given is written whether or not its flag
+    is set, a flag set without its buffer raises; out["poses"] may be `poses` itself) - then no
+    allocation beyond the cached workspace, no synchronisation, capturable."""
+    _contig(tsdf, "tsdf"); _contig(wsum, "wsum")
+    dev = _dev(tsdf, wsum, poses, disps, intrinsics, ix, weight)
+    _f32(tsdf, "tsdf"); _f32(wsum, "wsum")
+    if tsdf.dim() != 3 or wsum.shape != tsdf.shape:
+        raise PvoHipError("tsdf_track: tsdf and wsum must be [nz,ny,nx]")
+    a = _lib.TsdfTrackArgs()
+    out = _track_frames(a, "tsdf_track", dev, poses, disps, intrinsics, ix, weight, iters, band, huber, lm, ep, min_count, system, residual,
+                        jac, out)
+    a.tsdf, a.wsum = _ptr(tsdf), _ptr(wsum)
+    a.nz, a.ny, a.nx = tsdf.shape
+    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
+    a.voxel, a.min_weight = float(voxel), float(min_weight)
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_track_workspace_bytes(a.N, a.ht, a.wd))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_track(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_track")
+    return out
+
+
+def tsdf_sparse_track(vol, poses, disps, intrinsics, ix, weight=None, iters=10, band=0.9, huber=0.0, lm=1e-4, ep=1e-6, min_count=32,
+                      min_weight=1.0, system=False, residual=False, jac=False, out=None):
+    """tsdf_track against the brick volume `vol` (a dict, see _sparse_world; include/pvo_hip.h pvo_tsdf_sparse_track): every output has
+    the bytes of tsdf_track over the [8gz,8gy,8gx] volume that holds the bricks.  Parameters, defaults (which rest on nothing measured
+    on real sequences), outputs and out= as in tsdf_track."""
+    a = _lib.TsdfSparseTrackArgs()
+    c = _lib.TsdfSparseMeshArgs()                          # (the checks and the world's fields: _sparse_world fills coord / bricks too)
+    dev = _sparse_world(c, vol)
+    _dev(vol["grid"], poses, disps, intrinsics, ix, weight)
+    a.gz, a.gy, a.gx, a.cap = c.gz, c.gy, c.gx, c.cap
+    a.origin[0], a.origin[1], a.origin[2] = c.origin[0], c.origin[1], c.origin[2]
+    a.voxel, a.min_weight = c.voxel, float(min_weight)
+    out = _track_frames(a, "tsdf_sparse_track", dev, poses, disps, intrinsics, ix, weight, iters, band, huber, lm, ep, min_count, system,
+                        residual, jac, out)
+    a.grid, a.tsdf, a.wsum = _ptr(vol["grid"]), _ptr(vol["tsdf"]), _ptr(vol["wsum"])
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_tsdf_sparse_track_workspace_bytes(a.N, a.ht, a.wd))
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_sparse_track(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_track")
+    return out
+
+
 def _baseline(baseline, what):
     """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
     b = float(baseline)

@@ -93,6 +93,11 @@ class SparseTSDF:
         return db.tsdf_sparse_render(self.volume(), poses, intrinsics, ix, ht, wd, dz=dz, z_near=z_near, z_far=z_far,
                                      min_weight=min_weight, label=self.label, normals=normals, out=out)
 
+    def track(self, poses, disps, intrinsics, ix, weight=None, **kw):
+        """frame-to-model tracking against the bricks: the dict of droid_backends.tsdf_sparse_track (poses, info, and on request
+        system, residual, jac); kw as there"""
+        return db.tsdf_sparse_track(self.volume(), poses, disps, intrinsics, ix, weight=weight, **kw)
+
     def nbytes(self):
         """device bytes held: the grid and the pool"""
         return sum(t.numel() * t.element_size() for t in (self.grid, self.coord, self.counts, self.tsdf, self.wsum, self.rgb, self.label, self.lconf)
