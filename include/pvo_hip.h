@@ -1348,6 +1348,12 @@ int pvo_ba_plan(const int64_t* ii, const int64_t* jj, int E, int nframes, int HW
  *     The map is read at every step: it must stay allocated, [nframes,ht,wd], for as long as the workspace is used with it.
  *   pvo_ba_prior is pvo_ba with the term (disps_sens == NULL: pvo_ba itself, which is this call with NULL).
  * Limits: alpha > 0 where a map is given (PVO_EINVAL otherwise); fp32 only.
+ * What counts as a measurement is the test disps_sens > 0 alone: 0, a negative value, -inf and NaN (every comparison with it is
+ * false) are NO measurement - the pixel gets the bits it gets with 0 there.  +inf passes the test and is a POISONED OPERAND under
+ * pvo_ba's failure contract (above): w' = +inf at that pixel, the frame's Schur sums leave the fixed-point range, and the step is a
+ * status and a zero pose update - status_out[0] = 1, dx = 0, every pose keeps its bytes - never a wrong step; the depth-only step of
+ * that contract is non-finite at the pixel that carried the +inf and nowhere else.  (A frame none of whose rows reaches the pose
+ * system - in front of the window, all targets fixed - has no sum to flag: there a +inf is that pixel's depth alone.)
  * Deliberate difference from upstream: the term applies to a depth frame only where that frame has at least ONE OUT-EDGE in the
  * call's edge list.  Under edge sharding by source keyframe every rank plans all window frames as depth frames; a frame a rank
  * does not own has C = w = 0 there and keeps dz = 0, so the sharded result stays bit-identical to the whole graph's.  On a whole

@@ -10,6 +10,8 @@ Safe by construction: the first `warmup` calls run eagerly (MIOpen picks its ker
 an eager run of the same input, and any failure - capture not supported, mismatch - switches the instance back to eager for good.
 `pvo_amd.config.debug_config("hip_graphs", False)` disables capture process-wide (nothing is read from the environment).
 """
+import gc
+
 import torch
 
 from . import config
@@ -100,8 +102,21 @@ class GraphedCall:
         want = _flat(self.fn(*static_in))
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = self.fn(*static_in)
+        # No cyclic collection may run INSIDE the capture.  A GraphedCall and its owner refer to each other (fn is the owner's bound
+        # method), so a dropped MotionFilter - with its captured graphs and their private memory pool - is freed by the cycle collector
+        # whenever that next runs; when it ran between capture_begin and capture_end, releasing an older graph's memory is a call the
+        # capturing stream does not permit, the error is raised in a destructor and the process aborts.  torch.cuda.graph used to collect
+        # before every capture and no longer does (unless torch.compiler.config.force_cudagraph_gc), so: collect here, while nothing
+        # is capturing, and keep the collector off until the capture has ended.
+        gc.collect()
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                out = self.fn(*static_in)
+        finally:
+            if collecting:
+                gc.enable()
         outs = _flat(out)
         g.replay()
         torch.cuda.synchronize()

@@ -12,6 +12,9 @@ the comparison with a bound derived from the case's own sensitivity (`sensitivit
                        of pvo_ba_local's launch rule that the window reaches
     launch_form        that form, as a predicate over the graph (frame_rows, frame_paths): every GPU test asserts the one it claims
     case / admission   a (graph, regime, damping) triple with its fp64 step, s_case and the conditions it must meet to be used on the GPU
+The sensor-depth prior and stereo edges ride on the same kernels: reduced_system, reduced_abs, sys_bound / n_add take the prior
+(sens, alpha, prior=True), frame_blocks / frame_rows / fix_addends count a stereo edge's row block as ba_schur_body does - every one of
+them is what it was for a window without either.  Their windows, fields, mutations and cases are tests/ba_rider_reference.py's.
 
 ADMISSION (tests/test_ba_fp64_host.py asserts it for every name in ADMITTED, tests/test_ba_fp64_gpu.py runs exactly those):
   * 4 s_case <= 2e-3 for dx and for dz - the cap of tests/test_ba_calib_gpu.py; a case this sensitive is replaced, not loosened;
@@ -193,9 +196,10 @@ def masked_fraction(s):
 
 
 # ------------------------------------------------------------------------------------------------ the reduced system
-def _reduce(f, eta, ii, jj, t0, t1, magnitudes=False, q_from=None, stats=None):
+def _reduce(f, eta, ii, jj, t0, t1, magnitudes=False, q_from=None, stats=None, sens=None, alpha=C.ALPHA, disps=None):
     """calib_reference.step up to its damping line -> (A [6P,6P], b [6P]).  magnitudes: the fields are sums of magnitudes and the
-    Schur part is ADDED (every addend of A - E Q E^T by its absolute value); q_from: the Cii that Q is formed from"""
+    Schur part is ADDED (every addend of A - E Q E^T by its absolute value); q_from: the Cii that Q is formed from.
+    sens, alpha, disps: the sensor-depth prior (calib_reference.prior_terms); under `magnitudes` its addend joins w by its magnitude"""
     ii, jj = np.asarray(ii, np.int64), np.asarray(jj, np.int64)
     Hs, vs, Eii, Eij, Cii, bz = (f[k] for k in C.FIELDS[:6])
     HW, E, P = Cii.shape[1], ii.shape[0], t1 - t0
@@ -224,6 +228,9 @@ def _reduce(f, eta, ii, jj, t0, t1, magnitudes=False, q_from=None, stats=None):
     eta = np.asarray(eta, np.float64).reshape(-1, HW)
     add = np.broadcast_to(eta, (K, HW)).copy() if eta.shape[0] == 1 else eta.copy()
     assert add.shape == (K, HW)
+    if sens is not None:
+        add, w2 = C.prior_terms(add, w, disps, kx, np.bincount(ii, minlength=np.asarray(disps).shape[0])[kx], sens, alpha)
+        w = w + np.abs(w2 - w) if magnitudes else w2
     Q = 1.0 / (Cs + add)
     rows = [[] for _ in range(K)]
     for p in range(P):
@@ -249,26 +256,35 @@ def _reduce(f, eta, ii, jj, t0, t1, magnitudes=False, q_from=None, stats=None):
     return A, b
 
 
-def reduced_system(f, s, stats=None):
+def reduced_system(f, s, stats=None, sens=None, alpha=C.ALPHA):
     """(S [6P,6P], rhs [6P]) of the window `s` from the assembled fields `f`: the undamped A - E Q E^T and v - E Q w in fp64.
-    stats (a dict) receives "largest": the largest magnitude of one fixed-point addend (an edge's pose sums, a frame's Schur sums)"""
+    stats (a dict) receives "largest": the largest magnitude of one fixed-point addend (an edge's pose sums, a frame's Schur sums);
+    sens, alpha: the sensor-depth prior, as calib_reference.step's"""
     a = C.scene_args(s)
-    return _reduce(f, a[5], a[6], a[7], a[8], a[9], stats=stats)
+    return _reduce(f, a[5], a[6], a[7], a[8], a[9], stats=stats, sens=sens, alpha=alpha, disps=a[1])
 
 
-def reduced_abs(f, s):
+def reduced_abs(f, s, sens=None, alpha=C.ALPHA, mags=None):
     """T = (T_S, T_rhs): reduced_system's sums with every addend replaced by its absolute value, for the pose part (per edge,
     residual row and pixel: |w Ja Jb|, |w r Ja|) and the Schur part (|E| Q |E|^T and |E| Q |w| with |E|, |w| the per-frame sums of
-    per-row magnitudes |w Jz J|, |w r Jz|; Q itself, a sum of non-negative terms, is the one of `f`)."""
+    per-row magnitudes |w Jz J|, |w r Jz|; Q itself, a sum of non-negative terms, is the one of `f`).
+    sens, alpha: the sensor-depth prior - |alpha (d - s)| joins |w|; mags: the magnitude fields, where abs_fields' are not the window's
+    (tests/ba_rider_reference.py: a stereo edge's)"""
+    a = C.scene_args(s)
+    m = abs_fields(s) if mags is None else mags
+    return _reduce(m, a[5], a[6], a[7], a[8], a[9], magnitudes=True, q_from=f["Cii"], sens=sens, alpha=alpha, disps=a[1])
+
+
+def abs_fields(s):
+    """the assembled fields of the window with every per-pixel addend replaced by its magnitude (reduced_abs)"""
     a = C.scene_args(s)
     J = C.pixel_jacobians(a[0], a[1], a[2], a[3], a[4], a[6], a[7])
     w, r, Ji, Jj, Jz = J["w"], np.abs(J["r"]), np.abs(J["Ji"]), np.abs(J["Jj"]), np.abs(J["Jz"])
     es = lambda spec, *ops: np.einsum(spec, *ops, optimize=True)
-    m = dict(Hs=np.stack([es("ecx,ecax,ecbx->eab", w, A, B) for A, B in ((Ji, Ji), (Ji, Jj), (Jj, Ji), (Jj, Jj))]),
-             vs=np.stack([es("ecx,ecx,ecax->ea", w, r, A) for A in (Ji, Jj)]),
-             Eii=es("ecx,ecx,ecax->eax", w, Jz, Ji), Eij=es("ecx,ecx,ecax->eax", w, Jz, Jj),
-             Cii=es("ecx,ecx,ecx->ex", w, Jz, Jz), bz=es("ecx,ecx,ecx->ex", w, r, Jz))
-    return _reduce(m, a[5], a[6], a[7], a[8], a[9], magnitudes=True, q_from=f["Cii"])
+    return dict(Hs=np.stack([es("ecx,ecax,ecbx->eab", w, A, B) for A, B in ((Ji, Ji), (Ji, Jj), (Jj, Ji), (Jj, Jj))]),
+                vs=np.stack([es("ecx,ecx,ecax->ea", w, r, A) for A in (Ji, Jj)]),
+                Eii=es("ecx,ecx,ecax->eax", w, Jz, Ji), Eij=es("ecx,ecx,ecax->eax", w, Jz, Jj),
+                Cii=es("ecx,ecx,ecx->ex", w, Jz, Jz), bz=es("ecx,ecx,ecx->ex", w, r, Jz))
 
 
 def block_support(s):
@@ -295,29 +311,37 @@ def fix_addends(s):
     chunk of the launch's size (256, 512 or 1024: every chunk's tile-pair sum goes through scatter_tile's fix_add, in schur_pass,
     schur_rowpass and schur_rowpass_lds without part_out alike), or ONE for a staged frame - its chunks' fp32 sums are added in fp64
     by ba_schur_reduce_kernel (`v += static_cast<double>(a[u])`: exact to 2^-53, nothing at the 2^-24 scale of the bound) and that
-    sum is quantised once"""
+    sum is quantised once.  Per PAIR OF ROW BLOCKS (frame_blocks): beyond 64 out-edges nothing is merged, and an entry of block
+    (a, b) gets one addend per pair of row blocks that map to a and to b.
+    A STEREO edge under a baseline is NO addend, in either part: ba_assemble_kernel writes its `part` slab as 0.0f, the deal rows add
+    the zeros in double and __double2ll_rn(0.0 * kFix) is the integer 0 - added, but exact; and every tile pair that one of its zero
+    Eij rows enters is a chain of fp32 products with an exact 0 operand, +0 or -0, whose negation scatter_tile quantises to 0."""
     ii, jj, t0, t1 = s["ii"].numpy(), s["jj"].numpy(), s["t0"], s["t1"]
     P = t1 - t0
+    stereo = float(s.get("baseline", 0.0)) > 0
     paths = frame_paths(s)
     nS, nr = np.zeros((P, P)), np.zeros(P)
-    by_frame = {}
     for i, j in zip(ii, jj):
         pi, pj = int(i) - t0, int(j) - t0
+        if stereo and pi == pj:
+            continue
         for p in (pi, pj):
             if 0 <= p < P:
                 nS[p, p] += 1; nr[p] += 1
         if 0 <= pi < P and 0 <= pj < P:
             nS[max(pi, pj), min(pi, pj)] += 1
-        by_frame.setdefault(int(i), {pi}).add(pj)
-    for fr, ps in by_frame.items():
-        ps = [p for p in ps if 0 <= p < P]
+    for fr, blocks in frame_blocks(s).items():
+        mult = {}
+        for p, zero in blocks:
+            if not zero:
+                mult[p] = mult.get(p, 0) + 1
         chunks = paths[fr][2]
-        assert chunks > 0 or not ps
-        for a in ps:
-            nr[a] += chunks
-            for b in ps:
+        assert chunks > 0 or not blocks
+        for a in mult:
+            nr[a] += chunks * mult[a]
+            for b in mult:
                 if a >= b:
-                    nS[a, b] += chunks
+                    nS[a, b] += chunks * mult[a] * mult[b]
     return nS, nr
 
 
@@ -334,16 +358,38 @@ DENSE_MAX_POSES = 29      # kDenseMaxPoses
 FORM_NAMES = ("fused256", "window_staged", "window_mixed", "window_direct", "chunk512", "chunk1024")
 
 
-def frame_rows(s):
-    """depth frame -> rows of its M in ba_schur_body's row table: 6 for its own pose if that is free, 6 per DISTINCT free target pose
-    of its out-edges (edges that share a target are merged into one row block), and the w row if there is any row at all"""
+BALLOT_EDGES = 64         # ba_schur_body builds the row table by ballot (and merges edges that share a target) up to 64 out-edges
+
+
+def frame_blocks(s):
+    """depth frame -> the 6-row blocks of its M in ba_schur_body's row table (ba_schur.h, `if (in_lds && deg_all <= 64)` down to
+    `nrows_s = r` of the sequential walk), as a list of (window pose, zero): the frame's own pose first if it is free (kRowEi), then
+      up to 64 out-edges (the ballot path)   one block per DISTINCT free target pose, in the order of each target's first edge: edges
+                                             that share a target are led by the first and read their summed rows from Mrg (s_merged);
+      beyond (the sequential walk)           one block per out-edge with a free target, nothing merged.
+    A STEREO edge (i, i) has s_pose = jj[e] - t0 = pself: the frame's own pose is its target, so with pself free it is a leader like
+    any other and adds a SECOND block of six rows whose rowout entries are the own-pose block's, 6 pself + n - six more rows for the
+    frame, which can carry it over a row tile onto another path.  zero: the block's rows are exact zeros - a stereo edge's Eij under a
+    baseline (s["baseline"] > 0; ba_assemble_kernel stores 0.0f).  Only another stereo edge of the same frame shares that target: the
+    two merge into one block (0 + 0 in Mrg).  Without a baseline an edge (i, i) is an identity edge with rows of its own, not zero."""
     ii, jj, t0, t1 = s["ii"].numpy(), s["jj"].numpy(), s["t0"], s["t1"]
+    stereo = float(s.get("baseline", 0.0)) > 0
     out = {}
     for fr in np.unique(np.concatenate([np.arange(t0, t1), ii])):
-        tg = {int(j) for i, j in zip(ii, jj) if int(i) == int(fr) and t0 <= int(j) < t1}
-        r = 6 * (len(tg) + (1 if t0 <= int(fr) < t1 else 0))
-        out[int(fr)] = r + 1 if r else 0
+        fr = int(fr)
+        tg = [int(j) for i, j in zip(ii, jj) if int(i) == fr and t0 <= int(j) < t1]
+        if len([1 for i in ii if int(i) == fr]) <= BALLOT_EDGES:
+            tg = list(dict.fromkeys(tg))
+        blocks = [(fr - t0, False)] if t0 <= fr < t1 else []
+        out[fr] = blocks + [(j - t0, stereo and j == fr) for j in tg]
     return out
+
+
+def frame_rows(s):
+    """depth frame -> rows of its M in ba_schur_body's row table: 6 per block of frame_blocks - its own pose if that is free, each
+    DISTINCT free target pose of its out-edges (every such edge beyond 64 out-edges), a stereo edge's target, the frame's own pose,
+    among them - and the w row if there is any row at all"""
+    return {fr: (6 * len(b) + 1 if b else 0) for fr, b in frame_blocks(s).items()}
 
 
 def frame_paths(s):
@@ -419,7 +465,7 @@ def schur_chunk(s):
     return next(iter(frame_paths(s).values()))[1]
 
 
-def n_add(deg, pix=SCHUR_CHUNK):
+def n_add(deg, pix=SCHUR_CHUNK, prior=False):
     """the longest chain of fp32 additions behind one fixed-point addend, for a window whose frames have at most `deg` out-edges and
     whose Schur launch takes `pix` pixels per workgroup (the functions named are those the 256-pixel form was first derived from; the
     other forms are read off the same functions):
@@ -436,16 +482,24 @@ def n_add(deg, pix=SCHUR_CHUNK):
                   ba_schur_body); every tile pair is still one workgroup's chain, so they add nothing.  The operands are those of the
                   256-pixel form: ba_depth_kernel runs depth_pixel itself.
       dense window   schur_rowpass_lds<CNT, 256>: the same chain from LDS, 64 + 2 per chunk; a staged frame's chunk sums then meet in
-                  fp64 (ba_schur_reduce_kernel), which lengthens no fp32 chain - see fix_addends for what it does to n_fix."""
-    return max(12, pix // 4 + 2 + 2 * (deg - 1) + deg + 2)
+                  fp64 (ba_schur_reduce_kernel), which lengthens no fp32 chain - see fix_addends for what it does to n_fix.
+      the prior   (prior=True) depth_pixel's `wp = pr.alpha * (disps[fx] - s)` and `ww - wp`: the product and the subtraction from w,
+                  2 more on the w operand (a fused multiply-add would make them 1).  The difference d - s itself is exact where
+                  s / 2 <= d <= 2 s (Sterbenz), which tests/ba_rider_reference.py's sensor maps hold by construction (s within 10 %
+                  of d) and assert.  C + (m ? alpha : eta) is the same one addition.
+      stereo      a stereo edge (i, i) is one of the frame's out-edges: `deg` counts it (max_out_degree does), its Cii and bz are one
+                  more addend of C and w each.  stereo_pixel_terms (ba_assemble.h) forms them as pixel_terms does - wu Jz Jz, then
+                  `cii += wv * Jz * Jz` - so the per-pixel products stay under the same 16 units; its Eii / Eij are stored zeros."""
+    return max(12, pix // 4 + 2 + 2 * (deg - 1) + deg + 2 + (2 if prior else 0))
 
 
-def sys_bound(s, T):
+def sys_bound(s, T, prior=False):
     """per entry of (S, rhs): (n_add + 16) 2^-24 T + n_fix 2^-29.  16 units cover the per-pixel products - the 2^-20 relative
-    perturbation s_case is defined with; 2^-29 is half a unit of the 2^-28 fixed-point grid (fix_add, ba_workspace.h)."""
+    perturbation s_case is defined with; 2^-29 is half a unit of the 2^-28 fixed-point grid (fix_add, ba_workspace.h).
+    prior: T holds the sensor-depth prior's addend (reduced_abs with sens) and n_add its roundings"""
     TS, Tr = T
     nS, nr = fix_addends(s)
-    k = (n_add(max_out_degree(s), schur_chunk(s)) + 16) * 2.0 ** -24
+    k = (n_add(max_out_degree(s), schur_chunk(s), prior) + 16) * 2.0 ** -24
     return k * TS + np.kron(nS, np.ones((6, 6))) * 2.0 ** -29, k * Tr + np.repeat(nr, 6) * 2.0 ** -29
 
 

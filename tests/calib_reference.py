@@ -116,10 +116,29 @@ def perturbed(f, seed, scale=2.0 ** -20):
     return {k: f[k] * (1.0 + scale * g.uniform(-1.0, 1.0, f[k].shape)) for k in FIELDS}
 
 
-def step(f, poses, disps, intr, eta, ii, jj, t0, t1, lm, ep, ep_c=0.1, free_mask=15):
+def prior_terms(add, w, disps, kx, deg, sens, alpha, factor=None):
+    """the sensor-depth prior of include/pvo_hip.h (pvo_ba_depth_prior) on a step's depth terms: with s = sens[kx], d = disps[kx] and
+    m = (s > 0) & (the frame has an out-edge), add = where(m, alpha, add) and w = w - where(m, alpha (d - s), 0) -> (add, w).
+    factor [K,HW]: the addend alpha (d - s) times it (the perturbation of tests/ba_rider_reference.sensitivity)"""
+    F = disps.shape[0]
+    s = np.asarray(sens, np.float64).reshape(F, -1)[kx]
+    d = np.asarray(disps, np.float64).reshape(F, -1)[kx]
+    with np.errstate(invalid="ignore"):
+        m = (s > 0) & (np.asarray(deg) > 0)[:, None]
+        r = alpha * (d - s)
+    if factor is not None:
+        r = r * factor
+    return np.where(m, alpha, add), w - np.where(m, r, 0.0)
+
+
+ALPHA = 0.05      # rgbd_reference.ALPHA, the default of pvo_ba_prior's callers
+
+
+def step(f, poses, disps, intr, eta, ii, jj, t0, t1, lm, ep, ep_c=0.1, free_mask=15, sens=None, alpha=ALPHA, prior_factor=None):
     """one step from the assembled fields `f` -> dict(poses, disps, intr [fp32], dx [P,6], dc [4], dz [K,HW], kx, rejected,
     S_diag, Scc_diag [the undamped diagonals the damping read], reason); inputs are not modified.  A rejected step returns the inputs'
-    values and zeros; reason names the test that rejected it ("pose system", "complement", "non-finite", "focal"), None = accepted."""
+    values and zeros; reason names the test that rejected it ("pose system", "complement", "non-finite", "focal"), None = accepted.
+    sens [F,ht,wd] (optional): the sensor-depth prior with weight alpha (prior_terms); None is the step without it, bit for bit."""
     poses, disps = np.ascontiguousarray(poses, np.float32), np.ascontiguousarray(disps, np.float32)
     intr = np.ascontiguousarray(intr, np.float32)
     ii, jj = np.asarray(ii, np.int64), np.asarray(jj, np.int64)
@@ -153,6 +172,8 @@ def step(f, poses, disps, intr, eta, ii, jj, t0, t1, lm, ep, ep_c=0.1, free_mask
     eta = np.asarray(eta, np.float64).reshape(-1, HW)
     add = np.broadcast_to(eta, (K, HW)).copy() if eta.shape[0] == 1 else eta.copy()
     assert add.shape == (K, HW)
+    if sens is not None:
+        add, w = prior_terms(add, w, disps, kx, np.bincount(ii, minlength=F)[kx], sens, alpha, prior_factor)
     Q = 1.0 / (C + add)
     rows = [[] for _ in range(K)]
     for p in range(P):

@@ -5,25 +5,24 @@ two virtual ranks, the prior inside the native update, the ingest kernel, and th
 Which form of the launch rule (ba.hip, pvo_ba_local) a shape reaches, with chunks = ceil(HW / 256) and frames = min(F, P + 1):
   chunks x frames <= 192                          256-pixel chunks, the depth phase FUSED into the Schur kernel
   above that, P <= 29 (a dense window)            256-pixel chunks, ba_depth_kernel in front
-  above that, P > 29                              512- (up to 1024 workgroups) or 1024-pixel chunks, ba_depth_kernel in front"""
+  above that, P > 29                              512- (up to 1024 workgroups) or 1024-pixel chunks, ba_depth_kernel in front
+The prior against fp64 within derived bounds, in each of the six launch forms: tests/test_ba_riders_fp64_gpu.py."""
 from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
+import ba_reference as B
 import rgbd_reference as R
 
 pytestmark = pytest.mark.gpu
 
 
 def _form(s):
-    F, ht, wd = s["disps"].shape
-    P = s["t1"] - s["t0"]
-    wg = ((ht * wd + 255) // 256) * min(F, P + 1)
-    if wg <= 192:
-        return "fused"
-    return "depth kernel, dense window" if P <= 29 else ("depth kernel, 512" if wg <= 1024 else "depth kernel, 1024")
+    """ba_reference.launch_form, the one statement of the launch rule, under the names this module asserts"""
+    form = B.launch_form(s)
+    return {"fused256": "fused", "chunk512": "depth kernel, 512", "chunk1024": "depth kernel, 1024"}.get(form, "depth kernel, dense window")
 
 
 def _no_out_edges(F, radius, frame):

@@ -3,7 +3,8 @@
 identities that guard "off means untouched", two virtual ranks, the reprojection kernels with a baseline, stereo edges inside the
 native update (native, sharded and no-riders doors), and the closed loop through DepthVideo / DroidFrontend / the backend.
 
-Shapes: 9 x 12 (HW = 108: one partial assembly chunk) and 30 x 101 (HW = 3030: no multiple of 256, six assembly chunks, HW & 3 != 0)."""
+Shapes: 9 x 12 (HW = 108: one partial assembly chunk) and 30 x 101 (HW = 3030: no multiple of 256, six assembly chunks, HW & 3 != 0).
+Stereo edges against fp64 within derived bounds, in every launch form and row-table branch: tests/test_ba_riders_fp64_gpu.py."""
 from argparse import Namespace
 
 import numpy as np

@@ -416,6 +416,29 @@ def test_graphed_call_skips_only_arguments_the_caller_froze():
 
 
 @pytest.mark.gpu
+def test_graphed_call_keeps_the_cycle_collector_out_of_its_capture():
+    """a dropped owner of a GraphedCall is a reference cycle that holds captured graphs; the collector must not free one between
+    capture_begin and capture_end (pvo_amd/graphs.py, _capture): it is off while the stream captures and back on afterwards"""
+    import gc
+    from pvo_amd.graphs import GraphedCall
+    dev = torch.device("cuda:0")
+    seen = []
+
+    def fn(a):
+        seen.append((torch.cuda.is_current_stream_capturing(), gc.isenabled()))
+        return a + 1.0
+    g = GraphedCall(fn, warmup=1)
+    a = torch.arange(8.0, device=dev)
+    assert gc.isenabled()
+    with torch.no_grad():
+        for _ in range(3):
+            out = g(a).clone()                         # eager, capture, replay
+    assert g.replays >= 1 and not g.disabled and torch.equal(out, a + 1.0)
+    assert [on for capturing, on in seen if capturing] == [False] and all(on for capturing, on in seen if not capturing)
+    assert gc.isenabled()
+
+
+@pytest.mark.gpu
 def test_full_sequence_at_240x808_graphs_against_eager_with_segments_and_removals(cuda):
     """BASELINE.json configs[1]'s full-sequence form at the reference driver's input size (tools/test_vo.py's loop: Droid.track per
     frame, Droid.terminate; 240 x 808, panoptic segments, segm_filter on) - 44 frames, every frame a keyframe candidate, a quarter of the
