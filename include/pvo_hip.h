@@ -94,7 +94,9 @@ const char* pvo_last_hip_error(void);
  * and new entry points pvo_tsdf_render[_workspace_bytes] / pvo_tsdf_sparse_render[_workspace_bytes]; still 106, shard invariance:
  * no struct changed - new entry points pvo_ba_finish_graph / pvo_ba_solve_kind; still 106, frame-to-model tracking: no existing
  * struct changed - new structs pvo_tsdf_track_args / pvo_tsdf_sparse_track_args (with *_args_size()) and new entry points
- * pvo_tsdf_track[_workspace_bytes] / pvo_tsdf_sparse_track[_workspace_bytes]): a caller
+ * pvo_tsdf_track[_workspace_bytes] / pvo_tsdf_sparse_track[_workspace_bytes]; still 106, live volume: no existing struct changed -
+ * new structs pvo_tsdf_reintegrate_args / pvo_tsdf_sparse_reintegrate_args (with *_args_size()) and new entry points
+ * pvo_tsdf_reintegrate[_workspace_bytes] / pvo_tsdf_sparse_reintegrate[_workspace_bytes]): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -1214,6 +1216,101 @@ typedef struct pvo_tsdf_sparse_track_args {
 size_t pvo_tsdf_sparse_track_args_size(void);
 size_t pvo_tsdf_sparse_track_workspace_bytes(int N, int ht, int wd);
 int pvo_tsdf_sparse_track(const pvo_tsdf_sparse_track_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Live volume: keyframes de-integrated and re-fused as their poses move       */
+/* ------------------------------------------------------------------------- */
+
+/* pvo_tsdf_reintegrate: pvo_tsdf_integrate's volume kept current while keyframes still move (BundleFusion's re-integration).  Two
+ * frame sets over ONE nframes, ht, wd and intrinsics, in one pass over the volume:
+ *   REMOVE  poses_old [nframes,7], disps_old / weight_old [nframes,ht,wd] (weight_old NULL = 1), ix_old [N_old]: the keyframes AS THEY
+ *           WERE FUSED - the caller keeps that snapshot;
+ *   ADD     poses, disps, weight, ix [N]: the keyframes as they are now, exactly pvo_tsdf_integrate's operands.
+ * images (with IH, IW, img_stride, img_offset) serves both sets: a keyframe's picture does not change.  Either N may be 0.  The volume
+ * (tsdf, wsum, rgb or NULL, nz, ny, nx, origin, voxel), trunc, z_near and w_max are pvo_tsdf_integrate's; w_floor >= 0 is new.
+ *
+ * Per voxel, one thread runs one sequential loop: first the REMOVE slots ix_old[0..N_old) in order, then the ADD slots ix[0..N) in
+ * order.  An id outside [0, nframes) is skipped and never dereferenced.
+ *   An ADD slot is pvo_tsdf_integrate's step, by the same inline function (csrc/tsdf_fuse.h tsdf_fuse_frame).
+ *   A REMOVE slot forms the observation (val, w, colour) by pvo_tsdf_integrate's tests, in its order, on the REMOVE set's operands:
+ *   zc > z_near; ui = floor(u+0.5), vi = floor(v+0.5) inside the map; d and w finite and > 0; sdf = 1/d - zc not below -trunc;
+ *   val = min(1, sdf/trunc).  A pair that fails a test does nothing.  Otherwise, with Wn = W - w rounded to fp32:
+ *     !(Wn > w_floor): the voxel becomes EMPTY - tsdf = 0, wsum = 0, rgb = 0 - and the later slots of the call see an empty voxel;
+ *     else tsdf = clamp((tsdf*W - val*w) / Wn, -1, 1), every colour clamp((c*W - colour*w) / Wn, 0, 255), W = Wn.
+ *   w_max plays no part in a removal: where the cap was hit while fusing, W is no longer the sum of the weights and a removal is
+ *   approximate.  Nothing guards against that.
+ *   w_floor: W is an fp32 sum, so removing every observation a voxel ever got leaves W - sum(w) = a few ulps of the largest partial
+ *   sum and not 0, with a meaningless quotient.  A floor well above that (2^-10 for weights of order 1) and below the smallest
+ *   weight in use empties such voxels; 0 keeps only the exact case.
+ * A voxel is written only if some slot of either set contributed to it (an emptied voxel counts).  Two calls (remove-only, then
+ * add-only) leave the bytes of the one call; slot lists split over calls in order leave the bytes of one call; add-only leaves the
+ * bytes of pvo_tsdf_integrate.  Arithmetic is fp32 with contraction; tests/tsdf_reintegrate_reference.py carries the error bound.
+ *
+ * Two launches (the constants of both sets through the same function as pvo_tsdf_integrate's; one thread per voxel, x fastest, both
+ * loops inside: the volume is read once and written once whatever N_old + N is), no atomics, no allocation, no host synchronisation,
+ * no loop whose trip count depends on data: capturable, the same operands give the same bytes.  workspace:
+ * pvo_tsdf_reintegrate_workspace_bytes(N_old, N), 16-byte aligned (PVO_EWORKSPACE otherwise).
+ * Limits (PVO_EINVAL, nothing written): pvo_tsdf_integrate's; N_old >= 0; w_floor >= 0 and finite; with N_old > 0 a NULL poses_old /
+ * disps_old / ix_old, with N > 0 a NULL poses / disps / ix.  An empty volume, N_old + N == 0 or ht*wd == 0: PVO_OK, nothing done. */
+typedef struct pvo_tsdf_reintegrate_args {
+  float* tsdf;
+  float* wsum;
+  float* rgb;
+  int nz, ny, nx;
+  float origin[3];
+  float voxel, trunc, z_near, w_max, w_floor;
+  const float* intrinsics;
+  const float* poses_old;
+  const float* disps_old;
+  const float* weight_old;
+  const int64_t* ix_old;
+  const float* poses;
+  const float* disps;
+  const float* weight;
+  const int64_t* ix;
+  int N_old, N, nframes, ht, wd;
+  const uint8_t* images;
+  int IH, IW, img_stride, img_offset;
+} pvo_tsdf_reintegrate_args;
+size_t pvo_tsdf_reintegrate_args_size(void);
+size_t pvo_tsdf_reintegrate_workspace_bytes(int N_old, int N);
+int pvo_tsdf_reintegrate(const pvo_tsdf_reintegrate_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pvo_tsdf_sparse_reintegrate: pvo_tsdf_reintegrate on every voxel of every brick in use (the pool, coord, bricks, grid limits and
+ * kept of pvo_tsdf_sparse_integrate).  Each brick culls the REMOVE slots against the REMOVE set's constants and that set's zfar, and
+ * the ADD slots against the ADD set's, by pvo_tsdf_sparse_integrate's test; the survivors of each set, in slot order, go through the
+ * dense call's two inline functions with the voxel's GLOBAL integer index: a voxel of a brick ends with the BYTES pvo_tsdf_reintegrate
+ * leaves at that voxel of an [8gz,8gy,8gx] volume.  Bricks that become empty stay allocated; bricks for the ADD set's new poses are
+ * the caller's job (pvo_tsdf_sparse_allocate, before this call).  kept int32 [cap] or NULL: survivors per brick, both sets summed.
+ * Up to three launches (pvo_tsdf_sparse_integrate's frames kernel once per set that has slots; the bricks).  workspace:
+ * pvo_tsdf_sparse_reintegrate_workspace_bytes(N_old, N), 16-byte aligned.  Limits as pvo_tsdf_reintegrate with the grid limits of
+ * the brick volume; a NULL tsdf / wsum / coord / bricks with cap > 0.  cap == 0, N_old + N == 0 or ht*wd == 0: PVO_OK. */
+typedef struct pvo_tsdf_sparse_reintegrate_args {
+  float* tsdf;
+  float* wsum;
+  float* rgb;
+  const int32_t* coord;
+  const int32_t* bricks;
+  int gz, gy, gx, cap;
+  float origin[3];
+  float voxel, trunc, z_near, w_max, w_floor;
+  const float* intrinsics;
+  const float* poses_old;
+  const float* disps_old;
+  const float* weight_old;
+  const int64_t* ix_old;
+  const float* poses;
+  const float* disps;
+  const float* weight;
+  const int64_t* ix;
+  int N_old, N, nframes, ht, wd;
+  const uint8_t* images;
+  int IH, IW, img_stride, img_offset;
+  int32_t* kept;
+} pvo_tsdf_sparse_reintegrate_args;
+size_t pvo_tsdf_sparse_reintegrate_args_size(void);
+size_t pvo_tsdf_sparse_reintegrate_workspace_bytes(int N_old, int N);
+int pvo_tsdf_sparse_reintegrate(const pvo_tsdf_sparse_reintegrate_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

@@ -146,6 +146,12 @@ SIGNATURES = {
     "pvo_tsdf_sparse_track_args_size": (_sz, []),
     "pvo_tsdf_sparse_track_workspace_bytes": (_sz, [_i, _i, _i]),
     "pvo_tsdf_sparse_track": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_reintegrate_args_size": (_sz, []),
+    "pvo_tsdf_reintegrate_workspace_bytes": (_sz, [_i, _i]),
+    "pvo_tsdf_reintegrate": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_tsdf_sparse_reintegrate_args_size": (_sz, []),
+    "pvo_tsdf_sparse_reintegrate_workspace_bytes": (_sz, [_i, _i]),
+    "pvo_tsdf_sparse_reintegrate": (_i, [_vp, _vp, _sz, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -301,6 +307,24 @@ class TsdfSparseTrackArgs(_c.Structure):
     _fields_ = [("grid", _vp), ("tsdf", _vp), ("wsum", _vp), ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i)] + _TRACK_TAIL
 
 
+_REINTEGRATE_TAIL = [("origin", _f * 3), ("voxel", _f), ("trunc", _f), ("z_near", _f), ("w_max", _f), ("w_floor", _f),
+                     ("intrinsics", _vp), ("poses_old", _vp), ("disps_old", _vp), ("weight_old", _vp), ("ix_old", _vp),
+                     ("poses", _vp), ("disps", _vp), ("weight", _vp), ("ix", _vp),
+                     ("N_old", _i), ("N", _i), ("nframes", _i), ("ht", _i), ("wd", _i),
+                     ("images", _vp), ("IH", _i), ("IW", _i), ("img_stride", _i), ("img_offset", _i)]
+
+
+class TsdfReintegrateArgs(_c.Structure):
+    """pvo_tsdf_reintegrate_args"""
+    _fields_ = [("tsdf", _vp), ("wsum", _vp), ("rgb", _vp), ("nz", _i), ("ny", _i), ("nx", _i)] + _REINTEGRATE_TAIL
+
+
+class TsdfSparseReintegrateArgs(_c.Structure):
+    """pvo_tsdf_sparse_reintegrate_args"""
+    _fields_ = [("tsdf", _vp), ("wsum", _vp), ("rgb", _vp), ("coord", _vp), ("bricks", _vp),
+                ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i)] + _REINTEGRATE_TAIL + [("kept", _vp)]
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 PVO_KNOB_EDGE_BLOCKS = 4        # 0 shipped | 1 off | 2 + bits (third, low, agg, trunk): 2 ... 17
@@ -343,7 +367,9 @@ def load():
                        (lib.pvo_tsdf_sparse_mesh_args_size, TsdfSparseMeshArgs),
                        (lib.pvo_tsdf_panoptic_args_size, TsdfPanopticArgs), (lib.pvo_tsdf_mesh_labels_args_size, TsdfMeshLabelsArgs),
                        (lib.pvo_tsdf_render_args_size, TsdfRenderArgs), (lib.pvo_tsdf_sparse_render_args_size, TsdfSparseRenderArgs),
-                       (lib.pvo_tsdf_track_args_size, TsdfTrackArgs), (lib.pvo_tsdf_sparse_track_args_size, TsdfSparseTrackArgs)):
+                       (lib.pvo_tsdf_track_args_size, TsdfTrackArgs), (lib.pvo_tsdf_sparse_track_args_size, TsdfSparseTrackArgs),
+                       (lib.pvo_tsdf_reintegrate_args_size, TsdfReintegrateArgs),
+                       (lib.pvo_tsdf_sparse_reintegrate_args_size, TsdfSparseReintegrateArgs)):
         if fn() != ctypes.sizeof(struct):
             raise PvoHipError("libpvo_hip.so has a %d-byte %s; this binding is written for %d bytes - rebuild with "
                               "`python -m pvo_amd.build`" % (fn(), struct.__doc__, ctypes.sizeof(struct)))

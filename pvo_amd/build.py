@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "tsdf_sparse.hip",
     "tsdf_render.hip",
     "tsdf_track.hip",
+    "tsdf_reintegrate.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",

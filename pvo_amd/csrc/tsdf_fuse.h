@@ -89,6 +89,59 @@ __device__ __forceinline__ void tsdf_fuse_frame(Voxel& a, const float* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------ de-integration
+
+struct Observation { float val, w, cr, cg, cb; };
+
+// what frame f (>= 0, with the slot's constants c) contributes to the voxel (xf, yf, zf) under the operands of `in`: tsdf_fuse_frame's
+// tests in its order.  false: the pair contributes nothing (and `o` is not written)
+template <bool RGB>
+__device__ __forceinline__ bool tsdf_observe(Observation& o, const float* __restrict__ c, int f, float xf, float yf, float zf, bool live,
+                                             const Intr K, const Fuse in, long long HW, long long plane) {
+  const float zc = c[6] * xf + c[7] * yf + c[8] * zf + c[11];
+  const float xc = c[0] * xf + c[1] * yf + c[2] * zf + c[9];
+  const float yc = c[3] * xf + c[4] * yf + c[5] * zf + c[10];
+  const float u = K.fx * (xc / zc) + K.cx, v = K.fy * (yc / zc) + K.cy;
+  const int ui = pvo_floor_to_int(u + 0.5f), vi = pvo_floor_to_int(v + 0.5f);       // (saturating, NaN -> 0)
+  const bool hit = live && zc > in.z_near && ui >= 0 && ui < in.wd && vi >= 0 && vi < in.ht;
+  if (!hit) return false;                              // (a wave without a hit branches over the gathers)
+  const long long pix = f * HW + static_cast<long long>(vi) * in.wd + ui;
+  const float d = in.disps[pix];
+  const float w = in.weight ? in.weight[pix] : 1.0f;
+  if (!(d > 0.0f && d < __builtin_inff() && w > 0.0f && w < __builtin_inff())) return false;   // (NaN fails every comparison)
+  const float sdf = 1.0f / d - zc;
+  if (sdf < -in.trunc) return false;
+  o.val = fminf(1.0f, sdf / in.trunc);
+  o.w = w;
+  if (RGB) {                                           // BGR planes -> RGB
+    const uint8_t* im = in.images + 3 * plane * f + static_cast<long long>(in.stride * vi + in.offset) * in.IW + (in.stride * ui + in.offset);
+    o.cr = static_cast<float>(im[2 * plane]); o.cg = static_cast<float>(im[plane]); o.cb = static_cast<float>(im[0]);
+  }
+  return true;
+}
+
+// frame f as `in` holds it taken OUT of the voxel's running average (pvo_tsdf_reintegrate's REMOVE step): Wn = W - w; at or below
+// w_floor the voxel becomes empty, otherwise the average without the observation, clamped to its range.  in.w_max plays no part
+template <bool RGB>
+__device__ __forceinline__ void tsdf_unfuse_frame(Voxel& a, const float* __restrict__ c, int f, float xf, float yf, float zf, bool live,
+                                                  const Intr K, const Fuse in, long long HW, long long plane, float w_floor) {
+  Observation o;
+  if (!tsdf_observe<RGB>(o, c, f, xf, yf, zf, live, K, in, HW, plane)) return;
+  const float Wn = a.W - o.w;
+  a.touched = true;
+  if (!(Wn > w_floor)) {                               // nothing left that the roundings of W have not eaten
+    a.T = 0.0f; a.W = 0.0f; a.cr = 0.0f; a.cg = 0.0f; a.cb = 0.0f;
+    return;
+  }
+  a.T = fminf(1.0f, fmaxf(-1.0f, (a.T * a.W - o.val * o.w) / Wn));
+  if (RGB) {
+    a.cr = fminf(255.0f, fmaxf(0.0f, (a.cr * a.W - o.cr * o.w) / Wn));
+    a.cg = fminf(255.0f, fmaxf(0.0f, (a.cg * a.W - o.cg * o.w) / Wn));
+    a.cb = fminf(255.0f, fmaxf(0.0f, (a.cb * a.W - o.cb * o.w) / Wn));
+  }
+  a.W = Wn;
+}
+
 // ------------------------------------------------------------------------------------------------------------ surface nets
 
 // flag byte of a cell: bit 0 active, bits 1-3 a quad around the edge corner 0 -> corner 0 + e_a (a = x, y, z), bit 4 corner 0 inside

@@ -663,8 +663,8 @@ class DepthVideo:
 
     def tsdf(self, voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None, use_sigma=False, origin=None, dims=None,
              min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05, sparse=False, margin=2, panoptic=False, keep_rgb=False):
-        """the fused surface of keyframes ix (default: all stored ones; fuse after `terminate` - poses that move later are not
-        de-integrated): a TSDF volume of `voxel`-sized cells, truncation `trunc` (default 3 voxels), integrated natively
+        """the fused surface of keyframes ix (default: all stored ones; a one-off fusion of the video as it stands - a volume that
+        follows keyframes which move later is pvo_amd.live_map.LiveMap): a TSDF volume of `voxel`-sized cells, truncation `trunc` (default 3 voxels), integrated natively
         (pvo_tsdf_integrate) from exactly the pixels map_points(ix, thresh, full_res, reject, max_rel_sigma) keeps, and its surface-nets
         mesh (pvo_tsdf_mesh).  use_sigma (needs the variances of `uncertainty`): pixels are weighted by fusion_weights(keep, disps,
         sigma, rel0), sigma at the 1/8 cell for full_res.  origin [x,y,z] / dims (nz,ny,nx): the volume; default tsdf_bounds of the map's

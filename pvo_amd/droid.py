@@ -25,7 +25,7 @@ def default_args(**over):
              beta=0.6, filter_thresh=1.75, warmup=12, keyframe_thresh=2.25, frontend_thresh=12.0, frontend_window=25,
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
              segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1,
-             store_images=False, uncertainty=False, opt_intr=False, opt_intr_free="all", store_segment_ids=False)
+             store_images=False, uncertainty=False, opt_intr=False, opt_intr_free="all", store_segment_ids=False, live_map=None)
     # uncertainty: after every keyframe's last frontend update, estimate the window's inverse-depth variances and pose covariance from
     # the bundle adjustment's normal equations (DepthVideo.uncertainty; get_uncertainty(), get_map(max_rel_sigma=...)).  Read only: the
     # trajectory and the depths are bit for bit those of a run without it.  A window of more than 64 poses (frontend_window above 64) is
@@ -44,6 +44,10 @@ def default_args(**over):
     # its points.  False (default): nothing is allocated, no result changes, and get_map() returns points without colours.
     # store_segment_ids: keep every keyframe's panoptic ids AS GIVEN (DepthVideo.segms_raw, int32 [buffer,H/8,W/8]; `segms` relabels each
     # frame on its own) so that get_mesh(panoptic=True) can fuse them across frames.  False (default): nothing is allocated or changed.
+    # live_map: a dict of pvo_amd.live_map.LiveMap's keyword arguments (voxel, origin, dims at least) - a TSDF volume kept current WHILE
+    # tracking: track() fuses the keyframes that have left the frontend's window and re-fuses the ones whose pose or depth moved,
+    # terminate() brings it up to the last keyframe after the global bundle adjustment; get_live_map().  Not with pipelined.  None
+    # (default): nothing is imported, allocated or launched.
     a.update(over)
     return Namespace(**a)
 
@@ -56,6 +60,9 @@ class Droid:
                              "neither the sensor-depth prior nor stereo edges")
         if getattr(args, "opt_intr_free", "all") not in ("all", "focal"):
             raise ValueError("args.opt_intr_free must be 'all' or 'focal', got %r" % (args.opt_intr_free,))
+        if getattr(args, "live_map", None) is not None and getattr(args, "pipelined", False):
+            raise ValueError("args.live_map together with args.pipelined is not supported: between two pipelined track() calls a keyframe "
+                             "update is half done, and the live map would fuse it as it stands")
         self.load_weights(args.weights, args.use_aff_bri)
         self.video = DepthVideo(args.image_size, args.buffer, args.device, args.segm_filter, args.thresh,
                                 store_images=bool(getattr(args, "store_images", False)),
@@ -75,6 +82,12 @@ class Droid:
         self.filterx.before_context = self.frontend.keyframe_ahead
         self.backend = DroidBackend(self.net, self.video, args)
         self.traj_filler = PoseTrajectoryFiller(self.net, self.video, args.device)
+        self.live_map = None
+        if getattr(args, "live_map", None) is not None:
+            from .live_map import LiveMap
+            kw = dict(args.live_map)
+            kw.setdefault("lag", args.frontend_window)
+            self.live_map = LiveMap(self.video, **kw)
 
     def load_weights(self, weights, use_aff_bri=False):
         """droid.py:55-62; DataParallel's "module." prefix is stripped"""
@@ -107,6 +120,8 @@ class Droid:
             if not getattr(self.args, "pipelined", False):
                 self.filterx.track(tstamp, image, depth, intrinsics, segments, right=right)
                 self.frontend()
+                if self.live_map is not None:
+                    self.live_map.update()
                 return
             self.filterx.begin(tstamp, image, depth, intrinsics, segments, right=right)
             self.frontend.finish()
@@ -129,6 +144,8 @@ class Droid:
         self.backend(7)
         self._release_cached_memory()
         self.backend(12)
+        if self.live_map is not None:
+            self.live_map.update(upto=self.video.counter, force=False)
         traj = self.traj_filler(stream)
         return (traj.inv() if need_inv else traj).data.cpu().numpy()
 
@@ -184,9 +201,20 @@ class Droid:
         use_sigma=False, origin=None, dims=None, min_weight=1.0, w_max=0) - a dict of the mesh verts [V,3], normals [V,3], rgba [V,4],
         faces [F,3] and the volume tsdf, wsum [nz,ny,nx], origin, voxel.  sparse=True (with margin=2): a brick volume in place of the dense
         one, returned as `volume` (DepthVideo.tsdf).  panoptic=True (args.store_segment_ids): the keyframes' segment ids fused into the volume
-        as well - vlabel [V], one id per vertex, and the volumes label, lconf.  Call it after terminate(): poses that move later are not de-integrated."""
+        as well - vlabel [V], one id per vertex, and the volumes label, lconf.  A one-off fusion of the video as it stands: a volume
+        that follows the keyframes while they move is args.live_map / get_live_map()."""
         self.flush()
         return self.video.tsdf(**kw)
+
+    def get_live_map(self):
+        """the volume args.live_map keeps current and its mesh as it stands: LiveMap.as_volume() (tsdf, wsum, rgb with images, origin,
+        voxel; or volume = the SparseTSDF) plus verts, normals, rgba, faces.  Fused up to the keyframes that have left the frontend's
+        window, after terminate() up to the last one."""
+        if self.live_map is None:
+            raise RuntimeError("get_live_map() needs args.live_map (a dict of LiveMap's arguments: voxel, origin, dims, ...)")
+        out = self.live_map.as_volume()
+        out.update(self.live_map.mesh())
+        return out
 
     def get_renders(self, volume, **kw):
         """the fused volume seen from the keyframes (or from explicit poses): DepthVideo.tsdf_render(volume, ix=None, poses=None,

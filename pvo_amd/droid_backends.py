@@ -801,6 +801,105 @@ def tsdf_sparse_integrate(vol, poses, disps, intrinsics, ix, trunc, weight=None,
                   "tsdf_sparse_integrate_panoptic")
 
 
+def _reintegrate_sets(a, what, dev, intrinsics, remove, add, images, img_stride, img_offset):
+    """the two frame sets and the colour arguments of a re-integration into `a`; remove / add: (poses, disps, ix, weight or None) or
+    None (no slot).  Returns (N_old, N)"""
+    _contig(intrinsics, "intrinsics")
+    _f32(intrinsics, "intrinsics")
+    shape = None
+    for s, (tag, sfx) in ((remove, ("remove", "_old")), (add, ("add", ""))):
+        if s is None:
+            continue
+        poses, disps, ix, weight = s
+        for t, n in ((poses, "poses"), (disps, "disps"), (ix, "ix"), (weight, "weight")):
+            if t is not None:
+                _contig(t, "%s %s" % (tag, n))
+        _dev(intrinsics, poses, disps, ix, weight)
+        _long(ix, "%s ix" % tag)
+        for t, n in ((poses, "poses"), (disps, "disps"), (weight, "weight")):
+            if t is not None:
+                _f32(t, "%s %s" % (tag, n))
+        if disps.dim() != 3 or poses.shape[0] < disps.shape[0] or (weight is not None and weight.shape != disps.shape):
+            raise PvoHipError("%s: %s poses must cover the frames of disps [nframes,ht,wd], weight must have the shape of disps" % (what, tag))
+        if shape is not None and tuple(disps.shape) != shape:
+            raise PvoHipError("%s: the two sets must describe the same frames: disps %s against %s" % (what, tuple(disps.shape), shape))
+        shape = tuple(disps.shape)
+        setattr(a, "poses" + sfx, _ptr(poses))
+        setattr(a, "disps" + sfx, _ptr(disps))
+        setattr(a, "ix" + sfx, _ptr(ix))
+        setattr(a, "weight" + sfx, _ptr(weight))
+        setattr(a, "N" + sfx, ix.shape[0])
+    a.intrinsics = _ptr(intrinsics)
+    if shape is not None:
+        a.nframes, a.ht, a.wd = shape
+    if images is not None:
+        _contig(images, "images")
+        _dev(intrinsics, images)
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < a.nframes or images.shape[1] != 3:
+            raise PvoHipError("%s: images must be uint8 [nframes,3,IH,IW]" % what)
+        a.images, a.IH, a.IW, a.img_stride, a.img_offset = _ptr(images), images.shape[2], images.shape[3], int(img_stride), int(img_offset)
+    return a.N_old, a.N
+
+
+def _reintegrate_workspace(what, dev, need, workspace):
+    if workspace is None:
+        return _workspace(dev, need)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev or workspace.numel() < need:
+        raise PvoHipError("%s: workspace must be a contiguous uint8 device tensor of at least %d bytes" % (what, need))
+    return workspace
+
+
+def tsdf_reintegrate(tsdf, wsum, rgb, origin, voxel, trunc, intrinsics, remove=None, add=None, images=None, img_stride=8, img_offset=3,
+                     z_near=0.0, w_max=0.0, w_floor=2.0 ** -10, workspace=None):
+    """Take keyframes out of the caller's volume as they were fused and put keyframes in as they are now, in one pass (include/pvo_hip.h
+    pvo_tsdf_reintegrate).  remove / add: (poses [nframes,7], disps [nframes,ht,wd], ix int64 [n], weight [nframes,ht,wd] or None) or
+    None; `remove` holds the caller's SNAPSHOT of what was fused, `add` the present state; both over the same frames and one
+    intrinsics [4].  Per voxel the remove slots run first, in order, then the add slots; a voxel whose weight falls to w_floor or
+    below becomes empty (tsdf = wsum = rgb = 0).  images serves both sets.  A removal is approximate where w_max capped the weight.
+    workspace: a caller-owned uint8 tensor of pvo_tsdf_reintegrate_workspace_bytes(n_remove, n_add), or None for the cached one.
+    No allocation beyond that, no synchronisation."""
+    for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")):
+        if t is not None:
+            _contig(t, n)
+            _f32(t, n)
+    dev = _dev(tsdf, wsum, rgb, intrinsics)
+    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
+        raise PvoHipError("tsdf_reintegrate: tsdf and wsum must be [nz,ny,nx], rgb [nz,ny,nx,3]")
+    a = _lib.TsdfReintegrateArgs()
+    n_old, n = _reintegrate_sets(a, "tsdf_reintegrate", dev, intrinsics, remove, add, images, img_stride, img_offset)
+    a.tsdf, a.wsum, a.rgb = _ptr(tsdf), _ptr(wsum), _ptr(rgb)
+    a.nz, a.ny, a.nx = tsdf.shape
+    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
+    a.voxel, a.trunc, a.z_near, a.w_max, a.w_floor = float(voxel), float(trunc), float(z_near), float(w_max), float(w_floor)
+    lib = _lib.load()
+    ws = _reintegrate_workspace("tsdf_reintegrate", dev, lib.pvo_tsdf_reintegrate_workspace_bytes(n_old, n), workspace)
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_reintegrate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_reintegrate")
+
+
+def tsdf_sparse_reintegrate(vol, trunc, intrinsics, remove=None, add=None, images=None, img_stride=8, img_offset=3, z_near=0.0, w_max=0.0,
+                            w_floor=2.0 ** -10, kept=None, workspace=None):
+    """tsdf_reintegrate on the bricks in use of the brick volume `vol` (include/pvo_hip.h pvo_tsdf_sparse_reintegrate): every voxel of a
+    brick gets the bytes the dense call leaves at that voxel.  Bricks for the poses of `add` must exist already
+    (tsdf_sparse_allocate; SparseTSDF.reintegrate does it); bricks that become empty stay.  kept: int32 [cap] or None, survivors of
+    the cull per brick, both sets summed."""
+    a = _lib.TsdfSparseReintegrateArgs()
+    dev = _sparse_world(a, vol)
+    _dev(vol["grid"], intrinsics)
+    n_old, n = _reintegrate_sets(a, "tsdf_sparse_reintegrate", dev, intrinsics, remove, add, images, img_stride, img_offset)
+    a.tsdf, a.wsum, a.rgb = _ptr(vol["tsdf"]), _ptr(vol["wsum"]), _ptr(vol.get("rgb"))
+    a.trunc, a.z_near, a.w_max, a.w_floor = float(trunc), float(z_near), float(w_max), float(w_floor)
+    if kept is not None:
+        _contig(kept, "kept")
+        if kept.dtype != torch.int32 or kept.numel() < a.cap or kept.device != dev:
+            raise PvoHipError("tsdf_sparse_reintegrate: kept must be an int32 device tensor of at least cap elements")
+        a.kept = _ptr(kept)
+    lib = _lib.load()
+    ws = _reintegrate_workspace("tsdf_sparse_reintegrate", dev, lib.pvo_tsdf_sparse_reintegrate_workspace_bytes(n_old, n), workspace)
+    with torch.cuda.device(dev):
+        check(lib.pvo_tsdf_sparse_reintegrate(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "tsdf_sparse_reintegrate")
+
+
 def tsdf_sparse_mesh_into(vol, min_weight, out, label=None):
     """pvo_tsdf_sparse_mesh on caller-owned buffers (out as for tsdf_mesh_into; label int32 [cap,8,8,8]: out["vlabel"] as well,
     pvo_tsdf_sparse_mesh_panoptic).  No allocation beyond the cached workspace, no synchronisation."""

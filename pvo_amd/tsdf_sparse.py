@@ -83,6 +83,20 @@ class SparseTSDF:
                                  images=images if self.colours else None, img_stride=img_stride, img_offset=img_offset, z_near=z_near,
                                  w_max=w_max, kept=kept, **pan)
 
+    def reintegrate(self, intrinsics, remove=None, add=None, images=None, img_stride=8, img_offset=3, z_near=0.0, w_max=0.0,
+                    w_floor=2.0 ** -10, margin=2.0, kept=None):
+        """keyframes taken out as they were fused (remove) and put in as they are now (add), each (poses, disps, ix, weight or None) or
+        None, in one pass over the bricks (droid_backends.tsdf_sparse_reintegrate).  Bricks for `add` are allocated first - the one
+        synchronisation, and the pool grows as in allocate; bricks a removal empties stay allocated.  The segment-id vote cannot be
+        inverted (a Boyer-Moore majority keeps no history): a volume made with labels=True is refused."""
+        if self.labels:
+            raise ValueError("SparseTSDF.reintegrate: a volume made with labels=True cannot be re-integrated - the per-voxel label vote "
+                             "is a running majority and cannot be inverted; keep the labels in a volume fused after tracking")
+        if add is not None and add[2].numel():
+            self.allocate(add[0], add[1], intrinsics, add[2], weight=add[3], z_near=z_near, margin=margin)
+        db.tsdf_sparse_reintegrate(self.volume(), self.trunc, intrinsics, remove=remove, add=add, images=images if self.colours else None,
+                                   img_stride=img_stride, img_offset=img_offset, z_near=z_near, w_max=w_max, w_floor=w_floor, kept=kept)
+
     def mesh(self, min_weight=1.0, vcap=None, fcap=None):
         """the mesh dict of droid_backends.tsdf_sparse_mesh; with labels=True it has vlabel"""
         return db.tsdf_sparse_mesh(self.volume(), min_weight=min_weight, vcap=vcap, fcap=fcap, label=self.label)

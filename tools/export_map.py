@@ -4,6 +4,7 @@
                                [--reconstruction_path DIR] [--uncertainty [--max_rel_sigma X]]
                                [--mesh out.ply --voxel V [--trunc T] [--sigma_weight] [--sparse] [--panoptic [--instances_dir DIR]]
                                 [--render_dir DIR]]
+                               [--live_map out.ply --voxel V --origin X Y Z --dims NZ NY NX [--sparse]]
 
 --map writes the filtered point cloud of all keyframes after the global bundle adjustment (Droid.get_map: points confirmed by two
 neighbouring keyframes, pvo_map_points) as a binary little-endian PLY: x y z float, red green blue uchar, int label (the per-frame
@@ -23,7 +24,10 @@ also writes one mesh per id, DIR/segment_<id>.ply.  --render_dir DIR (with --mes
 DIR/depth_%06d.npy (f32 [ht,wd], 0 = no surface), normal_%06d.npy (f32 [ht,wd,3]), rgba_%06d.npy (uint8 [ht,wd,4]) and, with
 --panoptic, label_%06d.npy (int32 [ht,wd]: ids that are consistent across keyframes); it prints how each keyframe's own depth
 agrees with the fused surface (DepthVideo.model_residual).  Without --mesh the output is what it was without the option, and without
---sparse / --panoptic / --render_dir the mesh is.
+--sparse / --panoptic / --render_dir the mesh is.  --live_map also keeps a TSDF volume current WHILE tracking (args.live_map:
+pvo_amd.live_map.LiveMap over the world box --origin / --dims of --voxel sized cells, pvo_tsdf_reintegrate; with --sparse a brick
+volume), writes its mesh, and prints how many keyframe refreshes it took and how the live volume compares with one fused from scratch
+after the global bundle adjustment.  Without --live_map the output is what it was.
 """
 import os
 import sys
@@ -52,6 +56,9 @@ def parse_args(argv=None):
     p.add_argument("--panoptic", action="store_true", help="with --mesh: fuse the frames' panoptic ids, write a label per vertex")
     p.add_argument("--instances_dir", default=None, help="with --panoptic: also one segment_<id>.ply per id into this folder")
     p.add_argument("--render_dir", default=None, help="with --mesh: also depth / normal / rgba (/ label) images of the fused volume per keyframe")
+    p.add_argument("--live_map", default=None, help="also keep a live TSDF volume while tracking and write its mesh to this .ply")
+    p.add_argument("--origin", type=float, nargs=3, default=None, help="with --live_map: the centre of voxel (0,0,0), x y z")
+    p.add_argument("--dims", type=int, nargs=3, default=None, help="with --live_map: the volume's size in voxels, nz ny nx")
     own, rest = p.parse_known_args(argv)
     args = test_vo.parse_args(rest)
     for k, v in vars(own).items():
@@ -62,8 +69,10 @@ def parse_args(argv=None):
         p.error("--mesh needs --voxel V with V > 0")
     if args.sigma_weight and not (args.mesh is not None and args.uncertainty):
         p.error("--sigma_weight needs --mesh and --uncertainty")
-    if args.sparse and args.mesh is None:
+    if args.sparse and args.mesh is None and args.live_map is None:
         p.error("--sparse needs --mesh")
+    if args.live_map is not None and not (args.voxel is not None and args.voxel > 0 and args.origin is not None and args.dims is not None):
+        p.error("--live_map needs --voxel V with V > 0, --origin X Y Z and --dims NZ NY NX: the world box of a running session")
     if args.panoptic and args.mesh is None:
         p.error("--panoptic needs --mesh")
     if args.instances_dir is not None and not args.panoptic:
@@ -122,6 +131,26 @@ def write_renders(droid, args, volume):
                100.0 * float(share.mean()) if n else 0.0))
 
 
+def write_live_map(droid, args):
+    """the --live_map output: the live volume's mesh, and the volume against one fused from scratch now; returns the lines"""
+    from pvo_amd.handoff import write_ply_mesh
+    lm = droid.live_map
+    g = droid.get_live_map()
+    nv, nf = write_ply_mesh(args.live_map, g["verts"], g["faces"], g["rgba"], g["normals"])
+    line = ("live map: %d vertices, %d triangles written to %s; %d keyframes fused, %d keyframe refreshes while tracking"
+            % (nv, nf, args.live_map, len(lm.fused), lm.refreshed_total))
+    dims = lm.sparse.to_dense()["tsdf"].shape if lm.sparse is not None else lm.tsdf.shape
+    ref = droid.get_mesh(voxel=args.voxel, trunc=args.trunc, thresh=args.filter_thresh_map, origin=args.origin, dims=tuple(dims))
+    live = lm.sparse.to_dense() if lm.sparse is not None else {"tsdf": lm.tsdf, "wsum": lm.wsum}
+    both = (live["wsum"] >= lm.min_weight) & (ref["wsum"] >= lm.min_weight)
+    only = int(((live["wsum"] >= lm.min_weight) ^ (ref["wsum"] >= lm.min_weight)).sum())
+    d = (live["tsdf"] - ref["tsdf"])[both].abs()
+    line += ("\nlive volume against one fused from scratch after terminate: %d voxels usable in both, %d in only one; |tsdf difference| "
+             "mean %.5f max %.4f; from-scratch mesh %d vertices"
+             % (int(both.sum()), only, float(d.mean()) if d.numel() else 0.0, float(d.max()) if d.numel() else 0.0, ref["verts"].shape[0]))
+    return line
+
+
 def main(argv=None):
     from pvo_amd.droid import Droid
     from pvo_amd.handoff import save_reconstruction, write_kitti_trajectory, write_ply
@@ -132,6 +161,9 @@ def main(argv=None):
     args.upsample = bool(args.full_res)
     if args.datapath.endswith("20"):
         args.thresh = 0.9
+    if args.live_map is not None:
+        args.live_map_path, args.live_map = args.live_map, dict(voxel=args.voxel, trunc=args.trunc, origin=args.origin, dims=args.dims,
+                                                                sparse=args.sparse, thresh=args.filter_thresh_map)
     droid = Droid(args)
     with_segm = args.segm_filter or args.panoptic                      # (--panoptic reads the ids whether or not they filter the graph)
     for t, image, intr, segm in test_vo.image_stream(args.datapath, args.image_size, "val", with_segm):
@@ -146,6 +178,9 @@ def main(argv=None):
     print("map: %d points of %d keyframes written to %s" % (n, droid.video.counter, args.map))
     if args.mesh is not None:
         print(write_mesh(droid, args))
+    if getattr(args, "live_map_path", None) is not None:
+        args.live_map = args.live_map_path
+        print(write_live_map(droid, args))
     if args.reconstruction_path:
         for p in save_reconstruction(args.reconstruction_path, droid.video):
             print("wrote", p)
