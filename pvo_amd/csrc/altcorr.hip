@@ -184,14 +184,19 @@ extern "C" int pvo_altcorr_backward(const void* fmap1, const void* fmap2, const 
                                     int radius, int dtype, void* stream) {
   if (B < 0 || S < 0 || H1 < 0 || W1 < 0 || H2 < 0 || W2 < 0 || C <= 0 || radius < 0) return PVO_EINVAL;
   if (dtype != PVO_F32) return PVO_EUNSUPPORTED;
-  if (B == 0 || H1 * W1 == 0) return PVO_OK;
-  if (!fmap1 || !fmap1_grad || (S > 0 && (!coords || !corr_grad)) || (H2 * W2 > 0 && (!fmap2 || !fmap2_grad))) return PVO_EINVAL;
-  if (B > 65535) return PVO_EUNSUPPORTED;
-  hipStream_t st = pvo_stream(stream);
+  if (B == 0) return PVO_OK;
   const int HW = H1 * W1;
-  // fmap2_grad accumulates with atomics: zero it here so the caller may hand over torch.empty
+  if (H2 * W2 > 0 && !fmap2_grad) return PVO_EINVAL;
+  if (HW > 0) {
+    if (!fmap1 || !fmap1_grad || (S > 0 && (!coords || !corr_grad)) || (H2 * W2 > 0 && !fmap2)) return PVO_EINVAL;
+    if (B > 65535) return PVO_EUNSUPPORTED;
+  }
+  hipStream_t st = pvo_stream(stream);
+  // fmap2_grad accumulates with atomics: zero it here so the caller may hand over torch.empty - also when there is no
+  // source pixel to accumulate from (the header promises a fully written fmap2_grad)
   if (H2 * W2 > 0 && hipMemsetAsync(fmap2_grad, 0, sizeof(float) * static_cast<size_t>(B) * H2 * W2 * C, st) != hipSuccess)
     return PVO_ELAUNCH;
+  if (HW == 0) return PVO_OK;
   hipLaunchKernelGGL(altcorr_bwd_kernel, dim3((HW + 3) / 4, B), dim3(256), 0, st,
                      static_cast<const float*>(fmap1), static_cast<const float*>(fmap2), coords,
                      static_cast<const float*>(corr_grad), static_cast<float*>(fmap1_grad),

@@ -124,7 +124,9 @@ class AltCorrBlock:
         for i in range(num_levels):
             self.pyramid.append(f.permute(0, 2, 3, 1).contiguous().view(B, N, H // 2 ** i, W // 2 ** i, C))
             if i + 1 < num_levels:
-                f = F.avg_pool2d(f, 2, stride=2)
+                # fp32 maps: the four-term mean in fp64, rounded once (an fp32 sum rounds three times, and under cancellation
+                # its error is a multiple of the mean); 16-bit maps already accumulate wider than they store
+                f = F.avg_pool2d(f.double(), 2, stride=2).float() if f.dtype == torch.float32 else F.avg_pool2d(f, 2, stride=2)
 
     def corr_fn(self, coords, ii, jj):
         B, N, H, W, S, _ = coords.shape
