@@ -96,7 +96,9 @@ const char* pvo_last_hip_error(void);
  * struct changed - new structs pvo_tsdf_track_args / pvo_tsdf_sparse_track_args (with *_args_size()) and new entry points
  * pvo_tsdf_track[_workspace_bytes] / pvo_tsdf_sparse_track[_workspace_bytes]; still 106, live volume: no existing struct changed -
  * new structs pvo_tsdf_reintegrate_args / pvo_tsdf_sparse_reintegrate_args (with *_args_size()) and new entry points
- * pvo_tsdf_reintegrate[_workspace_bytes] / pvo_tsdf_sparse_reintegrate[_workspace_bytes]): a caller
+ * pvo_tsdf_reintegrate[_workspace_bytes] / pvo_tsdf_sparse_reintegrate[_workspace_bytes]; still 106, object motion: no existing
+ * struct changed - new struct pvo_object_motion_args (with pvo_object_motion_args_size()) and new entry points
+ * pvo_object_motion[_workspace_bytes]): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -1311,6 +1313,101 @@ typedef struct pvo_tsdf_sparse_reintegrate_args {
 size_t pvo_tsdf_sparse_reintegrate_args_size(void);
 size_t pvo_tsdf_sparse_reintegrate_workspace_bytes(int N_old, int N);
 int pvo_tsdf_sparse_reintegrate(const pvo_tsdf_sparse_reintegrate_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Object motion: a rigid transform per (edge, segment) from the full flow    */
+/* ------------------------------------------------------------------------- */
+
+/* pvo_object_motion: per JOB (an edge i -> j and a label of frame i) the A in SE(3) that takes the segment's points from camera i's
+ * frame at time i to camera j's frame at time j, so that they project onto the targets: a PnP problem, six unknowns, two residual rows
+ * per pixel, solved by Gauss-Newton for many small jobs at once (no counterpart in the reference).  Device pointers, dense, at 1/8
+ * resolution.  Stated per pixel and per evaluation: an implementation may order the work as it likes, as long as the sums below are
+ * formed in an order that depends on the shapes alone.
+ *
+ *   Frames: poses f32 [nframes,7] world-to-camera; disps f32 [nframes,ht,wd] inverse depth with intrinsics [4] for ht x wd;
+ *   labels int32 [nframes,ht,wd], any integers (no value has a meaning here).
+ *   Edges: ii, jj int64 [E];  target f32 [E,ht,wd,2]: the ABSOLUTE pixel coordinates (u, v) in frame jj[e] of the point seen at pixel
+ *   (vi, ui) of frame ii[e], the object's own motion included (from the factor graph: coords0 + full_flow);  weight f32 [E,ht,wd] or
+ *   NULL (= 1).
+ *   Jobs: job_edge int64 [N], job_label int32 [N]: job n's MEMBERS are the pixels of frame ii[job_edge[n]] whose label equals
+ *   job_label[n].  Several jobs may name one edge; two jobs may be identical (and then get identical bytes).
+ *   Start: start f32 [N,7] or NULL (= G_j G_i^-1 by csrc/se3.h's rel_pose: the object at rest in the world).
+ *   Parameters: iters in [0, PVO_OBJECT_MOTION_MAX_ITERS]; z_min > 0; huber >= 0 (0 = off); lm >= 0, ep >= 0; min_count >= 1.
+ *   Outputs, all written for every job (a caller never clears them):
+ *     rel       f32 [N,7]                  the final A; may be the very array `start` (the same pointer; no other overlap)
+ *     motion    f32 [N,7]                  T_w = G_j^-1 (A G_i), the object's motion in the WORLD frame (the identity, up to rounding,
+ *                                          for a static segment), from csrc/se3.h's quaternion product and rotation in fp32; the
+ *                                          quaternion is stored as the products come
+ *     info      f32 [N,iters+1,4]          per evaluation (E, count, max|xi| of the step taken from it, status); the last row is the
+ *                                          evaluation AT the final A, its step is 0.  count is exact below 2^24
+ *     system    f64 [N,27] or NULL         of the LAST evaluation: the undamped H (upper triangle, row-major, 21 values), then b
+ *     centroid  f32 [N,3] or NULL          G_i^-1 (c / count) of the last evaluation: the contributing points' mean in the world at
+ *                                          time i (c / count in fp64, rounded to fp32, then se3.h in fp32); 0 when count = 0
+ *     residual  f32 [N,ht,wd,2] or NULL    r at the final A, NaN where the pixel does not contribute to job n
+ *     jac       f32 [N,ht,wd,2,6] or NULL  J at the final A, 0 where it does not contribute (a diagnostic)
+ *
+ * One EVALUATION at A = (R, t), R the matrix of the quaternion as stored (no normalisation; R_00 = fma(-2, fma(y, y, z z), 1),
+ * R_01 = 2 fma(x, y, -(z w)), and so on), fp32, every multiply-add written below as fma one fused operation, every other operation
+ * rounded to fp32:
+ *   1. a member pixel (vi, ui) needs d finite and > 0 and w finite and > 0;  z = 1 / d,  rx = (ui - cx) / fx,  ry = (vi - cy) / fy,
+ *      Xi = (z rx, z ry, z).
+ *   2. Y_k = fma(R_k0, Xi_0, fma(R_k1, Xi_1, fma(R_k2, Xi_2, t_k))).  The pixel CONTRIBUTES iff in addition Y_z > z_min and both
+ *      target components are finite.
+ *   3. iz = 1 / Y_z,  qx = Y_x iz,  qy = Y_y iz;  r = (fma(fx, qx, cx) - tu,  fma(fy, qy, cy) - tv).
+ *   4. J = Jp [ I | -[Y]x ] (2 x 6), Jp = [[fx/Y_z, 0, -fx Y_x/Y_z^2], [0, fy/Y_z, -fy Y_y/Y_z^2]] - the pose-j Jacobian of the bundle
+ *      adjustment, the derivative of r under A <- Exp(xi) A, xi = (tau, phi), the retraction of pvo_ba, pvo_se3_unary and
+ *      pvo_tsdf_track - as:  ax = fx iz, ay = fy iz, mx = -(ax qx), my = -(ay qy);
+ *        J_u = (ax, 0, mx,  mx Y_y,  fma(ax, Y_z, -(mx Y_x)),  -(ax Y_y)),
+ *        J_v = (0, ay, my,  fma(my, Y_y, -(ay Y_z)),  -(my Y_x),  ay Y_x).
+ *   5. a = sqrt(fma(r_u, r_u, r_v r_v));  k = 1, rho = a a if huber == 0 or a <= huber;  otherwise k = huber / a,
+ *      rho = huber fma(2, a, -huber).
+ *   6. over the job's contributing pixels, with wu_i = (w k) J_u,i and wv_i = (w k) J_v,i:  H_ij += fma(wu_i, J_u,j, wv_i J_v,j),
+ *      b_i += fma(wu_i, r_u, wv_i r_v),  E += w rho,  count += 1,  c += Xi: 32 fp32 values per pixel.
+ *   7. they are summed in a tree fixed by the shapes alone (pvo_tsdf_track's): the 64 pixels of an 8 x 8 tile (six levels) and four
+ *      tiles side by side (two levels) in fp32, the rest in fp64.  A pixel that is no member or does not contribute enters as +0.
+ * One STEP:  A_d = H + diag(lm H_ii + ep);  Cholesky in fp64;  xi = -A_d^-1 b, rounded to fp32.  status = 1 if count < min_count; else
+ * 2 if a pivot is not finite and > 0 or xi is not finite; else 0.  Only with status 0 the step is applied:  A <- Exp(xi) A  with
+ * csrc/se3.h's retract (the product of two unit quaternions is stored as it comes).  Otherwise A stays.  The last row's status is
+ * formed in the same way; no step follows it.
+ * A job whose edge is outside [0, E), or whose edge names a frame outside [0, nframes): nothing of it is dereferenced; every row of
+ * info is (0, 0, 0, 4), rel is its start (the identity with start == NULL), motion is the identity, system, centroid and jac are 0,
+ * residual is NaN.  With E == 0 that is every job.
+ *
+ * 2 iters + 3 launches (the jobs' constants; per evaluation a job-major pixel kernel - grid (groups of four 8 x 8 tiles, jobs), a wave
+ * on a tile, which reads its 64 labels first and leaves a zero slab without touching disps, target or weight when none is a member -
+ * and one workgroup per job that sums, solves and retracts).  No atomics, no allocation, no host synchronisation: capturable; the same
+ * operands give the same bytes; no device loop's trip count depends on data.
+ * workspace: pvo_object_motion_workspace_bytes(N, ht, wd) bytes (PVO_EWORKSPACE otherwise), 16-byte aligned.
+ * Limits (PVO_EINVAL): a negative N, E, nframes, ht or wd; ht*wd >= 2^31; a parameter outside its range or not finite; then, unless
+ * N == 0 or ht*wd == 0 (PVO_OK, nothing written): a NULL intrinsics / job_edge / job_label / rel / motion / info, a NULL poses / disps /
+ * labels with nframes > 0, a NULL ii / jj / target with E > 0, N * workgroups per image >= 2^31; then the workspace. */
+#define PVO_OBJECT_MOTION_MAX_ITERS 64
+typedef struct pvo_object_motion_args {
+  const float* poses;
+  const float* disps;
+  const float* intrinsics;
+  const int32_t* labels;
+  const int64_t* ii;
+  const int64_t* jj;
+  const float* target;
+  const float* weight;
+  const int64_t* job_edge;
+  const int32_t* job_label;
+  const float* start;
+  int N, E, nframes, ht, wd;
+  int iters, min_count;
+  float z_min, huber, lm, ep;
+  float* rel;
+  float* motion;
+  float* info;
+  double* system;
+  float* centroid;
+  float* residual;
+  float* jac;
+} pvo_object_motion_args;
+size_t pvo_object_motion_args_size(void);
+size_t pvo_object_motion_workspace_bytes(int N, int ht, int wd);
+int pvo_object_motion(const pvo_object_motion_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

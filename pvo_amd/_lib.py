@@ -152,6 +152,9 @@ SIGNATURES = {
     "pvo_tsdf_sparse_reintegrate_args_size": (_sz, []),
     "pvo_tsdf_sparse_reintegrate_workspace_bytes": (_sz, [_i, _i]),
     "pvo_tsdf_sparse_reintegrate": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_object_motion_args_size": (_sz, []),
+    "pvo_object_motion_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pvo_object_motion": (_i, [_vp, _vp, _sz, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -325,6 +328,18 @@ class TsdfSparseReintegrateArgs(_c.Structure):
                 ("gz", _i), ("gy", _i), ("gx", _i), ("cap", _i)] + _REINTEGRATE_TAIL + [("kept", _vp)]
 
 
+OBJECT_MOTION_MAX_ITERS = 64               # PVO_OBJECT_MOTION_MAX_ITERS
+
+
+class ObjectMotionArgs(_c.Structure):
+    """pvo_object_motion_args"""
+    _fields_ = [("poses", _vp), ("disps", _vp), ("intrinsics", _vp), ("labels", _vp), ("ii", _vp), ("jj", _vp), ("target", _vp),
+                ("weight", _vp), ("job_edge", _vp), ("job_label", _vp), ("start", _vp),
+                ("N", _i), ("E", _i), ("nframes", _i), ("ht", _i), ("wd", _i), ("iters", _i), ("min_count", _i),
+                ("z_min", _f), ("huber", _f), ("lm", _f), ("ep", _f),
+                ("rel", _vp), ("motion", _vp), ("info", _vp), ("system", _vp), ("centroid", _vp), ("residual", _vp), ("jac", _vp)]
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 PVO_KNOB_EDGE_BLOCKS = 4        # 0 shipped | 1 off | 2 + bits (third, low, agg, trunk): 2 ... 17
@@ -369,7 +384,8 @@ def load():
                        (lib.pvo_tsdf_render_args_size, TsdfRenderArgs), (lib.pvo_tsdf_sparse_render_args_size, TsdfSparseRenderArgs),
                        (lib.pvo_tsdf_track_args_size, TsdfTrackArgs), (lib.pvo_tsdf_sparse_track_args_size, TsdfSparseTrackArgs),
                        (lib.pvo_tsdf_reintegrate_args_size, TsdfReintegrateArgs),
-                       (lib.pvo_tsdf_sparse_reintegrate_args_size, TsdfSparseReintegrateArgs)):
+                       (lib.pvo_tsdf_sparse_reintegrate_args_size, TsdfSparseReintegrateArgs),
+                       (lib.pvo_object_motion_args_size, ObjectMotionArgs)):
         if fn() != ctypes.sizeof(struct):
             raise PvoHipError("libpvo_hip.so has a %d-byte %s; this binding is written for %d bytes - rebuild with "
                               "`python -m pvo_amd.build`" % (fn(), struct.__doc__, ctypes.sizeof(struct)))

@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "tsdf_render.hip",
     "tsdf_track.hip",
     "tsdf_reintegrate.hip",
+    "object_motion.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",

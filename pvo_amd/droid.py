@@ -25,7 +25,8 @@ def default_args(**over):
              beta=0.6, filter_thresh=1.75, warmup=12, keyframe_thresh=2.25, frontend_thresh=12.0, frontend_window=25,
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
              segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1,
-             store_images=False, uncertainty=False, opt_intr=False, opt_intr_free="all", store_segment_ids=False, live_map=None)
+             store_images=False, uncertainty=False, opt_intr=False, opt_intr_free="all", store_segment_ids=False, live_map=None,
+             object_motion=None)
     # uncertainty: after every keyframe's last frontend update, estimate the window's inverse-depth variances and pose covariance from
     # the bundle adjustment's normal equations (DepthVideo.uncertainty; get_uncertainty(), get_map(max_rel_sigma=...)).  Read only: the
     # trajectory and the depths are bit for bit those of a run without it.  A window of more than 64 poses (frontend_window above 64) is
@@ -48,6 +49,10 @@ def default_args(**over):
     # tracking: track() fuses the keyframes that have left the frontend's window and re-fuses the ones whose pose or depth moved,
     # terminate() brings it up to the last keyframe after the global bundle adjustment; get_live_map().  Not with pipelined.  None
     # (default): nothing is imported, allocated or launched.
+    # object_motion: True, or a dict of pvo_amd.object_motion.ObjectTracks' keyword arguments (min_pixels, dynamic_share, iters, huber, ...) -
+    # after every keyframe's last frontend update the rigid motion of every segment between consecutive keyframes is solved from the
+    # graph's full flow (pvo_object_motion) and kept per (tstamp_i, tstamp_j, label); get_object_tracks().  Read only: the trajectory
+    # and the depths are bit for bit those of a run without it.  None (default): nothing is imported, allocated or launched.
     a.update(over)
     return Namespace(**a)
 
@@ -88,6 +93,11 @@ class Droid:
             kw = dict(args.live_map)
             kw.setdefault("lag", args.frontend_window)
             self.live_map = LiveMap(self.video, **kw)
+
+        om = getattr(args, "object_motion", None)
+        if om:
+            from .object_motion import ObjectTracks
+            self.frontend.object_tracks = ObjectTracks(self.video, **(dict(om) if isinstance(om, dict) else {}))
 
     def load_weights(self, weights, use_aff_bri=False):
         """droid.py:55-62; DataParallel's "module." prefix is stripped"""
@@ -205,6 +215,16 @@ class Droid:
         that follows the keyframes while they move is args.live_map / get_live_map()."""
         self.flush()
         return self.video.tsdf(**kw)
+
+    def get_object_tracks(self):
+        """{label: [entry, ...]} in time order, an entry per pair of consecutive keyframes on which the segment had enough pixels: dict
+        tstamp_i, tstamp_j, label, motion [7] (the segment's rigid motion in the world frame between the two keyframes, the identity
+        for a static one), centroid [3] (its points' mean in the world at time i), count, status (0 = solved), E.  Needs
+        args.object_motion."""
+        if self.frontend.object_tracks is None:
+            raise RuntimeError("get_object_tracks() needs args.object_motion (True, or a dict of ObjectTracks' arguments)")
+        self.flush()
+        return self.frontend.object_tracks.tracks()
 
     def get_live_map(self):
         """the volume args.live_map keeps current and its mesh as it stands: LiveMap.as_volume() (tsdf, wsum, rgb with images, origin,

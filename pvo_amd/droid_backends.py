@@ -1179,6 +1179,96 @@ def tsdf_sparse_track(vol, poses, disps, intrinsics, ix, weight=None, iters=10, 
     return out
 
 
+def object_motion(poses, disps, intrinsics, labels, ii, jj, target, job_edge, job_label, weight=None, start=None, iters=8, z_min=0.25,
+                  huber=0.0, lm=1e-4, ep=1e-6, min_count=16, system=False, centroid=False, residual=False, jac=False, out=None):
+    """Per-instance rigid motion from point correspondences (include/pvo_hip.h pvo_object_motion): per job n - the edge job_edge[n]
+    (int64 [N], into ii / jj int64 [E]) and the label job_label[n] (int32 [N]) - the A in SE(3) that takes the points of frame
+    i = ii[e] with that label (labels int32 [nframes,ht,wd], disps [nframes,ht,wd] inverse depth, intrinsics [4] for ht x wd) from
+    camera i at time i to camera j at time j, so that they project onto target [E,ht,wd,2] (ABSOLUTE pixel coordinates in frame j, the
+    object's motion included: the factor graph's coords0 + full_flow), weighted by weight [E,ht,wd] or None.  `iters` Gauss-Newton
+    steps from start [N,7] (None: G_j G_i^-1 of poses [nframes,7], the object at rest); pixels with depth beyond z_min in camera j
+    contribute; huber > 0 bounds a pixel's pull (in pixels); lm, ep damp the 6 x 6 system; a job with fewer than min_count
+    contributing pixels keeps its A.  Returns a dict: rel f32 [N,7] (the final A), motion f32 [N,7] (G_j^-1 A G_i, the motion in the
+    world frame: the identity for a static segment), info f32 [N,iters+1,4] = (E, count, max|xi| of the step taken, status) per
+    evaluation (status 0 = stepped, 1 = too few pixels, 2 = factorisation failed, 4 = no such edge or frame), and on request system
+    f64 [N,27] (the undamped H's upper triangle and b of the last evaluation), centroid f32 [N,3] (the contributing points' mean in
+    the world at time i), residual f32 [N,ht,wd,2] (NaN where the pixel does not contribute) and jac f32 [N,ht,wd,2,6].
+    The defaults iters = 8, z_min = 0.25, huber = 0, lm = 1e-4, ep = 1e-6 and min_count = 16 rest on nothing measured on real
+    sequences: they are the values the analytic test scene was checked with.
+    Shapes, dtypes, devices and contiguity are checked here (ValueError).
+    out=: caller-owned buffers (rel, motion and info, and any of system / centroid / residual / jac: a buffer given is written whether
+    or not its flag is set, a flag set without its buffer raises; out["rel"] may be `start` itself) - then no allocation beyond the
+    cached workspace, no synchronisation, capturable."""
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    named = (("poses", poses, f32), ("disps", disps, f32), ("intrinsics", intrinsics, f32), ("labels", labels, i32), ("ii", ii, i64),
+             ("jj", jj, i64), ("target", target, f32), ("job_edge", job_edge, i64), ("job_label", job_label, i32),
+             ("weight", weight, f32), ("start", start, f32))
+    dev = None
+    for name, t, dt in named:
+        if t is None:
+            if name in ("weight", "start"):
+                continue
+            raise ValueError("object_motion: %s is required" % name)
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError("object_motion: %s must be a device tensor (there is no CPU fallback)" % name)
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise ValueError("object_motion: %s must be on %s" % (name, dev))
+        if t.dtype != dt:
+            raise ValueError("object_motion: %s must be %s" % (name, dt))
+        if not t.is_contiguous():
+            raise ValueError("object_motion: %s must be contiguous" % name)
+    if disps.dim() != 3 or labels.shape != disps.shape or poses.shape != (disps.shape[0], 7) or intrinsics.numel() < 4:
+        raise ValueError("object_motion: disps and labels must be [nframes,ht,wd], poses [nframes,7] and intrinsics [4]")
+    nf, ht, wd = disps.shape
+    if ii.dim() != 1 or jj.shape != ii.shape or tuple(target.shape) != (ii.shape[0], ht, wd, 2):
+        raise ValueError("object_motion: ii and jj must be [E] and target [E,ht,wd,2]")
+    E = ii.shape[0]
+    if weight is not None and tuple(weight.shape) != (E, ht, wd):
+        raise ValueError("object_motion: weight must be [E,ht,wd]")
+    if job_edge.dim() != 1 or job_label.shape != job_edge.shape:
+        raise ValueError("object_motion: job_edge and job_label must be [N]")
+    N = job_edge.shape[0]
+    if start is not None and tuple(start.shape) != (N, 7):
+        raise ValueError("object_motion: start must be [N,7] (one per job)")
+    iters = int(iters)
+    if not 0 <= iters <= _lib.OBJECT_MOTION_MAX_ITERS:
+        raise ValueError("object_motion: iters must lie in [0, %d]" % _lib.OBJECT_MOTION_MAX_ITERS)
+    want = {"rel": ((N, 7), f32), "motion": ((N, 7), f32), "info": ((N, iters + 1, 4), f32)}
+    optional = {"system": ((N, 27), torch.float64), "centroid": ((N, 3), f32), "residual": ((N, ht, wd, 2), f32),
+                "jac": ((N, ht, wd, 2, 6), f32)}
+    for k, on in (("system", system), ("centroid", centroid), ("residual", residual), ("jac", jac)):
+        if on:
+            want[k] = optional[k]
+    if out is None:
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in want.items()}
+    else:
+        known = dict(want, **optional)
+        for k, t in out.items():
+            if k not in known:
+                raise ValueError("object_motion: out has no use for %r" % (k,))
+            shape, dt = known[k]
+            if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                raise ValueError("object_motion: out[%r] must be a contiguous %s %s on %s" % (k, dt, list(shape), dev))
+        missing = [k for k in want if k not in out]
+        if missing:
+            raise ValueError("object_motion: out lacks %s (rel, motion and info always, the others when asked for)" % ", ".join(missing))
+    a = _lib.ObjectMotionArgs()
+    a.poses, a.disps, a.intrinsics, a.labels = _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(labels)
+    a.ii, a.jj, a.target, a.weight = _ptr(ii), _ptr(jj), _ptr(target), _ptr(weight)
+    a.job_edge, a.job_label, a.start = _ptr(job_edge), _ptr(job_label), _ptr(start)
+    a.N, a.E, a.nframes, a.ht, a.wd = N, E, nf, ht, wd
+    a.iters, a.min_count = iters, int(min_count)
+    a.z_min, a.huber, a.lm, a.ep = float(z_min), float(huber), float(lm), float(ep)
+    a.rel, a.motion, a.info = _ptr(out["rel"]), _ptr(out["motion"]), _ptr(out["info"])
+    a.system, a.centroid, a.residual, a.jac = _ptr(out.get("system")), _ptr(out.get("centroid")), _ptr(out.get("residual")), _ptr(out.get("jac"))
+    lib = _lib.load()
+    ws = _workspace(dev, lib.pvo_object_motion_workspace_bytes(N, ht, wd))
+    with torch.cuda.device(dev):
+        check(lib.pvo_object_motion(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "object_motion")
+    return out
+
+
 def _baseline(baseline, what):
     """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
     b = float(baseline)

@@ -1023,6 +1023,16 @@ class FactorGraph:
         return self.video.uncertainty(*ops, lm=1e-4, ep=0.1)
 
     @torch.no_grad()
+    def object_motion(self, edges=None, min_pixels=64, dynamic_share=None, **kw):
+        """per-instance rigid motion on the graph's edges from the last update's full flow (pvo_object_motion): the targets are
+        coords0 + full_flow, the labels video.segms_raw when the video stores them, else video.segms[:, 0]; one job per (edge, label
+        of frame ii[e]) with at least min_pixels pixels; with dynamic_share only segments whose share of dynamic pixels
+        (sigmoid(raw_mask) < dy_thresh) reaches it.  pvo_amd.object_motion.graph_object_motion: read only, an export step (it
+        synchronises once for the job list).  Returns droid_backends.object_motion's dict plus job_edge, job_label, ii, jj."""
+        from .object_motion import graph_object_motion
+        return graph_object_motion(self, edges=edges, min_pixels=min_pixels, dynamic_share=dynamic_share, **kw)
+
+    @torch.no_grad()
     def calibrate(self, t0=None, t1=None, use_inactive=False, itrs=2, lm=1e-4, ep=0.1, ep_c=0.1, free="all", sharded=None):
         """online intrinsics calibration on the operands `uncertainty` reconstructs - the last update's `target_cam`, `weight`, eta rows
         and t0 / t1 rule: DepthVideo.ba_calib (`itrs` calibrating Gauss-Newton steps; poses, depths and the video's intrinsics are

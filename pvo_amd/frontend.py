@@ -13,6 +13,10 @@ from .factor_graph import FactorGraph
 
 
 class DroidFrontend:
+    # a pvo_amd.object_motion.ObjectTracks (Droid's args.object_motion): after a keyframe's LAST graph update the rigid motion of every
+    # segment between consecutive keyframes (read only).  None: nothing is imported, allocated or launched.
+    object_tracks = None
+
     def __init__(self, update_op, video, device="cuda:0", warmup=8, beta=0.3, frontend_nms=1, keyframe_thresh=4.0,
                  frontend_window=25, frontend_thresh=16.0, frontend_radius=2, max_factors=48, upsample=False, uncertainty=False,
                  opt_intr=False, opt_intr_free="all"):
@@ -86,6 +90,8 @@ class DroidFrontend:
             dist = self._dist.item()
         drop = self.keyframe_decision(self.count, dist) if self.keyframe_decision is not None else dist < self.keyframe_thresh
         if drop:
+            if self.object_tracks is not None:
+                self.object_tracks.remove(self.video.tstamp[self.t1 - 2].item())
             self.graph.rm_keyframe(self.t1 - 2)
             self.video.counter -= 1
             self.t1 -= 1
@@ -97,6 +103,8 @@ class DroidFrontend:
                 self.graph.calibrate(None, None, use_inactive=True, free=self.opt_intr_free)
             if getattr(self, "uncertainty", False):
                 self.graph.uncertainty(None, None, use_inactive=True)
+            if self.object_tracks is not None:
+                self.object_tracks.observe(self.graph)
         self.video.poses[self.t1] = self.video.poses[self.t1 - 1]
         self.video.disps[self.t1] = self.video.disps[self.t1 - 1].mean()
         self.video.dirty[min(self.graph._ii_h):self.t1] = True
@@ -114,6 +122,8 @@ class DroidFrontend:
             self.graph.calibrate(1, use_inactive=True, free=self.opt_intr_free)
         if getattr(self, "uncertainty", False):
             self.graph.uncertainty(1, use_inactive=True)
+        if self.object_tracks is not None:
+            self.object_tracks.observe(self.graph)
         self.video.poses[self.t1] = self.video.poses[self.t1 - 1].clone()
         self.video.disps[self.t1] = self.video.disps[self.t1 - 4:self.t1].mean()
         self.is_initialized = True
