@@ -98,7 +98,8 @@ const char* pvo_last_hip_error(void);
  * new structs pvo_tsdf_reintegrate_args / pvo_tsdf_sparse_reintegrate_args (with *_args_size()) and new entry points
  * pvo_tsdf_reintegrate[_workspace_bytes] / pvo_tsdf_sparse_reintegrate[_workspace_bytes]; still 106, object motion: no existing
  * struct changed - new struct pvo_object_motion_args (with pvo_object_motion_args_size()) and new entry points
- * pvo_object_motion[_workspace_bytes]): a caller
+ * pvo_object_motion[_workspace_bytes]; still 106, segment association: no existing struct changed - new struct
+ * pvo_segment_assoc_args (with pvo_segment_assoc_args_size()) and new entry point pvo_segment_associate): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -1408,6 +1409,66 @@ typedef struct pvo_object_motion_args {
 size_t pvo_object_motion_args_size(void);
 size_t pvo_object_motion_workspace_bytes(int N, int ht, int wd);
 int pvo_object_motion(const pvo_object_motion_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Segment association: the segments of frame i matched to those of frame j   */
+/* ------------------------------------------------------------------------- */
+
+/* pvo_segment_associate: per EDGE i -> j the segments of frame i carried along the flow into frame j, the contingency table of
+ * (label in i, label in j) and the mutual best match by intersection over union (no counterpart in the reference, whose ids come
+ * consistent from its video-panoptic module).  Device pointers, dense, at 1/8 resolution.  Every quantity is an integer or an exactly
+ * stated fp32 operation: the same operands give the same bytes, on any implementation.
+ *
+ *   Frames: labels int32 [nframes,ht,wd], dense per-frame labels in [0, S), 0 = no segment; a label outside [0, S) counts as 0.
+ *   cls int32 [nframes,S] or NULL: a class per (frame, label); segments of different class never match.
+ *   Edges: ii, jj int64 [E];  target f32 [E,ht,wd,2]: the ABSOLUTE pixel coordinates (x, y) in frame jj[e] of the point seen at the
+ *   pixel of frame ii[e] (from the factor graph: coords0 + full_flow);  valid uint8 [E,ht,wd] or NULL (= all): nonzero = the pixel counts.
+ *   Parameters: 1 <= S <= PVO_SEGMENT_ASSOC_MAX_S; min_iou finite and >= 0; form 0 (1, with S <= 128: the counting kernel keeps its
+ *   table in LDS - the same bytes, and on the window measured never the faster form: kept for measurements).
+ *   Outputs, all written for every edge (a caller never clears them; the first three are cleared by the call, on the stream):
+ *     overlap  int32 [E,S,S]    overlap[e,a,b] = the counted pixels of edge e with label a in frame i that land on label b in frame j,
+ *                               a = 0 and b = 0 included
+ *     area_i   int32 [E,S]      the counted pixels with source label a (the table's row sums)
+ *     area_j   int32 [E,S]      the pixels of the WHOLE frame jj[e] with label b, whatever landed there
+ *     match    int32 [E,S]      the b matched to a, or -1; match[e,0] = -1
+ *     match_n, match_d int32 [E,S]   n and d of the matched pair, 0 where there is none
+ *
+ * A source pixel p of edge e is COUNTED iff valid is NULL or nonzero at p, both target components (tx, ty) are finite, and with
+ * rx = floorf(tx + 0.5f), ry = floorf(ty + 0.5f) in fp32:  0 <= rx <= wd - 1 and 0 <= ry <= ht - 1, compared as floats before any
+ * conversion (a NaN, an infinity or 1e30 is dropped, never converted).  Then a = labels[ii[e], p], b = labels[jj[e], ry, rx].
+ * For a, b >= 1 with n = overlap[e,a,b] > 0 the IoU is the FRACTION n / d, d = area_i[e,a] + area_j[e,b] - n; fractions are compared
+ * by n1 d2 against n2 d1 in int64, never in floating point.  best_j(a): the b >= 1 of largest IoU, ties to the lowest b; best_i(b): the
+ * a >= 1 of largest IoU, ties to the lowest a; pairs with cls[ii[e],a] != cls[jj[e],b] take part in neither.
+ * match[e,a] = b iff b = best_j(a) exists, best_i(b) == a and (double)n >= (double)min_iou * (double)d (exact: n, d < 2^24).
+ * An edge whose ii or jj lies outside [0, nframes): nothing of it is dereferenced (checked in the kernels: the indices are device
+ * data); its tables are 0 and its matches -1.  A frame with no segments gives the same.
+ *
+ * Three launches: the clear; the counting kernel - workgroups of 256 over (edge, pixel chunk), the grid sized per edge, one atomic
+ * per (wave, distinct pair) into global memory (form 1: the S x S table in LDS, its nonzero cells handed in with one atomic each),
+ * area_j from frame jj[e]'s own pixels (once per edge); one workgroup per edge for the maxima and the mutual test.  Integer atomics only: the result does not depend
+ * on their order.  No workspace, no allocation, no host synchronisation: capturable.
+ * Limits (PVO_EINVAL): a NULL a; a negative E, nframes, ht or wd; ht*wd >= 2^24; S or min_iou or form outside its range, form 1 with S > 128; then, unless
+ * E == 0 (PVO_OK, nothing written): a NULL ii / jj / output, a NULL target with ht*wd > 0, a NULL labels with ht*wd > 0 and nframes > 0. */
+#define PVO_SEGMENT_ASSOC_MAX_S 1024
+typedef struct pvo_segment_assoc_args {
+  const int32_t* labels;
+  const int64_t* ii;
+  const int64_t* jj;
+  const float* target;
+  const uint8_t* valid;
+  const int32_t* cls;
+  int E, nframes, ht, wd, S;
+  float min_iou;
+  int form;
+  int* overlap;
+  int* area_i;
+  int* area_j;
+  int* match;
+  int* match_n;
+  int* match_d;
+} pvo_segment_assoc_args;
+size_t pvo_segment_assoc_args_size(void);
+int pvo_segment_associate(const pvo_segment_assoc_args* a, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

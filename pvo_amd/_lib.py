@@ -155,6 +155,8 @@ SIGNATURES = {
     "pvo_object_motion_args_size": (_sz, []),
     "pvo_object_motion_workspace_bytes": (_sz, [_i, _i, _i]),
     "pvo_object_motion": (_i, [_vp, _vp, _sz, _vp]),
+    "pvo_segment_assoc_args_size": (_sz, []),
+    "pvo_segment_associate": (_i, [_vp, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -340,6 +342,16 @@ class ObjectMotionArgs(_c.Structure):
                 ("rel", _vp), ("motion", _vp), ("info", _vp), ("system", _vp), ("centroid", _vp), ("residual", _vp), ("jac", _vp)]
 
 
+SEGMENT_ASSOC_MAX_S = 1024                 # PVO_SEGMENT_ASSOC_MAX_S
+
+
+class SegmentAssocArgs(_c.Structure):
+    """pvo_segment_assoc_args"""
+    _fields_ = [("labels", _vp), ("ii", _vp), ("jj", _vp), ("target", _vp), ("valid", _vp), ("cls", _vp),
+                ("E", _i), ("nframes", _i), ("ht", _i), ("wd", _i), ("S", _i), ("min_iou", _f), ("form", _i),
+                ("overlap", _vp), ("area_i", _vp), ("area_j", _vp), ("match", _vp), ("match_n", _vp), ("match_d", _vp)]
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 PVO_KNOB_EDGE_BLOCKS = 4        # 0 shipped | 1 off | 2 + bits (third, low, agg, trunk): 2 ... 17
@@ -385,7 +397,7 @@ def load():
                        (lib.pvo_tsdf_track_args_size, TsdfTrackArgs), (lib.pvo_tsdf_sparse_track_args_size, TsdfSparseTrackArgs),
                        (lib.pvo_tsdf_reintegrate_args_size, TsdfReintegrateArgs),
                        (lib.pvo_tsdf_sparse_reintegrate_args_size, TsdfSparseReintegrateArgs),
-                       (lib.pvo_object_motion_args_size, ObjectMotionArgs)):
+                       (lib.pvo_object_motion_args_size, ObjectMotionArgs), (lib.pvo_segment_assoc_args_size, SegmentAssocArgs)):
         if fn() != ctypes.sizeof(struct):
             raise PvoHipError("libpvo_hip.so has a %d-byte %s; this binding is written for %d bytes - rebuild with "
                               "`python -m pvo_amd.build`" % (fn(), struct.__doc__, ctypes.sizeof(struct)))

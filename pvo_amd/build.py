@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "tsdf_track.hip",
     "tsdf_reintegrate.hip",
     "object_motion.hip",
+    "segment_assoc.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",

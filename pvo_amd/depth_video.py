@@ -662,7 +662,8 @@ class DepthVideo:
         return origin, (g[2], g[1], g[0])
 
     def tsdf(self, voxel, trunc=None, ix=None, thresh=0.005, full_res=False, reject=None, use_sigma=False, origin=None, dims=None,
-             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05, sparse=False, margin=2, panoptic=False, keep_rgb=False):
+             min_weight=1.0, w_max=0, max_rel_sigma=None, rel0=0.05, sparse=False, margin=2, panoptic=False, keep_rgb=False,
+             labels=None):
         """the fused surface of keyframes ix (default: all stored ones; a one-off fusion of the video as it stands - a volume that
         follows keyframes which move later is pvo_amd.live_map.LiveMap): a TSDF volume of `voxel`-sized cells, truncation `trunc` (default 3 voxels), integrated natively
         (pvo_tsdf_integrate) from exactly the pixels map_points(ix, thresh, full_res, reject, max_rel_sigma) keeps, and its surface-nets
@@ -677,13 +678,22 @@ class DepthVideo:
         panoptic=True (a video made with store_segment_ids, ValueError otherwise): the frames' raw segment ids segms_raw[:n] are fused
         by a weighted vote per voxel (pvo_tsdf_integrate_panoptic; ids <= 0 = no segment) and every vertex gets the id of its cell's
         nearest labelled corner: the dict gains vlabel int32 [V] and the volumes label, lconf (sparse: the SparseTSDF holds them).
+        labels (with panoptic=True): an int32 [counter,h/8,w/8] label tensor fused in place of segms_raw[:n] - e.g.
+        pvo_amd.segment_tracks.SegmentTracks.track_map(), ids that stay the same across keyframes; then store_segment_ids is not needed.
         keep_rgb=True (dense, a video with images): the dict also keeps the colour volume rgb [nz,ny,nx,3], so that tsdf_render
         can colour its images (the SparseTSDF holds its own)."""
         trunc = 3.0 * float(voxel) if trunc is None else float(trunc)
         n = self.counter
-        if panoptic and self.segms_raw is None:
+        if panoptic and labels is None and self.segms_raw is None:
             raise ValueError("tsdf(panoptic=True) needs the raw segment ids: make the video with store_segment_ids=True")
-        labels = self.segms_raw[:n] if panoptic else None
+        if labels is not None:
+            if not panoptic:
+                raise ValueError("tsdf(labels=...) goes with panoptic=True")
+            if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != tuple(self.disps[:n].shape):
+                raise ValueError("tsdf(labels=...) must be an int32 tensor of shape %s" % (list(self.disps[:n].shape),))
+            labels = labels.to(self.device).contiguous()
+        else:
+            labels = self.segms_raw[:n] if panoptic else None
         m = self.map_points(ix=ix, thresh=thresh, full_res=full_res, reject=reject, max_rel_sigma=max_rel_sigma)
         if full_res:
             disps, intr, stride, offset, div = self.disps_up[:n], 8.0 * self.intrinsics[0], 1, 0, 8

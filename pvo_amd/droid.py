@@ -26,7 +26,7 @@ def default_args(**over):
              frontend_radius=2, frontend_nms=1, backend_thresh=15.0, backend_radius=2, backend_nms=3,
              segm_filter=False, thresh=0.8, half_update=True, pipelined=False, rgbd=False, stereo=False, stereo_baseline=0.1,
              store_images=False, uncertainty=False, opt_intr=False, opt_intr_free="all", store_segment_ids=False, live_map=None,
-             object_motion=None)
+             object_motion=None, segment_tracks=None)
     # uncertainty: after every keyframe's last frontend update, estimate the window's inverse-depth variances and pose covariance from
     # the bundle adjustment's normal equations (DepthVideo.uncertainty; get_uncertainty(), get_map(max_rel_sigma=...)).  Read only: the
     # trajectory and the depths are bit for bit those of a run without it.  A window of more than 64 poses (frontend_window above 64) is
@@ -53,6 +53,11 @@ def default_args(**over):
     # after every keyframe's last frontend update the rigid motion of every segment between consecutive keyframes is solved from the
     # graph's full flow (pvo_object_motion) and kept per (tstamp_i, tstamp_j, label); get_object_tracks().  Read only: the trajectory
     # and the depths are bit for bit those of a run without it.  None (default): nothing is imported, allocated or launched.
+    # segment_tracks: True, or a dict of pvo_amd.segment_tracks.SegmentTracks' keyword arguments (min_iou, cls_div); needs store_segment_ids -
+    # after every keyframe's last frontend update the keyframes' segments are associated along the graph's full flow
+    # (pvo_segment_associate) and every (tstamp, raw id) gets a track id that stays the same across keyframes; get_segment_tracks(),
+    # get_mesh(panoptic=True, track_ids=True), get_object_tracks(by_track=True).  Read only: the trajectory and the depths are bit for
+    # bit those of a run without it.  None (default): nothing is imported, allocated or launched.
     a.update(over)
     return Namespace(**a)
 
@@ -68,6 +73,8 @@ class Droid:
         if getattr(args, "live_map", None) is not None and getattr(args, "pipelined", False):
             raise ValueError("args.live_map together with args.pipelined is not supported: between two pipelined track() calls a keyframe "
                              "update is half done, and the live map would fuse it as it stands")
+        if getattr(args, "segment_tracks", None) and not getattr(args, "store_segment_ids", False):
+            raise ValueError("args.segment_tracks needs the raw segment ids: set args.store_segment_ids = True")
         self.load_weights(args.weights, args.use_aff_bri)
         self.video = DepthVideo(args.image_size, args.buffer, args.device, args.segm_filter, args.thresh,
                                 store_images=bool(getattr(args, "store_images", False)),
@@ -98,6 +105,12 @@ class Droid:
         if om:
             from .object_motion import ObjectTracks
             self.frontend.object_tracks = ObjectTracks(self.video, **(dict(om) if isinstance(om, dict) else {}))
+
+        self.segment_tracks = None
+        st = getattr(args, "segment_tracks", None)
+        if st:
+            from .segment_tracks import SegmentTracks
+            self.segment_tracks = self.frontend.segment_tracks = SegmentTracks(self.video, **(dict(st) if isinstance(st, dict) else {}))
 
     def load_weights(self, weights, use_aff_bri=False):
         """droid.py:55-62; DataParallel's "module." prefix is stripped"""
@@ -212,19 +225,44 @@ class Droid:
         faces [F,3] and the volume tsdf, wsum [nz,ny,nx], origin, voxel.  sparse=True (with margin=2): a brick volume in place of the dense
         one, returned as `volume` (DepthVideo.tsdf).  panoptic=True (args.store_segment_ids): the keyframes' segment ids fused into the volume
         as well - vlabel [V], one id per vertex, and the volumes label, lconf.  A one-off fusion of the video as it stands: a volume
-        that follows the keyframes while they move is args.live_map / get_live_map()."""
+        that follows the keyframes while they move is args.live_map / get_live_map().  track_ids=True (with panoptic=True, needs
+        args.segment_tracks): the ledger's track ids are fused in place of the ids as given (SegmentTracks.track_map), so that an
+        object numbered anew in every keyframe still gets one label."""
         self.flush()
+        if kw.pop("track_ids", False):
+            if self.segment_tracks is None:
+                raise RuntimeError("get_mesh(track_ids=True) needs args.segment_tracks (True, or a dict of SegmentTracks' arguments)")
+            kw["labels"] = self.segment_tracks.track_map(self.video)
         return self.video.tsdf(**kw)
 
-    def get_object_tracks(self):
+    def get_object_tracks(self, by_track=False):
         """{label: [entry, ...]} in time order, an entry per pair of consecutive keyframes on which the segment had enough pixels: dict
         tstamp_i, tstamp_j, label, motion [7] (the segment's rigid motion in the world frame between the two keyframes, the identity
         for a static one), centroid [3] (its points' mean in the world at time i), count, status (0 = solved), E.  Needs
-        args.object_motion."""
+        args.object_motion.  by_track=True (needs args.segment_tracks too): keyed by the track id of (tstamp_i, label) in place of the
+        label, each entry with its `track`; entries whose segment has no track are left out."""
         if self.frontend.object_tracks is None:
             raise RuntimeError("get_object_tracks() needs args.object_motion (True, or a dict of ObjectTracks' arguments)")
         self.flush()
-        return self.frontend.object_tracks.tracks()
+        tracks = self.frontend.object_tracks.tracks()
+        if not by_track:
+            return tracks
+        if self.segment_tracks is None:
+            raise RuntimeError("get_object_tracks(by_track=True) needs args.segment_tracks (True, or a dict of SegmentTracks' arguments)")
+        out = {}
+        for entry in sorted((e for es in tracks.values() for e in es), key=lambda e: (e["tstamp_i"], e["tstamp_j"], e["label"])):
+            track = self.segment_tracks.entries.get((entry["tstamp_i"], entry["label"]))
+            if track is not None:
+                out.setdefault(track, []).append(dict(entry, track=track))
+        return out
+
+    def get_segment_tracks(self):
+        """[(tstamp, raw id, track id), ...] in time order: the track id of every segment of every keyframe, the same for the same object
+        across keyframes as far as the flow carried it onto itself (pvo_amd.segment_tracks.SegmentTracks).  Needs args.segment_tracks."""
+        if self.segment_tracks is None:
+            raise RuntimeError("get_segment_tracks() needs args.segment_tracks (True, or a dict of SegmentTracks' arguments)")
+        self.flush()
+        return self.segment_tracks.table()
 
     def get_live_map(self):
         """the volume args.live_map keeps current and its mesh as it stands: LiveMap.as_volume() (tsdf, wsum, rgb with images, origin,

@@ -1269,6 +1269,72 @@ def object_motion(poses, disps, intrinsics, labels, ii, jj, target, job_edge, jo
     return out
 
 
+def segment_associate(labels, ii, jj, target, S, valid=None, cls=None, min_iou=0.25, out=None, form=0):
+    """Segments associated across keyframes (include/pvo_hip.h pvo_segment_associate): per edge e the segments of frame ii[e] (labels
+    int32 [nframes,ht,wd], dense in [0, S), 0 = no segment) carried to target [E,ht,wd,2] (ABSOLUTE (x, y) in frame jj[e]: the factor
+    graph's coords0 + full_flow, rounded to the nearest pixel; a pixel that leaves the frame or is not finite is dropped), counted
+    against frame jj[e]'s labels and matched by mutual best IoU.  valid uint8 [E,ht,wd] or None: only nonzero pixels count; cls int32
+    [nframes,S] or None: segments of different class never match; min_iou: the least IoU of a match.  ii, jj int64 [E].
+    Returns a dict of int32 tensors: overlap [E,S,S], area_i [E,S] (counted pixels per source label), area_j [E,S] (frame jj[e]'s
+    pixels per label), match [E,S] (the label of frame jj[e] matched to a, or -1), match_n, match_d [E,S] (the matched pair's IoU as
+    the fraction n / d; 0 without a match).  Integers throughout: the same operands give the same bytes.
+    Shapes, dtypes, devices and contiguity are checked here (ValueError).  out=: caller-owned buffers for all six - then no allocation,
+    no synchronisation, capturable.  form=1 (S <= 128): the counting kernel keeps its table in LDS (measurements; the same bytes)."""
+    i32, i64 = torch.int32, torch.int64
+    named = (("labels", labels, i32), ("ii", ii, i64), ("jj", jj, i64), ("target", target, torch.float32), ("valid", valid, torch.uint8),
+             ("cls", cls, i32))
+    dev = None
+    for name, t, dt in named:
+        if t is None:
+            if name in ("valid", "cls"):
+                continue
+            raise ValueError("segment_associate: %s is required" % name)
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError("segment_associate: %s must be a device tensor (there is no CPU fallback)" % name)
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise ValueError("segment_associate: %s must be on %s" % (name, dev))
+        if t.dtype != dt:
+            raise ValueError("segment_associate: %s must be %s" % (name, dt))
+        if not t.is_contiguous():
+            raise ValueError("segment_associate: %s must be contiguous" % name)
+    if labels.dim() != 3:
+        raise ValueError("segment_associate: labels must be [nframes,ht,wd]")
+    nf, ht, wd = labels.shape
+    if ht * wd >= 1 << 24:
+        raise ValueError("segment_associate: ht * wd must stay below 2^24 (the IoU threshold is exact up to there)")
+    if ii.dim() != 1 or jj.shape != ii.shape or tuple(target.shape) != (ii.shape[0], ht, wd, 2):
+        raise ValueError("segment_associate: ii and jj must be [E] and target [E,ht,wd,2]")
+    E, S = ii.shape[0], int(S)
+    if not 1 <= S <= _lib.SEGMENT_ASSOC_MAX_S:
+        raise ValueError("segment_associate: S must lie in [1, %d]" % _lib.SEGMENT_ASSOC_MAX_S)
+    if valid is not None and tuple(valid.shape) != (E, ht, wd):
+        raise ValueError("segment_associate: valid must be [E,ht,wd]")
+    if cls is not None and tuple(cls.shape) != (nf, S):
+        raise ValueError("segment_associate: cls must be [nframes,S]")
+    min_iou = float(min_iou)
+    if not (min_iou >= 0.0 and min_iou != float("inf")):
+        raise ValueError("segment_associate: min_iou must be finite and >= 0")
+    want = {"overlap": (E, S, S), "area_i": (E, S), "area_j": (E, S), "match": (E, S), "match_n": (E, S), "match_d": (E, S)}
+    if out is None:
+        out = {k: torch.empty(shape, dtype=i32, device=dev) for k, shape in want.items()}
+    else:
+        if set(out) != set(want):
+            raise ValueError("segment_associate: out must hold exactly %s" % ", ".join(want))
+        for k, shape in want.items():
+            t = out[k]
+            if not torch.is_tensor(t) or t.dtype != i32 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                raise ValueError("segment_associate: out[%r] must be a contiguous int32 %s on %s" % (k, list(shape), dev))
+    a = _lib.SegmentAssocArgs()
+    a.labels, a.ii, a.jj, a.target, a.valid, a.cls = _ptr(labels), _ptr(ii), _ptr(jj), _ptr(target), _ptr(valid), _ptr(cls)
+    a.E, a.nframes, a.ht, a.wd, a.S, a.min_iou, a.form = E, nf, ht, wd, S, min_iou, int(form)
+    a.overlap, a.area_i, a.area_j = _ptr(out["overlap"]), _ptr(out["area_i"]), _ptr(out["area_j"])
+    a.match, a.match_n, a.match_d = _ptr(out["match"]), _ptr(out["match_n"]), _ptr(out["match_d"])
+    with torch.cuda.device(dev):
+        check(_lib.load().pvo_segment_associate(ctypes.byref(a), _stream(dev)), "segment_associate")
+    return out
+
+
 def _baseline(baseline, what):
     """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
     b = float(baseline)

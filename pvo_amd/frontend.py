@@ -16,6 +16,9 @@ class DroidFrontend:
     # a pvo_amd.object_motion.ObjectTracks (Droid's args.object_motion): after a keyframe's LAST graph update the rigid motion of every
     # segment between consecutive keyframes (read only).  None: nothing is imported, allocated or launched.
     object_tracks = None
+    # a pvo_amd.segment_tracks.SegmentTracks (Droid's args.segment_tracks): after a keyframe's LAST graph update the keyframes' segments
+    # associated along the graph's edges (read only).  None: nothing is imported, allocated or launched.
+    segment_tracks = None
 
     def __init__(self, update_op, video, device="cuda:0", warmup=8, beta=0.3, frontend_nms=1, keyframe_thresh=4.0,
                  frontend_window=25, frontend_thresh=16.0, frontend_radius=2, max_factors=48, upsample=False, uncertainty=False,
@@ -92,6 +95,8 @@ class DroidFrontend:
         if drop:
             if self.object_tracks is not None:
                 self.object_tracks.remove(self.video.tstamp[self.t1 - 2].item())
+            if self.segment_tracks is not None:
+                self.segment_tracks.remove(self.video.tstamp[self.t1 - 2].item())
             self.graph.rm_keyframe(self.t1 - 2)
             self.video.counter -= 1
             self.t1 -= 1
@@ -105,6 +110,8 @@ class DroidFrontend:
                 self.graph.uncertainty(None, None, use_inactive=True)
             if self.object_tracks is not None:
                 self.object_tracks.observe(self.graph)
+            if self.segment_tracks is not None:
+                self.segment_tracks.observe(self.graph)
         self.video.poses[self.t1] = self.video.poses[self.t1 - 1]
         self.video.disps[self.t1] = self.video.disps[self.t1 - 1].mean()
         self.video.dirty[min(self.graph._ii_h):self.t1] = True
@@ -124,6 +131,8 @@ class DroidFrontend:
             self.graph.uncertainty(1, use_inactive=True)
         if self.object_tracks is not None:
             self.object_tracks.observe(self.graph)
+        if self.segment_tracks is not None:
+            self.segment_tracks.observe(self.graph)
         self.video.poses[self.t1] = self.video.poses[self.t1 - 1].clone()
         self.video.disps[self.t1] = self.video.disps[self.t1 - 4:self.t1].mean()
         self.is_initialized = True

@@ -2,7 +2,7 @@
 
     python tools/export_map.py --datapath <.../SceneXX> --weights <checkpoint.pth> --map out.ply [--full_res] [--filter_thresh_map 0.005]
                                [--reconstruction_path DIR] [--uncertainty [--max_rel_sigma X]]
-                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight] [--sparse] [--panoptic [--instances_dir DIR]]
+                               [--mesh out.ply --voxel V [--trunc T] [--sigma_weight] [--sparse] [--panoptic [--track_ids] [--instances_dir DIR]]
                                 [--render_dir DIR]]
                                [--live_map out.ply --voxel V --origin X Y Z --dims NZ NY NX [--sparse]]
 
@@ -19,7 +19,9 @@ with vertex normals, colours and triangle faces; --sigma_weight (with --uncertai
 variance instead of counting all alike; --sparse fuses into a brick volume over the map's full extent (pvo_tsdf_sparse_*) where the
 dense volume is clipped to what fits; --panoptic keeps the frames' panoptic ids as given (args.store_segment_ids), fuses them into the
 volume by a weighted vote (pvo_tsdf_integrate_panoptic) and adds `property int label` to the mesh's vertices, and --instances_dir DIR
-also writes one mesh per id, DIR/segment_<id>.ply.  --render_dir DIR (with --mesh) also looks at the fused volume from every keyframe
+also writes one mesh per id, DIR/segment_<id>.ply; --track_ids (with --panoptic) tracks with args.segment_tracks - the keyframes' segments
+associated along the graph's flow (pvo_segment_associate) - and fuses the ledger's track ids in place of the ids as given, for ids that
+a per-image panoptic network numbers anew in every frame.  --render_dir DIR (with --mesh) also looks at the fused volume from every keyframe
 (Droid.get_renders: pvo_tsdf_render / pvo_tsdf_sparse_render, at the resolution the volume was fused from) and writes per keyframe k
 DIR/depth_%06d.npy (f32 [ht,wd], 0 = no surface), normal_%06d.npy (f32 [ht,wd,3]), rgba_%06d.npy (uint8 [ht,wd,4]) and, with
 --panoptic, label_%06d.npy (int32 [ht,wd]: ids that are consistent across keyframes); it prints how each keyframe's own depth
@@ -54,6 +56,7 @@ def parse_args(argv=None):
     p.add_argument("--sigma_weight", action="store_true", help="with --mesh and --uncertainty: weight pixels by their variance")
     p.add_argument("--sparse", action="store_true", help="with --mesh: a brick volume over the map's full extent")
     p.add_argument("--panoptic", action="store_true", help="with --mesh: fuse the frames' panoptic ids, write a label per vertex")
+    p.add_argument("--track_ids", action="store_true", help="with --panoptic: fuse track ids associated across keyframes, not the ids as given")
     p.add_argument("--instances_dir", default=None, help="with --panoptic: also one segment_<id>.ply per id into this folder")
     p.add_argument("--render_dir", default=None, help="with --mesh: also depth / normal / rgba (/ label) images of the fused volume per keyframe")
     p.add_argument("--live_map", default=None, help="also keep a live TSDF volume while tracking and write its mesh to this .ply")
@@ -75,6 +78,8 @@ def parse_args(argv=None):
         p.error("--live_map needs --voxel V with V > 0, --origin X Y Z and --dims NZ NY NX: the world box of a running session")
     if args.panoptic and args.mesh is None:
         p.error("--panoptic needs --mesh")
+    if args.track_ids and not args.panoptic:
+        p.error("--track_ids needs --panoptic")
     if args.instances_dir is not None and not args.panoptic:
         p.error("--instances_dir needs --panoptic")
     if args.render_dir is not None and args.mesh is None:
@@ -88,6 +93,8 @@ def write_mesh(droid, args):
     kw = {"sparse": True} if args.sparse else {}
     if args.panoptic:
         kw["panoptic"] = True
+    if getattr(args, "track_ids", False):
+        kw["track_ids"] = True
     render_dir = getattr(args, "render_dir", None)
     if render_dir is not None and not args.sparse:
         kw["keep_rgb"] = True                                # (the dense colour volume, for the renders; the mesh is the same)
@@ -158,6 +165,8 @@ def main(argv=None):
     args.half_update = True
     args.store_images = True
     args.store_segment_ids = bool(args.panoptic)
+    if args.track_ids:
+        args.segment_tracks = True
     args.upsample = bool(args.full_res)
     if args.datapath.endswith("20"):
         args.thresh = 0.9
