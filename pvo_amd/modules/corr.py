@@ -206,9 +206,25 @@ class CorrVolumePool:
         elif self.tiled:
             db.corr_build_tiled(fmap1.contiguous(), fmap2.contiguous(), self.levels, st)
         else:
-            db.corr_build(fmap1.contiguous(), fmap2.contiguous(), self.num_levels, channels_last=True, out=self.levels, out_slots=st)
+            f1, f2 = fmap1.contiguous(), fmap2.contiguous()
+            if self._matrix_core(f1, f2):
+                db.corr_build(f1, f2, self.num_levels, channels_last=True, out=self.levels, out_slots=st)
+            else:
+                # slot output is a feature of the matrix-core path (pvo_corr_build returns PVO_EUNSUPPORTED for it on the generic one):
+                # fp32 / fp64 pools and odd channel counts build the new edges' pyramid densely and copy it into their slots
+                pyr = db.corr_build(f1, f2, self.num_levels, channels_last=True)
+                idx = st.long()
+                for lv, p in zip(self.levels, pyr):
+                    if p.numel():
+                        lv.index_copy_(0, idx, p)
         self.slots += new
         self._slots_t = None
+
+    @staticmethod
+    def _matrix_core(f1, f2):
+        """whether pvo_corr_build serves these channels-last features on the matrix cores (include/pvo_hip.h)"""
+        return (f1.dtype in (torch.float16, torch.bfloat16) and f1.shape[-1] in (16, 32, 64, 128)
+                and f1.data_ptr() % 16 == 0 and f2.data_ptr() % 16 == 0)
 
     def _grow(self, need):
         """more edges than slots (the reference's pyramid simply grows, e.g. a long --warmup initialisation): move to
