@@ -14,15 +14,11 @@
 // No atomics: a pixel's output index is a function of the keep bits alone, so the same operands give the same bytes in the same
 // order.  Compiled without multiply-add contraction (pvo_amd/build.py), like geom.hip.
 #include "depth_vote.h"
+#include "scan.h"
 
 namespace {
 
 constexpr int kBlock = 256;          // (b), (d): one pixel per thread, four waves
-constexpr int kScanThreads = 1024;   // (c)
-
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mask), 0));
-}
 
 // a frame id outside [0, nframes) contributes no point and is never dereferenced
 __device__ __forceinline__ bool frame_ok(long long f, int nframes) { return f >= 0 && f < nframes; }
@@ -75,32 +71,19 @@ __global__ __launch_bounds__(kBlock) void map_classify_kernel(
   if (tid == 0) counts[b * gridDim.x + blockIdx.x] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
 }
 
-// exclusive scan of counts[0, M) into base[0, M), M = N * G, in index order: thread t owns the contiguous chunk
-// [t * chunk, (t+1) * chunk).  frame_start[b] = base[b * G], frame_start[N] = the total (not clamped by any capacity).
+// exclusive scan of counts[0, M) into base[0, M), M = N * G, in index order (scan.h).  frame_start[b] = base[b * G],
+// frame_start[N] = the total (not clamped by any capacity).
 __global__ __launch_bounds__(kScanThreads) void map_scan_kernel(const int* __restrict__ counts, int* __restrict__ base,
                                                                 int* __restrict__ frame_start, int M, int G) {
-  const int tid = threadIdx.x;
-  const int chunk = (M + kScanThreads - 1) / kScanThreads;
-  const int lo = min(tid * chunk, M), hi = min(lo + chunk, M);
-  int s = 0;
-  for (int i = lo; i < hi; ++i) s += counts[i];
-  __shared__ int buf[2][kScanThreads];
-  int cur = 0;
-  buf[0][tid] = s;
-  __syncthreads();
-#pragma unroll
-  for (int off = 1; off < kScanThreads; off <<= 1) {      // Hillis-Steele, inclusive
-    buf[cur ^ 1][tid] = buf[cur][tid] + (tid >= off ? buf[cur][tid - off] : 0);
-    cur ^= 1;
-    __syncthreads();
+  const int* const cnt[1] = {counts};
+  int run[1], total[1];
+  const ScanChunk c = scan_counts(cnt, M, run, total);
+  for (int i = c.lo; i < c.hi; ++i) {
+    base[i] = run[0];
+    if (i % G == 0) frame_start[i / G] = run[0];
+    run[0] += counts[i];
   }
-  int run = buf[cur][tid] - s;                             // exclusive prefix of this thread's chunk
-  for (int i = lo; i < hi; ++i) {
-    base[i] = run;
-    if (i % G == 0) frame_start[i / G] = run;
-    run += counts[i];
-  }
-  if (tid == kScanThreads - 1) frame_start[M / G] = buf[cur][tid];
+  if (threadIdx.x == 0) frame_start[M / G] = total[0];
 }
 
 struct EmitOut {

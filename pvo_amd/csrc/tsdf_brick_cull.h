@@ -1,12 +1,18 @@
 // tsdf_brick_cull.h — what the brick volume's integration (tsdf_sparse.hip) and re-integration (tsdf_reintegrate.hip) share beyond the
-// voxel arithmetic of tsdf_fuse.h: the per-slot constants with the cull's scalars, and the test of one slot against one brick.  Both
-// translation units launch the same kernel and call the same function, so a brick keeps or drops a frame identically in either.
+// voxel arithmetic of tsdf_fuse.h: the per-slot constants with the cull's scalars, the test of one slot against one brick, and the
+// chunked cull of a whole table that hands a brick its surviving slots in order (the frame loop of BrickWalk, the brick volume's walker for the kernels of tsdf_fuse.h).  Both
+// translation units launch the same kernel and call the same functions, so a brick keeps or drops a frame identically in either.
 #pragma once
+#include "scan.h"
 #include "tsdf_fuse.h"
+#include "tsdf_host.h"
 
 namespace {
 
 constexpr int kCullBlock = 256;       // threads of sparse_frames_kernel
+using tsdf_volume::kB;
+constexpr int kBrick = kB * kB * kB;  // 512 voxels, one workgroup
+static_assert(kB == 8 && kBrick == 512, "the index arithmetic of the brick kernels shifts by 3 and 6");
 
 // per slot: the dense call's constants [0..12]; [13] zfar = the largest 1/d over the frame's valid pixels (-inf without one: a max,
 // so the order of the reduction does not matter); [14] |origin|_1 + |t|_1; [15] |1 - n| + n, n = |q|^2: R(q) as the contract
@@ -79,5 +85,77 @@ __device__ __forceinline__ bool brick_sees_frame(const float* __restrict__ c, fl
   }
   return true;
 }
+
+// the slots [0, N) of the table fc against the brick, 512 at a time (one per thread of the brick's workgroup); the survivors, in slot
+// order, applied to the thread's voxel by `apply`.  list [512] and wave_n [8] are LDS.  Returns the number of survivors
+template <typename Apply>
+__device__ __forceinline__ int brick_cull_and_apply(const float* __restrict__ fc, int N, float ccx, float ccy, float ccz, float msum,
+                                                    float voxel, const Intr K, const Fuse in, int* list, int* wave_n, Apply apply) {
+  const int tid = threadIdx.x;
+  int survivors = 0;
+  for (int c0 = 0; c0 < N; c0 += kBrick) {
+    // stage 1: slot c0 + tid against the brick; the survivors in slot order
+    const int b = c0 + tid;
+    const bool keep = b < N && brick_sees_frame(fc + static_cast<long long>(kFrameFloats) * b, ccx, ccy, ccz, msum, voxel, K, in);
+    const unsigned long long m = __ballot(keep);
+    if ((tid & 63) == 0) wave_n[tid >> 6] = __popcll(m);
+    __syncthreads();
+    int pos = lanes_below(m), n = 0;
+#pragma unroll
+    for (int w = 0; w < kBrick / 64; ++w) {
+      if (w < (tid >> 6)) pos += wave_n[w];
+      n += wave_n[w];
+    }
+    if (keep) list[pos] = b;
+    survivors += n;
+    __syncthreads();
+    // stage 2: the dense walk's loop over the survivors
+    for (int k = 0; k < n; ++k) {
+      const int s = __builtin_amdgcn_readfirstlane(list[k]);
+      const float* __restrict__ c = fc + static_cast<long long>(kFrameFloats) * s;    // wave-uniform
+      apply(c, __float_as_int(c[12]));
+    }
+    __syncthreads();                      // list and wave_n are rewritten by the next chunk
+  }
+  return survivors;
+}
+
+// the brick volume under the voxel walk of tsdf_fuse.h: one workgroup per brick in use, one thread per voxel
+struct BrickWalk {
+  static constexpr int kThreads = kBrick;
+  const int32_t* coord; const int32_t* bricks;
+  int cap;
+  float voxel;
+  int32_t* kept;                          // [cap] or NULL
+  struct Thread { long long i; float xf, yf, zf; bool live; float ccx, ccy, ccz, msum; int* list; int* wave_n; };
+
+  __device__ __forceinline__ bool enter(Thread& t) const {
+    const int slot = blockIdx.x;
+    if (slot >= min(bricks[0], cap)) return false;
+    t.i = static_cast<long long>(slot) * kBrick + threadIdx.x;
+    t.live = true;
+    return true;
+  }
+  __device__ __forceinline__ void locate(Thread& t) const {
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    __shared__ int list[kBrick];
+    __shared__ int wave_n[kBrick / 64];
+    t.list = list; t.wave_n = wave_n;
+    const int bz = coord[3 * slot], by = coord[3 * slot + 1], bx = coord[3 * slot + 2];
+    const int x = kB * bx + (tid & 7), y = kB * by + ((tid >> 3) & 7), z = kB * bz + (tid >> 6);
+    t.xf = static_cast<float>(x); t.yf = static_cast<float>(y); t.zf = static_cast<float>(z);
+    // the brick's centre (exact in fp32) and its largest index sum, for the cull
+    t.ccx = static_cast<float>(kB * bx) + 3.5f; t.ccy = static_cast<float>(kB * by) + 3.5f; t.ccz = static_cast<float>(kB * bz) + 3.5f;
+    t.msum = voxel * static_cast<float>(kB * (bx + by + bz) + 21);
+  }
+  template <typename Apply>
+  __device__ __forceinline__ int for_each_frame(const Thread& t, const float* __restrict__ fc, int N, const Intr K, const Fuse in,
+                                                Apply apply) const {
+    return brick_cull_and_apply(fc, N, t.ccx, t.ccy, t.ccz, t.msum, voxel, K, in, t.list, t.wave_n, apply);
+  }
+  __device__ __forceinline__ void keep(int n) const {
+    if (kept && threadIdx.x == 0) kept[blockIdx.x] = n;
+  }
+};
 
 }  // namespace

@@ -1,15 +1,12 @@
 // tsdf_fuse.h — the arithmetic the dense volume (tsdf.hip) and the brick volume (tsdf_sparse.hip) share: a slot's pre-multiplied frame
-// constants, the update of one voxel by one frame, and the surface-nets vertex of one cell.  Each is ONE inline function that both
-// translation units call with the same operands, so a voxel of a brick is meant to end with the bytes the dense kernel leaves at that
-// voxel (tests/test_tsdf_sparse_gpu.py holds the two against each other).
+// constants, a voxel's load and store, and the update of one voxel by one frame (in, and out again for the re-integration).  Each is
+// ONE inline function, called by ONE kernel body (below) that sees either volume through a walker, so a voxel of a brick ends with
+// the bytes the dense kernel leaves at that voxel (tests/test_tsdf_sparse_gpu.py holds the two against each other).  The surface-nets
+// vertex of a cell: tsdf_mesh.h.
 #pragma once
 #include "depth_vote.h"
 
 constexpr int kFrameFloats = 16;      // per slot: A[9] row-major, b[3], frame id (as int bits), [13..15] for the caller (tsdf.hip: unused)
-
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mask), 0));
-}
 
 struct Vol { float ox, oy, oz, voxel; };
 
@@ -44,8 +41,28 @@ struct LabelMaps { const int32_t* labels; int lh, lw, div; };
 // instantiations keep their argument layout and their code
 template <bool LAB> struct VoteVolumes {};
 template <> struct VoteVolumes<true> { int32_t* label; float* lconf; LabelMaps maps; };      // label, lconf: shaped like tsdf
-template <bool LAB> struct VertexLabels {};
-template <> struct VertexLabels<true> { const int32_t* label; int32_t* vlabel; };            // label: shaped like tsdf; vlabel [vcap]
+
+// the voxel at pool index i as a kernel holds it in registers (an empty one where !live), and back where a frame touched it
+template <bool RGB, bool LAB>
+__device__ __forceinline__ Voxel load_voxel(const float* __restrict__ tsdf, const float* __restrict__ wsum, const float* __restrict__ rgb,
+                                            const VoteVolumes<LAB> pan, long long i, bool live) {
+  Voxel a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, false, 0, 0.0f};
+  if (live) {
+    a.T = tsdf[i]; a.W = wsum[i];
+    if (RGB) { a.cr = rgb[3 * i]; a.cg = rgb[3 * i + 1]; a.cb = rgb[3 * i + 2]; }
+    if constexpr (LAB) { a.L = pan.label[i]; a.lc = pan.lconf[i]; }
+  }
+  return a;
+}
+
+template <bool RGB, bool LAB>
+__device__ __forceinline__ void store_voxel(const Voxel a, float* __restrict__ tsdf, float* __restrict__ wsum, float* __restrict__ rgb,
+                                            const VoteVolumes<LAB> pan, long long i) {
+  if (!a.touched) return;                 // (only a live voxel can be)
+  tsdf[i] = a.T; wsum[i] = a.W;
+  if (RGB) { rgb[3 * i] = a.cr; rgb[3 * i + 1] = a.cg; rgb[3 * i + 2] = a.cb; }
+  if constexpr (LAB) { pan.label[i] = a.L; pan.lconf[i] = a.lc; }
+}
 
 // frame f (>= 0, with the slot's constants c) applied to the voxel whose INTEGER index is (xf, yf, zf): the contract's sequence of
 // include/pvo_hip.h pvo_tsdf_integrate, one test after the other.  LAB: the contribution also casts its pixel's label into the
@@ -142,65 +159,84 @@ __device__ __forceinline__ void tsdf_unfuse_frame(Voxel& a, const float* __restr
   a.W = Wn;
 }
 
-// ------------------------------------------------------------------------------------------------------------ surface nets
+// ------------------------------------------------------------------------------------------------------------ the voxel walk
+//
+// ONE kernel body each for fusion and re-integration: it loads its voxel, runs its frame loops and stores the voxel.  A WALKER, the
+// kernel's first argument, says which voxel a thread owns and which slots of a frame table reach it:
+//   enter(t)                         false = the WHOLE workgroup has no voxel; else t.i = the pool index, t.live = the thread has a voxel
+//   locate(t)                        (t.xf, t.yf, t.zf) = the voxel's global integer index as floats, and what for_each_frame needs; called
+//                                    AFTER the voxel's loads are issued, so that they fly while the brick's coordinates are fetched
+//   for_each_frame(t, fc, N, K, in, apply)   apply(c, f) for the slots of fc [N] that may reach the voxel, in slot order; returns the
+//                                    number of slots kept for the workgroup (0 where nothing is culled)
+//   keep(n)                          the workgroup's count of kept slots, where the caller asked for it
+//   kThreads                         the workgroup, and the kernel's __launch_bounds__
+// DenseWalk (tsdf_dense_walk.h): raster index over [nz,ny,nx], every slot with f >= 0.  BrickWalk (tsdf_brick_cull.h): one workgroup
+// per brick in use, the slots culled per brick.  The slot constants are wave-uniform loads either way.
 
-// flag byte of a cell: bit 0 active, bits 1-3 a quad around the edge corner 0 -> corner 0 + e_a (a = x, y, z), bit 4 corner 0 inside
-constexpr int kActive = 1, kInsideA = 16;
+namespace {
 
-struct MeshOut { float* verts; float* normals; uint8_t* rgba; int32_t* faces; int vcap, fcap; };
-
-// vertex idx (< out.vcap) of the cell with the INTEGER index (cx, cy, cz) and corner values s[j] (j = 4 dz + 2 dy + dx); corner j's
-// colour is rgb[3 * at[j] ..] (rgb may be NULL): position, normal and colour as include/pvo_hip.h pvo_tsdf_mesh states them
-__device__ __forceinline__ void surface_net_vertex(const float (&s)[8], const float* __restrict__ rgb, const long long (&at)[8], int cx,
-                                                   int cy, int cz, float ox, float oy, float oz, float voxel, const MeshOut out, int idx) {
-  // mean of the crossings of the sign-changing edges, in cell coordinates; edges in the order x (from corners 0, 2, 4, 6),
-  // y (0, 1, 4, 5), z (0, 1, 2, 3)
-  float p[3] = {0.0f, 0.0f, 0.0f};
-  int n = 0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (j & (1 << a)) continue;
-      const float sa = s[j], sb = s[j | (1 << a)];
-      if ((sa < 0.0f) == (sb < 0.0f)) continue;
-      const float t = sa / (sa - sb);     // opposite sides: |sa - sb| = |sa| + |sb| > 0
-#pragma unroll
-      for (int e = 0; e < 3; ++e) p[e] += (e == a) ? t : static_cast<float>((j >> e) & 1);
-      ++n;
-    }
-  }
-  const float nf = static_cast<float>(n);
-  float* o = out.verts + 3ll * idx;
-  o[0] = ox + voxel * (static_cast<float>(cx) + p[0] / nf);
-  o[1] = oy + voxel * (static_cast<float>(cy) + p[1] / nf);
-  o[2] = oz + voxel * (static_cast<float>(cz) + p[2] / nf);
-  if (out.normals) {                      // central gradient of the eight corners, toward increasing tsdf
-    const float gx = ((s[1] - s[0]) + (s[3] - s[2])) + ((s[5] - s[4]) + (s[7] - s[6]));
-    const float gy = ((s[2] - s[0]) + (s[3] - s[1])) + ((s[6] - s[4]) + (s[7] - s[5]));
-    const float gz = ((s[4] - s[0]) + (s[5] - s[1])) + ((s[6] - s[2]) + (s[7] - s[3]));
-    const float len = sqrtf(gx * gx + gy * gy + gz * gz);
-    float* q = out.normals + 3ll * idx;
-    const bool zero = !(len > 0.0f);
-    q[0] = zero ? 0.0f : gx / len; q[1] = zero ? 0.0f : gy / len; q[2] = zero ? 0.0f : gz / len;
-  }
-  if (out.rgba) {
-    uchar4 c = make_uchar4(0, 0, 0, 255);
-    if (rgb) {
-      float acc[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int e = 0; e < 3; ++e) acc[e] += rgb[3 * at[j] + e];
-      }
-      // mean + 0.5, floored, clamped to [0, 255] (NaN -> 0)
-      c.x = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[0] * 0.125f + 0.5f))));
-      c.y = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[1] * 0.125f + 0.5f))));
-      c.z = static_cast<uint8_t>(min(255, max(0, pvo_floor_to_int(acc[2] * 0.125f + 0.5f))));
-    }
-    reinterpret_cast<uchar4*>(out.rgba)[idx] = c;
-  }
+// the frame loop runs inside, so the volume is read and written once per call whatever N is.  LAB: with the label vote on the
+// caller's label / lconf volumes, the kernel's last argument (empty without LAB, so the plain instantiations keep their code)
+template <typename W, bool RGB, bool LAB>
+__global__ __launch_bounds__(W::kThreads) void tsdf_integrate_kernel(const W w, float* __restrict__ tsdf, float* __restrict__ wsum,
+                                                                    float* __restrict__ rgb, const float* __restrict__ fc,
+                                                                    const float* __restrict__ intrinsics, const Fuse in, int N,
+                                                                    const VoteVolumes<LAB> pan) {
+  typename W::Thread t;
+  if (!w.enter(t)) return;                // (the whole workgroup)
+  const Intr K = load_intr(intrinsics);
+  const long long HW = static_cast<long long>(in.ht) * in.wd;
+  const long long plane = static_cast<long long>(in.IH) * in.IW;
+  Voxel a = load_voxel<RGB, LAB>(tsdf, wsum, rgb, pan, t.i, t.live);
+  w.locate(t);
+  const int n = w.for_each_frame(t, fc, N, K, in, [&](const float* __restrict__ c, int f) {
+    if constexpr (LAB) tsdf_fuse_frame<RGB, true>(a, c, f, t.xf, t.yf, t.zf, t.live, K, in, HW, plane, pan.maps);
+    else tsdf_fuse_frame<RGB>(a, c, f, t.xf, t.yf, t.zf, t.live, K, in, HW, plane);
+  });
+  w.keep(n);
+  store_voxel<RGB, LAB>(a, tsdf, wsum, rgb, pan, t.i);
 }
+
+// the REMOVE slots of fc_old [N_old] in order (tsdf_unfuse_frame under in_old), then the ADD slots of fc [N] in order (tsdf_fuse_frame
+// under in); keep: both sets summed
+template <typename W, bool RGB>
+__global__ __launch_bounds__(W::kThreads) void tsdf_reintegrate_kernel(const W w, float* __restrict__ tsdf, float* __restrict__ wsum,
+                                                                      float* __restrict__ rgb, const float* __restrict__ fc_old,
+                                                                      const float* __restrict__ fc, const float* __restrict__ intrinsics,
+                                                                      const Fuse in_old, const Fuse in, int N_old, int N, float w_floor) {
+  typename W::Thread t;
+  if (!w.enter(t)) return;                // (the whole workgroup)
+  const Intr K = load_intr(intrinsics);
+  const long long HW = static_cast<long long>(in.ht) * in.wd;
+  const long long plane = static_cast<long long>(in.IH) * in.IW;
+  const VoteVolumes<false> none = {};
+  Voxel a = load_voxel<RGB, false>(tsdf, wsum, rgb, none, t.i, t.live);
+  w.locate(t);
+  int n = w.for_each_frame(t, fc_old, N_old, K, in_old, [&](const float* __restrict__ c, int f) {
+    tsdf_unfuse_frame<RGB>(a, c, f, t.xf, t.yf, t.zf, t.live, K, in_old, HW, plane, w_floor);
+  });
+  n += w.for_each_frame(t, fc, N, K, in, [&](const float* __restrict__ c, int f) {
+    tsdf_fuse_frame<RGB>(a, c, f, t.xf, t.yf, t.zf, t.live, K, in, HW, plane);
+  });
+  w.keep(n);
+  store_voxel<RGB, false>(a, tsdf, wsum, rgb, none, t.i);
+}
+
+template <bool LAB>
+VoteVolumes<LAB> vote_volumes(const pvo_tsdf_panoptic_args* p) {
+  if constexpr (LAB) return {p->label, p->lconf, {p->labels, p->lh, p->lw, p->label_div}};
+  else return {};
+}
+
+// the operands of a fusion as the kernels take them, from either argument struct; disps / weight: the set's own
+template <typename Args>
+Fuse fuse_operands(const Args* a, const float* disps, const float* weight) {
+  return {disps, weight, a->images, a->ht, a->wd, a->IH, a->IW, a->img_stride, a->img_offset, a->trunc, a->z_near, a->w_max};
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------------------ labels of a cell
 
 // label of the vertex of the cell with corner values s[j]: the label of the corner with the smallest |tsdf| among the corners that
 // have one (> 0), ties to the lowest j, 0 without any; comparisons only (pvo_tsdf_mesh_panoptic)

@@ -8,41 +8,23 @@
 //              (d) alloc_count_kernel        per 256 grid entries: bricks held, bricks new (marked and not held)
 //              (e) alloc_scan_kernel         one workgroup: the bricks held, exclusive scan of the new ones behind them, bricks[0]
 //              (f) alloc_assign_kernel       grid and coord of the new bricks whose slot is below cap
-//   integrate  (a) sparse_frames_kernel      one workgroup per slot: the dense call's constants, zfar = max 1/d, the cull's scalars
-//              (b) sparse_integrate_kernel   one workgroup per brick, one thread per voxel: cull per chunk of 512 slots, survivors
-//                                            compacted in slot order, then the dense kernel's per-(voxel, frame) function
-//   mesh       classify / scan / vertices / faces as in tsdf.hip, one workgroup per brick, neighbours through the grid
-//   panoptic   (pvo_tsdf_sparse_integrate_panoptic / _mesh_panoptic) the LAB instantiations of sparse_integrate_kernel and
-//              sparse_verts_kernel in the same launches, as in tsdf.hip
+//   integrate  (a) sparse_frames_kernel      (tsdf_brick_cull.h) one workgroup per slot: the dense call's constants, zfar = max 1/d, the
+//                                            cull's scalars
+//              (b) tsdf_integrate_kernel<BrickWalk>  (tsdf_fuse.h) one workgroup per brick, one thread per voxel: cull per chunk of
+//                                            512 slots, survivors compacted in slot order, then the dense walk's per-(voxel, frame) function
+//   mesh       classify / scan / vertices / faces of tsdf_mesh.h over BrickCells: one workgroup per brick, neighbours through the grid
+//   panoptic   (pvo_tsdf_sparse_integrate_panoptic / _mesh_panoptic) the LAB instantiations of the integrate and the vertex kernel in
+//              the same launches, as in tsdf.hip
 //
 // No atomics anywhere: marks are same-value stores, every index is a function of flags alone, a voxel is one thread's sequential loop.
+#include "tsdf_mesh.h"
 #include "tsdf_brick_cull.h"
+
+using namespace tsdf_volume;
 
 namespace {
 
-constexpr int kB = PVO_TSDF_BRICK;
-constexpr int kBrick = kB * kB * kB;  // 512 voxels, one workgroup
 constexpr int kBlock = 256;
-constexpr int kScanThreads = 1024;
-static_assert(kB == 8 && kBrick == 512, "the index arithmetic below shifts by 3 and 6");
-
-// inclusive scan of one value per thread of a 1024-thread workgroup (Hillis-Steele); total = the last thread's
-__device__ __forceinline__ int scan_workgroup(int s, int (*buf)[kScanThreads], int& total) {
-  const int tid = threadIdx.x;
-  int cur = 0;
-  buf[0][tid] = s;
-  __syncthreads();
-#pragma unroll
-  for (int off = 1; off < kScanThreads; off <<= 1) {
-    buf[cur ^ 1][tid] = buf[cur][tid] + (tid >= off ? buf[cur][tid - off] : 0);
-    cur ^= 1;
-    __syncthreads();
-  }
-  const int inc = buf[cur][tid];
-  total = buf[cur][kScanThreads - 1];
-  __syncthreads();                        // buf is reused by the next scan
-  return inc;
-}
 
 // ------------------------------------------------------------------------------------------------------------ allocate
 
@@ -141,21 +123,15 @@ __global__ __launch_bounds__(kBlock) void alloc_count_kernel(const int32_t* __re
   }
 }
 
-// nbase[i] = bricks held + the new bricks of the workgroups before i (thread t owns a contiguous chunk, map_points.hip's scan);
-// bricks[0] = held + new, not clamped by cap
+// nbase[i] = bricks held + the new bricks of the workgroups before i (scan.h); bricks[0] = held + new, not clamped by cap
 __global__ __launch_bounds__(kScanThreads) void alloc_scan_kernel(const int* __restrict__ acount, const int* __restrict__ ncount,
                                                                   int* __restrict__ nbase, int32_t* __restrict__ bricks, int M) {
-  const int tid = threadIdx.x;
-  const int chunk = (M + kScanThreads - 1) / kScanThreads;
-  const int lo = static_cast<int>(min(static_cast<long long>(tid) * chunk, static_cast<long long>(M))), hi = min(lo + chunk, M);
-  __shared__ int buf[2][kScanThreads];
-  int sa = 0, sn = 0;
-  for (int i = lo; i < hi; ++i) { sa += acount[i]; sn += ncount[i]; }
-  int held, fresh;
-  scan_workgroup(sa, buf, held);
-  int run = held + scan_workgroup(sn, buf, fresh) - sn;
-  for (int i = lo; i < hi; ++i) { nbase[i] = run; run += ncount[i]; }
-  if (tid == 0) bricks[0] = held + fresh;
+  const int* const cnt[2] = {acount, ncount};
+  int run[2], total[2];
+  const ScanChunk c = scan_counts(cnt, M, run, total);
+  int next = total[0] + run[1];           // behind the bricks held
+  for (int i = c.lo; i < c.hi; ++i) { nbase[i] = next; next += ncount[i]; }
+  if (threadIdx.x == 0) bricks[0] = total[0] + total[1];
 }
 
 __global__ __launch_bounds__(kBlock) void alloc_assign_kernel(int32_t* __restrict__ grid, const uint8_t* __restrict__ marks, long long G,
@@ -178,257 +154,7 @@ __global__ __launch_bounds__(kBlock) void alloc_assign_kernel(int32_t* __restric
   coord[3 * slot + 2] = static_cast<int32_t>(i % gx);
 }
 
-// ------------------------------------------------------------------------------------------------------------ integrate
-
-// sparse_frames_kernel (per slot: the dense call's constants, zfar, the cull's scalars) and brick_sees_frame (one slot against one
-// brick): tsdf_brick_cull.h, shared with the re-integration (tsdf_reintegrate.hip)
-
-// LAB: with the label vote on the caller's label / lconf pools (pvo_tsdf_sparse_integrate_panoptic)
-template <bool RGB, bool LAB>
-__global__ __launch_bounds__(kBrick) void sparse_integrate_kernel(float* __restrict__ tsdf, float* __restrict__ wsum, float* __restrict__ rgb,
-                                                                 const int32_t* __restrict__ coord, const int32_t* __restrict__ bricks,
-                                                                 int cap, const float* __restrict__ fc,
-                                                                 const float* __restrict__ intrinsics, const Fuse in, int N, float voxel,
-                                                                 int32_t* __restrict__ kept, const VoteVolumes<LAB> pan) {
-  const int slot = blockIdx.x, tid = threadIdx.x;
-  if (slot >= min(bricks[0], cap)) return;              // (the whole workgroup)
-  const int bz = coord[3 * slot], by = coord[3 * slot + 1], bx = coord[3 * slot + 2];
-  const int x = kB * bx + (tid & 7), y = kB * by + ((tid >> 3) & 7), z = kB * bz + (tid >> 6);
-  const float xf = static_cast<float>(x), yf = static_cast<float>(y), zf = static_cast<float>(z);
-  const float ccx = static_cast<float>(kB * bx) + 3.5f, ccy = static_cast<float>(kB * by) + 3.5f, ccz = static_cast<float>(kB * bz) + 3.5f;
-  const float msum = voxel * static_cast<float>(kB * (bx + by + bz) + 21);
-  const Intr K = load_intr(intrinsics);
-  const long long HW = static_cast<long long>(in.ht) * in.wd;
-  const long long plane = static_cast<long long>(in.IH) * in.IW;
-  const long long i = static_cast<long long>(slot) * kBrick + tid;
-  Voxel a = {tsdf[i], wsum[i], 0.0f, 0.0f, 0.0f, false, 0, 0.0f};
-  if (RGB) { a.cr = rgb[3 * i]; a.cg = rgb[3 * i + 1]; a.cb = rgb[3 * i + 2]; }
-  if constexpr (LAB) { a.L = pan.label[i]; a.lc = pan.lconf[i]; }
-  __shared__ int list[kBrick];
-  __shared__ int wave_n[kBrick / 64];
-  int survivors = 0;
-  for (int c0 = 0; c0 < N; c0 += kBrick) {
-    // stage 1: slot c0 + tid against the brick; the survivors in slot order
-    const int b = c0 + tid;
-    const bool keep = b < N && brick_sees_frame(fc + static_cast<long long>(kFrameFloats) * b, ccx, ccy, ccz, msum, voxel, K, in);
-    const unsigned long long m = __ballot(keep);
-    if ((tid & 63) == 0) wave_n[tid >> 6] = __popcll(m);
-    __syncthreads();
-    int pos = lanes_below(m), n = 0;
-#pragma unroll
-    for (int w = 0; w < kBrick / 64; ++w) {
-      if (w < (tid >> 6)) pos += wave_n[w];
-      n += wave_n[w];
-    }
-    if (keep) list[pos] = b;
-    survivors += n;
-    __syncthreads();
-    // stage 2: the dense kernel's loop over the survivors
-    for (int k = 0; k < n; ++k) {
-      const int s = __builtin_amdgcn_readfirstlane(list[k]);
-      const float* __restrict__ c = fc + static_cast<long long>(kFrameFloats) * s;    // wave-uniform
-      if constexpr (LAB) tsdf_fuse_frame<RGB, true>(a, c, __float_as_int(c[12]), xf, yf, zf, true, K, in, HW, plane, pan.maps);
-      else tsdf_fuse_frame<RGB>(a, c, __float_as_int(c[12]), xf, yf, zf, true, K, in, HW, plane);
-    }
-    __syncthreads();                      // list and wave_n are rewritten by the next chunk
-  }
-  if (kept && tid == 0) kept[slot] = survivors;
-  if (a.touched) {
-    tsdf[i] = a.T; wsum[i] = a.W;
-    if (RGB) { rgb[3 * i] = a.cr; rgb[3 * i + 1] = a.cg; rgb[3 * i + 2] = a.cb; }
-    if constexpr (LAB) { pan.label[i] = a.L; pan.lconf[i] = a.lc; }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------ mesh
-
-struct Bricks {
-  const int32_t* grid; const int32_t* coord; const int32_t* bricks;
-  const float* tsdf; const float* wsum; const float* rgb;
-  int gz, gy, gx, cap;
-  float ox, oy, oz, voxel, min_weight;
-};
-
-// the slots of the 3 x 3 x 3 bricks around brick (bz,by,bx) into nb (LDS), -1 outside the grid; ends with a barrier
-__device__ __forceinline__ void load_neighbours(const Bricks g, int bz, int by, int bx, int* nb) {
-  const int tid = threadIdx.x;
-  if (tid < 27) {
-    const int z = bz + tid / 9 - 1, y = by + (tid / 3) % 3 - 1, x = bx + tid % 3 - 1;
-    const bool in = z >= 0 && z < g.gz && y >= 0 && y < g.gy && x >= 0 && x < g.gx;
-    const int s = in ? g.grid[(static_cast<long long>(z) * g.gy + y) * g.gx + x] : -1;
-    nb[tid] = s < g.cap ? s : -1;         // (a slot the pool does not have is no brick)
-  }
-  __syncthreads();
-}
-
-// pool index of the voxel at local (lz,ly,lx), each in [-1, 8], of the brick whose neighbours are nb; -1 in a brick that does not exist
-__device__ __forceinline__ long long voxel_at(const int* nb, int lz, int ly, int lx) {
-  const int s = nb[((lz >> 3) + 1) * 9 + ((ly >> 3) + 1) * 3 + ((lx >> 3) + 1)];
-  return s < 0 ? -1 : static_cast<long long>(s) * kBrick + (((lz & 7) << 6) | ((ly & 7) << 3) | (lx & 7));
-}
-
-// all eight corners of the cell at local (lz,ly,lx), each in [-1, 7], valid
-__device__ __forceinline__ bool cell_valid(const Bricks g, const int* nb, int lz, int ly, int lx) {
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const long long v = voxel_at(nb, lz + (j >> 2), ly + ((j >> 1) & 1), lx + (j & 1));
-    ok = ok && v >= 0 && g.wsum[v >= 0 ? v : 0] >= g.min_weight;
-  }
-  return ok;
-}
-
-__global__ __launch_bounds__(kBrick) void sparse_classify_kernel(const Bricks g, uint8_t* __restrict__ flags, int* __restrict__ vcount,
-                                                                int* __restrict__ qcount) {
-  const int slot = blockIdx.x, tid = threadIdx.x;
-  if (slot >= min(g.bricks[0], g.cap)) {  // (the whole workgroup) a slot not in use has no cell
-    if (tid == 0) { vcount[slot] = 0; qcount[slot] = 0; }
-    return;
-  }
-  __shared__ int nb[27];
-  const int bz = g.coord[3 * slot], by = g.coord[3 * slot + 1], bx = g.coord[3 * slot + 2];
-  load_neighbours(g, bz, by, bx, nb);
-  const int lx = tid & 7, ly = (tid >> 3) & 7, lz = tid >> 6;
-  int flag = 0;
-  bool valid = true;
-  int inside = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const long long v = voxel_at(nb, lz + (j >> 2), ly + ((j >> 1) & 1), lx + (j & 1));
-    valid = valid && v >= 0 && g.wsum[v >= 0 ? v : 0] >= g.min_weight;
-    inside |= (g.tsdf[v >= 0 ? v : 0] < 0.0f ? 1 : 0) << j;
-  }
-  if (valid && inside != 0 && inside != 255) {
-    flag = kActive | ((inside & 1) ? kInsideA : 0);
-    const int c[3] = {kB * bx + lx, kB * by + ly, kB * bz + lz};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const int b = (a + 1) % 3, cc = (a + 2) % 3;
-      if ((((inside >> (1 << a)) ^ inside) & 1) == 0 || c[b] < 1 || c[cc] < 1) continue;
-      // the three other cells around the edge share it, so they are not all on one side: active = all corners valid
-      int eb[3] = {0, 0, 0}, ec[3] = {0, 0, 0};
-      eb[b] = 1; ec[cc] = 1;
-      if (cell_valid(g, nb, lz - eb[2], ly - eb[1], lx - eb[0]) && cell_valid(g, nb, lz - eb[2] - ec[2], ly - eb[1] - ec[1], lx - eb[0] - ec[0]) &&
-          cell_valid(g, nb, lz - ec[2], ly - ec[1], lx - ec[0]))
-        flag |= 2 << a;
-    }
-  }
-  flags[static_cast<long long>(slot) * kBrick + tid] = static_cast<uint8_t>(flag);
-  const unsigned long long ma = __ballot(flag & kActive);
-  const int quads = __popcll(__ballot(flag & 2)) + __popcll(__ballot(flag & 4)) + __popcll(__ballot(flag & 8));
-  __shared__ int wave_v[kBrick / 64], wave_q[kBrick / 64];
-  if ((tid & 63) == 0) { wave_v[tid >> 6] = __popcll(ma); wave_q[tid >> 6] = quads; }
-  __syncthreads();
-  if (tid == 0) {
-    int v = 0, q = 0;
-#pragma unroll
-    for (int w = 0; w < kBrick / 64; ++w) { v += wave_v[w]; q += wave_q[w]; }
-    vcount[slot] = v; qcount[slot] = q;
-  }
-}
-
-// exclusive scans of vcount and qcount [M] in slot order; counts = (vertices, faces = 2 * quads), not clamped by any capacity
-__global__ __launch_bounds__(kScanThreads) void sparse_scan_kernel(const int* __restrict__ vcount, const int* __restrict__ qcount,
-                                                                   int* __restrict__ vbase, int* __restrict__ qbase,
-                                                                   int32_t* __restrict__ counts, int M) {
-  const int tid = threadIdx.x;
-  const int chunk = (M + kScanThreads - 1) / kScanThreads;
-  const int lo = static_cast<int>(min(static_cast<long long>(tid) * chunk, static_cast<long long>(M))), hi = min(lo + chunk, M);
-  __shared__ int buf[2][kScanThreads];
-  int sv = 0, sq = 0;
-  for (int i = lo; i < hi; ++i) { sv += vcount[i]; sq += qcount[i]; }
-  int nv, nq;
-  int rv = scan_workgroup(sv, buf, nv) - sv;
-  int rq = scan_workgroup(sq, buf, nq) - sq;
-  for (int i = lo; i < hi; ++i) { vbase[i] = rv; rv += vcount[i]; qbase[i] = rq; rq += qcount[i]; }
-  if (tid == 0) { counts[0] = nv; counts[1] = 2 * nq; }
-}
-
-// LAB: the vertex's label into vlabel as well (pvo_tsdf_sparse_mesh_panoptic)
-template <bool LAB>
-__global__ __launch_bounds__(kBrick) void sparse_verts_kernel(const Bricks g, const uint8_t* __restrict__ flags, const int* __restrict__ vbase,
-                                                             int32_t* __restrict__ vidx, const MeshOut out, const VertexLabels<LAB> lab) {
-  const int slot = blockIdx.x, tid = threadIdx.x;
-  if (slot >= min(g.bricks[0], g.cap)) return;          // (the whole workgroup)
-  __shared__ int nb[27];
-  const int bz = g.coord[3 * slot], by = g.coord[3 * slot + 1], bx = g.coord[3 * slot + 2];
-  load_neighbours(g, bz, by, bx, nb);
-  const long long k = static_cast<long long>(slot) * kBrick + tid;
-  const bool active = flags[k] & kActive;
-  const unsigned long long m = __ballot(active);
-  __shared__ int wave_n[kBrick / 64];
-  if ((tid & 63) == 0) wave_n[tid >> 6] = __popcll(m);
-  __syncthreads();
-  if (!active) return;
-  int idx = vbase[slot] + lanes_below(m);
-  for (int w = 0; w < (tid >> 6); ++w) idx += wave_n[w];
-  vidx[k] = idx;                          // (also beyond the capacity: the faces name the vertex by its index)
-  if (idx >= out.vcap) return;            // written nowhere; the caller sees counts[0] > vcap
-  const int lx = tid & 7, ly = (tid >> 3) & 7, lz = tid >> 6;
-  float s[8];
-  long long at[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    at[j] = voxel_at(nb, lz + (j >> 2), ly + ((j >> 1) & 1), lx + (j & 1));     // (an active cell: all eight exist)
-    s[j] = g.tsdf[at[j]];
-  }
-  surface_net_vertex(s, g.rgb, at, kB * bx + lx, kB * by + ly, kB * bz + lz, g.ox, g.oy, g.oz, g.voxel, out, idx);
-  if constexpr (LAB) lab.vlabel[idx] = surface_net_label(s, lab.label, at);
-}
-
-__global__ __launch_bounds__(kBrick) void sparse_faces_kernel(const Bricks g, const uint8_t* __restrict__ flags, const int* __restrict__ qbase,
-                                                             const int32_t* __restrict__ vidx, const MeshOut out) {
-  const int slot = blockIdx.x, tid = threadIdx.x;
-  if (slot >= min(g.bricks[0], g.cap)) return;          // (the whole workgroup)
-  __shared__ int nb[27];
-  const int bz = g.coord[3 * slot], by = g.coord[3 * slot + 1], bx = g.coord[3 * slot + 2];
-  load_neighbours(g, bz, by, bx, nb);
-  const long long k = static_cast<long long>(slot) * kBrick + tid;
-  const int flag = flags[k];
-  // quads are numbered cell by cell, inside a cell by axis: the quads of the lower lanes, whatever their axis, come first
-  const unsigned long long mx = __ballot(flag & 2), my = __ballot(flag & 4), mz = __ballot(flag & 8);
-  __shared__ int wave_n[kBrick / 64];
-  if ((tid & 63) == 0) wave_n[tid >> 6] = __popcll(mx) + __popcll(my) + __popcll(mz);
-  __syncthreads();
-  if (!(flag & 14)) return;
-  int q = qbase[slot] + lanes_below(mx) + lanes_below(my) + lanes_below(mz);
-  for (int w = 0; w < (tid >> 6); ++w) q += wave_n[w];
-  const int l[3] = {tid & 7, (tid >> 3) & 7, tid >> 6};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (!(flag & (2 << a))) continue;
-    int eb[3] = {0, 0, 0}, ec[3] = {0, 0, 0};
-    eb[(a + 1) % 3] = 1; ec[(a + 2) % 3] = 1;
-    // (a quad's four cells are active: their bricks exist)
-    const int q0 = vidx[k], q1 = vidx[voxel_at(nb, l[2] - eb[2], l[1] - eb[1], l[0] - eb[0])],
-              q2 = vidx[voxel_at(nb, l[2] - eb[2] - ec[2], l[1] - eb[1] - ec[1], l[0] - eb[0] - ec[0])],
-              q3 = vidx[voxel_at(nb, l[2] - ec[2], l[1] - ec[1], l[0] - ec[0])];
-    const bool fwd = (flag & kInsideA) != 0;            // corner 0 inside; otherwise its neighbour is: reversed winding
-    const int f0 = 2 * q, f1 = 2 * q + 1;
-    if (f0 < out.fcap) {
-      int32_t* o = out.faces + 3ll * f0;
-      o[0] = q0; o[1] = fwd ? q1 : q2; o[2] = fwd ? q2 : q1;
-    }
-    if (f1 < out.fcap) {
-      int32_t* o = out.faces + 3ll * f1;
-      o[0] = q0; o[1] = fwd ? q2 : q3; o[2] = fwd ? q3 : q2;
-    }
-    ++q;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------ host
-
-constexpr size_t kAlign = 256;
-inline size_t aligned(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-inline bool finite_f(float v) { return v - v == 0.0f; }
-
-constexpr int kMaxBricksPerAxis = (1 << 21) / kB;
-inline bool world_ok(int gz, int gy, int gx, int cap) {
-  return gz >= 0 && gy >= 0 && gx >= 0 && gz <= kMaxBricksPerAxis && gy <= kMaxBricksPerAxis && gx <= kMaxBricksPerAxis &&
-         static_cast<long long>(gz) * gy < (1ll << 31) && static_cast<long long>(gz) * gy * gx < (1ll << 31) && cap >= 0 &&
-         static_cast<long long>(cap) * kBrick < (1ll << 31);
-}
 
 struct AllocLayout { size_t marks, acount, ncount, nbase, frames, total; long long G, blocks; };
 inline AllocLayout alloc_layout(int gz, int gy, int gx, int N) {
@@ -439,24 +165,15 @@ inline AllocLayout alloc_layout(int gz, int gy, int gx, int N) {
   L.marks = 0;
   L.acount = aligned(L.G); L.ncount = L.acount + per; L.nbase = L.ncount + per;
   L.frames = L.nbase + per;
-  L.total = L.frames + aligned(sizeof(float) * kFrameFloats * static_cast<size_t>(N > 0 ? N : 0));
+  L.total = L.frames + table_bytes(N);
   return L;
 }
 
-struct SparseMeshLayout { size_t vcount, qcount, vbase, qbase, vidx, flags, total; };
-inline SparseMeshLayout sparse_mesh_layout(int cap) {
-  SparseMeshLayout L;
-  const size_t per = aligned(sizeof(int) * static_cast<size_t>(cap));
-  L.vcount = 0; L.qcount = per; L.vbase = 2 * per; L.qbase = 3 * per;
-  L.vidx = 4 * per;
-  L.flags = L.vidx + aligned(sizeof(int32_t) * static_cast<size_t>(cap) * kBrick);
-  L.total = L.flags + aligned(static_cast<size_t>(cap) * kBrick);
-  return L;
+inline MeshLayout brick_mesh_layout(int cap) {
+  return mesh_layout(static_cast<size_t>(cap), static_cast<size_t>(cap) * kBrick);
 }
 
 }  // namespace
-
-#define PVO_REQ(c) do { if (!(c)) return PVO_EINVAL; } while (0)
 
 extern "C" size_t pvo_tsdf_sparse_allocate_args_size(void) { return sizeof(pvo_tsdf_sparse_allocate_args); }
 extern "C" size_t pvo_tsdf_sparse_integrate_args_size(void) { return sizeof(pvo_tsdf_sparse_integrate_args); }
@@ -467,13 +184,11 @@ extern "C" size_t pvo_tsdf_sparse_allocate_workspace_bytes(int gz, int gy, int g
   return alloc_layout(gz, gy, gx, N).total;
 }
 
-extern "C" size_t pvo_tsdf_sparse_integrate_workspace_bytes(int N) {
-  return N <= 0 ? 0 : aligned(sizeof(float) * kFrameFloats * static_cast<size_t>(N));
-}
+extern "C" size_t pvo_tsdf_sparse_integrate_workspace_bytes(int N) { return table_bytes(N); }
 
 extern "C" size_t pvo_tsdf_sparse_mesh_workspace_bytes(int cap) {
   if (cap <= 0 || !world_ok(0, 0, 0, cap)) return 0;
-  return sparse_mesh_layout(cap).total;
+  return brick_mesh_layout(cap).total;
 }
 
 extern "C" int pvo_tsdf_sparse_allocate(const pvo_tsdf_sparse_allocate_args* a, void* workspace, size_t workspace_bytes, void* stream) {
@@ -482,7 +197,7 @@ extern "C" int pvo_tsdf_sparse_allocate(const pvo_tsdf_sparse_allocate_args* a, 
   PVO_REQ(a->N >= 0 && a->nframes >= 0 && a->ht >= 0 && a->wd >= 0 && static_cast<long long>(a->ht) * a->wd < (1ll << 31));
   PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->trunc > 0.0f && finite_f(a->trunc) && a->trunc / a->voxel <= 4096.0f);
   PVO_REQ(a->z_near >= 0.0f && finite_f(a->z_near) && a->margin >= 0.0f && a->margin <= static_cast<float>(kB));
-  PVO_REQ(finite_f(a->origin[0]) && finite_f(a->origin[1]) && finite_f(a->origin[2]));
+  PVO_REQ(origin_ok(a));
   const AllocLayout L = alloc_layout(a->gz, a->gy, a->gx, a->N);
   if (L.G == 0 || a->N == 0 || a->ht * a->wd == 0) return PVO_OK;         // nothing to mark
   PVO_REQ(a->grid && a->bricks && a->poses && a->disps && a->intrinsics && a->ix);
@@ -522,24 +237,13 @@ namespace {
 int sparse_integrate_impl(const pvo_tsdf_sparse_integrate_args* a, const pvo_tsdf_panoptic_args* p, bool panoptic, void* workspace,
                           size_t workspace_bytes, void* stream) {
   PVO_REQ(a);
-  if (panoptic) {
-    PVO_REQ(p && p->label && p->lconf && p->labels && p->label_div >= 1);
-    PVO_REQ(static_cast<long long>(p->lh) * p->label_div >= a->ht && static_cast<long long>(p->lw) * p->label_div >= a->wd);
-  }
+  if (panoptic) PVO_REQ(panoptic_ok(p, a));
   PVO_REQ(world_ok(a->gz, a->gy, a->gx, a->cap));
-  PVO_REQ(a->N >= 0 && a->nframes >= 0 && a->ht >= 0 && a->wd >= 0 && static_cast<long long>(a->ht) * a->wd < (1ll << 31));
-  PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->trunc > 0.0f && finite_f(a->trunc));
-  PVO_REQ(a->z_near >= 0.0f && finite_f(a->z_near) && a->w_max >= 0.0f && finite_f(a->w_max));
-  PVO_REQ(finite_f(a->origin[0]) && finite_f(a->origin[1]) && finite_f(a->origin[2]));
+  PVO_REQ(fuse_scalars_ok(a));
   if (a->cap == 0 || a->N == 0 || a->ht * a->wd == 0) return PVO_OK;      // nothing to fuse
   PVO_REQ(a->tsdf && a->wsum && a->coord && a->bricks && a->poses && a->disps && a->intrinsics && a->ix);
-  PVO_REQ(!a->rgb || a->images);                 // a colour pool needs the images
-  if (a->images) {
-    PVO_REQ(a->img_stride >= 1 && a->img_offset >= 0 && a->IH > 0 && a->IW > 0);
-    PVO_REQ(static_cast<long long>(a->img_stride) * (a->ht - 1) + a->img_offset < a->IH);
-    PVO_REQ(static_cast<long long>(a->img_stride) * (a->wd - 1) + a->img_offset < a->IW);
-  }
-  if (!workspace || workspace_bytes < pvo_tsdf_sparse_integrate_workspace_bytes(a->N)) return PVO_EWORKSPACE;
+  PVO_REQ(images_ok(a));
+  if (!workspace || workspace_bytes < table_bytes(a->N)) return PVO_EWORKSPACE;
   PVO_REQ(!(reinterpret_cast<uintptr_t>(workspace) & 15));
   hipStream_t s = pvo_stream(stream);
   float* fc = static_cast<float*>(workspace);
@@ -547,21 +251,12 @@ int sparse_integrate_impl(const pvo_tsdf_sparse_integrate_args* a, const pvo_tsd
   hipLaunchKernelGGL(sparse_frames_kernel, dim3(a->N), dim3(kCullBlock), 0, s, a->poses, a->ix, a->disps, a->weight, fc, a->nframes,
                      static_cast<long long>(a->ht) * a->wd, vol);
   PVO_CHECK_LAUNCH();
-  const Fuse in = {a->disps, a->weight, a->images, a->ht, a->wd, a->IH, a->IW, a->img_stride, a->img_offset, a->trunc, a->z_near, a->w_max};
-  if (panoptic) {
-    const VoteVolumes<true> pan = {p->label, p->lconf, {p->labels, p->lh, p->lw, p->label_div}};
-    if (a->rgb)
-      hipLaunchKernelGGL((sparse_integrate_kernel<true, true>), dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks,
-                         a->cap, fc, a->intrinsics, in, a->N, a->voxel, a->kept, pan);
-    else
-      hipLaunchKernelGGL((sparse_integrate_kernel<false, true>), dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks,
-                         a->cap, fc, a->intrinsics, in, a->N, a->voxel, a->kept, pan);
-  } else if (a->rgb)
-    hipLaunchKernelGGL((sparse_integrate_kernel<true, false>), dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks,
-                       a->cap, fc, a->intrinsics, in, a->N, a->voxel, a->kept, VoteVolumes<false>{});
-  else
-    hipLaunchKernelGGL((sparse_integrate_kernel<false, false>), dim3(a->cap), dim3(kBrick), 0, s, a->tsdf, a->wsum, a->rgb, a->coord, a->bricks,
-                       a->cap, fc, a->intrinsics, in, a->N, a->voxel, a->kept, VoteVolumes<false>{});
+  const Fuse in = fuse_operands(a, a->disps, a->weight);
+  const BrickWalk w = {a->coord, a->bricks, a->cap, a->voxel, a->kept};
+  pick_rgb_lab(a->rgb != nullptr, panoptic, [&](auto RGB, auto LAB) {
+    hipLaunchKernelGGL((tsdf_integrate_kernel<BrickWalk, decltype(RGB)::value, decltype(LAB)::value>), dim3(a->cap), dim3(BrickWalk::kThreads),
+                       0, s, w, a->tsdf, a->wsum, a->rgb, fc, a->intrinsics, in, a->N, vote_volumes<decltype(LAB)::value>(p));
+  });
   PVO_CHECK_LAUNCH();
   return PVO_OK;
 }
@@ -583,46 +278,20 @@ namespace {
 int sparse_mesh_impl(const pvo_tsdf_sparse_mesh_args* a, const pvo_tsdf_mesh_labels_args* p, bool panoptic, void* workspace,
                      size_t workspace_bytes, void* stream) {
   PVO_REQ(a);
-  if (panoptic) PVO_REQ(p && p->label && (a->vcap == 0 || p->vlabel));
+  if (panoptic) PVO_REQ(mesh_labels_ok(p, a));
   PVO_REQ(world_ok(a->gz, a->gy, a->gx, a->cap));
-  PVO_REQ(a->voxel > 0.0f && finite_f(a->voxel) && a->min_weight == a->min_weight);
-  PVO_REQ(finite_f(a->origin[0]) && finite_f(a->origin[1]) && finite_f(a->origin[2]));
-  PVO_REQ(a->vcap >= 0 && a->fcap >= 0 && a->counts && a->bricks);
-  PVO_REQ(!((reinterpret_cast<uintptr_t>(a->rgba) & 3)));
+  PVO_REQ(mesh_scalars_ok(a) && a->bricks);
   hipStream_t s = pvo_stream(stream);
-  if (a->cap == 0 || static_cast<long long>(a->gz) * a->gy * a->gx == 0) {     // no brick: the counts alone
-    const hipError_t e = hipMemsetAsync(a->counts, 0, 2 * sizeof(int32_t), s);
-    if (e != hipSuccess) { pvo_note_hip_error(static_cast<int>(e)); return PVO_ELAUNCH; }
-    return PVO_OK;
-  }
+  if (a->cap == 0 || static_cast<long long>(a->gz) * a->gy * a->gx == 0) return mesh_no_cell(a->counts, s);      // no brick
   PVO_REQ(a->grid && a->coord && a->tsdf && a->wsum);
-  PVO_REQ((a->vcap == 0 || a->verts) && (a->fcap == 0 || a->faces));
-  const SparseMeshLayout L = sparse_mesh_layout(a->cap);
+  PVO_REQ(mesh_outputs_ok(a));
+  const MeshLayout L = brick_mesh_layout(a->cap);
   if (!workspace || workspace_bytes < L.total) return PVO_EWORKSPACE;
   PVO_REQ(!(reinterpret_cast<uintptr_t>(workspace) & 7));
-  char* ws = static_cast<char*>(workspace);
-  int* vcount = reinterpret_cast<int*>(ws + L.vcount);
-  int* qcount = reinterpret_cast<int*>(ws + L.qcount);
-  int* vbase = reinterpret_cast<int*>(ws + L.vbase);
-  int* qbase = reinterpret_cast<int*>(ws + L.qbase);
-  int32_t* vidx = reinterpret_cast<int32_t*>(ws + L.vidx);
-  uint8_t* flags = reinterpret_cast<uint8_t*>(ws + L.flags);
-  const Bricks g = {a->grid, a->coord, a->bricks, a->tsdf, a->wsum, a->rgb, a->gz, a->gy, a->gx, a->cap,
-                    a->origin[0], a->origin[1], a->origin[2], a->voxel, a->min_weight};
+  const BrickCells g = {{a->tsdf, a->wsum, a->rgb, a->origin[0], a->origin[1], a->origin[2], a->voxel, a->min_weight},
+                        a->grid, a->coord, a->bricks, a->gz, a->gy, a->gx, a->cap};
   const MeshOut out = {a->verts, a->normals, a->rgba, a->faces, a->vcap, a->fcap};
-  const dim3 grid(static_cast<unsigned>(a->cap));
-  hipLaunchKernelGGL(sparse_classify_kernel, grid, dim3(kBrick), 0, s, g, flags, vcount, qcount);
-  PVO_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sparse_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, vcount, qcount, vbase, qbase, a->counts, a->cap);
-  PVO_CHECK_LAUNCH();
-  if (panoptic)
-    hipLaunchKernelGGL(sparse_verts_kernel<true>, grid, dim3(kBrick), 0, s, g, flags, vbase, vidx, out, VertexLabels<true>{p->label, p->vlabel});
-  else
-    hipLaunchKernelGGL(sparse_verts_kernel<false>, grid, dim3(kBrick), 0, s, g, flags, vbase, vidx, out, VertexLabels<false>{});
-  PVO_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sparse_faces_kernel, grid, dim3(kBrick), 0, s, g, flags, qbase, vidx, out);
-  PVO_CHECK_LAUNCH();
-  return PVO_OK;
+  return mesh_launch(g, a->cap, L, workspace, out, a->counts, panoptic ? p : nullptr, s);
 }
 
 }  // namespace

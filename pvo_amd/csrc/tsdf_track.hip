@@ -314,8 +314,6 @@ int launch(const V& vol, const Common& c, void* workspace, hipStream_t s) {
 
 }  // namespace
 
-#define PVO_REQ(c) do { if (!(c)) return PVO_EINVAL; } while (0)
-
 extern "C" size_t pvo_tsdf_track_args_size(void) { return sizeof(pvo_tsdf_track_args); }
 extern "C" size_t pvo_tsdf_sparse_track_args_size(void) { return sizeof(pvo_tsdf_sparse_track_args); }
 

@@ -1,8 +1,9 @@
 // tsdf_volume.h — where a cell's eight corners are stored: the dense volume and the brick volume as the adapters tsdf_ray.h's walk asks
-// for (n, tsdf, wsum, rgb, label, min_weight, corners(), kBricks), and the limits of the two volumes.  Shared by the render
+// for (n, tsdf, wsum, rgb, label, min_weight, corners(), kBricks); the limits of the two volumes come with tsdf_host.h.  Shared by the render
 // (tsdf_render.hip) and the frame-to-model tracker (tsdf_track.hip): both look at a volume through the same adapter, so the brick call
 // of either gives the bytes of its dense call.
 #pragma once
+#include "tsdf_host.h"
 #include "tsdf_ray.h"
 
 struct DenseVolume {
@@ -59,23 +60,3 @@ struct BrickVolume {
     return all ? 0 : 1;
   }
 };
-
-namespace tsdf_volume {
-
-// the limits of the two volumes and the workspace granule (host)
-constexpr size_t kAlign = 256;
-static inline size_t aligned(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-static inline bool finite_f(float v) { return v - v == 0.0f; }
-
-static inline bool volume_ok(int nz, int ny, int nx) {
-  return nz >= 0 && ny >= 0 && nx >= 0 && static_cast<long long>(nz) * ny < (1ll << 31) && static_cast<long long>(nz) * ny * nx < (1ll << 31);
-}
-constexpr int kB = PVO_TSDF_BRICK;
-constexpr int kMaxBricksPerAxis = (1 << 21) / kB;
-static inline bool world_ok(int gz, int gy, int gx, int cap) {
-  return gz >= 0 && gy >= 0 && gx >= 0 && gz <= kMaxBricksPerAxis && gy <= kMaxBricksPerAxis && gx <= kMaxBricksPerAxis &&
-         static_cast<long long>(gz) * gy < (1ll << 31) && static_cast<long long>(gz) * gy * gx < (1ll << 31) && cap >= 0 &&
-         static_cast<long long>(cap) * 512 < (1ll << 31);
-}
-
-}  // namespace tsdf_volume

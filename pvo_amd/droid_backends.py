@@ -604,6 +604,71 @@ def _mesh_labels(what, out, label, shape):
     return p
 
 
+def _check_dense(what, tsdf, wsum, rgb=None, with_rgb=True):
+    """the shapes of a dense volume: tsdf / wsum [nz,ny,nx], rgb [nz,ny,nx,3] or None"""
+    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
+        raise PvoHipError("%s: tsdf and wsum must be [nz,ny,nx]%s" % (what, ", rgb [nz,ny,nx,3]" if with_rgb else ""))
+
+
+def _fill_dense(a, tsdf, wsum, rgb, origin, voxel):
+    """a dense volume and its placement into the fields every dense struct has (rgb: where the struct has one)"""
+    a.tsdf, a.wsum = _ptr(tsdf), _ptr(wsum)
+    if hasattr(a, "rgb"):
+        a.rgb = _ptr(rgb)
+    a.nz, a.ny, a.nx = tsdf.shape
+    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
+    a.voxel = float(voxel)
+
+
+def _images(a, what, images, nframes, img_stride, img_offset, same_device_as=None):
+    """the images block of a fusion: uint8 [nframes,3,IH,IW] BGR sampled at [img_offset::img_stride], or None"""
+    if images is None:
+        return
+    _contig(images, "images")
+    if same_device_as is not None:
+        _dev(same_device_as, images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < nframes or images.shape[1] != 3:
+        raise PvoHipError("%s: images must be uint8 [nframes,3,IH,IW]" % what)
+    a.images, a.IH, a.IW, a.img_stride, a.img_offset = _ptr(images), images.shape[2], images.shape[3], int(img_stride), int(img_offset)
+
+
+def _kept(a, what, kept, dev):
+    """the brick calls' optional survivor counts: int32 [cap] on the pool's device"""
+    if kept is None:
+        return
+    _contig(kept, "kept")
+    if kept.dtype != torch.int32 or kept.numel() < a.cap or kept.device != dev:
+        raise PvoHipError("%s: kept must be an int32 device tensor of at least cap elements" % what)
+    a.kept = _ptr(kept)
+
+
+def _mesh_outputs(a, out):
+    a.vcap, a.fcap = out["verts"].shape[0], out["faces"].shape[0]
+    a.verts, a.normals, a.rgba, a.faces = _ptr(out["verts"]), _ptr(out.get("normals")), _ptr(out.get("rgba")), _ptr(out["faces"])
+    a.counts = ctypes.c_void_p(out["counts"].data_ptr())
+
+
+def _mesh(into, dev, vcap, fcap, labelled):
+    """what tsdf_mesh and tsdf_sparse_mesh share: the buffers for vcap vertices and fcap faces, into(out), the counts read back - the
+    call's one host synchronisation - and the same again with exactly the room needed if a capacity was exceeded"""
+    while True:
+        out = {"verts": torch.empty(vcap, 3, dtype=torch.float32, device=dev), "normals": torch.empty(vcap, 3, dtype=torch.float32, device=dev),
+               "rgba": torch.empty(vcap, 4, dtype=torch.uint8, device=dev), "faces": torch.empty(fcap, 3, dtype=torch.int32, device=dev),
+               "counts": torch.empty(2, dtype=torch.int32, device=dev)}
+        if labelled:
+            out["vlabel"] = torch.empty(vcap, dtype=torch.int32, device=dev)
+        into(out)
+        nv, nf = out["counts"].tolist()                 # the one synchronisation
+        if nv <= vcap and nf <= fcap:
+            break
+        vcap, fcap = max(nv, vcap), max(nf, fcap)
+    for k in ("verts", "normals", "rgba", "vlabel"):
+        if k in out:
+            out[k] = out[k][:nv]
+    out["faces"] = out["faces"][:nf]
+    return out
+
+
 def tsdf_integrate(tsdf, wsum, rgb, poses, disps, intrinsics, ix, origin, voxel, trunc, weight=None, images=None, img_stride=8,
                    img_offset=3, z_near=0.0, w_max=0.0, label=None, lconf=None, labels=None, label_div=1):
     """Fuse keyframes ix, in that order, into the caller's volume in place (include/pvo_hip.h pvo_tsdf_integrate): tsdf / wsum f32
@@ -623,20 +688,14 @@ def tsdf_integrate(tsdf, wsum, rgb, poses, disps, intrinsics, ix, origin, voxel,
                  (weight, "weight")):
         if t is not None:
             _f32(t, n)
-    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
-        raise PvoHipError("tsdf_integrate: tsdf and wsum must be [nz,ny,nx], rgb [nz,ny,nx,3]")
+    _check_dense("tsdf_integrate", tsdf, wsum, rgb)
     N, (nf, ht, wd) = ix.shape[0], disps.shape
     if poses.shape[0] < nf or (weight is not None and weight.shape != disps.shape):
         raise PvoHipError("tsdf_integrate: poses must cover the frames of disps, weight must have the shape of disps")
     a = _lib.TsdfIntegrateArgs()
-    if images is not None:
-        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < nf or images.shape[1] != 3:
-            raise PvoHipError("tsdf_integrate: images must be uint8 [nframes,3,IH,IW]")
-        a.images, a.IH, a.IW, a.img_stride, a.img_offset = _ptr(images), images.shape[2], images.shape[3], int(img_stride), int(img_offset)
-    a.tsdf, a.wsum, a.rgb = _ptr(tsdf), _ptr(wsum), _ptr(rgb)
-    a.nz, a.ny, a.nx = tsdf.shape
-    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
-    a.voxel, a.trunc, a.z_near, a.w_max = float(voxel), float(trunc), float(z_near), float(w_max)
+    _images(a, "tsdf_integrate", images, nf, img_stride, img_offset)
+    _fill_dense(a, tsdf, wsum, rgb, origin, voxel)
+    a.trunc, a.z_near, a.w_max = float(trunc), float(z_near), float(w_max)
     a.poses, a.disps, a.intrinsics, a.ix, a.weight = _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ix), _ptr(weight)
     a.N, a.nframes, a.ht, a.wd = N, nf, ht, wd
     p = _panoptic("tsdf_integrate", dev, tsdf.shape, nf, label, lconf, labels, label_div)
@@ -656,13 +715,9 @@ def tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out, label=None):
     (pvo_tsdf_mesh_panoptic).  No allocation beyond the cached workspace, no synchronisation."""
     dev = tsdf.device
     a = _lib.TsdfMeshArgs()
-    a.tsdf, a.wsum, a.rgb = _ptr(tsdf), _ptr(wsum), _ptr(rgb)
-    a.nz, a.ny, a.nx = tsdf.shape
-    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
-    a.voxel, a.min_weight = float(voxel), float(min_weight)
-    a.vcap, a.fcap = out["verts"].shape[0], out["faces"].shape[0]
-    a.verts, a.normals, a.rgba, a.faces = _ptr(out["verts"]), _ptr(out.get("normals")), _ptr(out.get("rgba")), _ptr(out["faces"])
-    a.counts = ctypes.c_void_p(out["counts"].data_ptr())
+    _fill_dense(a, tsdf, wsum, rgb, origin, voxel)
+    a.min_weight = float(min_weight)
+    _mesh_outputs(a, out)
     p = _mesh_labels("tsdf_mesh", out, label, tsdf.shape)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_mesh_workspace_bytes(a.nz, a.ny, a.nx))
@@ -684,33 +739,16 @@ def tsdf_mesh(tsdf, wsum, rgb, origin, voxel, min_weight=1.0, vcap=None, fcap=No
             _contig(t, n)
             _f32(t, n)
     dev = _dev(tsdf, wsum, rgb)
-    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
-        raise PvoHipError("tsdf_mesh: tsdf and wsum must be [nz,ny,nx], rgb [nz,ny,nx,3]")
+    _check_dense("tsdf_mesh", tsdf, wsum, rgb)
     nz, ny, nx = tsdf.shape
     cells = max(nz - 1, 0) * max(ny - 1, 0) * max(nx - 1, 0)
     vcap = min(cells, 8 * (nz * ny + ny * nx + nz * nx)) if vcap is None else int(vcap)
     fcap = 2 * vcap if fcap is None else int(fcap)
-    while True:
-        out = {"verts": torch.empty(vcap, 3, dtype=torch.float32, device=dev), "normals": torch.empty(vcap, 3, dtype=torch.float32, device=dev),
-               "rgba": torch.empty(vcap, 4, dtype=torch.uint8, device=dev), "faces": torch.empty(fcap, 3, dtype=torch.int32, device=dev),
-               "counts": torch.empty(2, dtype=torch.int32, device=dev)}
-        if label is not None:
-            out["vlabel"] = torch.empty(vcap, dtype=torch.int32, device=dev)
-        tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out, label=label)
-        nv, nf = out["counts"].tolist()                 # the one synchronisation
-        if nv <= vcap and nf <= fcap:
-            break
-        vcap, fcap = max(nv, vcap), max(nf, fcap)
-    for k in ("verts", "normals", "rgba", "vlabel"):
-        if k not in out:
-            continue
-        out[k] = out[k][:nv]
-    out["faces"] = out["faces"][:nf]
-    return out
+    return _mesh(lambda out: tsdf_mesh_into(tsdf, wsum, rgb, origin, voxel, min_weight, out, label=label), dev, vcap, fcap, label is not None)
 
 
 def _sparse_world(a, vol):
-    """the brick volume's fields every sparse call shares.  vol: a dict (pvo_amd.tsdf_sparse.SparseTSDF.volume()) with grid int32
+    """the brick volume's fields every sparse call shares, into those of them the struct `a` has.  vol: a dict (pvo_amd.tsdf_sparse.SparseTSDF.volume()) with grid int32
     [gz,gy,gx], coord int32 [cap,3], counts int32 [1], tsdf / wsum f32 [cap,8,8,8], rgb f32 [cap,8,8,8,3] or None, origin, voxel"""
     grid, coord, counts, tsdf, wsum, rgb = vol["grid"], vol["coord"], vol["counts"], vol["tsdf"], vol["wsum"], vol.get("rgb")
     for t, n in ((grid, "grid"), (coord, "coord"), (counts, "counts"), (tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")):
@@ -731,7 +769,10 @@ def _sparse_world(a, vol):
     a.cap = cap
     a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in vol["origin"]]
     a.voxel = float(vol["voxel"])
-    a.coord, a.bricks = _ptr(coord), _ptr(counts)
+    if hasattr(a, "coord"):
+        a.coord = _ptr(coord)
+    if hasattr(a, "bricks"):
+        a.bricks = _ptr(counts)
     return dev
 
 
@@ -778,18 +819,10 @@ def tsdf_sparse_integrate(vol, poses, disps, intrinsics, ix, trunc, weight=None,
     dev = _sparse_world(a, vol)
     _dev(vol["grid"], poses, disps, intrinsics, ix, weight, images)
     _sparse_frames(a, "tsdf_sparse_integrate", poses, disps, intrinsics, ix, weight)
-    if images is not None:
-        _contig(images, "images")
-        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < a.nframes or images.shape[1] != 3:
-            raise PvoHipError("tsdf_sparse_integrate: images must be uint8 [nframes,3,IH,IW]")
-        a.images, a.IH, a.IW, a.img_stride, a.img_offset = _ptr(images), images.shape[2], images.shape[3], int(img_stride), int(img_offset)
+    _images(a, "tsdf_sparse_integrate", images, a.nframes, img_stride, img_offset)
     a.tsdf, a.wsum, a.rgb = _ptr(vol["tsdf"]), _ptr(vol["wsum"]), _ptr(vol.get("rgb"))
     a.trunc, a.z_near, a.w_max = float(trunc), float(z_near), float(w_max)
-    if kept is not None:
-        _contig(kept, "kept")
-        if kept.dtype != torch.int32 or kept.numel() < a.cap or kept.device != dev:
-            raise PvoHipError("tsdf_sparse_integrate: kept must be an int32 device tensor of at least cap elements")
-        a.kept = _ptr(kept)
+    _kept(a, "tsdf_sparse_integrate", kept, dev)
     p = _panoptic("tsdf_sparse_integrate", dev, vol["tsdf"].shape, a.nframes, label, lconf, labels, label_div)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_sparse_integrate_workspace_bytes(a.N))
@@ -832,12 +865,7 @@ def _reintegrate_sets(a, what, dev, intrinsics, remove, add, images, img_stride,
     a.intrinsics = _ptr(intrinsics)
     if shape is not None:
         a.nframes, a.ht, a.wd = shape
-    if images is not None:
-        _contig(images, "images")
-        _dev(intrinsics, images)
-        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < a.nframes or images.shape[1] != 3:
-            raise PvoHipError("%s: images must be uint8 [nframes,3,IH,IW]" % what)
-        a.images, a.IH, a.IW, a.img_stride, a.img_offset = _ptr(images), images.shape[2], images.shape[3], int(img_stride), int(img_offset)
+    _images(a, what, images, a.nframes, img_stride, img_offset, same_device_as=intrinsics)
     return a.N_old, a.N
 
 
@@ -863,14 +891,11 @@ def tsdf_reintegrate(tsdf, wsum, rgb, origin, voxel, trunc, intrinsics, remove=N
             _contig(t, n)
             _f32(t, n)
     dev = _dev(tsdf, wsum, rgb, intrinsics)
-    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
-        raise PvoHipError("tsdf_reintegrate: tsdf and wsum must be [nz,ny,nx], rgb [nz,ny,nx,3]")
+    _check_dense("tsdf_reintegrate", tsdf, wsum, rgb)
     a = _lib.TsdfReintegrateArgs()
     n_old, n = _reintegrate_sets(a, "tsdf_reintegrate", dev, intrinsics, remove, add, images, img_stride, img_offset)
-    a.tsdf, a.wsum, a.rgb = _ptr(tsdf), _ptr(wsum), _ptr(rgb)
-    a.nz, a.ny, a.nx = tsdf.shape
-    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
-    a.voxel, a.trunc, a.z_near, a.w_max, a.w_floor = float(voxel), float(trunc), float(z_near), float(w_max), float(w_floor)
+    _fill_dense(a, tsdf, wsum, rgb, origin, voxel)
+    a.trunc, a.z_near, a.w_max, a.w_floor = float(trunc), float(z_near), float(w_max), float(w_floor)
     lib = _lib.load()
     ws = _reintegrate_workspace("tsdf_reintegrate", dev, lib.pvo_tsdf_reintegrate_workspace_bytes(n_old, n), workspace)
     with torch.cuda.device(dev):
@@ -889,11 +914,7 @@ def tsdf_sparse_reintegrate(vol, trunc, intrinsics, remove=None, add=None, image
     n_old, n = _reintegrate_sets(a, "tsdf_sparse_reintegrate", dev, intrinsics, remove, add, images, img_stride, img_offset)
     a.tsdf, a.wsum, a.rgb = _ptr(vol["tsdf"]), _ptr(vol["wsum"]), _ptr(vol.get("rgb"))
     a.trunc, a.z_near, a.w_max, a.w_floor = float(trunc), float(z_near), float(w_max), float(w_floor)
-    if kept is not None:
-        _contig(kept, "kept")
-        if kept.dtype != torch.int32 or kept.numel() < a.cap or kept.device != dev:
-            raise PvoHipError("tsdf_sparse_reintegrate: kept must be an int32 device tensor of at least cap elements")
-        a.kept = _ptr(kept)
+    _kept(a, "tsdf_sparse_reintegrate", kept, dev)
     lib = _lib.load()
     ws = _reintegrate_workspace("tsdf_sparse_reintegrate", dev, lib.pvo_tsdf_sparse_reintegrate_workspace_bytes(n_old, n), workspace)
     with torch.cuda.device(dev):
@@ -908,9 +929,7 @@ def tsdf_sparse_mesh_into(vol, min_weight, out, label=None):
     a.grid = _ptr(vol["grid"])
     a.tsdf, a.wsum, a.rgb = _ptr(vol["tsdf"]), _ptr(vol["wsum"]), _ptr(vol.get("rgb"))
     a.min_weight = float(min_weight)
-    a.vcap, a.fcap = out["verts"].shape[0], out["faces"].shape[0]
-    a.verts, a.normals, a.rgba, a.faces = _ptr(out["verts"]), _ptr(out.get("normals")), _ptr(out.get("rgba")), _ptr(out["faces"])
-    a.counts = ctypes.c_void_p(out["counts"].data_ptr())
+    _mesh_outputs(a, out)
     p = _mesh_labels("tsdf_sparse_mesh", out, label, vol["tsdf"].shape)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_sparse_mesh_workspace_bytes(a.cap))
@@ -929,23 +948,7 @@ def tsdf_sparse_mesh(vol, min_weight=1.0, vcap=None, fcap=None, label=None):
     cap = vol["tsdf"].shape[0]
     vcap = min(cap * _lib.TSDF_BRICK ** 3, max(1024, 96 * cap)) if vcap is None else int(vcap)
     fcap = 2 * vcap if fcap is None else int(fcap)
-    while True:
-        out = {"verts": torch.empty(vcap, 3, dtype=torch.float32, device=dev), "normals": torch.empty(vcap, 3, dtype=torch.float32, device=dev),
-               "rgba": torch.empty(vcap, 4, dtype=torch.uint8, device=dev), "faces": torch.empty(fcap, 3, dtype=torch.int32, device=dev),
-               "counts": torch.empty(2, dtype=torch.int32, device=dev)}
-        if label is not None:
-            out["vlabel"] = torch.empty(vcap, dtype=torch.int32, device=dev)
-        tsdf_sparse_mesh_into(vol, min_weight, out, label=label)
-        nv, nf = out["counts"].tolist()                 # the one synchronisation
-        if nv <= vcap and nf <= fcap:
-            break
-        vcap, fcap = max(nv, vcap), max(nf, fcap)
-    for k in ("verts", "normals", "rgba", "vlabel"):
-        if k not in out:
-            continue
-        out[k] = out[k][:nv]
-    out["faces"] = out["faces"][:nf]
-    return out
+    return _mesh(lambda out: tsdf_sparse_mesh_into(vol, min_weight, out, label=label), dev, vcap, fcap, label is not None)
 
 
 RENDER_MAX_SAMPLES = 65536                 # (z_far - z_near) / dz of pvo_tsdf_render
@@ -1030,17 +1033,14 @@ def tsdf_render(tsdf, wsum, rgb, origin, voxel, poses, intrinsics, ix, ht, wd, d
     for t, n in ((tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")):
         if t is not None:
             _f32(t, n)
-    if tsdf.dim() != 3 or wsum.shape != tsdf.shape or (rgb is not None and tuple(rgb.shape) != tuple(tsdf.shape) + (3,)):
-        raise PvoHipError("tsdf_render: tsdf and wsum must be [nz,ny,nx], rgb [nz,ny,nx,3]")
+    _check_dense("tsdf_render", tsdf, wsum, rgb)
     if label is not None and (label.dtype != torch.int32 or label.shape != tsdf.shape):
         raise PvoHipError("tsdf_render: label must be int32 with the shape of tsdf")
     a = _lib.TsdfRenderArgs()
     out = _render_views(a, "tsdf_render", dev, poses, intrinsics, ix, ht, wd, label, normals, out)
     a.dz, a.z_near, a.z_far = _render_range("tsdf_render", tsdf.shape, origin, voxel, poses, ix, dz, z_near, z_far)
-    a.tsdf, a.wsum, a.rgb, a.label = _ptr(tsdf), _ptr(wsum), _ptr(rgb), _ptr(label)
-    a.nz, a.ny, a.nx = tsdf.shape
-    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
-    a.voxel, a.min_weight = float(voxel), float(min_weight)
+    _fill_dense(a, tsdf, wsum, rgb, origin, voxel)
+    a.label, a.min_weight = _ptr(label), float(min_weight)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_render_workspace_bytes(a.N))
     with torch.cuda.device(dev):
@@ -1054,16 +1054,13 @@ def tsdf_sparse_render(vol, poses, intrinsics, ix, ht, wd, dz=None, z_near=0.0, 
     render over the [8gz,8gy,8gx] volume that holds the bricks, with rays jumping over bricks that do not exist.  label: the label pool
     int32 [cap,8,8,8].  Defaults (dz = 0.5 * voxel, z_far from the world's box), out= and the sample limit as in tsdf_render."""
     a = _lib.TsdfSparseRenderArgs()
-    c = _lib.TsdfSparseMeshArgs()                          # (the checks and the world's fields: _sparse_world fills coord / bricks too)
-    dev = _sparse_world(c, vol)
+    dev = _sparse_world(a, vol)
     _dev(vol["grid"], poses, intrinsics, ix, label)
     if label is not None:
         _contig(label, "label")
         if label.dtype != torch.int32 or label.shape != vol["tsdf"].shape:
             raise PvoHipError("tsdf_sparse_render: label must be int32 with the shape of the pool")
-    a.gz, a.gy, a.gx, a.cap = c.gz, c.gy, c.gx, c.cap
-    a.origin[0], a.origin[1], a.origin[2] = c.origin[0], c.origin[1], c.origin[2]
-    a.voxel, a.min_weight = c.voxel, float(min_weight)
+    a.min_weight = float(min_weight)
     out = _render_views(a, "tsdf_sparse_render", dev, poses, intrinsics, ix, ht, wd, label, normals, out)
     B = _lib.TSDF_BRICK
     a.dz, a.z_near, a.z_far = _render_range("tsdf_sparse_render", (B * a.gz, B * a.gy, B * a.gx), vol["origin"], vol["voxel"], poses, ix,
@@ -1141,15 +1138,12 @@ def tsdf_track(tsdf, wsum, origin, voxel, poses, disps, intrinsics, ix, weight=N
     _contig(tsdf, "tsdf"); _contig(wsum, "wsum")
     dev = _dev(tsdf, wsum, poses, disps, intrinsics, ix, weight)
     _f32(tsdf, "tsdf"); _f32(wsum, "wsum")
-    if tsdf.dim() != 3 or wsum.shape != tsdf.shape:
-        raise PvoHipError("tsdf_track: tsdf and wsum must be [nz,ny,nx]")
+    _check_dense("tsdf_track", tsdf, wsum, with_rgb=False)
     a = _lib.TsdfTrackArgs()
     out = _track_frames(a, "tsdf_track", dev, poses, disps, intrinsics, ix, weight, iters, band, huber, lm, ep, min_count, system, residual,
                         jac, out)
-    a.tsdf, a.wsum = _ptr(tsdf), _ptr(wsum)
-    a.nz, a.ny, a.nx = tsdf.shape
-    a.origin[0], a.origin[1], a.origin[2] = [float(v) for v in origin]
-    a.voxel, a.min_weight = float(voxel), float(min_weight)
+    _fill_dense(a, tsdf, wsum, None, origin, voxel)
+    a.min_weight = float(min_weight)
     lib = _lib.load()
     ws = _workspace(dev, lib.pvo_tsdf_track_workspace_bytes(a.N, a.ht, a.wd))
     with torch.cuda.device(dev):
@@ -1163,12 +1157,9 @@ def tsdf_sparse_track(vol, poses, disps, intrinsics, ix, weight=None, iters=10, 
     the bytes of tsdf_track over the [8gz,8gy,8gx] volume that holds the bricks.  Parameters, defaults (which rest on nothing measured
     on real sequences), outputs and out= as in tsdf_track."""
     a = _lib.TsdfSparseTrackArgs()
-    c = _lib.TsdfSparseMeshArgs()                          # (the checks and the world's fields: _sparse_world fills coord / bricks too)
-    dev = _sparse_world(c, vol)
+    dev = _sparse_world(a, vol)
     _dev(vol["grid"], poses, disps, intrinsics, ix, weight)
-    a.gz, a.gy, a.gx, a.cap = c.gz, c.gy, c.gx, c.cap
-    a.origin[0], a.origin[1], a.origin[2] = c.origin[0], c.origin[1], c.origin[2]
-    a.voxel, a.min_weight = c.voxel, float(min_weight)
+    a.min_weight = float(min_weight)
     out = _track_frames(a, "tsdf_sparse_track", dev, poses, disps, intrinsics, ix, weight, iters, band, huber, lm, ep, min_count, system,
                         residual, jac, out)
     a.grid, a.tsdf, a.wsum = _ptr(vol["grid"]), _ptr(vol["tsdf"]), _ptr(vol["wsum"])

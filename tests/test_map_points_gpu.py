@@ -98,6 +98,24 @@ def test_points_are_within_the_derived_bound(cuda, name, th):
         assert np.all(err <= ref["bound"][:, None])
 
 
+def test_more_workgroups_than_scan_threads(cuda):
+    """5 frames of 240 x 240: 5 * 225 = 1125 per-workgroup counts, so every thread of the one-workgroup scan owns MORE than one
+    (the scenes above stop at 60).  frame_start, the selection and the points against the reference."""
+    from pvo_amd import droid_backends as db
+    nf, ht, wd, th = 5, 240, 240, 0.2
+    assert nf * -(-ht * wd // 256) > 1024
+    poses, disps, intr = M.scene(M.SEED, nf, ht, wd, 0.02)
+    poses_d, disps_d, intr_d = poses.to(cuda), disps.to(cuda), intr.to(cuda)
+    ix = [3, 0, 4, 1, 2]
+    got = _host(db.map_points(poses_d, disps_d, intr_d, torch.tensor(ix, dtype=torch.long, device=cuda), torch.full((nf,), th, device=cuda)))
+    ref = M.map_reference(poses.numpy(), disps.numpy(), intr.numpy(), ix, _votes(cuda, poses_d, disps_d, intr_d, ix, th))
+    print("240x240x5: %d points, frame_start %s" % (ref["total"], ref["frame_start"].tolist()))
+    _assert_selection(got, ref)
+    assert ref["total"] > 0
+    err = np.abs(got["xyz"].astype(np.float64) - ref["xyz"])
+    assert np.all(err <= ref["bound"][:, None])
+
+
 def _buffers(cuda, cap, N, label=False):
     fill = lambda nbytes, dt: torch.full((cap, nbytes), SENTINEL, dtype=torch.uint8, device=cuda).view(dt)
     out = {"xyz": fill(12, torch.float32), "rgba": fill(4, torch.uint8), "src": fill(8, torch.int32),

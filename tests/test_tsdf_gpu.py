@@ -244,6 +244,37 @@ def test_mesh_of_volumes_without_a_surface(cuda):
 _system = {}
 
 
+def test_mesh_with_more_workgroups_than_scan_threads(cuda):
+    """[66,66,66]: 65^3 = 274 625 cells in 1073 workgroups, so every thread of the one-workgroup scan owns MORE than one count (the
+    fused scenes stop at 95 workgroups).  The volume is an analytic sphere, not a fusion: counts, the active cells in raster order
+    and the faces equal the reference's, vertices and normals lie within its bounds."""
+    from pvo_amd import droid_backends as db
+    dims, origin, voxel = (66, 66, 66), (-1.0, -0.5, 0.25), 0.05
+    tsdf = R.sphere_volume(dims, (32.3, 31.6, 33.7), 18.4, 3.0, cuda)
+    wsum = torch.ones_like(tsdf)
+    lib_blocks = -(-65 ** 3 // 256)
+    assert lib_blocks == 1073 and lib_blocks > 1024
+    host = tsdf.cpu().numpy()
+    assert not (host == 0).any()                                        # (no corner sits on the surface: inside / outside is unambiguous)
+    ref = R.mesh_reference(host, wsum.cpu().numpy(), None, origin, voxel, 1.0)
+    V, F = len(ref["verts"]), len(ref["faces"])
+    m = {k: v.cpu().numpy() for k, v in db.tsdf_mesh(tsdf, wsum, None, origin, voxel, min_weight=1.0).items()}
+    print("sphere in %s: %d vertices, %d faces" % (list(dims), V, F))
+    assert V > 20 and F > 20
+    assert m["counts"].tolist() == [V, F] and m["verts"].shape == (V, 3) and m["faces"].shape == (F, 3)
+    assert np.array_equal(m["faces"], ref["faces"])
+    # vertex i within the bound (some 1e-6) of the vertex of the reference's i-th active cell, whose neighbours are a voxel (0.05)
+    # away: the set of active cells and their raster order
+    ev = np.abs(m["verts"].astype(np.float64) - ref["verts"])
+    en = np.abs(m["normals"].astype(np.float64) - ref["normals"]).max(1)
+    print("   vertices: max error %.3e, max error / bound %.3f; normals: max error / bound %.3f"
+          % (ev.max(), (ev / ref["bound_v"]).max(), (en / ref["bound_n"]).max()))
+    assert np.all(ev <= ref["bound_v"]) and np.all(en <= ref["bound_n"])
+    # the active cells spread over many workgroups, with empty ones between them
+    groups = np.unique(((ref["cells"][:, 0] * 65 + ref["cells"][:, 1]) * 65 + ref["cells"][:, 2]) // 256)
+    assert 100 < len(groups) < lib_blocks
+
+
 def _droid(cuda):
     """a Droid whose video holds the analytic scene at 1/8 of 192 x 256 images: five keyframes, random colours"""
     if "droid" not in _system:

@@ -1,5 +1,5 @@
 """Panoptic surface reconstruction on the device: pvo_tsdf[_sparse]_integrate_panoptic and pvo_tsdf[_sparse]_mesh_panoptic
-(pvo_amd/csrc/tsdf_fuse.h, tsdf.hip, tsdf_sparse.hip) against tests/tsdf_panoptic_reference.py.  tsdf / wsum / rgb must be the BYTES the
+(pvo_amd/csrc/tsdf_fuse.h, tsdf_mesh.h, tsdf.hip, tsdf_sparse.hip) against tests/tsdf_panoptic_reference.py.  tsdf / wsum / rgb must be the BYTES the
 plain calls leave; label and lconf EQUAL to the reference on every touched voxel whose decisions are not within rounding of flipping
 (at most 1 % are); four deliberately wrong references that the same check must reject; split calls; bricks against the dense call;
 the vertex labels EQUAL to the rule on the kernel's own volume, with the plain mesh outputs unchanged; capture and replay; the system

@@ -355,13 +355,8 @@ def _meshed(cuda, name, weight=True):
     return _cache[key]
 
 
-@pytest.mark.parametrize("name", list(SR.SCENES))
-def test_mesh_equals_the_dense_mesh_of_the_densified_volume(cuda, name):
-    from pvo_amd import droid_backends as db
-    vol = _meshed(cuda, name)
-    d = vol.to_dense()
-    dense = {k: v.cpu().numpy() for k, v in db.tsdf_mesh(d["tsdf"], d["wsum"], d["rgb"], vol.origin, vol.voxel, min_weight=1.0).items()}
-    sparse = {k: v.cpu().numpy() for k, v in vol.mesh(min_weight=1.0).items()}
+def _assert_the_dense_mesh_in_sparse_order(name, vol, d, dense, sparse):
+    """sparse = the dense mesh of the densified volume d under the permutation _sparse_order, byte for byte; returns (V, F)"""
     V, F = dense["counts"].tolist()
     print("%s: %d vertices, %d faces" % (name, V, F))
     assert V > 20 and F > 20 and sparse["counts"].tolist() == [V, F]
@@ -378,6 +373,17 @@ def test_mesh_equals_the_dense_mesh_of_the_densified_volume(cuda, name):
     assert sorted(map(tuple, mapped)) == sorted(map(tuple, sparse["faces"]))
     # faces: by the owning cell (a face's first vertex) in sparse order, then axis - the dense order is (cell, axis) as well
     assert np.array_equal(sparse["faces"], mapped[np.argsort(mapped[:, 0], kind="stable")])
+    return V, F
+
+
+@pytest.mark.parametrize("name", list(SR.SCENES))
+def test_mesh_equals_the_dense_mesh_of_the_densified_volume(cuda, name):
+    from pvo_amd import droid_backends as db
+    vol = _meshed(cuda, name)
+    d = vol.to_dense()
+    dense = {k: v.cpu().numpy() for k, v in db.tsdf_mesh(d["tsdf"], d["wsum"], d["rgb"], vol.origin, vol.voxel, min_weight=1.0).items()}
+    sparse = {k: v.cpu().numpy() for k, v in vol.mesh(min_weight=1.0).items()}
+    V, F = _assert_the_dense_mesh_in_sparse_order(name, vol, d, dense, sparse)
     # the capacity protocol: one short of the need - full counts, nothing behind the capacity, the front unchanged
     short = _mesh_buffers(cuda, V - 1, F - 1)
     db.tsdf_sparse_mesh_into(vol.volume(), 1.0, short)
@@ -394,6 +400,33 @@ def test_mesh_equals_the_dense_mesh_of_the_densified_volume(cuda, name):
     assert none["counts"].tolist() == [0, 0] and bool((none["verts"].view(torch.uint8) == SENTINEL).all())
     empty = _volume(cuda, name)
     assert empty.mesh()["counts"].tolist() == [0, 0]
+
+
+def test_mesh_with_more_bricks_than_scan_threads(cuda):
+    """a world of 11 x 10 x 10 bricks, every one allocated: 1100 slots, so every thread of the one-workgroup scan owns MORE than one
+    count (the fused scenes hold a few dozen bricks).  The pool holds an analytic sphere (tests/tsdf_reference.sphere_volume) with
+    wsum = 1 and a colour ramp; the mesh equals the dense mesh of the densified volume as in the test above."""
+    from pvo_amd import droid_backends as db
+    from pvo_amd.tsdf_sparse import SparseTSDF
+    gdims = (11, 10, 10)
+    gz, gy, gx = gdims
+    vol = _fill(SparseTSDF((-1.0, -0.5, 0.25), gdims, 0.05, 0.15, colours=True, device=cuda, cap=1100))
+    assert vol.bricks == 1100 and vol.cap >= 1100 > 1024
+    dims = (8 * gz, 8 * gy, 8 * gx)
+    field = R.sphere_volume(dims, (40.3, 39.6, 43.7), 30.4, 3.0, cuda)
+    assert not bool((field == 0).any())
+    z, y, x = torch.meshgrid(*[torch.arange(n, dtype=torch.float32, device=cuda) for n in dims], indexing="ij")
+    ramp = torch.stack([(3 * x) % 256, (5 * y) % 256, (7 * z) % 256], -1)
+    to_pool = lambda t: t.view((gz, 8, gy, 8, gx, 8) + tuple(t.shape[3:])).permute(*((0, 2, 4, 1, 3, 5) + tuple(range(6, 3 + t.dim())))) \
+        .reshape((gz * gy * gx, 8, 8, 8) + tuple(t.shape[3:]))          # (_fill: slot = raster index of the brick)
+    vol.tsdf[:1100] = to_pool(field)
+    vol.wsum[:1100] = 1.0
+    vol.rgb[:1100] = to_pool(ramp)
+    d = vol.to_dense()
+    assert torch.equal(d["tsdf"], field) and torch.equal(d["rgb"], ramp)
+    dense = {k: v.cpu().numpy() for k, v in db.tsdf_mesh(d["tsdf"], d["wsum"], d["rgb"], vol.origin, vol.voxel, min_weight=1.0).items()}
+    sparse = {k: v.cpu().numpy() for k, v in vol.mesh(min_weight=1.0).items()}
+    _assert_the_dense_mesh_in_sparse_order("sphere in 11x10x10 bricks", vol, d, dense, sparse)
 
 
 def test_mesh_is_closed_inside_allocated_space_and_lies_on_the_surface(cuda):

@@ -286,6 +286,17 @@ def mesh_reference(tsdf, wsum, rgb, origin, voxel, min_weight=1.0):
                 E_col=EPS * (7 * 2040 + 256), cell_valid=all_valid)
 
 
+def sphere_volume(dims, centre, radius, trunc, device):
+    """torch f32 [nz,ny,nx] on `device`: the signed distance of every voxel index (x,y,z) to the sphere |p - centre| = radius (all in
+    voxels), divided by trunc and clamped to [-1, 1] - a closed surface for the mesh tests that need more cells than a fused scene has"""
+    import torch
+    nz, ny, nx = dims
+    ar = lambda n: torch.arange(n, dtype=torch.float32, device=device)
+    z, y, x = torch.meshgrid(ar(nz), ar(ny), ar(nx), indexing="ij")
+    d = torch.sqrt((x - centre[0]) ** 2 + (y - centre[1]) ** 2 + (z - centre[2]) ** 2) - radius
+    return torch.clamp(d / trunc, -1.0, 1.0).contiguous()
+
+
 def edge_shares(faces):
     """{(i, j) with i < j: the number of triangles that use the edge}"""
     from collections import Counter
