@@ -10,155 +10,133 @@ namespace {
 
 struct EdgeGeom { Pose G; float fx, fy, cx, cy; };
 
+// One pixel of an edge, projected (projective_transform_kernel, droid_kernels.cu:266-357): the target point (x, y, 1 / d, hh),
+// the MIN_DEPTH test, and per residual row (u, v) the weight w and the residual r.  The ONE statement of these float expressions:
+// the assembly, the stereo edges and the calibration stage all form their terms from it, so they agree bit for bit.
+struct EdgePixel { float x, y, hh, d, d2, wu, wv, ru, rv; bool ok; };
+
+__device__ __forceinline__ EdgePixel project_pixel(const EdgeGeom& g, float u, float v, float disp,
+                                                   float tu, float tv, float wgu, float wgv) {
+  float Xi[4] = {(u - g.cx) / g.fx, (v - g.cy) / g.fy, 1.0f, disp};
+  float Xj[4];
+  act4(g.G, Xi, Xj);
+  EdgePixel p;
+  p.x = Xj[0]; p.y = Xj[1]; p.hh = Xj[3];
+  p.ok = !(Xj[2] < kMinDepth);
+  p.d = p.ok ? 1.0f / Xj[2] : 0.0f;
+  p.d2 = p.d * p.d;
+  // droid_kernels.cu:290-291 write `.001 * weight`: a DOUBLE literal, so the product is formed in double and rounded to
+  // float once - not the same number as 0.001f * w (0.001f != 0.001).  Followed literally; `1.0 / Xj[2]` (:287) equals the
+  // correctly rounded float division (double rounding of a quotient is innocuous at 53 >= 2 * 24 + 2 bits).
+  p.wu = p.ok ? static_cast<float>(0.001 * static_cast<double>(wgu)) : 0.0f;
+  p.wv = p.ok ? static_cast<float>(0.001 * static_cast<double>(wgv)) : 0.0f;
+  p.ru = tu - (g.fx * p.d * p.x + g.cx);
+  p.rv = tv - (g.fy * p.d * p.y + g.cy);
+  return p;
+}
+
+// Jz = d(residual row)/d(disparity); ROW 0 = u, 1 = v
+template <int ROW>
+__device__ __forceinline__ float depth_jacobian(const EdgeGeom& g, const EdgePixel& p) {
+  if constexpr (ROW == 0) return g.fx * (g.G.t.x * p.d - g.G.t.z * (p.x * p.d2));
+  else return g.fy * (g.G.t.y * p.d - g.G.t.z * (p.y * p.d2));
+}
+
+// J = [Ji | Jj] of one residual row: Jj, then Ji = -Ad^T Jj
+template <int ROW>
+__device__ __forceinline__ void pose_jacobian(const EdgeGeom& g, const EdgePixel& p, float (&J)[12]) {
+  const float x = p.x, y = p.y, hh = p.hh, d = p.d, d2 = p.d2;
+  if constexpr (ROW == 0) {
+    J[6] = g.fx * (hh * d); J[7] = 0.0f; J[8] = g.fx * (-x * hh * d2);
+    J[9] = g.fx * (-x * y * d2); J[10] = g.fx * (1.0f + x * x * d2); J[11] = g.fx * (-y * d);
+  } else {
+    J[6] = 0.0f; J[7] = g.fy * (hh * d); J[8] = g.fy * (-y * hh * d2);
+    J[9] = g.fy * (-1.0f - y * y * d2); J[10] = g.fy * (x * y * d2); J[11] = g.fy * (x * d);
+  }
+  adjT(g.G, &J[6], &J[0]);
+#pragma unroll
+  for (int n = 0; n < 6; ++n) J[n] = -J[n];
+}
+
+// one residual row of pixel_terms: row 0 starts the depth-coupling terms, row 1 adds to them
+template <int ROW>
+__device__ __forceinline__ void pixel_row_terms(const EdgeGeom& g, const EdgePixel& p,
+                                                float (&h)[78], float (&vi)[6], float (&vj)[6],
+                                                float (&eii)[6], float (&eij)[6], float& cii, float& bzz) {
+  const float w = ROW == 0 ? p.wu : p.wv, r = ROW == 0 ? p.ru : p.rv;
+  float J[12];
+  pose_jacobian<ROW>(g, p, J);
+  const float Jz = depth_jacobian<ROW>(g, p);
+  {
+    int l = 0;
+#pragma unroll
+    for (int n = 0; n < 12; ++n) {
+      const float wj = w * J[n];
+#pragma unroll
+      for (int m = 0; m <= n; ++m) { h[l] += wj * J[m]; ++l; }
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < 6; ++n) {
+    vi[n] += w * r * J[n];
+    vj[n] += w * r * J[6 + n];
+    if constexpr (ROW == 0) { eii[n] = w * Jz * J[n]; eij[n] = w * Jz * J[6 + n]; }
+    else { eii[n] += w * Jz * J[n]; eij[n] += w * Jz * J[6 + n]; }
+  }
+  if constexpr (ROW == 0) { cii = w * Jz * Jz; bzz = w * r * Jz; }
+  else { cii += w * Jz * Jz; bzz += w * r * Jz; }
+}
+
 // one pixel of projective_transform_kernel (droid_kernels.cu:266-357): accumulates the
 // upper triangle h[78] of [Ji Jj]^T W [Ji Jj], the gradients vi/vj, and returns the
-// depth-coupling terms.
+// depth-coupling terms.  The two rows in turn: one J[12] is live at a time.
 __device__ __forceinline__ void pixel_terms(const EdgeGeom& g, float u, float v, float disp,
                                             float tu, float tv, float wgu, float wgv,
                                             float (&h)[78], float (&vi)[6], float (&vj)[6],
                                             float (&eii)[6], float (&eij)[6], float& cii, float& bzz) {
-  float Xi[4] = {(u - g.cx) / g.fx, (v - g.cy) / g.fy, 1.0f, disp};
-  float Xj[4];
-  act4(g.G, Xi, Xj);
-  const float x = Xj[0], y = Xj[1], hh = Xj[3];
-  const bool ok = !(Xj[2] < kMinDepth);
-  const float d = ok ? 1.0f / Xj[2] : 0.0f;
-  const float d2 = d * d;
-  // droid_kernels.cu:290-291 write `.001 * weight`: a DOUBLE literal, so the product is formed in double and rounded to
-  // float once - not the same number as 0.001f * w (0.001f != 0.001).  Followed literally; `1.0 / Xj[2]` (:287) equals the
-  // correctly rounded float division (double rounding of a quotient is innocuous at 53 >= 2 * 24 + 2 bits).
-  const float wu = ok ? static_cast<float>(0.001 * static_cast<double>(wgu)) : 0.0f;
-  const float wv = ok ? static_cast<float>(0.001 * static_cast<double>(wgv)) : 0.0f;
-  const float ru = tu - (g.fx * d * x + g.cx);
-  const float rv = tv - (g.fy * d * y + g.cy);
-  float J[12];   // [Ji | Jj]
-  float Jz;
-  // ---- x residual
-  J[6] = g.fx * (hh * d); J[7] = 0.0f; J[8] = g.fx * (-x * hh * d2);
-  J[9] = g.fx * (-x * y * d2); J[10] = g.fx * (1.0f + x * x * d2); J[11] = g.fx * (-y * d);
-  Jz = g.fx * (g.G.t.x * d - g.G.t.z * (x * d2));
-  adjT(g.G, &J[6], &J[0]);
-#pragma unroll
-  for (int n = 0; n < 6; ++n) J[n] = -J[n];
-  {
-    int l = 0;
-#pragma unroll
-    for (int n = 0; n < 12; ++n) {
-      const float wj = wu * J[n];
-#pragma unroll
-      for (int m = 0; m <= n; ++m) { h[l] += wj * J[m]; ++l; }
-    }
-  }
-#pragma unroll
-  for (int n = 0; n < 6; ++n) {
-    vi[n] += wu * ru * J[n];
-    vj[n] += wu * ru * J[6 + n];
-    eii[n] = wu * Jz * J[n];
-    eij[n] = wu * Jz * J[6 + n];
-  }
-  cii = wu * Jz * Jz;
-  bzz = wu * ru * Jz;
-  // ---- y residual
-  J[6] = 0.0f; J[7] = g.fy * (hh * d); J[8] = g.fy * (-y * hh * d2);
-  J[9] = g.fy * (-1.0f - y * y * d2); J[10] = g.fy * (x * y * d2); J[11] = g.fy * (x * d);
-  Jz = g.fy * (g.G.t.y * d - g.G.t.z * (y * d2));
-  adjT(g.G, &J[6], &J[0]);
-#pragma unroll
-  for (int n = 0; n < 6; ++n) J[n] = -J[n];
-  {
-    int l = 0;
-#pragma unroll
-    for (int n = 0; n < 12; ++n) {
-      const float wj = wv * J[n];
-#pragma unroll
-      for (int m = 0; m <= n; ++m) { h[l] += wj * J[m]; ++l; }
-    }
-  }
-#pragma unroll
-  for (int n = 0; n < 6; ++n) {
-    vi[n] += wv * rv * J[n];
-    vj[n] += wv * rv * J[6 + n];
-    eii[n] += wv * Jz * J[n];
-    eij[n] += wv * Jz * J[6 + n];
-  }
-  cii += wv * Jz * Jz;
-  bzz += wv * rv * Jz;
+  const EdgePixel p = project_pixel(g, u, v, disp, tu, tv, wgu, wgv);
+  pixel_row_terms<0>(g, p, h, vi, vj, eii, eij, cii, bzz);
+  pixel_row_terms<1>(g, p, h, vi, vj, eii, eij, cii, bzz);
 }
 
 // one pixel of a STEREO edge (i, i): g.G is the rig's fixed transform, so the residual depends on no pose - only the depth terms
-// remain.  The projection, the Z test, the weights and Jz are pixel_terms' own expressions in its own order.
+// remain.
 __device__ __forceinline__ void stereo_pixel_terms(const EdgeGeom& g, float u, float v, float disp,
                                                    float tu, float tv, float wgu, float wgv, float& cii, float& bzz) {
-  float Xi[4] = {(u - g.cx) / g.fx, (v - g.cy) / g.fy, 1.0f, disp};
-  float Xj[4];
-  act4(g.G, Xi, Xj);
-  const float x = Xj[0], y = Xj[1];
-  const bool ok = !(Xj[2] < kMinDepth);
-  const float d = ok ? 1.0f / Xj[2] : 0.0f;
-  const float d2 = d * d;
-  const float wu = ok ? static_cast<float>(0.001 * static_cast<double>(wgu)) : 0.0f;
-  const float wv = ok ? static_cast<float>(0.001 * static_cast<double>(wgv)) : 0.0f;
-  const float ru = tu - (g.fx * d * x + g.cx);
-  const float rv = tv - (g.fy * d * y + g.cy);
-  float Jz = g.fx * (g.G.t.x * d - g.G.t.z * (x * d2));
-  cii = wu * Jz * Jz;
-  bzz = wu * ru * Jz;
-  Jz = g.fy * (g.G.t.y * d - g.G.t.z * (y * d2));
-  cii += wv * Jz * Jz;
-  bzz += wv * rv * Jz;
+  const EdgePixel p = project_pixel(g, u, v, disp, tu, tv, wgu, wgv);
+  float Jz = depth_jacobian<0>(g, p);
+  cii = p.wu * Jz * Jz;
+  bzz = p.wu * p.ru * Jz;
+  Jz = depth_jacobian<1>(g, p);
+  cii += p.wv * Jz * Jz;
+  bzz += p.wv * p.rv * Jz;
 }
 
-// Entry t of an edge's 90 sums - upper triangle of [Ji Jj]^T W [Ji Jj] (78, droid_kernels.cu:309-315 ordering), vi (6), vj (6) -
-// added to the pose system in fixed point.
-__device__ __forceinline__ void pose_block_scatter(int t, double val, int pi, int pj, int P, long long* __restrict__ sys, int* __restrict__ meta) {
-  const bool iok = pi >= 0 && pi < P, jok = pj >= 0 && pj < P;
-  const int n6 = 6 * P;
-  if (t < 78) {
-    // invert l -> (n, m), m <= n
-    int n = 0, base = 0;
-    while (base + n + 1 <= t) { base += n + 1; ++n; }
-    const int m = t - base;
-    if (n < 6) {                                  // (ii,ii), symmetric
-      if (iok) {
-        fix_add(sys, static_cast<long long>(6 * pi + n) * n6 + 6 * pi + m, val, meta);
-        if (n != m) fix_add(sys, static_cast<long long>(6 * pi + m) * n6 + 6 * pi + n, val, meta);
-      }
-    } else if (m < 6) {                           // (ii,jj)[m][n-6] and (jj,ii)[n-6][m]
-      // only the LOWER block triangle of the system is ever read (the solve factorises it; an edge-sharded run all-reduces
-      // exactly those blocks): of the two mirrored off-diagonal blocks the one above the diagonal is not written.  Nothing at
-      // window size; a global bundle adjustment's Schur kernel is bound by these atomics (round 4)
-      if (iok && jok) {
-        if (pi > pj) fix_add(sys, static_cast<long long>(6 * pi + m) * n6 + 6 * pj + (n - 6), val, meta);
-        else fix_add(sys, static_cast<long long>(6 * pj + (n - 6)) * n6 + 6 * pi + m, val, meta);
-      }
-    } else {                                      // (jj,jj), symmetric
-      if (jok) {
-        fix_add(sys, static_cast<long long>(6 * pj + n - 6) * n6 + 6 * pj + m - 6, val, meta);
-        if (n != m) fix_add(sys, static_cast<long long>(6 * pj + m - 6) * n6 + 6 * pj + n - 6, val, meta);
-      }
-    }
-  } else if (t < 84) {
-    if (iok) fix_add(sys, static_cast<long long>(n6) * n6 + 6 * pi + (t - 78), val, meta);
-  } else {
-    if (jok) fix_add(sys, static_cast<long long>(n6) * n6 + 6 * pj + (t - 84), val, meta);
-  }
+// t -> (n, m), m <= n: the inverse of the row-major rank t = n (n + 1) / 2 + m of a triangle's entry
+__device__ __forceinline__ void tri_unrank(int t, int& n, int& m) {
+  int base = 0;
+  n = 0;
+  while (base + n + 1 <= t) { base += n + 1; ++n; }
+  m = t - base;
 }
 
-// The (at most two) entries of the pose system pose_block_scatter adds entry t of edge (pi -> pj) to; -1 = none.  Same case
-// analysis, kept beside it.
+// The (at most two) entries of the pose system that entry t of an edge's 90 sums - upper triangle of [Ji Jj]^T W [Ji Jj] (78,
+// droid_kernels.cu:309-315 ordering), vi (6), vj (6) - of edge (pi -> pj) is added to; -1 = none.
 __device__ __forceinline__ void pose_block_targets(int t, int pi, int pj, int P, long long idx[2]) {
   const bool iok = pi >= 0 && pi < P, jok = pj >= 0 && pj < P;
   const long long n6 = 6 * P;
   idx[0] = idx[1] = -1;
   if (t < 78) {
-    int n = 0, base = 0;
-    while (base + n + 1 <= t) { base += n + 1; ++n; }
-    const int m = t - base;
-    if (n < 6) {
+    int n, m;
+    tri_unrank(t, n, m);
+    if (n < 6) {                                  // (ii,ii), symmetric
       if (iok) { idx[0] = (6 * pi + n) * n6 + 6 * pi + m; if (n != m) idx[1] = (6 * pi + m) * n6 + 6 * pi + n; }
-    } else if (m < 6) {
+    } else if (m < 6) {                           // (ii,jj)[m][n-6] and (jj,ii)[n-6][m]
+      // only the LOWER block triangle of the system is ever read (the solve factorises it; an edge-sharded run all-reduces
+      // exactly those blocks): of the two mirrored off-diagonal blocks the one above the diagonal is not written.  Nothing at
+      // window size; a global bundle adjustment's Schur kernel is bound by these atomics (round 4)
       if (iok && jok) idx[0] = (pi > pj) ? (6 * pi + m) * n6 + 6 * pj + (n - 6) : (6 * pj + (n - 6)) * n6 + 6 * pi + m;
-    } else {
+    } else {                                      // (jj,jj), symmetric
       if (jok) { idx[0] = (6 * pj + n - 6) * n6 + 6 * pj + m - 6; if (n != m) idx[1] = (6 * pj + m - 6) * n6 + 6 * pj + n - 6; }
     }
   } else if (t < 84) {
@@ -166,6 +144,14 @@ __device__ __forceinline__ void pose_block_targets(int t, int pi, int pj, int P,
   } else {
     if (jok) idx[0] = n6 * n6 + 6 * pj + (t - 84);
   }
+}
+
+// ... and the sum itself added there in fixed point
+__device__ __forceinline__ void pose_block_scatter(int t, double val, int pi, int pj, int P, long long* __restrict__ sys, int* __restrict__ meta) {
+  long long idx[2];
+  pose_block_targets(t, pi, pj, P, idx);
+  if (idx[0] >= 0) fix_add(sys, idx[0], val, meta);
+  if (idx[1] >= 0) fix_add(sys, idx[1], val, meta);
 }
 
 __global__ __launch_bounds__(256) void ba_assemble_kernel(

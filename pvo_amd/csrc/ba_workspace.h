@@ -90,13 +90,15 @@ __host__ __device__ __forceinline__ int schur_stage_slot(int frame, int t0, int 
 }
 
 __host__ size_t align_up(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
+// the host's bound on the depth frames K = |unique([t0, t1) U ii)| of a call: rows of Q / w, and of every grid over depth frames
+__host__ int depth_rows_bound(int nframes, int P, int E) { return (nframes < P + E) ? nframes : (P + E); }
 
 __host__ Ws carve(void* base, int E, int P, int F, int HW) {
   Ws w{};
   char* p = static_cast<char*>(base);
   size_t off = 0;
   auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-  const int Kmax = (F < P + E) ? F : (P + E);
+  const int Kmax = depth_rows_bound(F, P, E);
   const size_t n6 = static_cast<size_t>(6) * (P > 0 ? P : 0);
   w.plan.kidx = reinterpret_cast<int*>(take(sizeof(int) * (F + 1)));
   w.plan.kx = reinterpret_cast<int*>(take(sizeof(int) * (F + 1)));

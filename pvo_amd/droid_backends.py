@@ -1393,6 +1393,39 @@ def _sens_map(disps_sens, disps, what):
         raise PvoHipError("%s: disps_sens must have disps' shape %s and device" % (what, tuple(disps.shape)))
 
 
+def _ba_operands(what, poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, *more_device, eta_f32=True, window_from_zero=True):
+    """the operand checks `ba`, `ba_uncertainty` and `ba_calib` share: contiguity, one device, dtypes, the pose window ->
+    (dev, F, ht, wd, HW, E, t0, t1, P).  `ba` switches two of them off: eta_f32 (its eta may be None, and it checks the dtype
+    itself) and window_from_zero (it leaves a negative or reversed window to the library)."""
+    for t, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
+                 (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
+        _contig(t, n)      # droid.cpp:103-109 checks exactly these
+    dev = _dev(poses, disps, intrinsics, targets, weights, eta, ii, jj, *more_device)
+    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (targets, "targets"),
+                 (weights, "weights")) + (((eta, "eta"),) if eta_f32 else ()):
+        _f32(t, n)
+    _long(ii, "ii"); _long(jj, "jj")
+    F, ht, wd = disps.shape
+    t0, t1 = int(t0), int(t1)
+    P = t1 - t0
+    if (window_from_zero and (P < 0 or t0 < 0)) or poses.shape[0] < t1 or F < t1:
+        raise PvoHipError("%s: pose window [%d,%d) exceeds the buffers (%d poses, %d depth maps)"
+                          % (what, t0, t1, poses.shape[0], F))
+    return dev, F, ht, wd, ht * wd, ii.shape[0], t0, t1, P
+
+
+def _depth_rows(K_eta, t0, t1, ii, dev):
+    """K = |unique([t0,t1) U ii)|, the rows of dz, is only known on the device.  eta carries one row per depth map (the
+    reference's C + eta broadcast requires it), so K == K_eta unless eta is a single broadcast row; only then is K read back
+    (one sync)."""
+    return K_eta if K_eta > 1 else int(torch.unique(torch.cat([torch.arange(t0, t1, device=dev), ii])).numel())
+
+
+def _status4(status, what):
+    if status is not None and (status.dtype != torch.int32 or status.numel() < 4):
+        raise PvoHipError("%s: status must be int32 with 4 elements" % what)
+
+
 def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iterations, lm, ep, motion_only,
        status=None, disps_sens=None, alpha=0.05, stereo_baseline=0.0):
     """droid.cpp:87-114 / ba_cuda droid_kernels.cu:1293-1410.
@@ -1407,22 +1440,8 @@ def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iteratio
     stereo_baseline = _baseline(stereo_baseline, "ba")
     if disps_sens is not None:
         _sens_map(disps_sens, disps, "ba")
-    for t, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
-                 (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
-        _contig(t, n)      # droid.cpp:103-109 checks exactly these
-    dev = _dev(poses, disps, intrinsics, targets, weights, eta, ii, jj)
-    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (targets, "targets"),
-                 (weights, "weights")):
-        _f32(t, n)
-    _long(ii, "ii"); _long(jj, "jj")
-    F, ht, wd = disps.shape
-    HW = ht * wd
-    E = ii.shape[0]
-    t0, t1 = int(t0), int(t1)
-    P = t1 - t0
-    if poses.shape[0] < t1 or F < t1:
-        raise PvoHipError("ba: pose window [%d,%d) exceeds the buffers (%d poses, %d depth maps)"
-                          % (t0, t1, poses.shape[0], F))
+    dev, F, ht, wd, HW, E, t0, t1, P = _ba_operands("ba", poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1,
+                                                    eta_f32=False, window_from_zero=False)
     if eta is not None and not motion_only:
         _f32(eta, "eta")
         eta = eta.contiguous().view(-1, HW)     # droid_kernels.cu:1376 eta.view({-1, ht*wd})
@@ -1431,15 +1450,7 @@ def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iteratio
         K_eta = 1
         if not motion_only:
             raise PvoHipError("ba: eta is required unless motion_only")
-    # K = |unique([t0,t1) U ii)| is only known on the device.  eta carries one row per depth
-    # map (the reference's C + eta broadcast requires it), so K == K_eta unless eta is a single
-    # broadcast row; only then is K read back (one sync) to size dz.
-    if motion_only:
-        K = 0
-    elif K_eta > 1 or E + P == 0:
-        K = K_eta if E + P > 0 else 0
-    else:
-        K = int(torch.unique(torch.cat([torch.arange(t0, t1, device=dev), ii])).numel())
+    K = 0 if motion_only or E + P == 0 else _depth_rows(K_eta, t0, t1, ii, dev)
     dx = torch.zeros(max(P, 0), 6, dtype=torch.float32, device=dev)
     dz = torch.zeros(K, HW, dtype=torch.float32, device=dev)
     lib = _lib.load()
@@ -1447,14 +1458,12 @@ def ba(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, iteratio
     ws = _workspace(dev, nbytes)
     with torch.cuda.device(dev):
         args = (_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(targets), _ptr(weights),
-                _ptr(eta) if eta is not None else ctypes.c_void_p(0), _ptr(ii), _ptr(jj),
+                _vp(eta), _ptr(ii), _ptr(jj),
                 E, F, ht, wd, K_eta, t0, t1, int(iterations), float(lm), float(ep),
-                1 if motion_only else 0, _ptr(dx), _ptr(dz), K,
-                _ptr(status) if status is not None else ctypes.c_void_p(0),
+                1 if motion_only else 0, _ptr(dx), _ptr(dz), K, _vp(status),
                 ctypes.c_void_p(ws.data_ptr()), ws.numel())
         if stereo_baseline != 0.0:
-            check(lib.pvo_ba_rig(*args, _ptr(disps_sens) if disps_sens is not None else ctypes.c_void_p(0), float(alpha), stereo_baseline,
-                                 _stream(dev)), "ba (stereo)")
+            check(lib.pvo_ba_rig(*args, _vp(disps_sens), float(alpha), stereo_baseline, _stream(dev)), "ba (stereo)")
         elif disps_sens is None:
             check(lib.pvo_ba(*args, _stream(dev)), "ba")
         else:
@@ -1532,8 +1541,7 @@ def _sigma_outputs(P, disps, var_cond, var_pose, status, what):
         _contig(t, n)
         if tuple(t.shape) != tuple(disps.shape) or t.device != disps.device:
             raise PvoHipError("%s: %s must have disps' shape %s and device" % (what, n, tuple(disps.shape)))
-    if status is not None and (status.dtype != torch.int32 or status.numel() < 4):
-        raise PvoHipError("%s: status must be int32 with 4 elements" % what)
+    _status4(status, what)
     return torch.zeros(6 * P, 6 * P, dtype=torch.float64, device=disps.device)
 
 
@@ -1569,19 +1577,8 @@ def ba_uncertainty(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, 
     stereo_baseline = _baseline(stereo_baseline, "ba_uncertainty")
     if disps_sens is not None:
         _sens_map(disps_sens, disps, "ba_uncertainty")
-    for t, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
-                 (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
-        _contig(t, n)
-    dev = _dev(poses, disps, intrinsics, targets, weights, eta, ii, jj, var_cond, var_pose, status)
-    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (targets, "targets"), (weights, "weights"), (eta, "eta")):
-        _f32(t, n)
-    _long(ii, "ii"); _long(jj, "jj")
-    F, ht, wd = disps.shape
-    HW, E = ht * wd, ii.shape[0]
-    t0, t1 = int(t0), int(t1)
-    P = t1 - t0
-    if P < 0 or t0 < 0 or poses.shape[0] < t1 or F < t1:
-        raise PvoHipError("ba_uncertainty: pose window [%d,%d) exceeds the buffers (%d poses, %d depth maps)" % (t0, t1, poses.shape[0], F))
+    dev, F, ht, wd, HW, E, t0, t1, P = _ba_operands("ba_uncertainty", poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1,
+                                                    var_cond, var_pose, status)
     eta = eta.contiguous().view(-1, HW)
     cov = _sigma_outputs(P, disps, var_cond, var_pose, status, "ba_uncertainty")
     lib = _lib.load()
@@ -1604,28 +1601,15 @@ def ba_calib(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, it
     poses and disps.  free_mask: bit n frees (fx, fy, cx, cy)[n]; a held parameter keeps its bytes.  Returns [dx [P,6], dz [K,ht*wd],
     dc [4]] of the last step (zeros when it was rejected).  status (optional int32[4]) receives [a step was rejected, K, eta-row
     mismatch, row-table overflow].  1 <= P <= BA_CALIB_MAX_POSES.  Runs on the workspace `ba` uses.  No host synchronisation."""
-    for t, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
-                 (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
-        _contig(t, n)
-    dev = _dev(poses, disps, intrinsics, targets, weights, eta, ii, jj, status)
-    for t, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (targets, "targets"), (weights, "weights"), (eta, "eta")):
-        _f32(t, n)
-    _long(ii, "ii"); _long(jj, "jj")
-    F, ht, wd = disps.shape
-    HW, E = ht * wd, ii.shape[0]
-    t0, t1 = int(t0), int(t1)
-    P = t1 - t0
-    if P < 0 or t0 < 0 or poses.shape[0] < t1 or F < t1:
-        raise PvoHipError("ba_calib: pose window [%d,%d) exceeds the buffers (%d poses, %d depth maps)" % (t0, t1, poses.shape[0], F))
+    dev, F, ht, wd, HW, E, t0, t1, P = _ba_operands("ba_calib", poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, status)
     if P > BA_CALIB_MAX_POSES:
         raise PvoHipError("ba_calib: at most %d window poses (got %d)" % (BA_CALIB_MAX_POSES, P))
     if intrinsics.numel() != 4:
         raise PvoHipError("ba_calib: intrinsics must hold the 4 values fx, fy, cx, cy")
-    if status is not None and (status.dtype != torch.int32 or status.numel() < 4):
-        raise PvoHipError("ba_calib: status must be int32 with 4 elements")
+    _status4(status, "ba_calib")
     eta = eta.contiguous().view(-1, HW)
     K_eta = eta.shape[0]
-    K = K_eta if K_eta > 1 else int(torch.unique(torch.cat([torch.arange(t0, t1, device=dev), ii])).numel())
+    K = _depth_rows(K_eta, t0, t1, ii, dev)
     dx = torch.zeros(max(P, 0), 6, dtype=torch.float32, device=dev)
     dz = torch.zeros(K, HW, dtype=torch.float32, device=dev)
     dc = torch.zeros(4, dtype=torch.float32, device=dev)
@@ -1676,7 +1660,7 @@ def ba_local(poses, disps, intrinsics, targets, weights, eta, ii, jj, t0, t1, mo
         K_eta = eta.shape[0]
     with torch.cuda.device(dev):
         check(_lib.load().pvo_ba_local(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(targets), _ptr(weights),
-                                       _ptr(eta) if eta is not None else ctypes.c_void_p(0), _ptr(ii), _ptr(jj),
+                                       _vp(eta), _ptr(ii), _ptr(jj),
                                        ii.shape[0], F, ht, wd, K_eta, int(t0), int(t1), (1 if motion_only else 0) | (2 if sys_is_zero else 0),
                                        _ptr(sys), ctypes.c_void_p(workspace.data_ptr()), workspace.numel(),
                                        _stream(dev)), "ba_local")
@@ -1738,6 +1722,12 @@ def ba_finish(poses, disps, sys, ii, jj, t0, t1, lm, ep, motion_only, workspace,
     dz = torch.zeros(int(dz_rows), ht * wd, dtype=torch.float32, device=dev) if outputs else None
     if not outputs:
         dz_rows = 0
+    lib = _lib.load()
+    # what every finish entry point takes behind its system (sys, or msg + first) and in front of its own tail
+    common = (_ptr(ii), _ptr(jj), ii.shape[0], F, ht, wd,
+              int(t0), int(t1), float(lm), float(ep), 1 if motion_only else 0,
+              int(clamp_frames), float(disp_min), _ptr(dx), _ptr(dz), int(dz_rows), _vp(status),
+              ctypes.c_void_p(workspace.data_ptr()), workspace.numel())
     if packed is not None:
         msg, first_dev = packed
         if rider is not None:
@@ -1745,32 +1735,18 @@ def ba_finish(poses, disps, sys, ii, jj, t0, t1, lm, ep, motion_only, workspace,
         if msg.dtype != torch.int64 or first_dev.dtype != torch.int32 or first_dev.shape[0] != P:
             raise PvoHipError("ba_finish: packed = (int64 message, int32 [P] structural envelope)")
         with torch.cuda.device(dev):
-            check(_lib.load().pvo_ba_finish_packed(
-                _ptr(poses), _ptr(disps), _ptr(msg), _ptr(first_dev), _ptr(ii), _ptr(jj), ii.shape[0], F, ht, wd,
-                int(t0), int(t1), float(lm), float(ep), 1 if motion_only else 0,
-                int(clamp_frames), float(disp_min), _ptr(dx), _ptr(dz), int(dz_rows),
-                _ptr(status) if status is not None else ctypes.c_void_p(0),
-                ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream(dev)), "ba_finish_packed")
+            check(lib.pvo_ba_finish_packed(_ptr(poses), _ptr(disps), _ptr(msg), _ptr(first_dev), *common, _stream(dev)), "ba_finish_packed")
         return [dx, dz]
     if graph_edges is not None:
         if rider is not None:
             raise PvoHipError("ba_finish: a rider and graph_edges together are not supported")
         with torch.cuda.device(dev):
-            check(_lib.load().pvo_ba_finish_graph(
-                _ptr(poses), _ptr(disps), _ptr(sys), _ptr(ii), _ptr(jj), ii.shape[0], F, ht, wd,
-                int(t0), int(t1), float(lm), float(ep), 1 if motion_only else 0,
-                int(clamp_frames), float(disp_min), _ptr(dx), _ptr(dz), int(dz_rows),
-                _ptr(status) if status is not None else ctypes.c_void_p(0),
-                ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), int(graph_edges), _stream(dev)), "ba_finish_graph")
+            check(lib.pvo_ba_finish_graph(_ptr(poses), _ptr(disps), _ptr(sys), *common, int(graph_edges), _stream(dev)), "ba_finish_graph")
         return [dx, dz]
     with torch.cuda.device(dev):
-        check(_lib.load().pvo_ba_finish_conv1x1(
-            _ptr(poses), _ptr(disps), _ptr(sys), _ptr(ii), _ptr(jj), ii.shape[0], F, ht, wd,
-            int(t0), int(t1), float(lm), float(ep), 1 if motion_only else 0,
-            int(clamp_frames), float(disp_min), _ptr(dx), _ptr(dz), int(dz_rows),
-            _ptr(status) if status is not None else ctypes.c_void_p(0),
-            ctypes.c_void_p(workspace.data_ptr()), workspace.numel(),
-            _ptr(rx), _ptr(rw), _bias(rb, rC, "rider bias") if rider is not None else ctypes.c_void_p(0), _ptr(ry),
+        check(lib.pvo_ba_finish_conv1x1(
+            _ptr(poses), _ptr(disps), _ptr(sys), *common,
+            _ptr(rx), _ptr(rw), _bias(rb, rC, "rider bias") if rider is not None else None, _ptr(ry),
             int(rrows), int(rC), int(rdt), _stream(dev)), "ba_finish")
     return [dx, dz] if rider is None else [dx, dz, ry]
 

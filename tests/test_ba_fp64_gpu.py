@@ -136,7 +136,7 @@ def _scaled_system(graph, target, damping):
         M = np.tril(M) + np.tril(M, -1).T
         Md = M.copy()
         v = np.diag(M)
-        Md[np.diag_indices(n)] = v + (ep + lm * v)                               # ba_prepare_kernel's expression (ba.hip)
+        Md[np.diag_indices(n)] = v + (ep + lm * v)                               # ba_prepare_kernel's expression (ba_solve.h)
         ev = np.linalg.eigvalsh(Md)
         return M, Md, np.rint(D * rhs * 2.0 ** 28) * 2.0 ** -28, float(ev[-1] / ev[0])
     if build(0.0, 0.0)[3] < target:                                            # spread the scales until the target is reached
