@@ -99,7 +99,9 @@ const char* pvo_last_hip_error(void);
  * pvo_tsdf_reintegrate[_workspace_bytes] / pvo_tsdf_sparse_reintegrate[_workspace_bytes]; still 106, object motion: no existing
  * struct changed - new struct pvo_object_motion_args (with pvo_object_motion_args_size()) and new entry points
  * pvo_object_motion[_workspace_bytes]; still 106, segment association: no existing struct changed - new struct
- * pvo_segment_assoc_args (with pvo_segment_assoc_args_size()) and new entry point pvo_segment_associate): a caller
+ * pvo_segment_assoc_args (with pvo_segment_assoc_args_size()) and new entry point pvo_segment_associate; still 106, feature
+ * transport: no existing struct changed - new structs pvo_transport_level / pvo_feature_transport_args (with
+ * pvo_feature_transport_args_size()) and new entry points pvo_feature_transport[_workspace_bytes]): a caller
  * checks pvo_version() == PVO_ABI_VERSION, or pvo_graph_update_args_size() == sizeof(pvo_graph_update_args), once after loading. */
 #define PVO_ABI_VERSION 106
 int pvo_version(void);
@@ -1469,6 +1471,73 @@ typedef struct pvo_segment_assoc_args {
 } pvo_segment_assoc_args;
 size_t pvo_segment_assoc_args_size(void);
 int pvo_segment_associate(const pvo_segment_assoc_args* a, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Feature transport: the previous frame's feature pyramid carried along the  */
+/* odometry's flow into the current frame (the VO -> VPS link)                */
+/* ------------------------------------------------------------------------- */
+
+/* pvo_feature_transport: a forward splat with a depth test, all pyramid levels of one (reference frame, current frame) pair in one
+ * call (reference counterpart: flow_transport_feature, flow_transport_feature_with_depth, pose_transport_depth and depth_filter of
+ * VPS_Module/detectron2/modeling/meta_arch/panoptic_fpn.py:310-431, which do this on the host through numpy and a sorted dict).
+ * All pointers are device pointers; feature maps are channels-last [H,W,C], 16-byte aligned.  Every quantity is an integer or an fp32
+ * operation ROUNDED ON ITS OWN (no fused multiply-add anywhere below): the same operands give the same bytes, on any implementation.
+ *
+ * Resize.  bilinear(A, Ha, Wa; H, W; x, y), the value of map A [Ha,Wa] at cell (x, y) of an H x W grid:
+ *   rw = W > 1 ? (float)(Wa-1) / (float)(W-1) : 0;  px = rw * (float)x;  x0 = min((int)px, Wa-1);  x1 = x0 + (x0 < Wa-1);
+ *   lx = px - (float)x0;  hx = 1 - lx;  the same in y;  value = hy*(hx*A[y0,x0] + lx*A[y0,x1]) + ly*(hx*A[y1,x0] + lx*A[y1,x1]).
+ *   (The align_corners resize of panoptic_fpn.py:433-438; bit equality with any library's resize is not promised.)
+ * Depth transport, only with rel_pose, at the depth map's own resolution before any resize:
+ *   Z = depth[v,u];  X = ((float)u - cx) / fx * Z;  Y = ((float)v - cy) / fy * Z;  depth'[v,u] = ((r20*X + r21*Y) + r22*Z) + t2
+ *   (into the workspace; depth' then takes depth's place).  A DISPARITY transported by rel_pose is left out: rel_pose with
+ *   order = -1 is PVO_EINVAL.
+ * Per level and source cell (x, y), s = y*W + x, with (fx_, fy_) = the bilinear sample of flow [Hf,Wf,2] on the level's grid:
+ *   the cell is DROPPED if either flow component is not finite.
+ *   PVO_TRANSPORT_NEAREST:   tx = (float)x + fx_*sx;  rx = floorf(tx + 0.5f);  the same in y with sy.
+ *   PVO_TRANSPORT_REFERENCE: qx = truncf(fx_);  dropped if qx <= -1 or qy <= -1 or |fx_| >= 32768 or |fy_| >= 32768;  rx = (float)x + qx.
+ *                            (The reference's astype(uint16) followed by its range mask: negative flows leave the image, the flow
+ *                            is added to level cells unscaled.  A flow beyond 32768 would WRAP back into the image there; here it is
+ *                            dropped.)
+ *   dropped unless 0 <= rx <= W-1 and 0 <= ry <= H-1, compared as floats before any conversion (1e30 is dropped, never converted).
+ *   With depth: d = the bilinear sample of depth (or depth') [Hd,Wd] on the level's grid; dropped unless d is finite and d > 0.
+ * Winner of a target cell among the cells that land on it: order = +1 the smallest d (d is a depth; what the reference does with
+ *   its "depth" file), order = -1 the largest d (d is a disparity: the nearer surface); without depth there is no key.  Ties go to
+ *   the LARGEST s (the reference's stable descending sort followed by last-write-wins, and its flow-only form).  One 64-bit
+ *   atomicMin per source cell on ((bits(d) or ~bits(d)) << 32) | ~s: the result does not depend on the order of the atomics.
+ * Outputs, every cell of every level written (a caller never clears anything; the key table is cleared by the call):
+ *   src[t] = the winner's s, or -1.  The cur half of out is a byte copy.  The transported half is the winner's C channels, +0 where
+ *   src is -1; with alpha == 1.0f a byte copy (NaN payloads and negative zeros survive), otherwise (dtype)((float)ref * alpha)
+ *   rounded to nearest even.
+ * At most four launches on `stream`: clear; depth transport (only with rel_pose); resolve (one thread per source cell of all levels in
+ * one grid); gather (all levels in one grid, 16 bytes per thread, no LDS).  No allocation, no host synchronisation: capturable.
+ * Limits (PVO_EINVAL): a NULL a; L outside [0, PVO_TRANSPORT_MAX_LEVELS]; an unknown dtype, mode or order; C < 1 or C * elemsize % 16
+ * != 0; a non-finite alpha; a negative dimension or H*W (Hf*Wf, Hd*Wd) >= 2^31; rel_pose without depth or without intrinsics; rel_pose
+ * with order = -1; then, unless L == 0 (PVO_OK, nothing written): a NULL ref / out / src of a level with H*W > 0, a ref / cur / out
+ * that is not 16-byte aligned, a NULL or empty flow (or an empty depth) when a level has cells, too small (or misaligned) a workspace. */
+#define PVO_TRANSPORT_MAX_LEVELS 8
+#define PVO_TRANSPORT_NEAREST   0
+#define PVO_TRANSPORT_REFERENCE 1
+typedef struct pvo_transport_level {
+  const void* ref;   /* [H,W,C]  features of the reference (previous) frame */
+  const void* cur;   /* [H,W,C]  features of the current frame, or NULL */
+  void* out;         /* cur != NULL: [H,W,2C] = [cur | alpha * transported];  cur == NULL: [H,W,C] = alpha * transported */
+  int32_t* src;      /* [H,W]    linear index of the source cell that won this cell, or -1 */
+  int H, W;
+  float sx, sy;      /* level cells per flow unit (nearest mode); ignored in reference mode */
+} pvo_transport_level;
+typedef struct pvo_feature_transport_args {
+  const float* flow;  int Hf, Wf;       /* [Hf,Wf,2] (x, y) */
+  const float* depth; int Hd, Wd;       /* [Hd,Wd] ordering key, or NULL (flow only) */
+  const float* rel_pose;                /* 12 f32, rows of [R|t] taking reference-camera points to the current camera, or NULL */
+  const float* intrinsics;              /* fx, fy, cx, cy at the depth map's resolution; needed iff rel_pose */
+  int C, dtype, L, mode, order;         /* dtype PVO_F16 / PVO_BF16 / PVO_F32; order +1: smaller key wins, -1: larger key wins */
+  float alpha;
+  pvo_transport_level level[PVO_TRANSPORT_MAX_LEVELS];
+} pvo_feature_transport_args;
+size_t pvo_feature_transport_args_size(void);
+/* 8 bytes per cell of all levels, plus Hd*Wd floats with rel_pose (each part rounded up to 16 bytes); 0 for arguments the call refuses */
+size_t pvo_feature_transport_workspace_bytes(const pvo_feature_transport_args* a);
+int pvo_feature_transport(const pvo_feature_transport_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SE3 element-wise operations (lietorch subset)                              */

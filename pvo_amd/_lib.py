@@ -157,6 +157,9 @@ SIGNATURES = {
     "pvo_object_motion": (_i, [_vp, _vp, _sz, _vp]),
     "pvo_segment_assoc_args_size": (_sz, []),
     "pvo_segment_associate": (_i, [_vp, _vp]),
+    "pvo_feature_transport_args_size": (_sz, []),
+    "pvo_feature_transport_workspace_bytes": (_sz, [_vp]),
+    "pvo_feature_transport": (_i, [_vp, _vp, _sz, _vp]),
     "pvo_ba_last_partition": (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp]),
     "pvo_ba_packed_elems": (_sz, [ctypes.POINTER(ctypes.c_int), _i]),
     "pvo_ba_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -352,6 +355,22 @@ class SegmentAssocArgs(_c.Structure):
                 ("overlap", _vp), ("area_i", _vp), ("area_j", _vp), ("match", _vp), ("match_n", _vp), ("match_d", _vp)]
 
 
+TRANSPORT_MAX_LEVELS = 8                   # PVO_TRANSPORT_MAX_LEVELS
+TRANSPORT_NEAREST, TRANSPORT_REFERENCE = 0, 1
+
+
+class TransportLevel(_c.Structure):
+    """pvo_transport_level"""
+    _fields_ = [("ref", _vp), ("cur", _vp), ("out", _vp), ("src", _vp), ("H", _i), ("W", _i), ("sx", _f), ("sy", _f)]
+
+
+class FeatureTransportArgs(_c.Structure):
+    """pvo_feature_transport_args"""
+    _fields_ = [("flow", _vp), ("Hf", _i), ("Wf", _i), ("depth", _vp), ("Hd", _i), ("Wd", _i), ("rel_pose", _vp), ("intrinsics", _vp),
+                ("C", _i), ("dtype", _i), ("L", _i), ("mode", _i), ("order", _i), ("alpha", _f),
+                ("level", TransportLevel * TRANSPORT_MAX_LEVELS)]
+
+
 PVO_OP_CONV128_WIDE, PVO_OP_SINGLE_STREAM, PVO_OP_ENC_SIDE_STREAM = 1, 2, 4
 PVO_KNOB_BA_SOLVER, PVO_KNOB_HEADS_GATHER_FLAT, PVO_KNOB_NO_RIDERS, PVO_KNOB_POST_SEPARATE = 0, 1, 2, 3
 PVO_KNOB_EDGE_BLOCKS = 4        # 0 shipped | 1 off | 2 + bits (third, low, agg, trunk): 2 ... 17
@@ -397,7 +416,8 @@ def load():
                        (lib.pvo_tsdf_track_args_size, TsdfTrackArgs), (lib.pvo_tsdf_sparse_track_args_size, TsdfSparseTrackArgs),
                        (lib.pvo_tsdf_reintegrate_args_size, TsdfReintegrateArgs),
                        (lib.pvo_tsdf_sparse_reintegrate_args_size, TsdfSparseReintegrateArgs),
-                       (lib.pvo_object_motion_args_size, ObjectMotionArgs), (lib.pvo_segment_assoc_args_size, SegmentAssocArgs)):
+                       (lib.pvo_object_motion_args_size, ObjectMotionArgs), (lib.pvo_segment_assoc_args_size, SegmentAssocArgs),
+                       (lib.pvo_feature_transport_args_size, FeatureTransportArgs)):
         if fn() != ctypes.sizeof(struct):
             raise PvoHipError("libpvo_hip.so has a %d-byte %s; this binding is written for %d bytes - rebuild with "
                               "`python -m pvo_amd.build`" % (fn(), struct.__doc__, ctypes.sizeof(struct)))

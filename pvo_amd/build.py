@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "tsdf_reintegrate.hip",
     "object_motion.hip",
     "segment_assoc.hip",
+    "feature_transport.hip",
     "gru_fused.hip",
     "graph_glue.hip",
     "conv_small.hip",
@@ -59,7 +60,9 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 # projmap / iproj / the depth filter's integer counts equal the kernel-text fixtures bit for bit (tests/test_kernel_text_goldens.py;
 # until round 5 the counts differed in ~0.5 % of the pixels, where |1/dj - 1/d| sat within a contraction's rounding of the threshold)
 # map_points.hip shares the depth filter's vote (csrc/depth_vote.h) and must get pvo_depth_filter's counts: the same flag
-EXTRA_FLAGS = {"geom.hip": ["-ffp-contract=off"], "map_points.hip": ["-ffp-contract=off"]}
+# feature_transport.hip states every fp32 rounding of its contract (include/pvo_hip.h pvo_feature_transport): the same flag
+EXTRA_FLAGS = {"geom.hip": ["-ffp-contract=off"], "map_points.hip": ["-ffp-contract=off"],
+               "feature_transport.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src):

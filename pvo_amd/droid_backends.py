@@ -1326,6 +1326,124 @@ def segment_associate(labels, ii, jj, target, S, valid=None, cls=None, min_iou=0
     return out
 
 
+_TRANSPORT_MODES = {"nearest": _lib.TRANSPORT_NEAREST, "reference": _lib.TRANSPORT_REFERENCE}
+
+
+def feature_transport(ref_feats, cur_feats, flow, scales=None, depth=None, order=1, rel_pose=None, intrinsics=None, alpha=1.0,
+                      mode="nearest", out=None):
+    """The previous frame's feature pyramid carried along the flow into the current frame (include/pvo_hip.h pvo_feature_transport):
+    a forward splat, the depth key deciding between the cells that land on one target.  ref_feats: a list of up to 8 channels-last
+    [1,C,H,W] tensors (float16, bfloat16 or float32, one C and dtype, C * itemsize % 16 == 0); cur_feats: the same shapes, or None.
+    flow float32 [Hf,Wf,2] (x, y); scales: per level (sx, sy), level cells per flow unit (nearest mode; None = 1); depth float32 [Hd,Wd]
+    or None; order +1: the smallest key wins (a depth), -1: the largest (a disparity); rel_pose 12 float32 ([R|t] rows, reference
+    camera -> current camera) with intrinsics float32 [4] at the depth map's resolution: the depth is carried into the current camera
+    first (order +1 only).  mode "nearest" (flow scaled to the level, rounded to nearest) or "reference" (the reference's rules).
+    Returns (outs, srcs): outs[l] channels-last [1,2C,H,W] = [cur | alpha * transported] ([1,C,H,W] without cur_feats), srcs[l] int32
+    [H,W], the source cell that won each cell or -1.  Shapes, dtypes, devices and contiguity are checked here (ValueError).
+    out=(outs, srcs): caller-owned buffers - then no allocation, no synchronisation, capturable."""
+    f32 = torch.float32
+    if not isinstance(ref_feats, (list, tuple)) or len(ref_feats) > _lib.TRANSPORT_MAX_LEVELS:
+        raise ValueError("feature_transport: ref_feats must be a list of at most %d tensors" % _lib.TRANSPORT_MAX_LEVELS)
+    L = len(ref_feats)
+    if cur_feats is not None and (not isinstance(cur_feats, (list, tuple)) or len(cur_feats) != L):
+        raise ValueError("feature_transport: cur_feats must be None or a list as long as ref_feats")
+    if mode not in _TRANSPORT_MODES:
+        raise ValueError("feature_transport: mode must be 'nearest' or 'reference'")
+    if order not in (1, -1):
+        raise ValueError("feature_transport: order must be +1 (smallest key wins) or -1 (largest key wins)")
+    alpha = float(alpha)
+    if alpha != alpha or alpha in (float("inf"), float("-inf")):
+        raise ValueError("feature_transport: alpha must be finite")
+    if rel_pose is not None and (depth is None or intrinsics is None):
+        raise ValueError("feature_transport: rel_pose needs depth and intrinsics")
+    if rel_pose is not None and order != 1:
+        raise ValueError("feature_transport: rel_pose carries a depth, not a disparity (order must be +1)")
+    if rel_pose is None and intrinsics is not None:
+        raise ValueError("feature_transport: intrinsics are given only with rel_pose")
+    dev = None
+    for name, t, shape in (("flow", flow, (None, None, 2)), ("depth", depth, (None, None)), ("rel_pose", rel_pose, None),
+                           ("intrinsics", intrinsics, (4,))):
+        if t is None:
+            if name == "flow":
+                raise ValueError("feature_transport: flow is required")
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError("feature_transport: %s must be a device tensor (there is no CPU fallback)" % name)
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise ValueError("feature_transport: %s must be on %s" % (name, dev))
+        if t.dtype != f32 or not t.is_contiguous():
+            raise ValueError("feature_transport: %s must be contiguous float32" % name)
+        if shape is None:
+            if t.numel() != 12:
+                raise ValueError("feature_transport: rel_pose must hold 12 values, the rows of [R|t]")
+        elif t.dim() != len(shape) or any(w is not None and w != n for w, n in zip(shape, t.shape)):
+            raise ValueError("feature_transport: %s must be %s" % (name, {"flow": "[Hf,Wf,2]", "depth": "[Hd,Wd]", "intrinsics": "[4]"}[name]))
+    C = dtype = None
+    for l in range(L):
+        for name, t in (("ref_feats", ref_feats[l]), ("cur_feats", None if cur_feats is None else cur_feats[l])):
+            if t is None:
+                if name == "ref_feats":
+                    raise ValueError("feature_transport: ref_feats[%d] is required" % l)
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+                raise ValueError("feature_transport: %s[%d] must be a tensor on %s (there is no CPU fallback)" % (name, l, dev))
+            if t.dim() != 4 or t.shape[0] != 1 or not t.is_contiguous(memory_format=torch.channels_last):
+                raise ValueError("feature_transport: %s[%d] must be a channels-last [1,C,H,W] tensor" % (name, l))
+            if C is None:
+                C, dtype = t.shape[1], t.dtype
+                if dtype not in (torch.float16, torch.bfloat16, f32) or C < 1 or (C * t.element_size()) % 16:
+                    raise ValueError("feature_transport: features must be float16, bfloat16 or float32 with C * itemsize % 16 == 0")
+            if t.shape[1] != C or t.dtype != dtype:
+                raise ValueError("feature_transport: every level must have the same C and dtype")
+            if name == "cur_feats" and t.shape != ref_feats[l].shape:
+                raise ValueError("feature_transport: cur_feats[%d] must have ref_feats[%d]'s shape" % (l, l))
+        if ref_feats[l].shape[2] * ref_feats[l].shape[3] >= 1 << 31:
+            raise ValueError("feature_transport: H * W must stay below 2^31")
+    if L and (flow.shape[0] < 1 or flow.shape[1] < 1 or (depth is not None and depth.numel() == 0)):
+        raise ValueError("feature_transport: flow and depth must not be empty")
+    if scales is None:
+        scales = [(1.0, 1.0)] * L
+    if len(scales) != L or any(len(s) != 2 for s in scales):
+        raise ValueError("feature_transport: scales must give (sx, sy) per level")
+    shapes = [tuple(t.shape[2:]) for t in ref_feats]
+    widths = [C * (1 if cur_feats is None or cur_feats[l] is None else 2) for l in range(L)]
+    if out is None:
+        outs = [_new_cl(1, widths[l], shapes[l][0], shapes[l][1], dtype, dev) for l in range(L)]
+        srcs = [torch.empty(shapes[l], dtype=torch.int32, device=dev) for l in range(L)]
+    else:
+        outs, srcs = out
+        if len(outs) != L or len(srcs) != L:
+            raise ValueError("feature_transport: out must be (outs, srcs), one tensor per level each")
+        for l in range(L):
+            o, s = outs[l], srcs[l]
+            if not torch.is_tensor(o) or o.device != dev or o.dtype != dtype or tuple(o.shape) != (1, widths[l]) + shapes[l] or \
+                    not o.is_contiguous(memory_format=torch.channels_last):
+                raise ValueError("feature_transport: outs[%d] must be a channels-last %s [1,%d,%d,%d] on %s"
+                                 % (l, dtype, widths[l], shapes[l][0], shapes[l][1], dev))
+            if not torch.is_tensor(s) or s.device != dev or s.dtype != torch.int32 or tuple(s.shape) != shapes[l] or not s.is_contiguous():
+                raise ValueError("feature_transport: srcs[%d] must be a contiguous int32 %s on %s" % (l, list(shapes[l]), dev))
+    if L == 0:
+        return list(outs), list(srcs)
+    a = _lib.FeatureTransportArgs()
+    a.flow, a.Hf, a.Wf = _ptr(flow), flow.shape[0], flow.shape[1]
+    a.depth, a.rel_pose, a.intrinsics = _ptr(depth), _ptr(rel_pose), _ptr(intrinsics)
+    a.Hd, a.Wd = (0, 0) if depth is None else depth.shape
+    a.C, a.dtype, a.L, a.mode, a.order, a.alpha = C, _DT[dtype], L, _TRANSPORT_MODES[mode], order, alpha
+    for l in range(L):
+        v = a.level[l]
+        v.ref, v.out, v.src = _ptr(ref_feats[l]), _ptr(outs[l]), _ptr(srcs[l])
+        v.cur = _ptr(None if cur_feats is None else cur_feats[l])
+        v.H, v.W = shapes[l]
+        v.sx, v.sy = float(scales[l][0]), float(scales[l][1])
+    lib = _lib.load()
+    need = lib.pvo_feature_transport_workspace_bytes(ctypes.byref(a))
+    ws = _workspace(dev, need)
+    with torch.cuda.device(dev):
+        check(lib.pvo_feature_transport(ctypes.byref(a), _ptr(ws), ws.numel(), _stream(dev)), "feature_transport")
+    return list(outs), list(srcs)
+
+
 def _baseline(baseline, what):
     """a stereo baseline: a finite number >= 0 (0 = no stereo edges)"""
     b = float(baseline)
